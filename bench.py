@@ -2,13 +2,21 @@
 """Headline benchmark: mel-frames/s of the FastSpeech2 mel forward on synthetic 256-phoneme x
 batch-32 inputs (BASELINE.json metric / configs[1]: FS2-27M, bf16, batch 32, 256 phonemes).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path (fs2_encode + fs2_decode through the drop-in model object)
 over one batch per rank, inputs already resident in HBM; with N > 1 every rank runs its own
 batch-32 shard (weak scaling) and the final mels are all-gathered with RCCL.  Rank 0 prints ONE
 JSON line.
+
+A plain run sets up, warms up (incl. the launch-mode choice below), times exactly K steps, writes
+--dump-outputs and prints the headline line (value, ms_per_step, launch mode).  --dump-outputs DIR:
+rank 0's outputs of the last timed step (the forward's output dict: mel, durations, masks,
+variances) as DIR/<name>.npy in float32 (at most 64 MB in all; a fixed seeded sample of an array
+beyond that); the inputs are seeded, so two builds can be compared output for output.
+--full adds every side measurement below, each in passes of its own behind the timed region:
+  dist          (N > 1) per-rank step times with and without the mel gather, RCCL version.
   roofline      the dominant kernel (the implicit-GEMM dense Conv1d): algorithmic FLOPs per launch /
                 average launch duration measured with HIP events on the launch stream inside the timed
                 region; traffic = HBM bytes per launch from this round's committed PMC passes.
@@ -59,7 +67,39 @@ def parse():
                     "the timed region takes the faster of 1 and this many, measured in the warm-up (FS2_BENCH_IN_FLIGHT pins it)")
     ap.add_argument("--parity-sample", type=int, default=0,
                     help="utterances of the workload the parity block checks against the oracle (0 = the whole batch, the default: ~3 s of CPU at C2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's outputs of the last timed step as DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements behind the timed region (dist, roofline, north_star_attention, "
+                         "encoder_mha_block, gpu_ms_per_step, value_incl_pcie, parity, training_step, cpu_baseline)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """The forward's output dict (nested CWT dicts flattened as `a.b`) -> path/<name>.npy, float32.  If the arrays exceed
+    DUMP_LIMIT_BYTES, every array over an even share of it is written as a fixed seeded sample of its flattened elements
+    (sorted indices, RandomState(0)) and its index set as <name>.index.npy."""
+    flat = {}
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{prefix}.{k}" if prefix else k, x)
+        elif isinstance(v, torch.Tensor):
+            flat[prefix] = v.detach().float().cpu().numpy()
+    walk("", out)
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in flat.values())
+    share = DUMP_LIMIT_BYTES // (2 * max(len(flat), 1))
+    for name, a in sorted(flat.items()):
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // 8, replace=False))
+            np.save(os.path.join(path, f"{name}.index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def physical_cores():
@@ -432,7 +472,10 @@ def main():
             return [model(batch, inference=True)]
         return pipes[n].submit(batch)
 
+    last_out = [None]  # the newest result in submission order: after the timed region's drain, its last step's outputs
+
     def on_result(out, gather):
+        last_out[0] = out
         if multi and gather:
             if pending:
                 pending.pop().wait()
@@ -544,6 +587,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out[0], args.dump_outputs)
     if trace is not None and rank == 0:
         print(f"closing sync: {(time.perf_counter() - t_sync) * 1e3:.2f} ms", file=sys.stderr)
         print("host ms per step():", " ".join(f"{t * 1e3:.2f}" for t in trace), file=sys.stderr)
@@ -553,7 +598,7 @@ def main():
     # step time, the bytes a rank contributes to the mel gather, and what the gather costs the step - the same K steps once more
     # WITHOUT the gather (forward only), same launch mode, same barrier + sync brackets; exposed = with - without
     dist_info = None
-    if multi:
+    if multi and args.full:
         cdev_i = dev if backend == "nccl" else torch.device("cpu")
         # alternating blocks (with / without the gather), medians: a single pass behind the timed region measured the clock
         # drift of a warm GPU rather than the gather (r04: "exposed" came out negative)
@@ -586,48 +631,49 @@ def main():
                     "with the asynchronous mel all-gather minus without it, medians of three alternating blocks of steps behind the timed region (the collective runs on the collective "
                     "library's stream underneath the next forward)"}
     model.engine.set_graphs(False)
-    # roofline pass: K eager steps with the events of the dominant launch class on; then the whole forward's kernel time from
-    # events around each step of a third pass (graphs again): ms_per_step against it says what the host adds
-    psteps = max(3, min(args.steps, 10))
-    model.engine.profile_reserve(kcls, psteps * (cfg.encoder_layers + cfg.decoder_layers) * 2 + 16)
-    model.engine.profile_enable(kcls, True)
-    for _ in range(psteps):
-        model(batch, inference=True)
-    torch.cuda.synchronize()
-    prof = model.engine.profile_read(kcls)
-    model.engine.profile_enable(kcls, False)
-    # the north star's attention figure (BASELINE.json: ">= 40 % of the bf16 MFMA roofline" on the attention GEMMs): the decoder
-    # stack's self-attention launches - the MFMA-bound instance (4 B T^2 H flops, AI = T / 2) - timed the same way, own pass
-    model.engine.profile_reserve(_lib.K_DEC_ATTENTION, psteps * cfg.decoder_layers + 16)
-    model.engine.profile_enable(_lib.K_DEC_ATTENTION, True)
-    for _ in range(psteps):
-        model(batch, inference=True)
-    torch.cuda.synchronize()
-    prof_att = model.engine.profile_read(_lib.K_DEC_ATTENTION)
-    model.engine.profile_enable(_lib.K_DEC_ATTENTION, False)
-    # the literal north-star instance: the ENCODER's self-attention block (in-projection + attention + out-projection + LayerNorm
-    # launches of ConformerEncoderLayer.forward, model.py:108-116) against SURVEY 8d's fused-MHA figure 8 B L H^2 + 4 B L^2 H
-    model.engine.profile_reserve(_lib.K_ENC_MHA, psteps * cfg.encoder_layers + 16)
-    model.engine.profile_enable(_lib.K_ENC_MHA, True)
-    for _ in range(psteps):
-        model(batch, inference=True)
-    torch.cuda.synchronize()
-    prof_mha = model.engine.profile_read(_lib.K_ENC_MHA)
-    model.engine.profile_enable(_lib.K_ENC_MHA, False)
-    # GPU time of one forward = the sum over every launch class (conv GEMMs, GEMMs, attention, row kernels) of the HIP-event
-    # intervals around its launches, in a pass of its own (eager; the dominant class is a subset of the conv / GEMM class)
-    all_cls = [_lib.K_CONV_GEMM, _lib.K_GEMM, _lib.K_ATTENTION, _lib.K_ROWOPS]
-    for k in all_cls:
-        model.engine.profile_reserve(k, psteps * 160 + 16)
-        model.engine.profile_enable(k, True)
-    for _ in range(psteps):
-        model(batch, inference=True)
-    torch.cuda.synchronize()
-    gpu_ms = 0.0
-    for k in all_cls:
-        gpu_ms += model.engine.profile_read(k)["ms"]
-        model.engine.profile_enable(k, False)
-    gpu_ms /= psteps
+    if args.full:
+        # roofline pass: K eager steps with the events of the dominant launch class on; then the whole forward's kernel time from
+        # events around each step of a third pass (graphs again): ms_per_step against it says what the host adds
+        psteps = max(3, min(args.steps, 10))
+        model.engine.profile_reserve(kcls, psteps * (cfg.encoder_layers + cfg.decoder_layers) * 2 + 16)
+        model.engine.profile_enable(kcls, True)
+        for _ in range(psteps):
+            model(batch, inference=True)
+        torch.cuda.synchronize()
+        prof = model.engine.profile_read(kcls)
+        model.engine.profile_enable(kcls, False)
+        # the north star's attention figure (BASELINE.json: ">= 40 % of the bf16 MFMA roofline" on the attention GEMMs): the decoder
+        # stack's self-attention launches - the MFMA-bound instance (4 B T^2 H flops, AI = T / 2) - timed the same way, own pass
+        model.engine.profile_reserve(_lib.K_DEC_ATTENTION, psteps * cfg.decoder_layers + 16)
+        model.engine.profile_enable(_lib.K_DEC_ATTENTION, True)
+        for _ in range(psteps):
+            model(batch, inference=True)
+        torch.cuda.synchronize()
+        prof_att = model.engine.profile_read(_lib.K_DEC_ATTENTION)
+        model.engine.profile_enable(_lib.K_DEC_ATTENTION, False)
+        # the literal north-star instance: the ENCODER's self-attention block (in-projection + attention + out-projection + LayerNorm
+        # launches of ConformerEncoderLayer.forward, model.py:108-116) against SURVEY 8d's fused-MHA figure 8 B L H^2 + 4 B L^2 H
+        model.engine.profile_reserve(_lib.K_ENC_MHA, psteps * cfg.encoder_layers + 16)
+        model.engine.profile_enable(_lib.K_ENC_MHA, True)
+        for _ in range(psteps):
+            model(batch, inference=True)
+        torch.cuda.synchronize()
+        prof_mha = model.engine.profile_read(_lib.K_ENC_MHA)
+        model.engine.profile_enable(_lib.K_ENC_MHA, False)
+        # GPU time of one forward = the sum over every launch class (conv GEMMs, GEMMs, attention, row kernels) of the HIP-event
+        # intervals around its launches, in a pass of its own (eager; the dominant class is a subset of the conv / GEMM class)
+        all_cls = [_lib.K_CONV_GEMM, _lib.K_GEMM, _lib.K_ATTENTION, _lib.K_ROWOPS]
+        for k in all_cls:
+            model.engine.profile_reserve(k, psteps * 160 + 16)
+            model.engine.profile_enable(k, True)
+        for _ in range(psteps):
+            model(batch, inference=True)
+        torch.cuda.synchronize()
+        gpu_ms = 0.0
+        for k in all_cls:
+            gpu_ms += model.engine.profile_read(k)["ms"]
+            model.engine.profile_enable(k, False)
+        gpu_ms /= psteps
 
     cdev = dev if backend == "nccl" else torch.device("cpu")
     t_max = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -641,28 +687,29 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = total_frames * args.steps / elapsed
-        n = max(prof["launches"], 1)
-        avg_s = prof["ms"] / n * 1e-3
-        achieved = (prof["flops"] / n) / avg_s if avg_s > 0 else 0.0
-        peak = MFMA_PEAK["fp32" if args.precision == "fp32" else "bf16"]
-        traffic, traffic_src = None, None
-        if os.path.exists(TRAFFIC_FILE) and args.config == "c2" and args.precision == "bf16" and args.batch == 32:
-            try:
-                tj = json.load(open(TRAFFIC_FILE))
-                traffic = tj.get("conv_gemm_hbm_bytes_per_launch")
-                import hashlib
-                here = hashlib.sha256(open(os.path.join(ROOT, "lightningfastspeech2_amd", "csrc", "gemm_mfma.hip"), "rb").read()).hexdigest()[:16]
-                sha_matches = tj.get("kernel_source_sha256") == here
-                traffic_src = (f"profiles/{os.path.basename(TRAFFIC_FILE)}: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + --pmc WRITE_SIZE, "
-                               "separate passes over this launch shape (tools/pmc_traffic.sh); kernel source at commit "
-                               f"{tj.get('kernel_commit', '?')} (git log -1 -- csrc/gemm_mfma.hip), measured at {tj.get('measured_at_commit', '?')}; "
-                               f"sha256 of the measured csrc/gemm_mfma.hip {tj.get('kernel_source_sha256', '?')} "
-                               + ("== this checkout's" if sha_matches else f"!= this checkout's {here}: the kernel source changed since the counters were read"))
-            except Exception:
-                traffic = None
-        na = max(prof_att["launches"], 1)
-        att_s = prof_att["ms"] / na * 1e-3
-        att_tf = (prof_att["flops"] / na) / att_s / 1e12 if att_s > 0 else 0.0
+        if args.full:
+            n = max(prof["launches"], 1)
+            avg_s = prof["ms"] / n * 1e-3
+            achieved = (prof["flops"] / n) / avg_s if avg_s > 0 else 0.0
+            peak = MFMA_PEAK["fp32" if args.precision == "fp32" else "bf16"]
+            traffic, traffic_src = None, None
+            if os.path.exists(TRAFFIC_FILE) and args.config == "c2" and args.precision == "bf16" and args.batch == 32:
+                try:
+                    tj = json.load(open(TRAFFIC_FILE))
+                    traffic = tj.get("conv_gemm_hbm_bytes_per_launch")
+                    import hashlib
+                    here = hashlib.sha256(open(os.path.join(ROOT, "lightningfastspeech2_amd", "csrc", "gemm_mfma.hip"), "rb").read()).hexdigest()[:16]
+                    sha_matches = tj.get("kernel_source_sha256") == here
+                    traffic_src = (f"profiles/{os.path.basename(TRAFFIC_FILE)}: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + --pmc WRITE_SIZE, "
+                                   "separate passes over this launch shape (tools/pmc_traffic.sh); kernel source at commit "
+                                   f"{tj.get('kernel_commit', '?')} (git log -1 -- csrc/gemm_mfma.hip), measured at {tj.get('measured_at_commit', '?')}; "
+                                   f"sha256 of the measured csrc/gemm_mfma.hip {tj.get('kernel_source_sha256', '?')} "
+                                   + ("== this checkout's" if sha_matches else f"!= this checkout's {here}: the kernel source changed since the counters were read"))
+                except Exception:
+                    traffic = None
+            na = max(prof_att["launches"], 1)
+            att_s = prof_att["ms"] / na * 1e-3
+            att_tf = (prof_att["flops"] / na) / att_s / 1e12 if att_s > 0 else 0.0
         line = {
             "metric": "mel-frames/sec (whole node), 256-phoneme batch-32",
             "value": value, "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -679,49 +726,51 @@ def main():
                        "frames_per_utterance": T, "global_batch": args.batch * world,
                        "parallelism": f"dp{world} (utterance shards, RCCL all-gather of mels only)" if multi else "single GPU",
                        "params": cfg.param_count()},
-            # which roof bounds the dominant launch: its algorithmic intensity (FLOPs / algorithmic bytes, both accounted by the engine)
-            # against the machine balance 2.5 PF / 8 TB/s = 312 FLOP/B.  The dense conv (1.8 kFLOP/B) and the K = 768 pointwise GEMM
-            # (607) are MFMA-bound; the K = 256 pointwise GEMM of the reference-default model (204: 25 MB in, 101 MB out) is HBM-bound
-            "roofline": (lambda ai, bpl: {
-                         **({"bound": "mfma", "achieved": achieved / 1e12, "peak": peak / 1e12, "unit": "TFLOP/s", "frac": achieved / peak}
-                            if ai >= peak / HBM_PEAK else
-                            {"bound": "hbm", "achieved": bpl / avg_s / 1e9 if avg_s > 0 else 0.0, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                             "frac": bpl / avg_s / HBM_PEAK if avg_s > 0 else 0.0, "mfma_frac": achieved / peak}),
-                         "algorithmic_intensity_flop_per_byte": ai, "bytes_per_launch": bpl,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": ("gemm_conv_slab_kernel: decoder FFN conv1, implicit-GEMM Conv1d "
-                                    f"M={args.batch * T} N={cfg.decoder_conv_filter_size} K={cfg.decoder_kernel_sizes[0]}x{cfg.hidden}")
-                         if not cfg.decoder_depthwise_conv else
-                         (f"{'gemm_persist_kernel' if cfg.hidden > 256 else 'gemm_wres_kernel'}: decoder FFN pointwise conv1.1 (behind the depth-wise conv) "
-                          f"M={args.batch * T} N={cfg.decoder_conv_filter_size} K={cfg.hidden}")})(
-                             prof["flops"] / max(prof["bytes"], 1.0), prof["bytes"] / n) | {
-                         "launches_timed": prof["launches"], "avg_launch_us": avg_s * 1e6,
-                         "flops_per_launch": prof["flops"] / n,
-                         "measured": f"HIP events on the launch stream around every launch of this class in {psteps} eager steps of the same "
-                                     "workload right behind the timed region (the timed steps replay hipGraphs, which hold no event records)"},
-            "north_star_attention": {
-                "kernel": f"decoder self-attention (QK^T, softmax, PV fused): {args.batch * cfg.decoder_head} x {T} queries x {T} keys, head dim "
-                          f"{cfg.hidden // cfg.decoder_head}; attention_pipe_kernel where it applies (bf16, head dim 128)",
-                "achieved": att_tf, "peak": peak / 1e12, "unit": "TFLOP/s", "frac": att_tf * 1e12 / peak,
-                "avg_launch_us": att_s * 1e6, "launches_timed": prof_att["launches"], "flops_per_launch": prof_att["flops"] / na,
-                "what": "BASELINE.json north_star: >= 40 % of the bf16 MFMA roofline on the attention GEMMs; the encoder's instance "
-                        "(256 keys) is ingest-bound (profiles/HISTORY.md §4), this is the MFMA-bound one; HIP events, own pass of eager steps"},
-            "encoder_mha_block": (lambda n_, s_: {
-                "kernel": "encoder self-attention block = two launches per layer (r06): in-projection GEMM; attn_out_ln_kernel = self-attention of both "
-                          "heads + out-projection + residual + LayerNorm (three launches where that kernel does not apply: H != 256, fp32, knob 1340)",
-                "achieved": (prof_mha["flops"] / n_) / s_ / 1e12 if s_ > 0 else 0.0, "peak": peak / 1e12, "unit": "TFLOP/s",
-                "frac": (prof_mha["flops"] / n_) / s_ / peak if s_ > 0 else 0.0, "avg_block_us": s_ * 1e6, "blocks_timed": prof_mha["launches"],
-                "flops_per_block": prof_mha["flops"] / n_,
-                "ingest_roofline": encoder_mha_ingest_bound(cfg, args.batch, args.phones, s_,
-                                                            fused_tail=args.precision == "bf16" and cfg.hidden == 256 and cfg.encoder_head == 2
-                                                            and 1340 not in [k["knob"] for k in applied_knobs]),
-                "what": "BASELINE.json north_star names the encoder attention; SURVEY 8d: only the fused block (8 B L H^2 + 4 B L^2 H, AI ~ 724) can "
-                        "be MFMA-bound.  Two of its three launches are fused (r06, DESIGN.md §4.3): at B x L = 8192 rows the block is neither MFMA- nor "
-                        "HBM-bound - `ingest_roofline` prices it against what bounds launches of this size, the bytes each CU pulls through "
-                        "L2 -> LDS at the measured per-CU ceiling; `frac` against the MFMA peak is kept for the record; HIP events around the "
-                        "block, one forward at a time"})(max(prof_mha["launches"], 1), prof_mha["ms"] / max(prof_mha["launches"], 1) * 1e-3),
-            "gpu_ms_per_step": gpu_ms,
-            "gpu_ms_per_step_is": f"sum of HIP-event intervals around every kernel launch of a forward, {psteps} eager steps behind the timed region",
+            **({
+                # which roof bounds the dominant launch: its algorithmic intensity (FLOPs / algorithmic bytes, both accounted by the engine)
+                # against the machine balance 2.5 PF / 8 TB/s = 312 FLOP/B.  The dense conv (1.8 kFLOP/B) and the K = 768 pointwise GEMM
+                # (607) are MFMA-bound; the K = 256 pointwise GEMM of the reference-default model (204: 25 MB in, 101 MB out) is HBM-bound
+                "roofline": (lambda ai, bpl: {
+                             **({"bound": "mfma", "achieved": achieved / 1e12, "peak": peak / 1e12, "unit": "TFLOP/s", "frac": achieved / peak}
+                                if ai >= peak / HBM_PEAK else
+                                {"bound": "hbm", "achieved": bpl / avg_s / 1e9 if avg_s > 0 else 0.0, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                                 "frac": bpl / avg_s / HBM_PEAK if avg_s > 0 else 0.0, "mfma_frac": achieved / peak}),
+                             "algorithmic_intensity_flop_per_byte": ai, "bytes_per_launch": bpl,
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel": ("gemm_conv_slab_kernel: decoder FFN conv1, implicit-GEMM Conv1d "
+                                        f"M={args.batch * T} N={cfg.decoder_conv_filter_size} K={cfg.decoder_kernel_sizes[0]}x{cfg.hidden}")
+                             if not cfg.decoder_depthwise_conv else
+                             (f"{'gemm_persist_kernel' if cfg.hidden > 256 else 'gemm_wres_kernel'}: decoder FFN pointwise conv1.1 (behind the depth-wise conv) "
+                              f"M={args.batch * T} N={cfg.decoder_conv_filter_size} K={cfg.hidden}")})(
+                                 prof["flops"] / max(prof["bytes"], 1.0), prof["bytes"] / n) | {
+                             "launches_timed": prof["launches"], "avg_launch_us": avg_s * 1e6,
+                             "flops_per_launch": prof["flops"] / n,
+                             "measured": f"HIP events on the launch stream around every launch of this class in {psteps} eager steps of the same "
+                                         "workload right behind the timed region (the timed steps replay hipGraphs, which hold no event records)"},
+                "north_star_attention": {
+                    "kernel": f"decoder self-attention (QK^T, softmax, PV fused): {args.batch * cfg.decoder_head} x {T} queries x {T} keys, head dim "
+                              f"{cfg.hidden // cfg.decoder_head}; attention_pipe_kernel where it applies (bf16, head dim 128)",
+                    "achieved": att_tf, "peak": peak / 1e12, "unit": "TFLOP/s", "frac": att_tf * 1e12 / peak,
+                    "avg_launch_us": att_s * 1e6, "launches_timed": prof_att["launches"], "flops_per_launch": prof_att["flops"] / na,
+                    "what": "BASELINE.json north_star: >= 40 % of the bf16 MFMA roofline on the attention GEMMs; the encoder's instance "
+                            "(256 keys) is ingest-bound (profiles/HISTORY.md §4), this is the MFMA-bound one; HIP events, own pass of eager steps"},
+                "encoder_mha_block": (lambda n_, s_: {
+                    "kernel": "encoder self-attention block = two launches per layer (r06): in-projection GEMM; attn_out_ln_kernel = self-attention of both "
+                              "heads + out-projection + residual + LayerNorm (three launches where that kernel does not apply: H != 256, fp32, knob 1340)",
+                    "achieved": (prof_mha["flops"] / n_) / s_ / 1e12 if s_ > 0 else 0.0, "peak": peak / 1e12, "unit": "TFLOP/s",
+                    "frac": (prof_mha["flops"] / n_) / s_ / peak if s_ > 0 else 0.0, "avg_block_us": s_ * 1e6, "blocks_timed": prof_mha["launches"],
+                    "flops_per_block": prof_mha["flops"] / n_,
+                    "ingest_roofline": encoder_mha_ingest_bound(cfg, args.batch, args.phones, s_,
+                                                                fused_tail=args.precision == "bf16" and cfg.hidden == 256 and cfg.encoder_head == 2
+                                                                and 1340 not in [k["knob"] for k in applied_knobs]),
+                    "what": "BASELINE.json north_star names the encoder attention; SURVEY 8d: only the fused block (8 B L H^2 + 4 B L^2 H, AI ~ 724) can "
+                            "be MFMA-bound.  Two of its three launches are fused (r06, DESIGN.md §4.3): at B x L = 8192 rows the block is neither MFMA- nor "
+                            "HBM-bound - `ingest_roofline` prices it against what bounds launches of this size, the bytes each CU pulls through "
+                            "L2 -> LDS at the measured per-CU ceiling; `frac` against the MFMA peak is kept for the record; HIP events around the "
+                            "block, one forward at a time"})(max(prof_mha["launches"], 1), prof_mha["ms"] / max(prof_mha["launches"], 1) * 1e-3),
+                "gpu_ms_per_step": gpu_ms,
+                "gpu_ms_per_step_is": f"sum of HIP-event intervals around every kernel launch of a forward, {psteps} eager steps behind the timed region",
+            } if args.full else {}),
             "in_flight": n_pick,
             "ms_per_step_one_in_flight": min((v for k, v in tune.items() if k.endswith("/1")), default=None),
             "in_flight_is": "forwards in flight in the timed region (lightningfastspeech2_amd.model.ForwardPipeline: one engine replica, HIP "
@@ -738,7 +787,7 @@ def main():
             line["dist"] = dist_info
         if applied_knobs:
             line["knobs_applied"] = applied_knobs  # FS2_GEMM_KNOBS / FS2_XCD_REMAP: an A/B line says which switches it ran under
-        if not multi:
+        if not multi and args.full:
             # the boundary takes device pointers; a host caller also pays H2D of phones + speaker and D2H of the
             # fp32 mels + mask per batch (SURVEY 8d's metric definition): timed separately, never `value`
             hp = torch.from_numpy(inp["phones"]).pin_memory()
@@ -808,17 +857,17 @@ def main():
                                                f"{hmel.numel() * 4 / 1e6:.1f} MB D2H); in_flight > 1: the device-to-host copy of batch i on a "
                                                "copy stream under batch i + 1's forward; timed until the last host copy has landed; each leg = the fastest of "
                                                "three repeats of its loop (repeats_ms_per_step)"}
-        if not multi and not args.no_parity:
+        if args.full and not multi and not args.no_parity:
             try:
                 line["parity"] = parity_block(cfg, sd, args, dev, model)
             except Exception as ex:  # never lose the timed line to the checker
                 line["parity"] = {"error": repr(ex)}
-        if not multi and not args.no_train and args.precision in ("bf16", "fp32"):
+        if args.full and not multi and not args.no_train and args.precision in ("bf16", "fp32"):
             try:  # side measurement, never `value`: the same workload through the training step
                 line["training_step"] = training_block(cfg, sd, args, inp, T)
             except Exception as ex:
                 line["training_step"] = {"error": repr(ex)}
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, sd, args)
         print(json.dumps(line), flush=True)
     for pp in pipes.values():

@@ -1,6 +1,7 @@
 """Lightning-style checkpoints: a pickle written by torch.save of the dict Lightning writes - hyper_parameters
 as pytorch_lightning's AttributeDict, state_dict of tensors, the on_save_checkpoint extras (fastspeech2.py:622-634) - read
 back without Lightning installed, the class-default CWT pitch transform included, strict and tolerant loads."""
+import json
 import os
 import sys
 import types
@@ -131,45 +132,30 @@ def test_opaque_lightning_objects_do_not_break_the_load(tmp_path):
     del pickle
 
 
-def _reference_order_or_skip(cfg):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import ref_import
-    if not ref_import.reference_available():
-        pytest.skip("reference checkout absent")
-    m, _ = ref_import.load_reference()
-    return m
+def _order_cfg():
+    return _cfg(priors=["energy", "duration"], encoder_depthwise_conv=True, decoder_depthwise_conv=False,
+                stats={"pitch": {"min": 60.0, "max": 400.0, "mean": 180.0, "std": 40.0},
+                       "energy": {"min": -3.0, "max": 3.0, "mean": 0.0, "std": 1.0}, "snr": {"min": -1.0, "max": 4.0, "mean": 1.2, "std": 2.0},
+                       "energy_prior": {"min": -1.0, "max": 1.0, "mean": 0.0, "std": 1.0},
+                       "duration_prior": {"min": 0.0, "max": 9.0, "mean": 3.0, "std": 1.0}})
 
 
 def test_parameter_order_follows_the_reference_modules():
     """optimizer.state_dict() numbers parameters in FastSpeech2.parameters() order: module registration order of
     fastspeech2.py:242-438 (phone_embedding, encoder, variance_adaptor, decoder, linear, prior_embeddings, speaker_embedding),
-    in-module order = the real modules' named_parameters()."""
-    cfg = _cfg(priors=["energy", "duration"], encoder_depthwise_conv=True, decoder_depthwise_conv=False,
-               stats={"pitch": {"min": 60.0, "max": 400.0, "mean": 180.0, "std": 40.0},
-                      "energy": {"min": -3.0, "max": 3.0, "mean": 0.0, "std": 1.0}, "snr": {"min": -1.0, "max": 4.0, "mean": 1.2, "std": 2.0},
-                      "energy_prior": {"min": -1.0, "max": 1.0, "mean": 0.0, "std": 1.0},
-                      "duration_prior": {"min": 0.0, "max": 9.0, "mean": 3.0, "std": 1.0}})
+    in-module order = the real modules' named_parameters() (tests/golden/reference_param_order.json, tools/gen_golden_random.py)."""
+    cfg = _order_cfg()
     order = ck.parameter_order(cfg)
     tops = [n.split(".")[0] for n in order]
     firsts = [t for i, t in enumerate(tops) if i == 0 or tops[i - 1] != t]
     assert firsts == ["phone_embedding", "encoder", "variance_adaptor", "decoder", "linear", "prior_embeddings", "speaker_embedding"]
     assert "positional_encoding.pe" not in order and "variance_adaptor.encoders.pitch.bins" in order  # bins are frozen Parameters
-    m = _reference_order_or_skip(cfg)
-    nv = len(cfg.variances)
-    va = m.VarianceAdaptor(cfg.stats, list(cfg.variances), list(cfg.variance_levels[:nv]), list(cfg.variance_transforms[:nv]),
-                           list(cfg.variance_nlayers[:nv]), list(cfg.variance_kernel_size[:nv]), [0.5] * nv, cfg.variance_filter_size,
-                           cfg.variance_nbins, cfg.variance_depthwise_conv, cfg.duration_nlayers, False, cfg.duration_kernel_size, 0.5,
-                           cfg.duration_filter_size, cfg.duration_depthwise_conv, cfg.hidden, 2756.25)
-    assert [n for n in order if n.startswith("variance_adaptor.")] == ["variance_adaptor." + n for n, _ in va.named_parameters()]
-    for side, heads, F, k, dw in (("encoder", cfg.encoder_head, cfg.encoder_conv_filter_size, cfg.encoder_kernel_sizes[0], True),
-                                  ("decoder", cfg.decoder_head, cfg.decoder_conv_filter_size, cfg.decoder_kernel_sizes[0], False)):
-        layer = m.ConformerEncoderLayer(cfg.hidden, heads, conv_in=cfg.hidden, conv_filter_size=F, conv_kernel=(k, 1), batch_first=True,
-                                        dropout=0.1, conv_depthwise=dw)
-        assert [n for n in order if n.startswith(f"{side}.layers.0.")] == [f"{side}.layers.0." + n for n, _ in layer.named_parameters()]
-    pe = m.PriorEmbedding(cfg.hidden, cfg.variance_nbins, cfg.stats["energy_prior"])
-    assert [n for n in order if n.startswith("prior_embeddings.energy.")] == ["prior_embeddings.energy." + n for n, _ in pe.named_parameters()]
-    se = m.SpeakerEmbedding(cfg.hidden, "dvector")
-    assert [n for n in order if n.startswith("speaker_embedding.")] == ["speaker_embedding." + n for n, _ in se.named_parameters()]
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_param_order.json")) as f:
+        ref = json.load(f)
+    assert ref.pop("config_json") == cfg.to_json(), "config drifted from the fixture"
+    assert set(ref) == {"variance_adaptor", "encoder.layers.0", "decoder.layers.0", "prior_embeddings.energy", "speaker_embedding"}
+    for prefix, names in ref.items():
+        assert [n for n in order if n.startswith(prefix + ".")] == [f"{prefix}.{n}" for n in names], prefix
 
 
 def test_optimizer_state_round_trips_through_lightning_layout():

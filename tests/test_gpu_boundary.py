@@ -331,7 +331,7 @@ def test_bench_under_torchrun_over_rccl_one_rank():
     env = dict(os.environ, FS2_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--config", "ref-default", "--batch", "4", "--phones", "32"]
+           "--config", "ref-default", "--batch", "4", "--phones", "32", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -355,7 +355,8 @@ def test_forced_dist_line_agrees_with_the_plain_line():
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
         if force:
             env["FS2_BENCH_FORCE_DIST"] = "1"
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "3", "--no-cpu-baseline", "--no-parity", "--no-train"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-parity",
+               "--no-train"]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -365,3 +366,31 @@ def test_forced_dist_line_agrees_with_the_plain_line():
     # (7 %: the gather's ~4 % plus what two processes on one box differ by; the test failed once at 5 % and passed on the next box)
     assert abs(b - a) <= 0.07 * a, (a, b, forced[0]["dist"])
     assert min(l["dist"]["gather_ms_exposed"] for l in forced) <= 0.07 * a
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run times exactly --steps steps and prints the headline line without the --full side measurements;
+    --dump-outputs writes the last timed step's outputs as float32 .npy files, the same ones on a second run with the same
+    arguments (seeded inputs, a forward without atomics)."""
+    def run(d):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--config", "ref-default",
+               "--batch", "4", "--phones", "32", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    line = run(tmp_path / "a")
+    T = 32 * 6
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["config"]["frames_per_utterance"] == T
+    assert line["unit"] == "mel-frames/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 4 * T) <= 1e-6 * 4 * T   # value = frames per step / one step's time
+    for k in ("roofline", "north_star_attention", "encoder_mha_block", "gpu_ms_per_step", "value_incl_pcie", "parity", "training_step",
+              "cpu_baseline", "dist"):
+        assert k not in line, k
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert {"mel", "tgt_mask", "src_mask", "duration_rounded", "duration_prediction"} <= set(a)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["mel"].shape == (4, T, 80) and np.isfinite(a["mel"]).all() and float(np.abs(a["mel"]).max()) > 0
+    assert not a["tgt_mask"].any() and (a["duration_rounded"] == 6).all()
+    run(tmp_path / "b")
+    for k, v in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), v), k

@@ -17,7 +17,7 @@ for cfg in c2 c3 c5; do
   for N in 1 2 4 8; do
     if [ $N -gt $NG ]; then echo "skip $cfg N=$N: $NG GPU(s) visible" >&2; continue; fi
     PORT=$((PORT + 1))
-    EXTRA="--config $cfg --batch $B --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-train"
+    EXTRA="--full --config $cfg --batch $B --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-train"
     if [ $N -eq 1 ]; then  # the plain single-GPU line AND the forced multi-rank path at world size 1 (must agree within noise)
       python $R/bench.py --gpus 1 $EXTRA > $O/${TAG}_scale_${cfg}_n1.json 2> $O/${TAG}_scale_${cfg}_n1.err
       FS2_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $PORT \
