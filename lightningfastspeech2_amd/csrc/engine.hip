@@ -1053,7 +1053,8 @@ size_t persist_bytes(const fs2_engine* e, int B, int L) {
         if (e->cfg.var_level[v]) pv += al(ML * 4) + (e->cfg.var_cwt[v] ? al(ML * 10 * 4) + al((size_t)B * 8) : 0);
     return al((size_t)B * H * 4) + 2 * al(ML * H * esz) + al(ML * 4) + 2 * al(ML * 4) + 2 * al((size_t)B * 4) + al(ML) + pv + 4096;
 }
-// scratch of the encode phase: the encoder's layer scratch + the CWT head's (M, 12) spectrogram of a phone-level CWT variance
+// scratch of the encode phase: the encoder's layer scratch + the CWT head's (M, 12) spectrogram, one buffer that every phone-level
+// CWT variance reuses (encode_body)
 size_t encode_scratch_bytes(const fs2_engine* e, int B, int L) {
     size_t cw = 0;
     for (int v = 0; v < e->cfg.n_variances; ++v)
@@ -1479,18 +1480,25 @@ static int encode_body(fs2_engine* e, const int64_t* phones, const float* speake
     CHK(predictor(e, st, e->dur, e->xA, B, L, e->src_mask, e->dur_pred, sc));
     // phone-level variance encoders (variance_levels[i] == "phone"), in list order, AFTER the duration predictor has seen x and BEFORE
     // the length regulator: each adds its embedding to the rows that get regulated                      model.py:276-294
+    // The rows ping-pong between xA and xB through local pointers (variance_stage swaps them where the embedding rode in the predictor
+    // launch) and end in xA, where decode regulates them from: a replayed graph does not run this body (run_phase).
+    void* x = e->xA;
+    void* xalt = e->xB;
+    float* spec12 = nullptr;  // the CWT head's (M, 12) spectrogram: one buffer, reused by every phone-level CWT variance
     for (int v = 0; v < c.n_variances; ++v) {
         if (!c.var_level[v]) continue;
         CwtOut cwo;
         if (c.var_cwt[v]) {
-            cwo.spec12 = (float*)e->scratch.take(ML * 12 * 4);
-            if (!cwo.spec12) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
+            if (!spec12) spec12 = (float*)e->scratch.take(ML * 12 * 4);
+            if (!spec12) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
+            cwo.spec12 = spec12;
             cwo.mean_std = e->pv_ms[v];
             cwo.spec_out = e->pv_spec[v];
         }
-        CHK(variance_stage(e, st, v, e->xA, e->xB, B, L, e->src_mask, e->pv_pred[v], sc, c.var_cwt[v] ? &cwo : nullptr, false, e->dbg_enc));
+        CHK(variance_stage(e, st, v, x, xalt, B, L, e->src_mask, e->pv_pred[v], sc, c.var_cwt[v] ? &cwo : nullptr, false, e->dbg_enc));
         e->forced_idx[v] = nullptr, e->forced_tgt[v] = nullptr;  // one-shot, consumed here
     }
+    if (x != e->xA) HIPCHK(e, hipMemcpyAsync(e->xA, x, ML * H * esz, hipMemcpyDeviceToDevice, st));  // an odd number of swaps
     DurationArgs da{e->dur_pred, e->src_mask, forced, e->d_dur, e->d_cum, e->d_totals, e->d_guard, B, L};
     if (launch_durations(da, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "durations launch failed");
     HIPCHK(e, hipMemcpyAsync(e->h_pinned, e->d_totals, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st));
@@ -1620,6 +1628,9 @@ static void drop_graphs(fs2_engine* e) {
 // then on one hipGraphLaunch.  The caller's stream (the legacy null stream included, which cannot be captured itself) is ordered
 // around it with two events.  Anything a capture cannot hold (debug taps, per-class profiling events, one-shot forced buckets or
 // priors) takes the plain path.
+// Rule for a body: a replay runs its launches, not its host code.  So nothing that fs2_decode or the next fs2_encode reads may be
+// host state that the body changes (an engine pointer swapped, a buffer chosen by parity): such a change happens at capture only
+// and is missing on every replay.  Ping-pong choices live in the body's locals.
 static int run_phase(fs2_engine* e, std::vector<fs2_engine::GraphEntry>& cache, const std::vector<uint64_t>& key, bool plain,
                      hipStream_t st, const std::function<int(hipStream_t)>& body) {
     static const bool gdbg = getenv("FS2_GRAPH_DEBUG") != nullptr;
