@@ -572,6 +572,12 @@ int fs2_op_adamw_shadow(float* p, const float* g, float* m, float* v, void* shad
 int fs2_op_bucket_embed_target(int32_t dtype, const void* x, const float* target, const float* bins, const float* emb,
                                int32_t nbins, float std, float mean, const float* pe, const float* spk, void* y,
                                int32_t* idx_out, int32_t B, int32_t T, int32_t H, void* hip_stream);
+/* the CWT pitch head on its own (VarianceEncoder.forward's CWT branch behind the predictor, model.py:412-431 + cwt.py:18-21,49-50; for
+ * the operator tests): out_conv (B*T, F) rows of the last predictor layer in `dtype`, spec (B*T, ld_spec >= 10) fp32 head rows whose
+ * first 10 columns are the scales, mask (B*T) 1 = pad or null -> mean_std (B, 2), pred (B, T), spec_out (B, T, 10) or null */
+int fs2_op_cwt_head(int32_t dtype, const void* out_conv, const float* spec, int32_t ld_spec, const uint8_t* mask,
+                    const float* ms_w, const float* ms_b, float* mean_std, float* pred, float* spec_out, int32_t B, int32_t T,
+                    int32_t F, void* hip_stream);
 
 /* ================================================================================================
  * HiFi-GAN generator: the step right after the mel forward.  Replaces

@@ -224,6 +224,7 @@ def load():
     lib.fs2_op_transpose_weight_tiles.argtypes = [i32, i32, i32]
     lib.fs2_op_transpose_weight_batch.argtypes = [vp, i32, C.c_int64, vp]
     lib.fs2_op_bucket_embed_target.argtypes = [i32, vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.fs2_op_cwt_head.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     if lib.fs2_abi_version() != FS2_ABI_VERSION:
         raise Fs2LibraryError("libfs2_hip.so ABI version mismatch")
     _lib = lib

@@ -623,5 +623,12 @@ int fs2_op_bucket_embed_target(int32_t dtype, const void* x, const float* target
     a.bucket_src = target;
     return launch_bucket_embed(a, dtype, (hipStream_t)stream);
 }
+int fs2_op_cwt_head(int32_t dtype, const void* out_conv, const float* spec, int32_t ld_spec, const uint8_t* mask,
+                    const float* ms_w, const float* ms_b, float* mean_std, float* pred, float* spec_out, int32_t B, int32_t T,
+                    int32_t F, void* stream) {
+    if (ld_spec < 10 || F <= 0) return FS2_ERR_SHAPE;
+    CwtArgs a{out_conv, spec, ld_spec, mask, ms_w, ms_b, mean_std, pred, spec_out, B, T, F};
+    return launch_cwt_head(a, dtype, (hipStream_t)stream);
+}
 
 }  // extern "C"

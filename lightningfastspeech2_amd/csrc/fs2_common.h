@@ -151,6 +151,14 @@ __device__ inline float row16_max(float v) {
     return v;
 }
 __device__ inline float wave_sum(float v) { return group4_sum(row16_sum(v)); }
+// a * b + c as the reference's two tensor ops: the product rounded to fp32, then the sum.  __fmul_rn / __fadd_rn are plain * and +
+// to the compiler, which contracts them into one FMA (a single rounding) under hipcc's default -ffp-contract=fast: a value within an
+// ulp of a bin edge then lands in the neighbouring bucket.  The pragma keeps the two roundings.
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float m = a * b;
+    return m + c;
+}
 __device__ inline float wave_max(float v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     v = row16_max(v);

@@ -573,11 +573,12 @@ __global__ __launch_bounds__(NWV * 64, MINW) void predictor_fused_kernel(Predict
                 const int row = base + j, t = t0 + row;
                 okr[j] = row < R - halo && t < S;
                 const int rc = okr[j] ? row : halo, tc = okr[j] ? t : t0 + halo;
-                const float v = __fadd_rn(__fmul_rn(red[1][rc], p.be_std), p.be_mean);
+                const float v = mul_then_add(red[1][rc], p.be_std, p.be_mean);
                 int lo = 0;
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
                     if (k < nb) lo += __popcll(__ballot(bl[k] < v));
+                if (v != v) lo = nedge;  // NaN -> the last bucket, as torch.bucketize (and the stand-alone launch)
                 xv[j] = *(const XV*)(xg + (size_t)tc * PF_H);
                 ev[j] = *(const float4*)(p.be_emb + (size_t)lo * PF_H + lane_t * 4);
                 if (p.be_pe) pv[j] = *(const float4*)(p.be_pe + (size_t)tc * PF_H + lane_t * 4);

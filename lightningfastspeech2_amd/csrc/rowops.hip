@@ -643,7 +643,7 @@ int launch_regulate(const RegulateArgs& a, int dtype, hipStream_t stream) {
 // Variance embedding add (VarianceEncoder.forward inference branch, model.py:434-438, and the
 // adaptor's x = x + emb, model.py:333):  idx = bucketize(pred*std + mean, bins) (right=False);
 // y = x + Emb[idx]; optionally the decoder-side  y = (y + pe[t]) + spk[b]  (fastspeech2.py:705-718)
-// fused behind it.  The compare is fp32 mul-then-add (no FMA) like the reference's tensor ops.
+// fused behind it.  The compare is fp32 mul-then-add (mul_then_add: no FMA) like the reference's tensor ops.
 // =============================================================================================
 // One wave per BE_ROWS consecutive rows.  bucketize = lower_bound over the sorted bin edges = the NUMBER
 // of edges < v: the wave holds the edges in registers (BE_MAXB per lane, loaded once) and counts with
@@ -673,7 +673,7 @@ __global__ __launch_bounds__(256) void bucket_embed_kernel(BucketArgs p) {
         const float* e = nullptr;
         if (p.pred) {
             const float src = p.bucket_src ? p.bucket_src[row] : p.pred[p.pred_per_utt ? b : row];
-            const float v = __fadd_rn(__fmul_rn(src, p.std), p.mean);
+            const float v = mul_then_add(src, p.std, p.mean);
             int lo = 0;
             if (fast) {
 #pragma unroll
@@ -686,6 +686,7 @@ __global__ __launch_bounds__(256) void bucket_embed_kernel(BucketArgs p) {
                     if (p.bins[mid] < v) lo = mid + 1; else hi = mid;
                 }
             }
+            if (v != v) lo = nedge;  // NaN: torch.bucketize counts !(edge >= v), every edge -> the last bucket
             if (p.forced_idx) {
                 lo = p.forced_idx[row];
                 lo = lo < 0 ? 0 : (lo >= p.nbins ? p.nbins - 1 : lo);
@@ -821,7 +822,7 @@ __global__ __launch_bounds__(256) void cwt_recompose_kernel(CwtArgs p) {
     for (int t = tid; t < p.T; t += 256) { const float d = pr[t] - m; q = fmaf(d, d, q); }
     const float sd = sqrtf(block_sum_256(q, sh) / (float)(p.T - 1));  // torch.std: unbiased (T = 1 -> NaN, as the reference)
     const float mean_b = p.mean_std[2 * b], std_b = p.mean_std[2 * b + 1];
-    for (int t = tid; t < p.T; t += 256) pr[t] = __fadd_rn(__fmul_rn((pr[t] - m) / (sd + 1e-7f), std_b), mean_b);
+    for (int t = tid; t < p.T; t += 256) pr[t] = mul_then_add((pr[t] - m) / (sd + 1e-7f), std_b, mean_b);
 }
 
 int launch_cwt_head(const CwtArgs& a, int dtype, hipStream_t stream) {

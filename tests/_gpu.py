@@ -312,3 +312,118 @@ def spk_proj(dvec, w, b):
     ok(lib().fs2_op_spk_proj(p(dd), p(wd), p(bd), p(out), B, H, Din, stream()), "spk_proj")
     torch.cuda.synchronize()
     return out.cpu()
+
+
+# ------------------------------------------------------------------------------------------------
+# Sentinel-filled outputs (tests/test_gpu_decisions.py): a row the kernel never writes, or a write past the end, shows up
+# instead of passing by the luck of what torch.empty handed out.  These return (status, outputs...) and never raise on a status.
+def sentinel(rows, width, dtype):
+    """(rows + 1, width) device buffer: floats NaN, integers / masks bytes of 0x5a; the last row is the guard row."""
+    if dtype in (torch.float32, torch.bfloat16):
+        return torch.full((rows + 1, width), float("nan"), dtype=dtype, device=DEV)
+    t = torch.empty((rows + 1, width), dtype=dtype, device=DEV)
+    t.view(torch.uint8).fill_(0x5A)
+    return t
+
+
+def bits(t):
+    """Raw bits of a float tensor (bf16 -> int16, fp32 -> int32) on the host: equality of these is bit equality."""
+    t = t.detach().cpu().contiguous()
+    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def to_bits(x, dtype):
+    """fp32 reference values -> the bits they have in the engine dtype (one round-to-nearest-even for bf16)."""
+    return bits(torch.as_tensor(x).float().to(tdt(dtype)))
+
+
+def guard_intact(buf):
+    """The guard row behind the end still holds the sentinel."""
+    fresh = sentinel(0, buf.shape[1], buf.dtype)
+    return torch.equal(buf[-1:].contiguous().view(torch.uint8).cpu(), fresh.view(torch.uint8).cpu())
+
+
+def untouched(buf):
+    """Every byte of the buffer still holds the sentinel (an op that declined its shape wrote nothing)."""
+    fresh = sentinel(buf.shape[0] - 1, buf.shape[1], buf.dtype)
+    return torch.equal(buf.view(torch.uint8).cpu(), fresh.view(torch.uint8).cpu())
+
+
+def durations_s(dur_pred, src_mask, forced=None):
+    """-> status, dur, cum (B, L) int32, totals, guard (B,) int32, all guard rows intact?"""
+    B, L = dur_pred.shape
+    dp = torch.as_tensor(dur_pred).float().to(DEV).contiguous()
+    mk = torch.as_tensor(src_mask).to(torch.uint8).to(DEV).contiguous()
+    fd = None if forced is None else torch.as_tensor(forced).to(torch.int32).to(DEV).contiguous()
+    dur, cum = sentinel(B, L, torch.int32), sentinel(B, L, torch.int32)
+    tot, grd = sentinel(B, 1, torch.int32), sentinel(B, 1, torch.int32)
+    st = lib().fs2_op_durations(p(dp), p(mk), p(fd), p(dur), p(cum), p(tot), p(grd), B, L, stream())
+    torch.cuda.synchronize()
+    intact = all(guard_intact(b) for b in (dur, cum, tot, grd))
+    return st, dur[:B].cpu(), cum[:B].cpu(), tot[:B, 0].cpu(), grd[:B, 0].cpu(), intact
+
+
+def regulate_s(dtype, x, cum, totals, B, L, T, H):
+    """-> status, y buffer (B*T + 1, H) on the device, mask buffer (B + 1, T) uint8 on the device (raw bytes)."""
+    xd = to_dev(x, dtype)
+    cd = torch.as_tensor(cum).to(torch.int32).to(DEV).contiguous()
+    td = torch.as_tensor(totals).to(torch.int32).to(DEV).contiguous()
+    y, mk = sentinel(B * T, H, tdt(dtype)), sentinel(B, T, torch.uint8)
+    st = lib().fs2_op_regulate(dtype, p(xd), p(cd), p(td), p(y), p(mk), B, L, T, H, stream())
+    torch.cuda.synchronize()
+    return st, y, mk
+
+
+def bucket_embed_s(entry, dtype, x, src, bins, emb, std, mean, pe, spk, B, T, H):
+    """entry: "row" (fs2_op_bucket_embed), "utt" (fs2_op_bucket_embed_utt: src (B,), std 1, mean 0, no pe / spk) or "target"
+    (fs2_op_bucket_embed_target).  -> status, y buffer (B*T + 1, H), idx buffer (B*T + 1, 1) int32, both on the device."""
+    xd = to_dev(x, dtype)
+    f = lambda a: None if a is None else torch.as_tensor(a).float().to(DEV).contiguous()
+    sd, bd, ed, ped, spd = f(src), f(bins), f(emb), f(pe), f(spk)
+    nb = 0 if emb is None else emb.shape[0]
+    y, idx = sentinel(B * T, H, tdt(dtype)), sentinel(B * T, 1, torch.int32)
+    if entry == "utt":
+        assert std == 1.0 and mean == 0.0 and pe is None and spk is None
+        st = lib().fs2_op_bucket_embed_utt(dtype, p(xd), p(sd), p(bd), p(ed), nb, p(y), p(idx), B, T, H, stream())
+    else:
+        fn = lib().fs2_op_bucket_embed if entry == "row" else lib().fs2_op_bucket_embed_target
+        st = fn(dtype, p(xd), p(sd), p(bd), p(ed), nb, float(std), float(mean), p(ped), p(spd), p(y), p(idx), B, T, H, stream())
+    torch.cuda.synchronize()
+    return st, y, idx
+
+
+def embed_s(dtype, phones, table, pe, spk, n_phones):
+    """-> status, x buffer (B*L + 1, H), src_mask buffer (B + 1, L) uint8, on the device."""
+    B, L = phones.shape
+    H = table.shape[1]
+    ph = torch.as_tensor(phones).long().to(DEV).contiguous()
+    f = lambda a: torch.as_tensor(a).float().to(DEV).contiguous()
+    td, ped, sd = f(table), f(pe), f(spk)
+    x, mk = sentinel(B * L, H, tdt(dtype)), sentinel(B, L, torch.uint8)
+    st = lib().fs2_op_embed(dtype, p(ph), p(td), p(ped), p(sd), p(x), p(mk), B, L, H, n_phones, stream())
+    torch.cuda.synchronize()
+    return st, x, mk
+
+
+def spk_proj_s(dvec, w, b):
+    """-> status, out buffer (B + 1, H) fp32 on the device."""
+    B, Din = dvec.shape
+    H = w.shape[0]
+    f = lambda a: torch.as_tensor(a).float().to(DEV).contiguous()
+    dd, wd, bd = f(dvec), f(w), f(b)
+    out = sentinel(B, H, torch.float32)
+    st = lib().fs2_op_spk_proj(p(dd), p(wd), p(bd), p(out), B, H, Din, stream())
+    torch.cuda.synchronize()
+    return st, out
+
+
+def cwt_head_s(dtype, out_conv, spec, mask, ms_w, ms_b, B, T, F):
+    """fs2_op_cwt_head: out_conv (B*T, F), spec (B*T, ld_spec) -> status, mean_std (B + 1, 2), pred (B + 1, T), spec_out (B*T + 1, 10) buffers."""
+    od = to_dev(out_conv, dtype)
+    f = lambda a: torch.as_tensor(a).float().to(DEV).contiguous()
+    sd, wd, bd = f(spec), f(ms_w), f(ms_b)
+    md = None if mask is None else torch.as_tensor(mask).to(torch.uint8).to(DEV).contiguous()
+    ms, pred, so = sentinel(B, 2, torch.float32), sentinel(B, T, torch.float32), sentinel(B * T, 10, torch.float32)
+    st = lib().fs2_op_cwt_head(dtype, p(od), p(sd), int(spec.shape[1]), p(md), p(wd), p(bd), p(ms), p(pred), p(so), B, T, F, stream())
+    torch.cuda.synchronize()
+    return st, ms, pred, so
