@@ -12,6 +12,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -31,8 +32,17 @@ struct Arena {
     char* base = nullptr;
     size_t cap = 0, off = 0;
     bool external = false;  // caller-owned memory (fs2_set_workspace): never freed or grown here
+    bool overflow = false;  // a take() since the last reserve() did not fit (a null result cannot say so: offset 0 of a counting arena is null)
+    // An arena that only counts: no memory behind it, every take() fits and hands out no pointer; a layout function run on it leaves
+    // the size of its region in `off`.
+    static Arena counting() {
+        Arena a;
+        a.cap = ~(size_t)0;
+        return a;
+    }
     int reserve(size_t bytes) {
         off = 0;
+        overflow = false;
         if (bytes <= cap) return FS2_OK;
         if (external) return FS2_ERR_NOMEM;
         if (base) (void)hipFree(base);
@@ -45,9 +55,9 @@ struct Arena {
     }
     void* take(size_t bytes) {
         const size_t a = (off + 255) & ~(size_t)255;
-        if (a + bytes > cap) return nullptr;
+        if (a + bytes > cap) { overflow = true; return nullptr; }
         off = a + bytes;
-        return base + a;
+        return base ? base + a : nullptr;
     }
     void release() {
         if (base && !external) (void)hipFree(base);
@@ -128,32 +138,29 @@ struct ProfSlot {
     double flops = 0, bytes = 0;
 };
 
-}  // namespace
+struct PersistBufs {  // what fs2_encode leaves for fs2_decode
+    float* spk = nullptr;
+    void *xA = nullptr, *xB = nullptr;  // (B*L, H) encoder ping-pong; xA = encoder_out
+    float* dur_pred = nullptr;
+    int32_t *d_dur = nullptr, *d_cum = nullptr, *d_totals = nullptr, *d_guard = nullptr;
+    uint8_t* src_mask = nullptr;
+    // phone-level variances (fs2_config::var_level; model.py:276-294): predictions (B*L) and, for a CWT head, spectrogram (B*L, 10) +
+    // (B, 2) mean / std - produced by fs2_encode, kept in the persist arena, copied out by fs2_decode
+    float* pv_pred[FS2_MAX_VARIANCES] = {nullptr, nullptr, nullptr, nullptr};
+    float* pv_spec[FS2_MAX_VARIANCES] = {nullptr, nullptr, nullptr, nullptr};
+    float* pv_ms[FS2_MAX_VARIANCES] = {nullptr, nullptr, nullptr, nullptr};
+};
 
-struct fs2_engine {
+// An engine is three parts.  Model: what fs2_create / fs2_finalize produce and nobody writes afterwards - fs2_clone shares it (one
+// assignment: a field added here reaches every clone).  Switches: the A/B settings a clone inherits.  Everything else in fs2_engine
+// is the run state of one engine.
+struct Model {
     fs2_config cfg;
     int dt = FS2_F32;          // configured mode (FS2_F32 / FS2_BF16 / FS2_MIXED)
     int fdt = FS2_F32, bdt = FS2_F32;  // arithmetic of the front (encoder + variance adaptor: every discrete decision)
                                        // and of the back (decoder + mel head); they differ only in FS2_MIXED
     size_t esz = 4;            // bytes per activation element, the larger of the two (arena sizing)
-    char err[512];
-    bool finalized = false;
-    bool debug = false;
-    bool fuse_predictor = true;
-    // fs2_set_graphs: the decode phase replayed as a hipGraph (one launch instead of ~50) once a shape / buffer signature repeats
-    bool use_graph = false;
-    struct GraphEntry { std::vector<uint64_t> key; hipGraphExec_t exec = nullptr; uint64_t stamp = 0; bool bad = false; };
-    std::vector<GraphEntry> dgraphs, egraphs;  // decode phase / encode phase
-    hipStream_t gstream = nullptr;
-    hipEvent_t gev_in = nullptr, gev_out = nullptr;
-    uint64_t gclock = 0;
-    long graph_replays = 0;
-    bool zero_pad_mel = false;
-    bool defer_ln = true;      // hidden > 256, depth-wise blocks: LayerNorm deferred into its consumers (A/B: fs2_set_deferred_layernorm)
-    Tuning tune;               // this engine's A/B switches (fs2_set_tuning; copied by fs2_clone): every launch of the engine points at them
-    bool fold_ln = true;       // ... and a block's closing norm2 folded into the next block's in-projection (bf16; A/B: fs2_set_folded_layernorm)
     bool front_split = false;  // FS2_MIXED_X3 / FS2_F32_X3: the fp32 GEMMs / convs (the front's / all of them) run as bf16 x 3 split products
-    std::map<std::string, HostTensor> host;
     std::map<std::string, std::vector<int64_t>> spec;
     // device weight blocks: owned jointly by an engine and its fs2_clone()s (freed with the last of them)
     struct DevAllocs {
@@ -171,23 +178,37 @@ struct fs2_engine {
     float* mel_wg = nullptr;
     bool mel_fold = false;
     std::vector<VarianceW> priors_w;  // bins + relu(embedding) per prior (predictor unused)
+};
+struct Switches {
+    bool fuse_predictor = true;
+    // fs2_set_graphs: the decode phase replayed as a hipGraph (one launch instead of ~50) once a shape / buffer signature repeats
+    bool use_graph = false;
+    bool zero_pad_mel = false;
+    bool defer_ln = true;      // hidden > 256, depth-wise blocks: LayerNorm deferred into its consumers (A/B: fs2_set_deferred_layernorm)
+    bool fold_ln = true;       // ... and a block's closing norm2 folded into the next block's in-projection (bf16; A/B: fs2_set_folded_layernorm)
+    Tuning tune;               // this engine's A/B switches (fs2_set_tuning; copied by fs2_clone): every launch of the engine points at them
+};
+
+}  // namespace
+
+struct fs2_engine : Model, Switches {
+    char err[512];
+    bool finalized = false;
+    bool debug = false;        // (not inherited by a clone)
+    struct GraphEntry { std::vector<uint64_t> key; hipGraphExec_t exec = nullptr; uint64_t stamp = 0; bool bad = false; };
+    std::vector<GraphEntry> dgraphs, egraphs;  // decode phase / encode phase
+    hipStream_t gstream = nullptr;
+    hipEvent_t gev_in = nullptr, gev_out = nullptr;
+    uint64_t gclock = 0;
+    long graph_replays = 0;
+    std::map<std::string, HostTensor> host;  // fs2_load_weight's tensors, until fs2_finalize has packed them
     const float* priors_dev = nullptr;
     int priors_B = 0;
-    // run state
     Arena persist, scratch, dbg, dbg_enc;
     int B = 0, L = 0, T = 0;
     bool encoded = false;
     bool mid_forward = false;  // fs2_encode done, fs2_decode not yet: the persist arena is live
-    void *xA = nullptr, *xB = nullptr;  // (B*L, H) encoder ping-pong; xA = encoder_out
-    float* spk = nullptr;
-    float* dur_pred = nullptr;
-    // phone-level variances (fs2_config::var_level; model.py:276-294): predictions (B*L) and, for a CWT head, spectrogram (B*L, 10) +
-    // (B, 2) mean / std - produced by fs2_encode, kept in the persist arena, copied out by fs2_decode
-    float* pv_pred[FS2_MAX_VARIANCES] = {nullptr, nullptr, nullptr, nullptr};
-    float* pv_spec[FS2_MAX_VARIANCES] = {nullptr, nullptr, nullptr, nullptr};
-    float* pv_ms[FS2_MAX_VARIANCES] = {nullptr, nullptr, nullptr, nullptr};
-    int32_t *d_dur = nullptr, *d_cum = nullptr, *d_totals = nullptr, *d_guard = nullptr;
-    uint8_t* src_mask = nullptr;
+    PersistBufs ps;               // this batch's buffers in the persist arena (layout_persist)
     int32_t* h_pinned = nullptr;  // 2*B ints: totals, guard
     int h_pinned_cap = 0;
     std::vector<int32_t> totals, guard;
@@ -458,14 +479,16 @@ int make_layer(fs2_engine* e, const std::string& p, int H, int F, bool dw, Layer
     }
     return FS2_OK;
 }
-// The in-projection of block `p` with the previous block's norm2 (`pp`.norm2) folded in: see LayerW::in_proj_f.  bf16 stacks of wide
-// depth-wise blocks only (the blocks whose LayerNorms are deferred, conformer()).
-int make_folded_in_proj(fs2_engine* e, const std::string& p, const std::string& pp, int H, LayerW* L) {
-    const HostTensor& w = W(e, p + ".self_attn.in_proj_weight");   // (3H, H)
-    const HostTensor& b = W(e, p + ".self_attn.in_proj_bias");
-    const HostTensor& g = W(e, pp + ".norm2.weight");
-    const HostTensor& be = W(e, pp + ".norm2.bias");
-    const int N = 3 * H;
+// A Linear (weight `lw` (N, H), bias `lb`) with the LayerNorm `norm` in front of it folded in, to run on that norm's pre-norm rows:
+// W' = W diag(gamma), b' = b + W beta, wg[n] = sum_k W'[n][k] of the bf16 values as stored (see LayerW::in_proj_f).  bf16 stacks of wide
+// depth-wise blocks only (the blocks whose LayerNorms are deferred, conformer()): a block's in-projection behind the previous block's
+// norm2, the mel head behind the last decoder block's.
+int make_norm_folded(fs2_engine* e, const std::string& lw, const std::string& lb, const std::string& norm, ConvW* out, float** wg_out) {
+    const HostTensor& w = W(e, lw);
+    const HostTensor& b = W(e, lb);
+    const HostTensor& g = W(e, norm + ".weight");
+    const HostTensor& be = W(e, norm + ".bias");
+    const int N = (int)w.shape[0], H = (int)w.shape[1];
     std::vector<float> wf((size_t)N * H), bf(N), wg(N);
     for (int n = 0; n < N; ++n) {
         double bacc = b.data[n], gacc = 0;
@@ -478,12 +501,26 @@ int make_folded_in_proj(fs2_engine* e, const std::string& p, const std::string& 
         bf[n] = (float)bacc;
         wg[n] = (float)gacc;
     }
-    L->in_proj_f.N = N; L->in_proj_f.Cin = H; L->in_proj_f.taps = 1; L->in_proj_f.dt = FS2_BF16;
-    CHK(upload_mat(e, wf.data(), wf.size(), &L->in_proj_f.w, FS2_BF16));
-    CHK(upload_f32(e, bf.data(), bf.size(), &L->in_proj_f.b));
-    CHK(upload_f32(e, wg.data(), wg.size(), &L->in_wg));
-    L->has_fold = true;
-    return FS2_OK;
+    out->N = N; out->Cin = H; out->taps = 1; out->dt = FS2_BF16;
+    CHK(upload_mat(e, wf.data(), wf.size(), &out->w, FS2_BF16));
+    CHK(upload_f32(e, bf.data(), bf.size(), &out->b));
+    return upload_f32(e, wg.data(), wg.size(), wg_out);
+}
+
+// The single-launch predictors read one stacked vector each of every layer's conv bias (`bias_name` within the layer) and LayerNorm
+// gamma / beta.
+int upload_stacked_vectors(fs2_engine* e, const std::string& p, int nl, const char* bias_name, PredictorW* P) {
+    std::vector<float> bias, g, b;
+    for (int j = 0; j < nl; ++j) {
+        const std::string q = p + ".layers." + std::to_string(j) + ".layers";
+        const auto &hb = W(e, q + bias_name).data, &hg = W(e, q + ".2.weight").data, &hbe = W(e, q + ".2.bias").data;
+        bias.insert(bias.end(), hb.begin(), hb.end());
+        g.insert(g.end(), hg.begin(), hg.end());
+        b.insert(b.end(), hbe.begin(), hbe.end());
+    }
+    CHK(upload_f32(e, bias.data(), bias.size(), &P->bias_all));
+    CHK(upload_f32(e, g.data(), g.size(), &P->g_all));
+    return upload_f32(e, b.data(), b.size(), &P->b_all);
 }
 
 int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool dw, PredictorW* P, int dt, bool cwt = false) {
@@ -535,25 +572,15 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
     if (!dw && nl && cin == filt && predictor_fused_supported(dt, filt, taps, nl, 1)) {
         const size_t lb = predictor_packed_bytes_per_layer();
         CHK(dev_alloc(e, &P->wpk, lb * nl));
-        std::vector<float> bias, g, b;
-        for (int j = 0; j < nl; ++j) {
-            const std::string q = p + ".layers." + std::to_string(j) + ".layers";
-            CHK(launch_pack_predictor_weights(P->layers[j].c.w, (char*)P->wpk + lb * j, nullptr));
-            const auto &hb = W(e, q + ".0.module.bias").data, &hg = W(e, q + ".2.weight").data, &hbe = W(e, q + ".2.bias").data;
-            bias.insert(bias.end(), hb.begin(), hb.end());
-            g.insert(g.end(), hg.begin(), hg.end());
-            b.insert(b.end(), hbe.begin(), hbe.end());
-        }
+        for (int j = 0; j < nl; ++j) CHK(launch_pack_predictor_weights(P->layers[j].c.w, (char*)P->wpk + lb * j, nullptr));
         HIPCHK(e, hipStreamSynchronize(nullptr));
-        CHK(upload_f32(e, bias.data(), bias.size(), &P->bias_all));
-        CHK(upload_f32(e, g.data(), g.size(), &P->g_all));
-        CHK(upload_f32(e, b.data(), b.size(), &P->b_all));
+        CHK(upload_stacked_vectors(e, p, nl, ".0.module.bias", P));
     } else if (dw && nl && cin == filt && P->layers[0].dw.k == 3 && P->layers[0].dw.C == filt && predictor_fused_supported(dt, filt, 3, nl, 1)) {
         // depth-wise layers in the single launch (predictor_fused_kernel<..., DW>): the pointwise weights in fragment order (one tap),
         // the depth-wise taps as (layer, tap, channel) fp32
         const size_t lb = predictor_packed_bytes_per_layer(1);
         CHK(dev_alloc(e, &P->wpk, lb * nl));
-        std::vector<float> bias, g, b, dww((size_t)nl * 3 * filt), dwb;
+        std::vector<float> dww((size_t)nl * 3 * filt), dwb;
         for (int j = 0; j < nl; ++j) {
             const std::string q = p + ".layers." + std::to_string(j) + ".layers";
             CHK(launch_pack_predictor_weights(P->layers[j].c.w, (char*)P->wpk + lb * j, nullptr, 1));
@@ -561,15 +588,9 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
             for (int c2 = 0; c2 < filt; ++c2)
                 for (int t = 0; t < 3; ++t) dww[((size_t)j * 3 + t) * filt + c2] = hw[(size_t)c2 * 3 + t];
             dwb.insert(dwb.end(), hdb.begin(), hdb.end());
-            const auto &hb = W(e, q + ".0.module.1.bias").data, &hg = W(e, q + ".2.weight").data, &hbe = W(e, q + ".2.bias").data;
-            bias.insert(bias.end(), hb.begin(), hb.end());
-            g.insert(g.end(), hg.begin(), hg.end());
-            b.insert(b.end(), hbe.begin(), hbe.end());
         }
         HIPCHK(e, hipStreamSynchronize(nullptr));
-        CHK(upload_f32(e, bias.data(), bias.size(), &P->bias_all));
-        CHK(upload_f32(e, g.data(), g.size(), &P->g_all));
-        CHK(upload_f32(e, b.data(), b.size(), &P->b_all));
+        CHK(upload_stacked_vectors(e, p, nl, ".0.module.1.bias", P));
         CHK(upload_f32(e, dww.data(), dww.size(), &P->dw_all));
         CHK(upload_f32(e, dwb.data(), dwb.size(), &P->dwb_all));
     } else if (!dw && nl && cin == filt && dt == FS2_F32 && e->front_split && predictor_fused_x3_supported(filt, taps, nl, 1)) {
@@ -577,7 +598,6 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
         // [layer][step = tap * 8 + kb][32-channel group][2][lane] x 8 values (pack_predictor_weights_kernel's map), packed here
         const size_t per = predictor_packed_bytes_per_layer() / 2;  // bf16 values per layer
         std::vector<unsigned short> hi(per * nl), lo(per * nl);
-        std::vector<float> bias, g, b;
         for (int j = 0; j < nl; ++j) {
             const std::string q = p + ".layers." + std::to_string(j) + ".layers";
             const HostTensor& w = W(e, q + ".0.module.weight");  // (filt, filt, 3)
@@ -598,18 +618,12 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
                             }
                         }
             }
-            const auto &hb = W(e, q + ".0.module.bias").data, &hg = W(e, q + ".2.weight").data, &hbe = W(e, q + ".2.bias").data;
-            bias.insert(bias.end(), hb.begin(), hb.end());
-            g.insert(g.end(), hg.begin(), hg.end());
-            b.insert(b.end(), hbe.begin(), hbe.end());
         }
         CHK(dev_alloc(e, &P->wpk, hi.size() * 2));
         CHK(dev_alloc(e, &P->wpk_lo, lo.size() * 2));
         HIPCHK(e, hipMemcpy(P->wpk, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
         HIPCHK(e, hipMemcpy(P->wpk_lo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
-        CHK(upload_f32(e, bias.data(), bias.size(), &P->bias_all));
-        CHK(upload_f32(e, g.data(), g.size(), &P->g_all));
-        CHK(upload_f32(e, b.data(), b.size(), &P->b_all));
+        CHK(upload_stacked_vectors(e, p, nl, ".0.module.bias", P));
     }
     return FS2_OK;
 }
@@ -670,13 +684,24 @@ struct RowScale {  // x of the GEMM is a pre-norm tensor whose LayerNorm is fold
     const float* rowstats;  // (M) float2 (rstd, rstd * mean): launch_rowstats_finish
     const float* wg;
 };
-int gemm(fs2_engine* e, hipStream_t st, const ConvW& w, const void* x, void* c, int M, int S, bool relu, int out_dt,
-         const LnFuse* ln = nullptr, int extra_class = -1, const uint8_t* zero_rows = nullptr, const Deferred* df = nullptr,
-         void* c_lo = nullptr, const RowScale* rs = nullptr) {
+// What a gemm() may ask for beyond y = act(x w^T + b).  A call site names the fields it sets, in declaration order: {.ln = &ln}
+// (designated initialisers: C++20, which hipcc's clang also takes in its C++17 mode, silently unless -pedantic)
+struct GemmOpt {
+    const LnFuse* ln = nullptr;
+    int extra_class = -1;               // a second profiling class the launch is timed under
+    const uint8_t* zero_rows = nullptr; // rows whose mask byte is set are stored as 0
+    const Deferred* deferred = nullptr;
+    void* c_lo = nullptr;               // the fp32 result stored as bf16 head (c) + tail (c_lo): the split attention's input
+    const RowScale* rowscale = nullptr;
+};
+int gemm(fs2_engine* e, hipStream_t st, const ConvW& w, const void* x, void* c, int M, int S, bool relu, int out_dt, const GemmOpt& o = {}) {
+    const LnFuse* ln = o.ln;
+    const Deferred* df = o.deferred;
+    const RowScale* rs = o.rowscale;
     GemmArgs a;
     a.tune = &e->tune;
-    a.zero_rows = zero_rows;
-    a.C_lo = c_lo;
+    a.zero_rows = o.zero_rows;
+    a.C_lo = o.c_lo;
     if (rs) { a.rs_stats = rs->rowstats; a.rs_wg = rs->wg; }
     if (df) {
         a.epi_res = df->res; a.epi_res_stats = df->res_stats; a.epi_res_g = df->res_g; a.epi_res_b = df->res_b;
@@ -712,7 +737,7 @@ int gemm(fs2_engine* e, hipStream_t st, const ConvW& w, const void* x, void* c, 
     const double wsz = w.dt == FS2_BF16 ? 2 : 4;
     const double by = (double)M * w.Cin * wsz + (double)a.N * a.K * wsz + (double)M * a.N * osz;
     Bracket br(e, w.taps > 1 ? FS2_K_CONV_GEMM : FS2_K_GEMM, st, fl, by);
-    Bracket br2(e, extra_class >= 0 ? extra_class : FS2_K_COUNT - 1, st, fl, by, extra_class >= 0);
+    Bracket br2(e, o.extra_class >= 0 ? o.extra_class : FS2_K_COUNT - 1, st, fl, by, o.extra_class >= 0);
     const int r = launch_gemm(a, w.dt, out_dt, st);
     if (r != FS2_OK) return fail(e, r, "gemm launch failed (M=%d N=%d K=%d)", M, a.N, a.K);
     return FS2_OK;
@@ -767,18 +792,30 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
     // multiplies them with three bf16 MFMAs per product and hands back fp32 rows (attention.hip, X3)
     // the encoder's whole self-attention block as one timed class (in-projection .. out-projection + LayerNorm): 8 S H^2 + 4 S^2 H flops
     // per utterance (SURVEY 8d's fused-MHA figure), bytes: x in + out, the three weight matrices
-    Bracket* mha = is_decoder ? nullptr : new Bracket(e, FS2_K_ENC_MHA, st, 8.0 * M * (double)H * H + 4.0 * B * (double)S * S * H,
-                                                      2.0 * M * H * dsz + 4.0 * H * H * dsz);
-    struct MhaEnd { Bracket*& b; ~MhaEnd() { delete b; b = nullptr; } } mha_end{mha};
+    std::optional<Bracket> mha;  // closed behind the out-projection (reset()), or by an error return
+    if (!is_decoder) mha.emplace(e, FS2_K_ENC_MHA, st, 8.0 * M * (double)H * H + 4.0 * B * (double)S * S * H, 2.0 * M * H * dsz + 4.0 * H * H * dsz);
     const bool x3 = e->front_split && dt == FS2_F32 && e->tune.attn_x3;
     void* qkv_lo = x3 ? (void*)((char*)sc.qkv + (size_t)M * 3 * H * 2) : nullptr;
     if (prenorm_in) {
         if (!w.has_fold || !(w.depthwise && H > 256 && e->defer_ln)) return fail(e, FS2_ERR_STATE, "pre-norm block input without folded weights");
         const RowScale rs{sc.rsf, w.in_wg};
-        CHK(gemm(e, st, w.in_proj_f, x, sc.qkv, M, M, false, dt, nullptr, -1, nullptr, nullptr, nullptr, &rs));
+        CHK(gemm(e, st, w.in_proj_f, x, sc.qkv, M, M, false, dt, {.rowscale = &rs}));
     } else {
-        CHK(gemm(e, st, w.in_proj, x, sc.qkv, M, M, false, dt, nullptr, -1, nullptr, nullptr, qkv_lo));
+        CHK(gemm(e, st, w.in_proj, x, sc.qkv, M, M, false, dt, {.c_lo = qkv_lo}));
     }
+    const int ffn_class = is_decoder ? FS2_K_DEC_FFN_CONV1 : -1;
+    // the block's second half on tmp = LN1(x + out_proj(att)): x = LN2(tmp + conv2(relu(conv1([dwconv] tmp))))
+    const auto ffn = [&]() -> int {
+        const void* in = tmp;
+        if (w.depthwise) {
+            CHK(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt));
+            in = sc.u;
+        }
+        CHK(gemm(e, st, w.c1, in, sc.hid, M, S, true, dt, {.extra_class = ffn_class}));
+        LnFuse ln;
+        ln.res = tmp; ln.g = w.g2; ln.b = w.b2; ln.tmp = sc.proj;
+        return gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, {.ln = &ln});
+    };
     AttnArgs a;
     a.tune = &e->tune;
     a.qkv_lo = qkv_lo;
@@ -800,17 +837,8 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
             const int r = launch_attn_out_ln(ao, st);
             if (r != FS2_OK) return fail(e, r, "fused attention + out-projection launch failed");
         }
-        delete mha; mha = nullptr;
-        if (w.depthwise) {
-            CHK(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt));
-            CHK(gemm(e, st, w.c1, sc.u, sc.hid, M, S, true, dt, nullptr, is_decoder ? FS2_K_DEC_FFN_CONV1 : -1));
-        } else {
-            CHK(gemm(e, st, w.c1, tmp, sc.hid, M, S, true, dt, nullptr, is_decoder ? FS2_K_DEC_FFN_CONV1 : -1));
-        }
-        LnFuse ln;  // x = LN2(tmp + conv2(hid))
-        ln.res = tmp; ln.g = w.g2; ln.b = w.b2; ln.tmp = sc.proj;
-        CHK(gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, &ln));
-        return FS2_OK;
+        mha.reset();
+        return ffn();
     }
     {
         Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * M * H * dsz);
@@ -831,14 +859,14 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
         Deferred d1;
         d1.res = x; d1.stats_out = sc.st1;
         if (prenorm_in) { d1.res_stats = sc.st2; d1.res_g = pg; d1.res_b = pb; }                      // x = LN2_prev(v2_prev), on load
-        CHK(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, nullptr, -1, nullptr, &d1));       // tmp = v1
-        delete mha; mha = nullptr;
+        CHK(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, {.deferred = &d1}));               // tmp = v1
+        mha.reset();
         LnOnLoad l1{sc.st1, w.g1, w.b1};
         CHK(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt, &l1));
-        CHK(gemm(e, st, w.c1, sc.u, sc.hid, M, S, true, dt, nullptr, is_decoder ? FS2_K_DEC_FFN_CONV1 : -1));
+        CHK(gemm(e, st, w.c1, sc.u, sc.hid, M, S, true, dt, {.extra_class = ffn_class}));
         Deferred d2;
         d2.res = tmp; d2.res_stats = sc.st1; d2.res_g = w.g1; d2.res_b = w.b1; d2.stats_out = sc.st2;
-        CHK(gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, nullptr, -1, nullptr, &d2));                // x = v2 (x is free by now)
+        CHK(gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, {.deferred = &d2}));                        // x = v2 (x is free by now)
         if (leave_prenorm) {  // the next block folds LN2 in: its in-projection wants (rstd, rstd * mean) per row
             if (launch_rowstats_finish(sc.st2, ln_parts(H), H, 1e-5f, sc.rsf, M, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "row statistics launch failed");
             return FS2_OK;
@@ -848,21 +876,10 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
     {   // tmp = LN1(x + out_proj(att))
         LnFuse ln;
         ln.res = x; ln.g = w.g1; ln.b = w.b1; ln.tmp = sc.proj;
-        CHK(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, &ln));
-        delete mha; mha = nullptr;
+        CHK(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, {.ln = &ln}));
+        mha.reset();
     }
-    if (w.depthwise) {
-        CHK(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt));
-        CHK(gemm(e, st, w.c1, sc.u, sc.hid, M, S, true, dt, nullptr, is_decoder ? FS2_K_DEC_FFN_CONV1 : -1));
-    } else {
-        CHK(gemm(e, st, w.c1, tmp, sc.hid, M, S, true, dt, nullptr, is_decoder ? FS2_K_DEC_FFN_CONV1 : -1));
-    }
-    {   // x = LN2(tmp + conv2(hid))
-        LnFuse ln;
-        ln.res = tmp; ln.g = w.g2; ln.b = w.b2; ln.tmp = sc.proj;
-        CHK(gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, &ln));
-    }
-    return FS2_OK;
+    return ffn();
 }
 
 // The torch-1.10 container loop (fastspeech2.py:249-262: for layer in layers: x = layer(x, ...), no final norm).  Between two wide
@@ -900,48 +917,40 @@ struct EmbedTail {  // the VarianceEncoder's bucketize + embedding add (+ pe + s
     const float* spk;
 };
 
+// The CWT ending on the last layer's activations (model.py:412-431): 10-scale head, utterance-level mean / std, recomposition
+int cwt_head(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* act, const CwtOut& cw, const uint8_t* mask, float* pred, int B, int S) {
+    CHK(gemm(e, st, P.head_mat, act, cw.spec12, B * S, B * S, false, FS2_F32));
+    CwtArgs ca{act, cw.spec12, 12, mask, P.ms_w, P.ms_b, cw.mean_std, pred, cw.spec_out, B, S, P.filt};
+    if (launch_cwt_head(ca, P.dt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "cwt head launch failed");
+    return FS2_OK;
+}
+
 int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x, int B, int S, const uint8_t* mask,
               float* pred, const LayerScratch& sc, const CwtOut* cw = nullptr, const EmbedTail* tail = nullptr, bool* tail_done = nullptr) {
     const int M = B * S;
     if (tail_done) *tail_done = false;
     if (P.cwt && !cw) return fail(e, FS2_ERR_STATE, "CWT predictor without its output buffers");
-    if (P.wpk && P.wpk_lo && e->fuse_predictor && P.dt == FS2_F32 && e->front_split &&
-        predictor_fused_x3_supported(P.filt, P.layers[0].c.taps, (int)P.layers.size(), S)) {
-        // the split arithmetic's single launch (fp32 rows in, and out of the embedding tail)
+    // the whole predictor as one launch (predictor_fused.hip): in the split arithmetic (fp32 rows in, and out of the embedding tail), or in bf16
+    const int nl = (int)P.layers.size(), taps = P.dw_all ? 3 : P.layers[0].c.taps;
+    const bool one_x3 = P.wpk && P.wpk_lo && e->fuse_predictor && P.dt == FS2_F32 && e->front_split && predictor_fused_x3_supported(P.filt, taps, nl, S);
+    if (one_x3 || (P.wpk && !P.wpk_lo && e->fuse_predictor && predictor_fused_supported(P.dt, P.filt, taps, nl, S))) {
         PredictorArgs a;
         a.x = x; a.wpk = P.wpk; a.wpk_lo = P.wpk_lo; a.bias = P.bias_all; a.ln_g = P.g_all; a.ln_b = P.b_all;
-        a.head_w = P.head_w; a.head_b = P.head_b; a.mask = mask; a.pred = pred;
-        a.B = B; a.S = S; a.H = P.filt; a.nlayers = (int)P.layers.size(); a.taps = P.layers[0].c.taps; a.eps = 1e-5f;
-        const bool with_tail = tail && tail_done && !P.cwt && tail->y != x && tail->nbins >= 2 && tail->nbins - 1 <= 512;
-        if (with_tail) {
-            a.be_y = tail->y; a.be_bins = tail->bins; a.be_emb = tail->emb; a.be_nbins = tail->nbins;
-            a.be_std = tail->std; a.be_mean = tail->mean; a.be_pe = tail->pe; a.be_spk = tail->spk;
-        }
-        const double fl = 2.0 * M * (double)P.filt * P.filt * a.taps * a.nlayers;
-        Bracket br(e, FS2_K_CONV_GEMM, st, fl, (double)M * P.filt * 4 + (double)M * 4 + (with_tail ? 2.0 * M * P.filt * 4 : 0.0));
-        Bracket brp(e, FS2_K_PREDICTOR, st, fl, (double)M * P.filt * 4 + (double)M * 4 + (with_tail ? 2.0 * M * P.filt * 4 : 0.0), x != e->xA && x != e->xB);
-        const int r = launch_predictor_fused_x3(a, st);
-        if (r != FS2_OK) return fail(e, r, "fused predictor (split arithmetic) launch failed (B=%d S=%d)", B, S);
-        if (with_tail) *tail_done = true;
-        return FS2_OK;
-    }
-    if (P.wpk && !P.wpk_lo && e->fuse_predictor && predictor_fused_supported(P.dt, P.filt, P.dw_all ? 3 : P.layers[0].c.taps, (int)P.layers.size(), S)) {
-        PredictorArgs a;
-        a.x = x; a.wpk = P.wpk; a.bias = P.bias_all; a.ln_g = P.g_all; a.ln_b = P.b_all;
         a.dw_w = P.dw_all; a.dw_b = P.dwb_all;  // depth-wise layers: wpk = their pointwise halves
         a.head_w = P.head_w; a.head_b = P.head_b; a.mask = mask; a.pred = pred;
-        a.B = B; a.S = S; a.H = P.filt; a.nlayers = (int)P.layers.size(); a.taps = P.dw_all ? 3 : P.layers[0].c.taps; a.eps = 1e-5f;
+        a.B = B; a.S = S; a.H = P.filt; a.nlayers = nl; a.taps = taps; a.eps = 1e-5f;
         const bool with_tail = tail && tail_done && !P.cwt && tail->y != x && tail->nbins >= 2 && tail->nbins - 1 <= 512;
         if (with_tail) {
             a.be_y = tail->y; a.be_bins = tail->bins; a.be_emb = tail->emb; a.be_nbins = tail->nbins;
             a.be_std = tail->std; a.be_mean = tail->mean; a.be_pe = tail->pe; a.be_spk = tail->spk;
         }
-        const double fl = (P.dw_all ? 2.0 * M * (double)P.filt * (P.filt + 3) : 2.0 * M * (double)P.filt * P.filt * a.taps) * a.nlayers;
-        const double by = (double)M * P.filt * 2 + (double)M * 4 + (with_tail ? 2.0 * M * P.filt * 2 : 0.0);
+        const double rsz = one_x3 ? 4 : 2;  // bytes per element of a row
+        const double fl = (P.dw_all ? 2.0 * M * (double)P.filt * (P.filt + 3) : 2.0 * M * (double)P.filt * P.filt * taps) * nl;
+        const double by = (double)M * P.filt * rsz + (double)M * 4 + (with_tail ? 2.0 * M * P.filt * rsz : 0.0);
         Bracket br(e, FS2_K_CONV_GEMM, st, fl, by);
-        Bracket brp(e, FS2_K_PREDICTOR, st, fl, by, x != e->xA && x != e->xB);
-        const int r = launch_predictor_fused(a, st);
-        if (r != FS2_OK) return fail(e, r, "fused predictor launch failed (B=%d S=%d)", B, S);
+        Bracket brp(e, FS2_K_PREDICTOR, st, fl, by, x != e->ps.xA && x != e->ps.xB);
+        const int r = one_x3 ? launch_predictor_fused_x3(a, st) : launch_predictor_fused(a, st);
+        if (r != FS2_OK) return fail(e, r, "fused predictor%s launch failed (B=%d S=%d)", one_x3 ? " (split arithmetic)" : "", B, S);
         if (with_tail) *tail_done = true;
         return FS2_OK;
     }
@@ -961,7 +970,7 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
             Deferred d;
             d.stats_out = stats[j & 1];
             if (j + 1 == P.layers.size() && !P.cwt && P.head_gw) { d.head_gw = P.head_gw; d.head_out = sc.hd; d.head_done = &head_done; }
-            CHK(gemm(e, st, Lw.c, sc.u, out, M, S, true, P.dt, nullptr, -1, nullptr, &d));
+            CHK(gemm(e, st, Lw.c, sc.u, out, M, S, true, P.dt, {.deferred = &d}));
             src = out;
             prev = &Lw;
         }
@@ -974,10 +983,7 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
         }
         if (!P.cwt) return norm_only(e, st, P.dt, src, stl, prev->g, prev->b, nullptr, M, P.filt, P.head_w, P.head_b, mask, pred);
         CHK(norm_only(e, st, P.dt, src, stl, prev->g, prev->b, (void*)src, M, P.filt));
-        CHK(gemm(e, st, P.head_mat, src, cw->spec12, M, M, false, FS2_F32));
-        CwtArgs ca{src, cw->spec12, 12, mask, P.ms_w, P.ms_b, cw->mean_std, pred, cw->spec_out, B, S, P.filt};
-        if (launch_cwt_head(ca, P.dt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "cwt head launch failed");
-        return FS2_OK;
+        return cwt_head(e, st, P, src, *cw, mask, pred, B, S);
     }
     const void* src = x;
     for (size_t j = 0; j < P.layers.size(); ++j) {
@@ -995,33 +1001,21 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
         if (Lw.depthwise) {
             CHK(dwconv(e, st, Lw.dw, src, sc.u, B, S, P.dt));
             ln.tmp = other;  // src (= other for j > 0) is dead once the depth-wise conv has run
-            CHK(gemm(e, st, Lw.c, sc.u, keep ? out : nullptr, M, S, true, P.dt, &ln));
+            CHK(gemm(e, st, Lw.c, sc.u, keep ? out : nullptr, M, S, true, P.dt, {.ln = &ln}));
         } else {
             ln.tmp = sc.u;
-            CHK(gemm(e, st, Lw.c, src, keep ? out : nullptr, M, S, true, P.dt, &ln));
+            CHK(gemm(e, st, Lw.c, src, keep ? out : nullptr, M, S, true, P.dt, {.ln = &ln}));
         }
         src = out;
     }
-    if (P.cwt) {  // model.py:412-431: 10-scale head, utterance-level mean/std, recomposition
-        CHK(gemm(e, st, P.head_mat, src, cw->spec12, M, M, false, FS2_F32));
-        CwtArgs ca{src, cw->spec12, 12, mask, P.ms_w, P.ms_b, cw->mean_std, pred, cw->spec_out, B, S, P.filt};
-        if (launch_cwt_head(ca, P.dt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "cwt head launch failed");
-    }
-    return FS2_OK;
+    return P.cwt ? cwt_head(e, st, P, src, *cw, mask, pred, B, S) : FS2_OK;
 }
 
-size_t layer_scratch_bytes(const fs2_engine* e, int B, int S) {
-    const fs2_config& c = e->cfg;
-    const size_t H = c.hidden, M = (size_t)B * S, esz = e->esz;
-    size_t Fm = c.enc_filter > c.dec_filter ? c.enc_filter : c.dec_filter;
-    size_t Pm = H;
-    if ((size_t)c.var_filter > Pm) Pm = c.var_filter;
-    if ((size_t)c.dur_filter > Pm) Pm = c.dur_filter;
-    const size_t Spad = ((size_t)S + 63) / 64 * 64;
-    return al(M * 3 * H * esz) + 3 * al(M * Pm * esz) + al(M * Fm * esz) + al((size_t)B * H * Spad * esz) +
-           al((size_t)B * (Spad / 64) * 8) + 2 * al(M * (size_t)ln_parts((int)Pm) * 8) + al(M * 8) + al(M * 16) + 4096;
-}
-int take_layer_scratch(fs2_engine* e, Arena& ar, int B, int S, LayerScratch* sc) {
+// ---- workspace layout ---------------------------------------------------------------------------
+// One function per region (persist; the scratch of the encode and of the decode phase, each ending in / holding a stack's layer
+// scratch) takes the region's buffers from an arena, in a fixed order, and says whether they all fit.  The SIZE of a region is the same
+// function run on an arena that only counts (the *_need functions): a new buffer is one take() here and nothing else.
+bool layout_layer_scratch(const fs2_engine* e, Arena& ar, int B, int S, LayerScratch* sc) {
     const fs2_config& c = e->cfg;
     const size_t H = c.hidden, M = (size_t)B * S, esz = e->esz;
     size_t Fm = c.enc_filter > c.dec_filter ? c.enc_filter : c.dec_filter;
@@ -1041,32 +1035,94 @@ int take_layer_scratch(fs2_engine* e, Arena& ar, int B, int S, LayerScratch* sc)
     sc->u = ar.take(M * Pm * esz);
     sc->vt = ar.take((size_t)B * H * sc->Spad * esz);
     sc->bits = (uint64_t*)ar.take((size_t)B * sc->nw64 * 8);
-    if (!sc->st1 || !sc->st2 || !sc->rsf || !sc->hd || !sc->qkv || !sc->att || !sc->proj || !sc->hid || !sc->u || !sc->vt || !sc->bits)
-        return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
-    return FS2_OK;
+    return !ar.overflow;
 }
 
-size_t persist_bytes(const fs2_engine* e, int B, int L) {
-    const size_t H = e->cfg.hidden, ML = (size_t)B * L, esz = e->esz;
-    size_t pv = 0;
-    for (int v = 0; v < e->cfg.n_variances; ++v)
-        if (e->cfg.var_level[v]) pv += al(ML * 4) + (e->cfg.var_cwt[v] ? al(ML * 10 * 4) + al((size_t)B * 8) : 0);
-    return al((size_t)B * H * 4) + 2 * al(ML * H * esz) + al(ML * 4) + 2 * al(ML * 4) + 2 * al((size_t)B * 4) + al(ML) + pv + 4096;
+bool layout_persist(const fs2_engine* e, Arena& ar, int B, int L, PersistBufs* p) {
+    const fs2_config& c = e->cfg;
+    const size_t H = c.hidden, ML = (size_t)B * L, esz = e->esz;
+    p->spk = (float*)ar.take((size_t)B * H * 4);
+    p->xA = ar.take(ML * H * esz);
+    p->xB = ar.take(ML * H * esz);
+    p->dur_pred = (float*)ar.take(ML * 4);
+    p->d_dur = (int32_t*)ar.take(ML * 4);
+    p->d_cum = (int32_t*)ar.take(ML * 4);
+    p->d_totals = (int32_t*)ar.take((size_t)2 * B * 4);  // [totals | guard flags]: one read-back
+    p->d_guard = p->d_totals ? p->d_totals + B : nullptr;
+    p->src_mask = (uint8_t*)ar.take(ML);
+    for (int v = 0; v < FS2_MAX_VARIANCES; ++v) {
+        p->pv_pred[v] = p->pv_spec[v] = p->pv_ms[v] = nullptr;
+        if (v >= c.n_variances || !c.var_level[v]) continue;
+        p->pv_pred[v] = (float*)ar.take(ML * 4);
+        if (c.var_cwt[v]) {
+            p->pv_spec[v] = (float*)ar.take(ML * 10 * 4);
+            p->pv_ms[v] = (float*)ar.take((size_t)B * 8);
+        }
+    }
+    return !ar.overflow;
 }
-// scratch of the encode phase: the encoder's layer scratch + the CWT head's (M, 12) spectrogram, one buffer that every phone-level
-// CWT variance reuses (encode_body)
-size_t encode_scratch_bytes(const fs2_engine* e, int B, int L) {
-    size_t cw = 0;
-    for (int v = 0; v < e->cfg.n_variances; ++v)
-        if (e->cfg.var_level[v] && e->cfg.var_cwt[v]) cw = al((size_t)B * L * 12 * 4) + 512;
-    return layer_scratch_bytes(e, B, L) + cw;
+
+struct EncodeScratch {
+    LayerScratch sc;
+    float* spec12 = nullptr;  // the CWT head's (M, 12) spectrogram: one buffer that every phone-level CWT variance reuses (encode_body)
+};
+bool layout_encode_scratch(const fs2_engine* e, Arena& ar, int B, int L, EncodeScratch* s) {
+    const fs2_config& c = e->cfg;
+    layout_layer_scratch(e, ar, B, L, &s->sc);
+    bool phone_cwt = false;
+    for (int v = 0; v < c.n_variances; ++v) phone_cwt = phone_cwt || (c.var_level[v] && c.var_cwt[v]);
+    s->spec12 = phone_cwt ? (float*)ar.take((size_t)B * L * 12 * 4) : nullptr;
+    return !ar.overflow;
 }
-size_t decode_scratch_bytes(const fs2_engine* e, int B, int T) {
-    const size_t H = e->cfg.hidden, MT = (size_t)B * T, esz = e->esz;
-    size_t cw = 0;
-    for (int v = 0; v < e->cfg.n_variances; ++v)
-        if (e->cfg.var_cwt[v]) cw = al(MT * 12 * 4) + al((size_t)B * 8) + 512;  // the CWT head's spectrogram + (mean, std)
-    return layer_scratch_bytes(e, B, T) + 2 * al(MT * H * esz) + al(MT) + (size_t)e->cfg.n_variances * al(MT * 4) + cw + 4096;
+
+struct DecodeScratch {
+    void *yA, *yB;  // (B*T, H) ping-pong
+    uint8_t* tmask;
+    float* vpred[FS2_MAX_VARIANCES];  // frame-level variances
+    int last_frame_v;                 // the last FRAME-level variance: pe + spk ride in its embedding add
+    float *cw_spec, *cw_ms;           // a frame-level CWT head's (M, 12) spectrogram + (B, 2) mean / std
+    LayerScratch sc;
+};
+// mask / variance predictions go straight into the caller's buffers when it wants them (out); out == nullptr: the caller's worst
+// case, no buffer of its own
+bool layout_decode_scratch(const fs2_engine* e, Arena& ar, int B, int T, const fs2_outputs* out, DecodeScratch* s) {
+    const fs2_config& c = e->cfg;
+    const size_t H = c.hidden, MT = (size_t)B * T, esz = e->esz;
+    s->yA = ar.take(MT * H * esz);
+    s->yB = ar.take(MT * H * esz);
+    s->tmask = out && out->tgt_mask ? out->tgt_mask : (uint8_t*)ar.take(MT);
+    s->last_frame_v = -1;
+    bool frame_cwt = false;
+    for (int v = 0; v < FS2_MAX_VARIANCES; ++v) {
+        s->vpred[v] = nullptr;
+        if (v >= c.n_variances || c.var_level[v]) continue;
+        s->last_frame_v = v;
+        frame_cwt = frame_cwt || c.var_cwt[v];
+        s->vpred[v] = out && out->variances[v] ? out->variances[v] : (float*)ar.take(MT * 4);
+    }
+    s->cw_spec = frame_cwt ? (float*)ar.take(MT * 12 * 4) : nullptr;
+    s->cw_ms = frame_cwt ? (float*)ar.take((size_t)B * 8) : nullptr;
+    layout_layer_scratch(e, ar, B, T, &s->sc);
+    return !ar.overflow;
+}
+
+size_t persist_need(const fs2_engine* e, int B, int L) {
+    Arena a = Arena::counting();
+    PersistBufs p;
+    layout_persist(e, a, B, L, &p);
+    return a.off;
+}
+size_t encode_scratch_need(const fs2_engine* e, int B, int L) {
+    Arena a = Arena::counting();
+    EncodeScratch s;
+    layout_encode_scratch(e, a, B, L, &s);
+    return a.off;
+}
+size_t decode_scratch_need(const fs2_engine* e, int B, int T) {
+    Arena a = Arena::counting();
+    DecodeScratch s;
+    layout_decode_scratch(e, a, B, T, nullptr, &s);
+    return a.off;
 }
 // Grow-only engine arena, or the caller's buffer (fs2_set_workspace) which must already be large enough.
 int ensure_arena(fs2_engine* e, Arena& ar, size_t need, const char* what) {
@@ -1086,6 +1142,13 @@ int tap_store(fs2_engine* e, hipStream_t st, const std::string& name, const void
     if (r != FS2_OK) return fail(e, r, "convert launch failed");
     e->taps[name] = {dst, n * 4};
     return FS2_OK;
+}
+
+void drop_graphs(fs2_engine* e) {
+    for (auto& g : e->dgraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    for (auto& g : e->egraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    e->dgraphs.clear();
+    e->egraphs.clear();
 }
 
 }  // namespace
@@ -1134,22 +1197,10 @@ int fs2_clone(const fs2_engine* src, fs2_engine** out) {
     if (!src || !out) return FS2_ERR_ARG;
     if (!src->finalized) return FS2_ERR_STATE;
     fs2_engine* e = new fs2_engine();
-    e->cfg = src->cfg;
-    e->dt = src->dt; e->fdt = src->fdt; e->bdt = src->bdt; e->esz = src->esz;
+    static_cast<Model&>(*e) = *src;     // shared: the weights stay where they are (dev_allocs counts the owners)
+    static_cast<Switches&>(*e) = *src;  // inherited
     e->err[0] = 0;
     e->finalized = true;
-    e->fuse_predictor = src->fuse_predictor;
-    e->use_graph = src->use_graph;
-    e->zero_pad_mel = src->zero_pad_mel;
-    e->defer_ln = src->defer_ln;
-    e->fold_ln = src->fold_ln;
-    e->tune = src->tune;
-    e->front_split = src->front_split;
-    e->spec = src->spec;
-    e->dev_allocs = src->dev_allocs;
-    e->phone_table = src->phone_table; e->pe = src->pe; e->spk_w = src->spk_w; e->spk_b = src->spk_b;
-    e->enc = src->enc; e->dec = src->dec; e->dur = src->dur; e->vars = src->vars; e->mel = src->mel; e->priors_w = src->priors_w;
-    e->mel_f = src->mel_f; e->mel_wg = src->mel_wg; e->mel_fold = src->mel_fold;
     *out = e;
     return FS2_OK;
 }
@@ -1163,8 +1214,7 @@ int fs2_destroy(fs2_engine* e) {
     e->dbg.release();
     e->dbg_enc.release();
     if (e->h_pinned) (void)hipHostFree(e->h_pinned);
-    for (auto& g : e->dgraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    for (auto& g : e->egraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    drop_graphs(e);
     if (e->gev_in) (void)hipEventDestroy(e->gev_in);
     if (e->gev_out) (void)hipEventDestroy(e->gev_out);
     if (e->gstream) (void)hipStreamDestroy(e->gstream);
@@ -1209,10 +1259,14 @@ int fs2_finalize(fs2_engine* e) {
     for (int i = 0; i < c.dec_layers; ++i)
         CHK(make_layer(e, "decoder.layers." + std::to_string(i), H, c.dec_filter, c.dec_depthwise, &e->dec[i], e->bdt));
     if (H > 256) {  // stacks of wide depth-wise bf16 blocks: norm2 of block i - 1 folded into the in-projection of block i
-        for (int i = 1; i < c.enc_layers && c.enc_depthwise && e->fdt == FS2_BF16; ++i)
-            CHK(make_folded_in_proj(e, "encoder.layers." + std::to_string(i), "encoder.layers." + std::to_string(i - 1), H, &e->enc[i]));
-        for (int i = 1; i < c.dec_layers && c.dec_depthwise && e->bdt == FS2_BF16; ++i)
-            CHK(make_folded_in_proj(e, "decoder.layers." + std::to_string(i), "decoder.layers." + std::to_string(i - 1), H, &e->dec[i]));
+        const auto fold_in_proj = [&](const std::string& stack, int i, LayerW* L) -> int {
+            const std::string p = stack + std::to_string(i) + ".self_attn.in_proj_";
+            CHK(make_norm_folded(e, p + "weight", p + "bias", stack + std::to_string(i - 1) + ".norm2", &L->in_proj_f, &L->in_wg));
+            L->has_fold = true;
+            return FS2_OK;
+        };
+        for (int i = 1; i < c.enc_layers && c.enc_depthwise && e->fdt == FS2_BF16; ++i) CHK(fold_in_proj("encoder.layers.", i, &e->enc[i]));
+        for (int i = 1; i < c.dec_layers && c.dec_depthwise && e->bdt == FS2_BF16; ++i) CHK(fold_in_proj("decoder.layers.", i, &e->dec[i]));
     }
     CHK(make_predictor(e, "variance_adaptor.duration_predictor", c.dur_nlayers, c.dur_filter, c.dur_depthwise, &e->dur, e->fdt));
     e->vars.resize(c.n_variances);
@@ -1230,26 +1284,8 @@ int fs2_finalize(fs2_engine* e) {
     // (the row-scaled product with an fp32 store exists for narrow heads only - launch_gemm_plain: N < 192 -; a wider mel head keeps the
     //  normalise-only pass + the plain mel GEMM)
     if (H > 256 && c.dec_layers > 0 && c.dec_depthwise && e->bdt == FS2_BF16 && c.n_mels < 192) {
-        // mel = Linear(LN2_last(v2)) evaluated on v2: W' = W diag(gamma2), b' = b + W beta2, wg[n] = sum_k W'[n][k] as stored (make_folded_in_proj)
-        const std::string pp = "decoder.layers." + std::to_string(c.dec_layers - 1);
-        const HostTensor &w = W(e, "linear.weight"), &b = W(e, "linear.bias"), &g = W(e, pp + ".norm2.weight"), &be = W(e, pp + ".norm2.bias");
-        const int N = (int)b.data.size();
-        std::vector<float> wf((size_t)N * H), bf(N), wg(N);
-        for (int n = 0; n < N; ++n) {
-            double bacc = b.data[n], gacc = 0;
-            for (int k = 0; k < H; ++k) {
-                const float v = (float)((double)w.data[(size_t)n * H + k] * g.data[k]);
-                wf[(size_t)n * H + k] = v;
-                bacc += (double)w.data[(size_t)n * H + k] * be.data[k];
-                gacc += (double)bf16_to_f32(f32_to_bf16(v));
-            }
-            bf[n] = (float)bacc;
-            wg[n] = (float)gacc;
-        }
-        e->mel_f.N = N; e->mel_f.Cin = H; e->mel_f.taps = 1; e->mel_f.dt = FS2_BF16;
-        CHK(upload_mat(e, wf.data(), wf.size(), &e->mel_f.w, FS2_BF16));
-        CHK(upload_f32(e, bf.data(), bf.size(), &e->mel_f.b));
-        CHK(upload_f32(e, wg.data(), wg.size(), &e->mel_wg));
+        // mel = Linear(LN2_last(v2)) evaluated on v2
+        CHK(make_norm_folded(e, "linear.weight", "linear.bias", "decoder.layers." + std::to_string(c.dec_layers - 1) + ".norm2", &e->mel_f, &e->mel_wg));
         e->mel_fold = true;
     }
     e->priors_w.resize(c.n_priors);
@@ -1312,9 +1348,9 @@ int fs2_set_zero_pad_mel(fs2_engine* e, int32_t on) {
 
 int fs2_workspace_bytes(const fs2_engine* e, int32_t B, int32_t L, int32_t T, size_t* persist, size_t* scratch) {
     if (!e || B <= 0 || L <= 0 || T < 0) return FS2_ERR_ARG;
-    if (persist) *persist = persist_bytes(e, B, L);
+    if (persist) *persist = persist_need(e, B, L);
     if (scratch) {
-        const size_t enc = encode_scratch_bytes(e, B, L), dec = T > 0 ? decode_scratch_bytes(e, B, T) : 0;
+        const size_t enc = encode_scratch_need(e, B, L), dec = T > 0 ? decode_scratch_need(e, B, T) : 0;
         *scratch = enc > dec ? enc : dec;
     }
     return FS2_OK;
@@ -1339,8 +1375,7 @@ int fs2_set_frames(fs2_engine* e, int32_t T) {
     return FS2_OK;
 }
 
-static void drop_graphs(fs2_engine* e);
-static int encode_body(fs2_engine* e, const int64_t* phones, const float* speaker, const int32_t* forced, LayerScratch& sc, hipStream_t st);
+static int encode_body(fs2_engine* e, const int64_t* phones, const float* speaker, const int32_t* forced, const EncodeScratch& es, hipStream_t st);
 
 // One VarianceEncoder.forward (model.py:409-441) on the (B*S, H) rows x: the predictor, then x += Embedding[bucketize(pred * std + mean)]
 // (or of the forced indices / targets: model.py:417-422), optionally + pe + spk behind the last frame-level variance
@@ -1355,7 +1390,7 @@ static int variance_stage(fs2_engine* e, hipStream_t st, int v, void*& x, void*&
     const bool tail_ok = e->tune.pred_fuse_embed && !e->debug && !e->forced_idx[v] && !e->forced_tgt[v] && !c.var_cwt[v] &&
                          (e->fdt == FS2_BF16 || (e->fdt == FS2_F32 && e->front_split && e->vars[v].pred.wpk_lo)) && H == 256;
     const EmbedTail tl{xalt, e->vars[v].bins, e->vars[v].emb, c.var_nbins, c.var_std[v], c.var_mean[v],
-                       add_pe_spk ? e->pe : nullptr, add_pe_spk ? e->spk : nullptr};
+                       add_pe_spk ? e->pe : nullptr, add_pe_spk ? e->ps.spk : nullptr};
     bool tail_done = false;
     CHK(predictor(e, st, e->vars[v].pred, x, B, S, mask, vpred, sc, cwo, tail_ok ? &tl : nullptr, &tail_done));
     if (tail_done) {
@@ -1370,7 +1405,7 @@ static int variance_stage(fs2_engine* e, hipStream_t st, int v, void*& x, void*&
     }
     Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * M * H * esz);
     BucketArgs ba{x, vpred, e->vars[v].bins, e->vars[v].emb, c.var_nbins, c.var_std[v], c.var_mean[v],
-                  add_pe_spk ? e->pe : nullptr, add_pe_spk ? e->spk : nullptr, x, idx, B, S, (int)H,
+                  add_pe_spk ? e->pe : nullptr, add_pe_spk ? e->ps.spk : nullptr, x, idx, B, S, (int)H,
                   e->forced_idx[v], 0, e->forced_tgt[v]};
     if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "bucket_embed launch failed");
     return FS2_OK;
@@ -1385,7 +1420,6 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
     if (L > e->cfg.pe_len) return fail(e, FS2_ERR_SHAPE, "L=%d exceeds positional table %d", L, e->cfg.pe_len);
     hipStream_t st = (hipStream_t)stream;
     const fs2_config& c = e->cfg;
-    const size_t H = c.hidden, ML = (size_t)B * L, esz = e->esz;
     e->encoded = false;
     e->mid_forward = false;
     e->B = B;
@@ -1393,32 +1427,13 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
     e->taps.clear();
     // the arenas are reused across calls: earlier work on this stream that still reads them is
     // ordered before the kernels below; a (rare) growth reallocates after a device sync
-    CHK(ensure_arena(e, e->persist, persist_bytes(e, B, L), "persist"));
-    CHK(ensure_arena(e, e->scratch, encode_scratch_bytes(e, B, L), "scratch"));
-    e->spk = (float*)e->persist.take((size_t)B * H * 4);
-    e->xA = e->persist.take(ML * H * esz);
-    e->xB = e->persist.take(ML * H * esz);
-    e->dur_pred = (float*)e->persist.take(ML * 4);
-    e->d_dur = (int32_t*)e->persist.take(ML * 4);
-    e->d_cum = (int32_t*)e->persist.take(ML * 4);
-    e->d_totals = (int32_t*)e->persist.take((size_t)2 * B * 4);  // [totals | guard flags]: one read-back
-    e->d_guard = e->d_totals ? e->d_totals + B : nullptr;
-    e->src_mask = (uint8_t*)e->persist.take(ML);
-    bool pv_ok = true, pv_forced = false;
-    for (int v = 0; v < c.n_variances; ++v) {
-        e->pv_pred[v] = e->pv_spec[v] = e->pv_ms[v] = nullptr;
-        if (!c.var_level[v]) continue;
-        e->pv_pred[v] = (float*)e->persist.take(ML * 4);
-        if (c.var_cwt[v]) {
-            e->pv_spec[v] = (float*)e->persist.take(ML * 10 * 4);
-            e->pv_ms[v] = (float*)e->persist.take((size_t)B * 8);
-        }
-        pv_ok = pv_ok && e->pv_pred[v] && (!c.var_cwt[v] || (e->pv_spec[v] && e->pv_ms[v]));
-        pv_forced = pv_forced || e->forced_idx[v] || e->forced_tgt[v];
-    }
-    if (!e->src_mask || !pv_ok) return fail(e, FS2_ERR_NOMEM, "persist arena too small");
-    LayerScratch sc;
-    CHK(take_layer_scratch(e, e->scratch, B, L, &sc));
+    CHK(ensure_arena(e, e->persist, persist_need(e, B, L), "persist"));
+    CHK(ensure_arena(e, e->scratch, encode_scratch_need(e, B, L), "scratch"));
+    if (!layout_persist(e, e->persist, B, L, &e->ps)) return fail(e, FS2_ERR_NOMEM, "persist arena too small");
+    EncodeScratch es;
+    if (!layout_encode_scratch(e, e->scratch, B, L, &es)) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
+    bool pv_forced = false;
+    for (int v = 0; v < c.n_variances; ++v) pv_forced = pv_forced || (c.var_level[v] && (e->forced_idx[v] || e->forced_tgt[v]));
     if (e->h_pinned_cap < 2 * B) {
         if (e->h_pinned) (void)hipHostFree(e->h_pinned);
         e->h_pinned = nullptr;
@@ -1432,7 +1447,7 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
                                      (uint64_t)speaker, (uint64_t)forced, (uint64_t)e->h_pinned, (uint64_t)e->fuse_predictor, (uint64_t)e->tune.gen,
                                      (uint64_t)e->defer_ln, (uint64_t)e->front_split, (uint64_t)e->fold_ln};
         const bool plain = c.n_priors != 0 || pv_forced;  // a prior tensor / a phone-level forced target is a one-shot pointer of the call
-        CHK(run_phase(e, e->egraphs, key, plain, st, [&](hipStream_t s2) { return encode_body(e, phones, speaker, forced, sc, s2); }));
+        CHK(run_phase(e, e->egraphs, key, plain, st, [&](hipStream_t s2) { return encode_body(e, phones, speaker, forced, es, s2); }));
     }
     HIPCHK(e, hipStreamSynchronize(st));  // the one host sync of the forward (output shape)
     e->totals.assign(e->h_pinned, e->h_pinned + B);
@@ -1447,61 +1462,55 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
     return FS2_OK;
 }
 
-static int encode_body(fs2_engine* e, const int64_t* phones, const float* speaker, const int32_t* forced, LayerScratch& sc, hipStream_t st) {
+static int encode_body(fs2_engine* e, const int64_t* phones, const float* speaker, const int32_t* forced, const EncodeScratch& es, hipStream_t st) {
     const fs2_config& c = e->cfg;
+    const PersistBufs& ps = e->ps;
+    const LayerScratch& sc = es.sc;
     const int B = e->B, L = e->L;
     const size_t H = c.hidden, ML = (size_t)B * L, esz = e->esz;
     {   // speaker projection + phone embedding + PE                       fastspeech2.py:651-660
         Bracket br(e, FS2_K_ROWOPS, st, 0, ML * H * esz);
-        SpkProjArgs sp{speaker, e->spk_w, e->spk_b, e->spk, B, (int)H, c.dvec_dim};
+        SpkProjArgs sp{speaker, e->spk_w, e->spk_b, ps.spk, B, (int)H, c.dvec_dim};
         if (launch_spk_proj(sp, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "spk_proj launch failed");
-        EmbedArgs em{phones, e->phone_table, e->pe, e->spk, e->xA, e->src_mask, B, L, (int)H, c.n_phones};
+        EmbedArgs em{phones, e->phone_table, e->pe, ps.spk, ps.xA, ps.src_mask, B, L, (int)H, c.n_phones};
         if (launch_embed(em, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "embed launch failed");
-        MaskBitsArgs mb{e->src_mask, sc.bits, B, L, sc.nw64};
+        MaskBitsArgs mb{ps.src_mask, sc.bits, B, L, sc.nw64};
         if (launch_mask_bits(mb, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "mask_bits launch failed");
     }
-    CHK(run_stack(e, st, e->enc, e->xA, e->xB, B, L, c.enc_heads, sc, false));  // fastspeech2.py:685
+    CHK(run_stack(e, st, e->enc, ps.xA, ps.xB, B, L, c.enc_heads, sc, false));  // fastspeech2.py:685
     if (e->debug) {  // the reference's encoder output, i.e. before the prior embeddings are added
         const size_t need_d = al(ML * H * 4) + (size_t)c.n_variances * al(ML * 4) + 4096;
         if (need_d > e->dbg_enc.cap) HIPCHK(e, hipDeviceSynchronize());
         if (e->dbg_enc.reserve(need_d) != FS2_OK) return fail(e, FS2_ERR_NOMEM, "debug arena");
-        CHK(tap_store(e, st, "encoder_out", e->xA, ML * H, e->fdt, &e->dbg_enc));
+        CHK(tap_store(e, st, "encoder_out", ps.xA, ML * H, e->fdt, &e->dbg_enc));
     }
     if (c.n_priors) {                                                        // fastspeech2.py:687-692
         if (!e->priors_dev || e->priors_B != B) return fail(e, FS2_ERR_STATE, "fs2_set_priors(B=%d) required before fs2_encode", B);
         for (int p = 0; p < c.n_priors; ++p) {
-            BucketArgs ba{e->xA, e->priors_dev + (size_t)p * B, e->priors_w[p].bins, e->priors_w[p].emb, c.var_nbins,
-                          1.0f, 0.0f, nullptr, nullptr, e->xA, nullptr, B, L, (int)H, nullptr, 1};
+            BucketArgs ba{ps.xA, e->priors_dev + (size_t)p * B, e->priors_w[p].bins, e->priors_w[p].emb, c.var_nbins,
+                          1.0f, 0.0f, nullptr, nullptr, ps.xA, nullptr, B, L, (int)H, nullptr, 1};
             if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "prior embedding launch failed");
         }
         e->priors_dev = nullptr;  // one-shot
     }
     // duration predictor + rounding + prefix sums                          model.py:259,299-309
-    CHK(predictor(e, st, e->dur, e->xA, B, L, e->src_mask, e->dur_pred, sc));
+    CHK(predictor(e, st, e->dur, ps.xA, B, L, ps.src_mask, ps.dur_pred, sc));
     // phone-level variance encoders (variance_levels[i] == "phone"), in list order, AFTER the duration predictor has seen x and BEFORE
     // the length regulator: each adds its embedding to the rows that get regulated                      model.py:276-294
     // The rows ping-pong between xA and xB through local pointers (variance_stage swaps them where the embedding rode in the predictor
     // launch) and end in xA, where decode regulates them from: a replayed graph does not run this body (run_phase).
-    void* x = e->xA;
-    void* xalt = e->xB;
-    float* spec12 = nullptr;  // the CWT head's (M, 12) spectrogram: one buffer, reused by every phone-level CWT variance
+    void* x = ps.xA;
+    void* xalt = ps.xB;
     for (int v = 0; v < c.n_variances; ++v) {
         if (!c.var_level[v]) continue;
-        CwtOut cwo;
-        if (c.var_cwt[v]) {
-            if (!spec12) spec12 = (float*)e->scratch.take(ML * 12 * 4);
-            if (!spec12) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
-            cwo.spec12 = spec12;
-            cwo.mean_std = e->pv_ms[v];
-            cwo.spec_out = e->pv_spec[v];
-        }
-        CHK(variance_stage(e, st, v, x, xalt, B, L, e->src_mask, e->pv_pred[v], sc, c.var_cwt[v] ? &cwo : nullptr, false, e->dbg_enc));
+        const CwtOut cwo{es.spec12, ps.pv_ms[v], ps.pv_spec[v]};
+        CHK(variance_stage(e, st, v, x, xalt, B, L, ps.src_mask, ps.pv_pred[v], sc, c.var_cwt[v] ? &cwo : nullptr, false, e->dbg_enc));
         e->forced_idx[v] = nullptr, e->forced_tgt[v] = nullptr;  // one-shot, consumed here
     }
-    if (x != e->xA) HIPCHK(e, hipMemcpyAsync(e->xA, x, ML * H * esz, hipMemcpyDeviceToDevice, st));  // an odd number of swaps
-    DurationArgs da{e->dur_pred, e->src_mask, forced, e->d_dur, e->d_cum, e->d_totals, e->d_guard, B, L};
+    if (x != ps.xA) HIPCHK(e, hipMemcpyAsync(ps.xA, x, ML * H * esz, hipMemcpyDeviceToDevice, st));  // an odd number of swaps
+    DurationArgs da{ps.dur_pred, ps.src_mask, forced, ps.d_dur, ps.d_cum, ps.d_totals, ps.d_guard, B, L};
     if (launch_durations(da, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "durations launch failed");
-    HIPCHK(e, hipMemcpyAsync(e->h_pinned, e->d_totals, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(e->h_pinned, ps.d_totals, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st));
     return FS2_OK;
 }
 
@@ -1526,44 +1535,28 @@ static int decode_body(fs2_engine* e, const fs2_outputs* out, hipStream_t st) {
     const size_t H = c.hidden, MT = (size_t)B * T, ML = (size_t)B * L, esz = e->esz;
     // the phone-level outputs live in the engine's persistent arena (decode does not touch it): copied out BEHIND the decode
     // launches - three hipMemcpyAsync cost the host ~15 us each, which the GPU would otherwise spend idle at the seam
+    const PersistBufs& ps = e->ps;
     auto phone_outputs = [&]() -> int {
-        if (out->duration_prediction) HIPCHK(e, hipMemcpyAsync(out->duration_prediction, e->dur_pred, ML * 4, hipMemcpyDeviceToDevice, st));
-        if (out->duration_rounded) HIPCHK(e, hipMemcpyAsync(out->duration_rounded, e->d_dur, ML * 4, hipMemcpyDeviceToDevice, st));
-        if (out->src_mask) HIPCHK(e, hipMemcpyAsync(out->src_mask, e->src_mask, ML, hipMemcpyDeviceToDevice, st));
+        if (out->duration_prediction) HIPCHK(e, hipMemcpyAsync(out->duration_prediction, ps.dur_pred, ML * 4, hipMemcpyDeviceToDevice, st));
+        if (out->duration_rounded) HIPCHK(e, hipMemcpyAsync(out->duration_rounded, ps.d_dur, ML * 4, hipMemcpyDeviceToDevice, st));
+        if (out->src_mask) HIPCHK(e, hipMemcpyAsync(out->src_mask, ps.src_mask, ML, hipMemcpyDeviceToDevice, st));
         for (int v = 0; v < c.n_variances; ++v) {  // phone-level variances: (B, L) outputs, produced by the encode phase
             if (!c.var_level[v]) continue;
-            if (out->variances[v]) HIPCHK(e, hipMemcpyAsync(out->variances[v], e->pv_pred[v], ML * 4, hipMemcpyDeviceToDevice, st));
-            if (c.var_cwt[v] && out->var_spectrogram[v]) HIPCHK(e, hipMemcpyAsync(out->var_spectrogram[v], e->pv_spec[v], ML * 10 * 4, hipMemcpyDeviceToDevice, st));
-            if (c.var_cwt[v] && out->var_mean_std[v]) HIPCHK(e, hipMemcpyAsync(out->var_mean_std[v], e->pv_ms[v], (size_t)B * 8, hipMemcpyDeviceToDevice, st));
+            if (out->variances[v]) HIPCHK(e, hipMemcpyAsync(out->variances[v], ps.pv_pred[v], ML * 4, hipMemcpyDeviceToDevice, st));
+            if (c.var_cwt[v] && out->var_spectrogram[v]) HIPCHK(e, hipMemcpyAsync(out->var_spectrogram[v], ps.pv_spec[v], ML * 10 * 4, hipMemcpyDeviceToDevice, st));
+            if (c.var_cwt[v] && out->var_mean_std[v]) HIPCHK(e, hipMemcpyAsync(out->var_mean_std[v], ps.pv_ms[v], (size_t)B * 8, hipMemcpyDeviceToDevice, st));
         }
         return FS2_OK;
     };
     if (T == 0) { e->encoded = false; e->mid_forward = false; return phone_outputs(); }
 
-    CHK(ensure_arena(e, e->scratch, decode_scratch_bytes(e, B, T), "scratch"));  // too small: the caller may retry with more
+    CHK(ensure_arena(e, e->scratch, decode_scratch_need(e, B, T), "scratch"));  // too small: the caller may retry with more
     e->mid_forward = false;  // from here on the encoder state is consumed by this call
-    void* yA = e->scratch.take(MT * H * esz);
-    void* yB = e->scratch.take(MT * H * esz);
-    // mask / variance predictions go straight into the caller's buffers when it wants them
-    uint8_t* tmask = out->tgt_mask ? out->tgt_mask : (uint8_t*)e->scratch.take(MT);
-    float* vpred[FS2_MAX_VARIANCES] = {nullptr, nullptr, nullptr, nullptr};
-    int last_frame_v = -1;  // the last FRAME-level variance: pe + spk ride in its embedding add
-    for (int v = 0; v < c.n_variances; ++v) {
-        if (c.var_level[v]) continue;
-        last_frame_v = v;
-        vpred[v] = out->variances[v] ? out->variances[v] : (float*)e->scratch.take(MT * 4);
-        if (!vpred[v]) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
-    }
-    float *cw_spec = nullptr, *cw_ms = nullptr;
-    for (int v = 0; v < c.n_variances; ++v)
-        if (c.var_cwt[v] && !c.var_level[v] && !cw_spec) {
-            cw_spec = (float*)e->scratch.take(MT * 12 * 4);
-            cw_ms = (float*)e->scratch.take((size_t)B * 8);
-            if (!cw_spec || !cw_ms) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
-        }
-    LayerScratch sc;
-    CHK(take_layer_scratch(e, e->scratch, B, T, &sc));
-    if (!yA || !yB || !tmask) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
+    DecodeScratch ds;
+    if (!layout_decode_scratch(e, e->scratch, B, T, out, &ds)) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
+    void *yA = ds.yA, *yB = ds.yB;  // swapped below: locals (run_phase's rule for a body)
+    uint8_t* const tmask = ds.tmask;
+    const LayerScratch& sc = ds.sc;
     if (e->debug) {
         const size_t need_d = 3 * al(MT * H * 4) + (size_t)c.n_variances * al(MT * 4) + 4096;
         if (need_d > e->dbg.cap) HIPCHK(e, hipDeviceSynchronize());
@@ -1572,7 +1565,7 @@ static int decode_body(fs2_engine* e, const fs2_outputs* out, hipStream_t st) {
 
     {   // length regulator                                                  model.py:311,349-370
         Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * MT * H * esz);
-        RegulateArgs ra{e->xA, e->d_cum, e->d_totals, yA, tmask, B, L, T, (int)H};
+        RegulateArgs ra{ps.xA, ps.d_cum, ps.d_totals, yA, tmask, B, L, T, (int)H};
         if (launch_regulate(ra, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "regulate launch failed");
         MaskBitsArgs mb{tmask, sc.bits, B, T, sc.nw64};
         if (launch_mask_bits(mb, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "mask_bits launch failed");
@@ -1582,17 +1575,12 @@ static int decode_body(fs2_engine* e, const fs2_outputs* out, hipStream_t st) {
     const bool fuse_pe = !e->debug;
     for (int v = 0; v < c.n_variances; ++v) {
         if (c.var_level[v]) continue;  // phone level: done by the encode phase
-        CwtOut cwo;
-        if (c.var_cwt[v]) {
-            cwo.spec12 = cw_spec;
-            cwo.mean_std = out->var_mean_std[v] ? out->var_mean_std[v] : cw_ms;
-            cwo.spec_out = out->var_spectrogram[v];
-        }
-        CHK(variance_stage(e, st, v, yA, yB, B, T, tmask, vpred[v], sc, c.var_cwt[v] ? &cwo : nullptr, v == last_frame_v && fuse_pe, e->dbg));
+        const CwtOut cwo{ds.cw_spec, out->var_mean_std[v] ? out->var_mean_std[v] : ds.cw_ms, out->var_spectrogram[v]};
+        CHK(variance_stage(e, st, v, yA, yB, B, T, tmask, ds.vpred[v], sc, c.var_cwt[v] ? &cwo : nullptr, v == ds.last_frame_v && fuse_pe, e->dbg));
     }
     if (e->debug) CHK(tap_store(e, st, "adaptor_out", yA, MT * H, e->fdt));
-    if (!fuse_pe || last_frame_v < 0) {  // y = (x + pe) + spk               fastspeech2.py:705-718
-        BucketArgs ba{yA, nullptr, nullptr, nullptr, 0, 0.f, 0.f, e->pe, e->spk, yA, nullptr, B, T, (int)H, nullptr};
+    if (!fuse_pe || ds.last_frame_v < 0) {  // y = (x + pe) + spk            fastspeech2.py:705-718
+        BucketArgs ba{yA, nullptr, nullptr, nullptr, 0, 0.f, 0.f, e->pe, ps.spk, yA, nullptr, B, T, (int)H, nullptr};
         if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "pe/spk add launch failed");
     }
     if (e->fdt != e->bdt) {  // FS2_MIXED: the decoder's input, rounded once to the back dtype (yB is free until layer 0 writes it)
@@ -1606,19 +1594,12 @@ static int decode_body(fs2_engine* e, const fs2_outputs* out, hipStream_t st) {
     if (e->debug) CHK(tap_store(e, st, "decoder_out", yA, MT * H, e->bdt));
     if (out->mel && dec_pre) {                                               // fastspeech2.py:723
         const RowScale rs{sc.rsf, e->mel_wg};
-        CHK(gemm(e, st, e->mel_f, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, nullptr, -1, e->zero_pad_mel ? tmask : nullptr, nullptr, nullptr, &rs));
+        CHK(gemm(e, st, e->mel_f, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, {.zero_rows = e->zero_pad_mel ? tmask : nullptr, .rowscale = &rs}));
     } else if (out->mel) {
-        CHK(gemm(e, st, e->mel, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, nullptr, -1, e->zero_pad_mel ? tmask : nullptr));
+        CHK(gemm(e, st, e->mel, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, {.zero_rows = e->zero_pad_mel ? tmask : nullptr}));
     }
     for (int v = 0; v < FS2_MAX_VARIANCES; ++v) e->forced_idx[v] = nullptr, e->forced_tgt[v] = nullptr;  // one-shot
     return phone_outputs();
-}
-
-static void drop_graphs(fs2_engine* e) {
-    for (auto& g : e->dgraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    for (auto& g : e->egraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    e->dgraphs.clear();
-    e->egraphs.clear();
 }
 
 // A phase of the forward (encode: embedding .. durations + the totals' copy to pinned memory; decode: length regulator .. mel head:
@@ -1698,10 +1679,10 @@ int fs2_decode(fs2_engine* e, const fs2_outputs* out, void* stream) {
     if (plain) return decode_body(e, out, st);
     // the arena may grow (device sync + hipMalloc) only outside a capture; the body's own call is then a no-op
     const char* base0 = e->scratch.base;
-    CHK(ensure_arena(e, e->scratch, decode_scratch_bytes(e, e->B, e->T), "scratch"));
+    CHK(ensure_arena(e, e->scratch, decode_scratch_need(e, e->B, e->T), "scratch"));
     if (e->scratch.base != base0) drop_graphs(e);
     std::vector<uint64_t> key = {(uint64_t)e->B, (uint64_t)e->L, (uint64_t)e->T, (uint64_t)e->scratch.base, (uint64_t)e->persist.base,
-                                 (uint64_t)e->xA, (uint64_t)e->d_cum, (uint64_t)e->spk, (uint64_t)e->zero_pad_mel, (uint64_t)e->fuse_predictor, (uint64_t)e->tune.gen,
+                                 (uint64_t)e->ps.xA, (uint64_t)e->ps.d_cum, (uint64_t)e->ps.spk,(uint64_t)e->zero_pad_mel, (uint64_t)e->fuse_predictor, (uint64_t)e->tune.gen,
                                  (uint64_t)e->defer_ln, (uint64_t)e->front_split, (uint64_t)e->fold_ln, (uint64_t)out->mel, (uint64_t)out->tgt_mask,
                                  (uint64_t)out->duration_prediction, (uint64_t)out->duration_rounded, (uint64_t)out->src_mask};
     for (int v = 0; v < FS2_MAX_VARIANCES; ++v) {

@@ -56,6 +56,39 @@ def test_create_validates_config(lib):
     lib.fs2_destroy(h)
 
 
+def _workspace_configs():
+    cwt_stats = {"pitch": {"min": 0.2, "max": 5.0, "mean": 0.1, "std": 1.5}, "energy": {"min": 0.3, "max": 4.0, "mean": 0.0, "std": 1.0},
+                 "snr": {"min": -1.0, "max": 4.0, "mean": 1.2, "std": 2.0}}
+    phone_cwt2 = Fs2Config(**{**preset("c2").to_dict(), "variance_levels": ["phone", "phone", "frame"],
+                              "variance_transforms": ["cwt", "cwt", "none"], "stats": cwt_stats})
+    return [("c2-bf16", preset("c2"), _lib.FS2_BF16), ("c3-bf16", preset("c3"), _lib.FS2_BF16),
+            ("ref-default-fp32", preset("ref-default"), _lib.FS2_F32), ("c2-phone-cwt2-bf16", phone_cwt2, _lib.FS2_BF16)]
+
+
+def test_workspace_bytes_grow_with_the_shape(lib):
+    """Callers size their two buffers once, for their largest (B, L, T), and run every smaller shape in them: so both sizes
+    fs2_workspace_bytes reports must be non-decreasing in each of B, L and T, and persist (the encode phase's state) must not
+    depend on T.  No device needed: the sizes are the workspace layout run on an arena that only counts."""
+    Bs, Ls, Ts = (1, 4), (1, 63, 64, 65), (0, 1, 64, 65, 300)
+    for name, cfg, dtype in _workspace_configs():
+        st, h = _create(lib, cfg, dtype)
+        assert st == 0, lib.fs2_last_error(h)
+        size = {}
+        for B in Bs:
+            for L in Ls:
+                for T in Ts:
+                    p, s = C.c_size_t(), C.c_size_t()
+                    assert lib.fs2_workspace_bytes(h, B, L, T, C.byref(p), C.byref(s)) == 0
+                    assert p.value > 0 and s.value > 0, (name, B, L, T)
+                    size[B, L, T] = (p.value, s.value)
+        lib.fs2_destroy(h)
+        for (B, L, T), (p, s) in size.items():
+            assert p == size[B, L, Ts[0]][0], (name, B, L, T)  # persist: no T in it
+            bigger = [(b2, L, T) for b2 in Bs if b2 > B] + [(B, l2, T) for l2 in Ls if l2 > L] + [(B, L, t2) for t2 in Ts if t2 > T]
+            for k in bigger:
+                assert size[k][0] >= p and size[k][1] >= s, (name, (B, L, T), k)
+
+
 def test_recipe_with_five_priors_fits_the_abi(lib):
     # scripts/train.sh:27,49 of the reference: four variances, five priors
     names = ["pitch", "energy", "snr", "srmr"]
