@@ -51,7 +51,14 @@ enum fs2_dtype {
     FS2_BF16 = 1,
     FS2_MIXED = 2,    /* engine modes only (fs2_config.dtype): fp32 "front" + bf16 "back", see fs2_config.dtype */
     FS2_MIXED_X3 = 3, /* the same with the front's GEMMs / convs as bf16 x 3 split products of fp32 operands */
-    FS2_F32_X3 = 4    /* engine mode: F32 storage and row arithmetic everywhere, EVERY GEMM / conv as bf16 x 3 split products */
+    FS2_F32_X3 = 4,   /* engine mode: F32 storage and row arithmetic everywhere, EVERY GEMM / conv as bf16 x 3 split products */
+    FS2_F16 = 5,      /* storage / operator dtype: IEEE binary16 operands, fp32 accumulate.  Stores SATURATE: a value beyond +-65504 (an
+                         infinity included) is stored as +-65504, NaN stays NaN, everything else rounds to nearest-even (subnormals
+                         included) - on the device and in fs2_finalize's weight conversion alike.  Taken by fs2_op_gemm / _gemm_add /
+                         _gemm_ln / _gemm_stats / _gemm_rowscale_dt, fs2_op_attention (+ _scratch_bytes), fs2_op_attn_out_ln, fs2_op_layernorm, fs2_op_dwconv and
+                         fs2_op_convert; every other operator (the training step's, bgemm, the attention backward, the predictor,
+                         the row kernels of the front, the vocoder) answers FS2_ERR_ARG / FS2_ERR_SHAPE, a *_supported query 0 */
+    FS2_MIXED_F16_X3 = 6 /* engine mode: MIXED_X3's front, launch for launch; the back (decoder stack, the mel Linear's operands) in F16 */
 };
 
 /* Mirrors the hparams that shape FastSpeech2.forward (fastspeech2.py:46-130). */
@@ -71,7 +78,10 @@ typedef struct fs2_config {
                               6e-8 or bf16's 4e-3): 3 bf16 MFMAs per 32 k-values instead of 8 fp32 MFMAs;
                               F32_X3 = F32 with every GEMM / conv (both sides) evaluated that way: the parity mode's layout,
                               attention, LayerNorm, heads and decisions logic at about half its time (C2: 8.1 vs 15.2 ms per
-                              forward); measured 1.4e-5 on the mel against F32 under equal decisions */
+                              forward); measured 1.4e-5 on the mel against F32 under equal decisions;
+                              MIXED_F16_X3 = MIXED_X3 with the decoder's stored tensors and matrix operands in IEEE binary16 instead
+                              of bf16 (three more mantissa bits at the same MFMA rate; saturating stores, see FS2_F16): the
+                              front, and with it every decision, is MIXED_X3's bit for bit; the mel leaves as fp32 */
     int32_t n_phones;      /* len(phone2id) */
     int32_t hidden;        /* encoder_hidden == decoder_hidden */
     int32_t n_mels;
@@ -288,6 +298,14 @@ int fs2_op_gemm_add(int32_t dtype, const void* x, const void* w, const float* bi
  * (fastspeech2.py:723; N < 192: the 128 x 128 kernel's epilogue).  bf16 only; FS2_ERR_SHAPE otherwise. */
 int fs2_op_gemm_rowscale(const void* x, const void* w, const float* bias, const float* rowstats, const float* wg,
                          void* c, int32_t M, int32_t N, int32_t Cin, void* hip_stream);
+/* The same with the operand type named: dtype = FS2_BF16 or FS2_F16 (x, w), out_dtype = dtype, or FS2_F32 for a narrow head (N < 192). */
+int fs2_op_gemm_rowscale_dt(int32_t dtype, int32_t out_dtype, const void* x, const void* w, const float* bias, const float* rowstats,
+                            const float* wg, void* c, int32_t M, int32_t N, int32_t Cin, void* hip_stream);
+/* The deferred-LayerNorm epilogue by itself (N >= 192): c = v = act(x w^T + bias) [+ res] (res may be NULL) stored unnormalised, and per
+ * row and 256-column tile the partial (sum v, sum v^2) -> stats (M, ceil(N / 256)) float2, the input of fs2_op_rowstats_finish.
+ * dtype (x, w, res, c) = FS2_F32, FS2_BF16 or FS2_F16; a residual behind a ReLU is FS2_ERR_SHAPE. */
+int fs2_op_gemm_stats(int32_t dtype, const void* x, const void* w, const float* bias, const void* res, void* c, float* stats, int32_t M,
+                      int32_t N, int32_t Cin, int32_t relu, void* hip_stream);
 /* parts (M, nparts) float2 partial (sum, sum of squares) over ncols columns per row - what the deferred-LayerNorm GEMM epilogue
  * leaves, one per 256-column tile - -> out (M) float2 (rstd, rstd * mean) */
 int fs2_op_rowstats_finish(const float* parts, int32_t nparts, int32_t ncols, float eps, float* out, int32_t M, void* hip_stream);
@@ -363,8 +381,8 @@ int fs2_op_embed(int32_t dtype, const int64_t* phones, const float* table, const
 int fs2_op_spk_proj(const float* dvec, const float* w, const float* b, float* spk, int32_t B, int32_t H,
                     int32_t Din, void* hip_stream);
 /* The encoder-side fused launch (r06; nn.MultiheadAttention's core + out_proj + the residual + norm1 of ConformerEncoderLayer.forward,
- * model.py:108-116, behind the in-projection GEMM): out = LayerNorm(res + softmax(q k^T / sqrt(d) + key padding) v w_out^T + bias), bf16,
- * H = 256, two heads.  qkv (B*S, 3H), key_pad_mask (B, S) 1 = pad, w_out (H, H) bf16, res / out (B*S, H) bf16 (out may alias res),
+ * model.py:108-116, behind the in-projection GEMM): out = LayerNorm(res + softmax(q k^T / sqrt(d) + key padding) v w_out^T + bias), bf16
+ * or f16 (dtype names the type of qkv, w_out, res and out), H = 256, two heads.  qkv (B*S, 3H), key_pad_mask (B, S) 1 = pad, w_out (H, H), res / out (B*S, H) in that dtype (out may alias res),
  * scratch = H * H * 2 + B * ceil(S / 64) * 8 bytes.  FS2_ERR_SHAPE for other shapes / dtypes. */
 int fs2_op_attn_out_ln(int32_t dtype, const void* qkv, const uint8_t* key_pad_mask, const void* w_out, const float* bias, const void* res,
                        const float* ln_g, const float* ln_b, void* out, void* scratch, int32_t B, int32_t S, int32_t H, int32_t heads,
@@ -406,8 +424,13 @@ int fs2_op_soft_dtw(const float* x, const float* y, int32_t B, int32_t N, int32_
 size_t fs2_op_soft_dtw_grad_scratch_bytes(int32_t B, int32_t N, int32_t M);
 int fs2_op_soft_dtw_grad(const float* x, const float* y, int32_t B, int32_t N, int32_t M, int32_t D, float gamma, float* out,
                          float* grad_x, void* scratch, size_t scratch_bytes, void* hip_stream);
-/* dtype conversion helpers for tests: fp32 <-> engine dtype, n elements, device pointers */
+/* dtype conversion helpers for tests: fp32 <-> engine dtype (FS2_BF16 or FS2_F16; fp32 -> FS2_F16 saturates, see fs2_dtype), n elements,
+ * device pointers */
 int fs2_op_convert(int32_t src_dtype, int32_t dst_dtype, const void* src, void* dst, size_t n, void* hip_stream);
+/* The same fp32 -> FS2_F16 conversion on the HOST (host pointers, no device needed): the routine fs2_finalize converts the decoder's
+ * weights with in FS2_MIXED_F16_X3, bit for bit what a device store gives - clamp to +-65504, round to nearest-even, NaN kept.  For
+ * callers that prepare FS2_F16 operands of the fs2_op_* entry points themselves. */
+int fs2_host_f32_to_f16(const float* src, uint16_t* dst, size_t n);
 
 /* ================================================================================================
  * Training step: the operators the reference gets from autograd in

@@ -26,6 +26,7 @@ FS2_NAME_LEN = 32
 FS2_OK = 0
 FS2_ERR_HIP, FS2_ERR_SHAPE, FS2_ERR_ARG, FS2_ERR_WEIGHT, FS2_ERR_STATE, FS2_ERR_NOMEM = 1, 2, 3, 4, 5, 6
 FS2_F32, FS2_BF16, FS2_MIXED, FS2_MIXED_X3, FS2_F32_X3 = 0, 1, 2, 3, 4
+FS2_F16, FS2_MIXED_F16_X3 = 5, 6  # IEEE binary16 storage (operators) / the engine mode built on it (include/fs2.h)
 K_CONV_GEMM, K_GEMM, K_ATTENTION, K_ROWOPS, K_DEC_FFN_CONV1, K_DEC_ATTENTION, K_ENC_MHA, K_PREDICTOR = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -135,6 +136,7 @@ def load():
     lib.fs2_profile_read.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.fs2_op_convert.argtypes = [i32, i32, vp, vp, C.c_size_t, vp]
+    lib.fs2_host_f32_to_f16.argtypes = [vp, vp, C.c_size_t]
     lib.fs2_op_predictor.argtypes = [i32, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.fs2_op_attn_out_ln.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.fs2_op_predictor_dw.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -152,6 +154,8 @@ def load():
     lib.fs2_op_gemm_relu_dropout.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_uint64, C.c_uint64, vp]
     lib.fs2_op_gemm_add.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.fs2_op_gemm_rowscale.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.fs2_op_gemm_rowscale_dt.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.fs2_op_gemm_stats.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.fs2_op_rowstats_finish.argtypes = [vp, i32, i32, C.c_float, vp, i32, vp]
     lib.fs2_op_gemm_head.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.fs2_op_head_finish.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, i32, vp]

@@ -352,13 +352,13 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 2 && D == 128) ? 2 : 1) void
                     const int flat = ch * Vec16<T>::N + e;
                     f[e] = sacc[flat >> 4][flat & 15];
                 }
-                pf[ch] = Vec16<T>::pack(f);
+                pf[ch] = Vec16<T>::pack_bounded(f);
                 if constexpr (X3) {  // p = head + tail
                     float g[Vec16<T>::N];
                     Vec16<T>::unpack(pf[ch], g);
     #pragma unroll
                     for (int e = 0; e < Vec16<T>::N; ++e) g[e] = f[e] - g[e];
-                    pfl[ch] = Vec16<T>::pack(g);
+                    pfl[ch] = Vec16<T>::pack_bounded(g);
                 }
             }
             }
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 2 && D == 128) ? 2 : 1) void
                 if constexpr (sizeof(OT) == 4) {
                     *(float4*)(dst + dv) = make_float4(v0, v1, v2, v3);
                 } else {
-                    *(uint2*)(dst + dv) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+                    *(uint2*)(dst + dv) = make_uint2(pack2<OT>(v0, v1), pack2<OT>(v2, v3));
                 }
             }
     }
@@ -462,9 +462,10 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 2 && D == 128) ? 2 : 1) void
 struct AttnOutSmem {
     static constexpr int TILE_B = 128 * 128;  // a 64-key x 128-dim bf16 K (or row-major V) tile
 };
+template <typename T>  // bf16 or f16
 __global__ __launch_bounds__(256, 2) void attn_out_ln_kernel(AttnOutArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using T = bf16;
+    static_assert(sizeof(T) == 2, "16-bit storage");
     constexpr int D = 128, HH = 256, KVB = 64, E16 = 8, KC = Mma32<T>::K_PER_CHUNK, NQC = D / KC, KRB = D * 2, KNS = KRB / 16;
     constexpr int NKB = KVB / 32, ND = D / 32, TILE_B = AttnOutSmem::TILE_B, NINST = TILE_B / 1024 / 2;
     constexpr float THR = 6.0f;
@@ -629,7 +630,7 @@ __global__ __launch_bounds__(256, 2) void attn_out_ln_kernel(AttnOutArgs p) {
                     const int flat = ch * 8 + e;
                     f[e] = sacc[flat >> 4][flat & 15];
                 }
-                pf[ch] = Vec16<T>::pack(f);
+                pf[ch] = Vec16<T>::pack_bounded(f);
             }
         }
         dma_drain();
@@ -675,8 +676,8 @@ __global__ __launch_bounds__(256, 2) void attn_out_ln_kernel(AttnOutArgs p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int L = h * 16 + nd * 4 + g;
-                const uint2 o2 = make_uint2(pack_bf16x2(oacc[nd][4 * g + 0] * inv, oacc[nd][4 * g + 1] * inv),
-                                            pack_bf16x2(oacc[nd][4 * g + 2] * inv, oacc[nd][4 * g + 3] * inv));
+                const uint2 o2 = make_uint2(pack2<T>(oacc[nd][4 * g + 0] * inv, oacc[nd][4 * g + 1] * inv),
+                                            pack2<T>(oacc[nd][4 * g + 2] * inv, oacc[nd][4 * g + 3] * inv));
                 *(uint2*)(slab + row * (HH * 2) + (sw.slot(L, row) << 4) + hi * 8) = o2;
             }
     }
@@ -783,15 +784,16 @@ __global__ __launch_bounds__(256, 2) void attn_out_ln_kernel(AttnOutArgs p) {
 }
 
 bool attn_out_ln_supported(int dtype, int H, int heads, int S) {
-    return dtype == FS2_BF16 && H == 256 && heads == 2 && S >= 1 && (size_t)S * 3 * H * 2 < 0xFFFFF000ull;
+    return is_16bit(dtype) && H == 256 && heads == 2 && S >= 1 && (size_t)S * 3 * H * 2 < 0xFFFFF000ull;
 }
-int launch_attn_out_ln(const AttnOutArgs& a, hipStream_t stream) {
-    if (!attn_out_ln_supported(FS2_BF16, a.H, a.heads, a.S)) return FS2_ERR_SHAPE;
+int launch_attn_out_ln(const AttnOutArgs& a, int dtype, hipStream_t stream) {
+    if (!attn_out_ln_supported(dtype, a.H, a.heads, a.S)) return FS2_ERR_SHAPE;
     if (!a.qkv || !a.kbits || !a.wpk || !a.bias || !a.res || !a.ln_g || !a.ln_b || !a.out || a.out == a.qkv) return FS2_ERR_ARG;
     if (((uintptr_t)a.qkv | (uintptr_t)a.wpk | (uintptr_t)a.bias | (uintptr_t)a.res | (uintptr_t)a.ln_g | (uintptr_t)a.ln_b | (uintptr_t)a.out) & 15) return FS2_ERR_ARG;
     if (a.B <= 0) return FS2_OK;
     const int nq = (a.S + 63) / 64, B8 = (a.B + 7) / 8 * 8;
-    hipLaunchKernelGGL(attn_out_ln_kernel, dim3((unsigned)(B8 * nq)), dim3(256), 0, stream, a);
+    if (dtype == FS2_F16) hipLaunchKernelGGL(attn_out_ln_kernel<f16>, dim3((unsigned)(B8 * nq)), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(attn_out_ln_kernel<bf16>, dim3((unsigned)(B8 * nq)), dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
@@ -854,11 +856,12 @@ static int launch_td(const AttnArgs& a, hipStream_t stream) {
 
 int launch_transpose_v(const AttnArgs& a, int dtype, hipStream_t stream) {
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
-    if (dtype == FS2_BF16) return FS2_OK;  // bf16 attention reads V row-major with the hardware transpose read
+    if (is_16bit(dtype)) return FS2_OK;  // 16-bit attention reads V row-major with the hardware transpose read (ds_read_b64_tr_b16: any 16-bit type)
+    if (dtype != FS2_F32) return FS2_ERR_ARG;
     if (a.Spad % 64 || a.Spad < a.S || a.H % a.heads) return FS2_ERR_SHAPE;
     const int d = a.H / a.heads;
 #define FS2_TV_CASE(DD)                                                          \
-    if (d == DD) return dtype == FS2_BF16 ? launch_tv<bf16, DD>(a, stream) : launch_tv<float, DD>(a, stream);
+    if (d == DD) return launch_tv<float, DD>(a, stream);
     FS2_TV_CASE(32)
     FS2_TV_CASE(64)
     FS2_TV_CASE(128)
@@ -894,6 +897,8 @@ static int launch_x3(const AttnArgs& a, hipStream_t stream) {
 
 
 int launch_attention(const AttnArgs& a, int dtype, hipStream_t stream) {
+    if (!is_storage_dtype(dtype)) return FS2_ERR_ARG;
+    if (dtype == FS2_F16 && (a.lse2 || a.drop_p > 0.f)) return FS2_ERR_ARG;  // the training path's by-products: fp32 / bf16 only
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
     if (a.Spad % 64 || a.Spad < a.S || a.H % a.heads) return FS2_ERR_SHAPE;
     if (a.qkv_lo) {  // split arithmetic: bf16 head / tail operands, fp32 rows out (dtype names the STORAGE mode: fp32)
@@ -922,7 +927,7 @@ int launch_attention(const AttnArgs& a, int dtype, hipStream_t stream) {
     }
     const int d = a.H / a.heads;
 #define FS2_ATTN_CASE(DD)                                                        \
-    if (d == DD) return dtype == FS2_BF16 ? launch_td<bf16, DD>(a, stream) : launch_td<float, DD>(a, stream);
+    if (d == DD) return dtype == FS2_BF16 ? launch_td<bf16, DD>(a, stream) : (dtype == FS2_F16 ? launch_td<f16, DD>(a, stream) : launch_td<float, DD>(a, stream));
     FS2_ATTN_CASE(32)
     FS2_ATTN_CASE(64)
     FS2_ATTN_CASE(128)

@@ -656,6 +656,8 @@ __global__ __launch_bounds__(256, NQBMAX >= 2 ? 1 : 2) void attention_pipe_kerne
 }  // namespace
 
 // bf16, head dim 128, no attention-weight dropout; variant: 2 = 64 queries per wave (one workgroup per CU), 1 = 32 (two)
+// bf16 ONLY, never FS2_F16: the kernel keeps no running maximum - p = exp2(s - m0) with m0 taken from a row's first 32 keys - which
+// bf16's exponent range absorbs and binary16's does not (p overflows at 2^16).  f16 attention is attention_kernel's online softmax.
 bool attention_pipe_supported(const AttnArgs& a, int dtype) {
     return dtype == FS2_BF16 && a.H == a.heads * kD && a.drop_p == 0.f && a.S >= 1 && a.S <= 4096;
 }

@@ -984,6 +984,7 @@ size_t col_sum_ws_bytes(int M, int N, int seg) {
     return (size_t)CS_CTR * sizeof(unsigned) + (size_t)nseg * cs_chunks(M, seg) * N * sizeof(float);
 }
 int launch_col_sum(const ColSumArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the training step takes fp32 or bf16 tensors
     if (a.M <= 0 || a.N <= 0 || (a.seg > 0 && a.M % a.seg) || !a.ws) return FS2_ERR_SHAPE;
     if (a.out2 && (a.n1 <= 0 || a.n1 >= a.N)) return FS2_ERR_ARG;
     const int nseg = a.seg > 0 ? a.M / a.seg : 1, nchunk = cs_chunks(a.M, a.seg);
@@ -1028,9 +1029,10 @@ int launch_softmax_bwd(const SoftmaxArgs& a, int dtype, hipStream_t stream) {
 }
 
 int launch_ew(const EwArgs& a0, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the training step takes fp32 or bf16 tensors
     if (!a0.n) return FS2_OK;
     EwArgs a = a0;
-    const size_t ne = dtype == FS2_BF16 ? 8 : 4, esz = dtype == FS2_BF16 ? 2 : 4;
+    const size_t esz = elem_bytes(dtype), ne = 16 / esz;
     const bool al = (((uintptr_t)a.a | (uintptr_t)a.b | (uintptr_t)a.out) & 15) == 0;
     if (al && a.n >= ne) {
         EwArgs v = a;
@@ -1059,6 +1061,7 @@ size_t scatter_rows_ws_bytes(int R, int H, int V) {
     return (size_t)nchunk * V * H * sizeof(float) + col_sum_ws_bytes(nchunk, V * H, 0);
 }
 int launch_scatter_rows(const ScatterRowsArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the training step takes fp32 or bf16 tensors
     if (a.R <= 0 || a.V <= 0 || (!a.idx32 && !a.idx64)) return FS2_ERR_ARG;
     if (a.ws && scatter_chunked(a.R, a.V)) {
         const int nchunk = (a.R + SR_CHUNK - 1) / SR_CHUNK;
@@ -1074,6 +1077,7 @@ int launch_scatter_rows(const ScatterRowsArgs& a, int dtype, hipStream_t stream)
 }
 
 int launch_regulate_bwd(const RegulateBwdArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the training step takes fp32 or bf16 tensors
     const long n = (long)a.B * a.L;
     const dim3 g((unsigned)((n + 3) / 4));
     if (dtype == FS2_BF16) hipLaunchKernelGGL(regulate_bwd_kernel<bf16>, g, dim3(256), 0, stream, a);

@@ -24,6 +24,9 @@ int launch_convert(const ConvertArgs& a, int sdt, int ddt, hipStream_t st) {
     else if (sdt == FS2_F32 && ddt == FS2_BF16) hipLaunchKernelGGL((convert_kernel<float, bf16>), g, b, 0, st, (const float*)a.src, (bf16*)a.dst, a.n);
     else if (sdt == FS2_BF16 && ddt == FS2_F32) hipLaunchKernelGGL((convert_kernel<bf16, float>), g, b, 0, st, (const bf16*)a.src, (float*)a.dst, a.n);
     else if (sdt == FS2_BF16 && ddt == FS2_BF16) hipLaunchKernelGGL((convert_kernel<bf16, bf16>), g, b, 0, st, (const bf16*)a.src, (bf16*)a.dst, a.n);
+    else if (sdt == FS2_F32 && ddt == FS2_F16) hipLaunchKernelGGL((convert_kernel<float, f16>), g, b, 0, st, (const float*)a.src, (f16*)a.dst, a.n);
+    else if (sdt == FS2_F16 && ddt == FS2_F32) hipLaunchKernelGGL((convert_kernel<f16, float>), g, b, 0, st, (const f16*)a.src, (float*)a.dst, a.n);
+    else if (sdt == FS2_F16 && ddt == FS2_F16) hipLaunchKernelGGL((convert_kernel<f16, f16>), g, b, 0, st, (const f16*)a.src, (f16*)a.dst, a.n);
     else return FS2_ERR_ARG;
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
@@ -178,15 +181,36 @@ int fs2_op_gemm_add(int32_t dtype, const void* x, const void* w, const float* bi
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
 }
 
+// The deferred-LayerNorm epilogue by itself: c = v = act(x w^T + bias) [+ res] stored as it is, and per row and 256-column tile the
+// partial (sum v, sum v^2) -> stats (M, ceil(N / 256)) float2 - what a wide depth-wise block's out-projection / conv2 leaves for
+// fs2_op_rowstats_finish and the consumers that normalise on load.  dtype: FS2_F32, FS2_BF16 or FS2_F16 (x, w, res, c).
+int fs2_op_gemm_stats(int32_t dtype, const void* x, const void* w, const float* bias, const void* res, void* c, float* stats, int32_t M,
+                      int32_t N, int32_t Cin, int32_t relu, void* stream) {
+    if (!x || !w || !c || !stats) return FS2_ERR_ARG;
+    GemmArgs a;
+    a.X = x; a.W = w; a.bias = bias; a.C = c;
+    a.M = M; a.N = N; a.K = Cin; a.ldx = Cin; a.ldc = N;
+    a.Cin = Cin; a.taps = 1; a.pad = 0; a.S = M; a.relu = relu;
+    a.epi_res = res; a.stats_out = stats; a.ln_eps = 1e-5f;
+    if (N < 192) return FS2_ERR_SHAPE;  // slab / persistent kernels only
+    return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
+}
+
 int fs2_op_gemm_rowscale(const void* x, const void* w, const float* bias, const float* rowstats, const float* wg,
                          void* c, int32_t M, int32_t N, int32_t Cin, void* stream) {
+    return fs2_op_gemm_rowscale_dt(FS2_BF16, FS2_BF16, x, w, bias, rowstats, wg, c, M, N, Cin, stream);
+}
+// ... with the operand type named: dtype = FS2_BF16 or FS2_F16 (x, w), out_dtype = the same, or FS2_F32 for a narrow head (N < 192)
+int fs2_op_gemm_rowscale_dt(int32_t dtype, int32_t out_dtype, const void* x, const void* w, const float* bias, const float* rowstats,
+                            const float* wg, void* c, int32_t M, int32_t N, int32_t Cin, void* stream) {
     if (!x || !w || !bias || !rowstats || !wg || !c) return FS2_ERR_ARG;
+    if (!is_16bit(dtype)) return FS2_ERR_ARG;
     GemmArgs a;
     a.X = x; a.W = w; a.bias = bias; a.C = c;
     a.M = M; a.N = N; a.K = Cin; a.ldx = Cin; a.ldc = N;
     a.Cin = Cin; a.taps = 1; a.pad = 0; a.S = M; a.relu = 0;
     a.rs_stats = rowstats; a.rs_wg = wg;
-    return launch_gemm(a, FS2_BF16, FS2_BF16, (hipStream_t)stream);
+    return launch_gemm(a, dtype, out_dtype, (hipStream_t)stream);
 }
 int fs2_op_rowstats_finish(const float* parts, int32_t nparts, int32_t ncols, float eps, float* out, int32_t M, void* stream) {
     return launch_rowstats_finish(parts, nparts, ncols, eps, out, M, (hipStream_t)stream);
@@ -277,7 +301,7 @@ size_t fs2_op_attention_scratch_bytes(int32_t dtype, int32_t B, int32_t S, int32
     (void)heads;
     const size_t Spad = ((size_t)S + 63) / 64 * 64;
     if (bits_bytes) *bits_bytes = (size_t)B * (Spad / 64) * 8;
-    return (size_t)B * H * Spad * (dtype == FS2_BF16 ? 2 : 4);
+    return (size_t)B * H * Spad * elem_bytes(dtype);
 }
 
 int fs2_op_attention(int32_t dtype, const void* qkv, const uint8_t* key_pad_mask, void* out, void* vt_scratch,
@@ -314,7 +338,7 @@ int fs2_op_attn_out_ln(int32_t dtype, const void* qkv, const uint8_t* key_pad_ma
     a.qkv = qkv; a.kbits = bits; a.wpk = scratch; a.bias = bias; a.res = res; a.ln_g = ln_g; a.ln_b = ln_b; a.out = out;
     a.B = B; a.S = S; a.H = H; a.heads = heads; a.nw64 = nw64;
     a.scale_log2e = (float)(1.4426950408889634 / sqrt((double)(H / heads))); a.eps = 1e-5f;
-    return launch_attn_out_ln(a, st);
+    return launch_attn_out_ln(a, dtype, st);
 }
 
 // The split-arithmetic attention on an fp32 (B*S, 3H) qkv tensor: head / tail split pass (the engine's in-projection writes the two
@@ -352,6 +376,7 @@ int fs2_op_gemm_split_out(const void* x, const void* w, const float* bias, void*
 int fs2_op_attention_train(int32_t dtype, const void* qkv, const uint8_t* key_pad_mask, void* out, void* vt_scratch,
                            uint64_t* bits_scratch, float* lse2, int32_t B, int32_t S, int32_t H, int32_t heads, float drop_p,
                            uint64_t drop_seed, uint64_t drop_key, void* stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the training step takes fp32 or bf16 tensors
     hipStream_t st = (hipStream_t)stream;
     const int Spad = (S + 63) / 64 * 64;
     MaskBitsArgs mb{key_pad_mask, bits_scratch, B, S, Spad / 64};
@@ -387,7 +412,7 @@ int fs2_op_layernorm(int32_t dtype, const void* x, const void* res, const float*
 int fs2_op_layernorm_head(int32_t dtype, const void* x, const void* res, const float* gamma, const float* beta, void* y,
                           const float* dot_w, const float* dot_b_dev, const uint8_t* mask, float* pred, int32_t M, int32_t H,
                           void* stream) {
-    if (!dot_w || !dot_b_dev || !pred) return FS2_ERR_ARG;
+    if (!dot_w || !dot_b_dev || !pred || !is_f32_or_bf16(dtype)) return FS2_ERR_ARG;
     LayerNormArgs a;
     a.x = x; a.res = res; a.gamma = gamma; a.beta = beta; a.y = y;
     a.dot_w = dot_w; a.dot_b = 0.f; a.mask = mask; a.pred = pred;
@@ -397,7 +422,7 @@ int fs2_op_layernorm_head(int32_t dtype, const void* x, const void* res, const f
 }
 int fs2_op_layernorm_dropout(int32_t dtype, const void* x, const void* res, const float* gamma, const float* beta, void* y,
                              int32_t M, int32_t H, float drop_p, uint64_t seed, uint64_t key, void* stream) {
-    if (!(drop_p >= 0.f && drop_p < 1.f) || !y) return FS2_ERR_ARG;
+    if (!(drop_p >= 0.f && drop_p < 1.f) || !y || !is_f32_or_bf16(dtype)) return FS2_ERR_ARG;
     LayerNormArgs a;
     a.x = x; a.res = res; a.gamma = gamma; a.beta = beta; a.y = y;
     a.dot_w = nullptr; a.dot_b = 0.f; a.mask = nullptr; a.pred = nullptr;

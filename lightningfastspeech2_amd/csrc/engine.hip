@@ -156,9 +156,9 @@ struct PersistBufs {  // what fs2_encode leaves for fs2_decode
 // is the run state of one engine.
 struct Model {
     fs2_config cfg;
-    int dt = FS2_F32;          // configured mode (FS2_F32 / FS2_BF16 / FS2_MIXED)
-    int fdt = FS2_F32, bdt = FS2_F32;  // arithmetic of the front (encoder + variance adaptor: every discrete decision)
-                                       // and of the back (decoder + mel head); they differ only in FS2_MIXED
+    int dt = FS2_F32;          // configured mode (an fs2_dtype engine mode)
+    int fdt = FS2_F32, bdt = FS2_F32;  // storage dtype of the front (encoder + variance adaptor: every discrete decision)
+                                       // and of the back (decoder + mel head); they differ in the FS2_MIXED* modes (back: bf16 or f16)
     size_t esz = 4;            // bytes per activation element, the larger of the two (arena sizing)
     bool front_split = false;  // FS2_MIXED_X3 / FS2_F32_X3: the fp32 GEMMs / convs (the front's / all of them) run as bf16 x 3 split products
     std::map<std::string, std::vector<int64_t>> spec;
@@ -319,7 +319,8 @@ void build_spec(fs2_engine* e) {
 int check_config(fs2_engine* e) {
     const fs2_config& c = e->cfg;
     if (c.abi_version != FS2_ABI_VERSION) return fail(e, FS2_ERR_ARG, "abi_version %d != %d", c.abi_version, FS2_ABI_VERSION);
-    if (c.dtype != FS2_F32 && c.dtype != FS2_BF16 && c.dtype != FS2_MIXED && c.dtype != FS2_MIXED_X3 && c.dtype != FS2_F32_X3)
+    if (c.dtype != FS2_F32 && c.dtype != FS2_BF16 && c.dtype != FS2_MIXED && c.dtype != FS2_MIXED_X3 && c.dtype != FS2_F32_X3 &&
+        c.dtype != FS2_MIXED_F16_X3)  // (FS2_F16 alone is a storage dtype of the operators, not an engine mode)
         return fail(e, FS2_ERR_ARG, "bad dtype");
     const int H = c.hidden;
     if (H <= 0 || H % 64 || H > 1024) return fail(e, FS2_ERR_SHAPE, "hidden=%d must be a multiple of 64, <= 1024", H);
@@ -376,8 +377,10 @@ int upload_f32(fs2_engine* e, const float* h, size_t n, float** out) {
 }
 int upload_mat(fs2_engine* e, const float* h, size_t n, void** out, int dt) {
     if (dt == FS2_F32) return upload_f32(e, h, n, (float**)out);
+    if (!is_16bit(dt)) return fail(e, FS2_ERR_ARG, "upload_mat: not a storage dtype");
     std::vector<unsigned short> tmp(n);
-    for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_bf16(h[i]).v;
+    if (dt == FS2_F16) for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_f16_sat(h[i]).v;  // the device stores' rule, bit for bit
+    else for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_bf16(h[i]).v;
     CHK(dev_alloc(e, out, n * 2));
     HIPCHK(e, hipMemcpy(*out, tmp.data(), n * 2, hipMemcpyHostToDevice));
     return FS2_OK;
@@ -472,7 +475,7 @@ int make_layer(fs2_engine* e, const std::string& p, int H, int F, bool dw, Layer
         CHK(make_conv(e, p + ".conv2.weight", p + ".conv2.bias", &L->c2, dt));
     }
     const bool is_enc = p.compare(0, 8, "encoder.") == 0;
-    if (dt == FS2_BF16 && H == 256 && (is_enc ? e->cfg.enc_heads : e->cfg.dec_heads) == 2) {  // attn_out_ln_kernel's weight stream
+    if (is_16bit(dt) && H == 256 && (is_enc ? e->cfg.enc_heads : e->cfg.dec_heads) == 2) {  // attn_out_ln_kernel's weight stream (a 16-bit shuffle)
         CHK(dev_alloc(e, &L->wo_pk, predictor_packed_bytes_per_layer(1)));
         CHK(launch_pack_predictor_weights(L->out_proj.w, L->wo_pk, nullptr, 1));
         HIPCHK(e, hipStreamSynchronize(nullptr));
@@ -483,7 +486,7 @@ int make_layer(fs2_engine* e, const std::string& p, int H, int F, bool dw, Layer
 // W' = W diag(gamma), b' = b + W beta, wg[n] = sum_k W'[n][k] of the bf16 values as stored (see LayerW::in_proj_f).  bf16 stacks of wide
 // depth-wise blocks only (the blocks whose LayerNorms are deferred, conformer()): a block's in-projection behind the previous block's
 // norm2, the mel head behind the last decoder block's.
-int make_norm_folded(fs2_engine* e, const std::string& lw, const std::string& lb, const std::string& norm, ConvW* out, float** wg_out) {
+int make_norm_folded(fs2_engine* e, const std::string& lw, const std::string& lb, const std::string& norm, ConvW* out, float** wg_out, int dt) {
     const HostTensor& w = W(e, lw);
     const HostTensor& b = W(e, lb);
     const HostTensor& g = W(e, norm + ".weight");
@@ -496,13 +499,13 @@ int make_norm_folded(fs2_engine* e, const std::string& lw, const std::string& lb
             const float v = (float)((double)w.data[(size_t)n * H + k] * g.data[k]);
             wf[(size_t)n * H + k] = v;
             bacc += (double)w.data[(size_t)n * H + k] * be.data[k];
-            gacc += (double)bf16_to_f32(f32_to_bf16(v));  // of the values the MFMAs will multiply with
+            gacc += (double)(dt == FS2_F16 ? f16_to_f32(f32_to_f16_sat(v)) : bf16_to_f32(f32_to_bf16(v)));  // of the values the MFMAs will multiply with
         }
         bf[n] = (float)bacc;
         wg[n] = (float)gacc;
     }
-    out->N = N; out->Cin = H; out->taps = 1; out->dt = FS2_BF16;
-    CHK(upload_mat(e, wf.data(), wf.size(), &out->w, FS2_BF16));
+    out->N = N; out->Cin = H; out->taps = 1; out->dt = dt;
+    CHK(upload_mat(e, wf.data(), wf.size(), &out->w, dt));
     CHK(upload_f32(e, bf.data(), bf.size(), &out->b));
     return upload_f32(e, wg.data(), wg.size(), wg_out);
 }
@@ -732,9 +735,9 @@ int gemm(fs2_engine* e, hipStream_t st, const ConvW& w, const void* x, void* c, 
         *df->head_done = gemm_head_supported(a, w.dt, out_dt);
         if (!*df->head_done) { a.head_gw = nullptr; a.head_out = nullptr; }
     }
-    const double osz = out_dt == FS2_BF16 ? 2 : 4;
+    const double osz = (double)elem_bytes(out_dt);
     const double fl = 2.0 * M * (double)a.N * a.K;
-    const double wsz = w.dt == FS2_BF16 ? 2 : 4;
+    const double wsz = (double)elem_bytes(w.dt);
     const double by = (double)M * w.Cin * wsz + (double)a.N * a.K * wsz + (double)M * a.N * osz;
     Bracket br(e, w.taps > 1 ? FS2_K_CONV_GEMM : FS2_K_GEMM, st, fl, by);
     Bracket br2(e, o.extra_class >= 0 ? o.extra_class : FS2_K_COUNT - 1, st, fl, by, o.extra_class >= 0);
@@ -750,7 +753,7 @@ int dwconv(fs2_engine* e, hipStream_t st, const DwW& w, const void* x, void* y, 
     if (ln) { a.ln_stats = ln->stats; a.ln_g = ln->g; a.ln_b = ln->b; a.ln_parts = ln_parts(w.C); }
     a.x = x; a.w = w.w; a.bias = w.b; a.y = y;
     a.B = B; a.S = S; a.C = w.C; a.k = w.k; a.pad = (w.k - 1) / 2;
-    Bracket br(e, FS2_K_ROWOPS, st, 2.0 * B * S * (double)w.C * w.k, 2.0 * B * S * (double)w.C * (dt == FS2_BF16 ? 2 : 4));
+    Bracket br(e, FS2_K_ROWOPS, st, 2.0 * B * S * (double)w.C * w.k, 2.0 * B * S * (double)w.C * (double)elem_bytes(dt));
     const int r = launch_dwconv(a, dt, st);
     if (r != FS2_OK) return fail(e, r, "dwconv launch failed");
     return FS2_OK;
@@ -763,7 +766,7 @@ int norm_only(fs2_engine* e, hipStream_t st, int dt, const void* v, const float*
     l.x = v; l.res = nullptr; l.gamma = g; l.beta = b; l.y = y;
     l.dot_w = dot_w; l.dot_b = dot_b; l.mask = mask; l.pred = pred;
     l.M = M; l.H = H; l.eps = 1e-5f;
-    Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * M * (double)H * (dt == FS2_BF16 ? 2 : 4));
+    Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * M * (double)H * (double)elem_bytes(dt));
     if (launch_layernorm(l, dt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "normalise-only LayerNorm launch failed");
     return FS2_OK;
 }
@@ -786,7 +789,7 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
               const LayerScratch& sc, bool is_decoder, bool prenorm_in = false, const float* pg = nullptr, const float* pb = nullptr,
               bool leave_prenorm = false) {
     const int H = e->cfg.hidden, M = B * S, dt = w.in_proj.dt;
-    const double dsz = dt == FS2_BF16 ? 2 : 4;
+    const double dsz = (double)elem_bytes(dt);
     // fp32 storage with the bf16 x 3 split products (FS2_F32_X3 / the front of FS2_MIXED_X3): the attention takes the split
     // arithmetic too - the in-projection stores its fp32 result as bf16 head + tail (the same bytes, no extra pass), the attention
     // multiplies them with three bf16 MFMAs per product and hands back fp32 rows (attention.hip, X3)
@@ -834,7 +837,7 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
         ao.B = B; ao.S = S; ao.H = H; ao.heads = heads; ao.nw64 = sc.nw64; ao.scale_log2e = a.scale_log2e; ao.eps = 1e-5f;
         {
             Bracket br(e, FS2_K_ATTENTION, st, 4.0 * B * (double)S * S * H + 2.0 * M * (double)H * H, 5.0 * M * H * dsz + (double)H * H * dsz);
-            const int r = launch_attn_out_ln(ao, st);
+            const int r = launch_attn_out_ln(ao, dt, st);
             if (r != FS2_OK) return fail(e, r, "fused attention + out-projection launch failed");
         }
         mha.reset();
@@ -1173,6 +1176,12 @@ const char* fs2_status_string(int s) {
 
 const char* fs2_last_error(const fs2_engine* e) { return e ? e->err : "null engine"; }
 
+int fs2_host_f32_to_f16(const float* src, uint16_t* dst, size_t n) {
+    if ((!src || !dst) && n) return FS2_ERR_ARG;
+    for (size_t i = 0; i < n; ++i) dst[i] = f32_to_f16_sat(src[i]).v;
+    return FS2_OK;
+}
+
 int fs2_create(const fs2_config* cfg, fs2_engine** out) {
     if (!cfg || !out) return FS2_ERR_ARG;
     fs2_engine* e = new fs2_engine();
@@ -1183,9 +1192,10 @@ int fs2_create(const fs2_config* cfg, fs2_engine** out) {
     if (r != FS2_OK) return r;
     e->dt = cfg->dtype;
     e->fdt = cfg->dtype == FS2_BF16 ? FS2_BF16 : FS2_F32;
-    e->bdt = (cfg->dtype == FS2_F32 || cfg->dtype == FS2_F32_X3) ? FS2_F32 : FS2_BF16;
-    e->esz = cfg->dtype == FS2_BF16 ? 2 : 4;
-    e->front_split = cfg->dtype == FS2_MIXED_X3 || cfg->dtype == FS2_F32_X3;  // every fp32-weight GEMM / conv as bf16 x 3 split products
+    e->bdt = (cfg->dtype == FS2_F32 || cfg->dtype == FS2_F32_X3) ? FS2_F32 : (cfg->dtype == FS2_MIXED_F16_X3 ? FS2_F16 : FS2_BF16);
+    e->esz = elem_bytes(e->fdt) > elem_bytes(e->bdt) ? elem_bytes(e->fdt) : elem_bytes(e->bdt);
+    // every fp32-weight GEMM / conv as bf16 x 3 split products (nothing in the front looks at bdt: FS2_MIXED_F16_X3's front IS FS2_MIXED_X3's)
+    e->front_split = cfg->dtype == FS2_MIXED_X3 || cfg->dtype == FS2_F32_X3 || cfg->dtype == FS2_MIXED_F16_X3;
     build_spec(e);
     return FS2_OK;
 }
@@ -1258,15 +1268,15 @@ int fs2_finalize(fs2_engine* e) {
     e->dec.resize(c.dec_layers);
     for (int i = 0; i < c.dec_layers; ++i)
         CHK(make_layer(e, "decoder.layers." + std::to_string(i), H, c.dec_filter, c.dec_depthwise, &e->dec[i], e->bdt));
-    if (H > 256) {  // stacks of wide depth-wise bf16 blocks: norm2 of block i - 1 folded into the in-projection of block i
+    if (H > 256) {  // stacks of wide depth-wise 16-bit (bf16 / f16) blocks: norm2 of block i - 1 folded into the in-projection of block i
         const auto fold_in_proj = [&](const std::string& stack, int i, LayerW* L) -> int {
             const std::string p = stack + std::to_string(i) + ".self_attn.in_proj_";
-            CHK(make_norm_folded(e, p + "weight", p + "bias", stack + std::to_string(i - 1) + ".norm2", &L->in_proj_f, &L->in_wg));
+            CHK(make_norm_folded(e, p + "weight", p + "bias", stack + std::to_string(i - 1) + ".norm2", &L->in_proj_f, &L->in_wg, L->in_proj.dt));
             L->has_fold = true;
             return FS2_OK;
         };
         for (int i = 1; i < c.enc_layers && c.enc_depthwise && e->fdt == FS2_BF16; ++i) CHK(fold_in_proj("encoder.layers.", i, &e->enc[i]));
-        for (int i = 1; i < c.dec_layers && c.dec_depthwise && e->bdt == FS2_BF16; ++i) CHK(fold_in_proj("decoder.layers.", i, &e->dec[i]));
+        for (int i = 1; i < c.dec_layers && c.dec_depthwise && is_16bit(e->bdt); ++i) CHK(fold_in_proj("decoder.layers.", i, &e->dec[i]));
     }
     CHK(make_predictor(e, "variance_adaptor.duration_predictor", c.dur_nlayers, c.dur_filter, c.dur_depthwise, &e->dur, e->fdt));
     e->vars.resize(c.n_variances);
@@ -1283,9 +1293,9 @@ int fs2_finalize(fs2_engine* e) {
     CHK(make_conv(e, "linear.weight", "linear.bias", &e->mel, e->bdt));
     // (the row-scaled product with an fp32 store exists for narrow heads only - launch_gemm_plain: N < 192 -; a wider mel head keeps the
     //  normalise-only pass + the plain mel GEMM)
-    if (H > 256 && c.dec_layers > 0 && c.dec_depthwise && e->bdt == FS2_BF16 && c.n_mels < 192) {
+    if (H > 256 && c.dec_layers > 0 && c.dec_depthwise && is_16bit(e->bdt) && c.n_mels < 192) {
         // mel = Linear(LN2_last(v2)) evaluated on v2
-        CHK(make_norm_folded(e, "linear.weight", "linear.bias", "decoder.layers." + std::to_string(c.dec_layers - 1) + ".norm2", &e->mel_f, &e->mel_wg));
+        CHK(make_norm_folded(e, "linear.weight", "linear.bias", "decoder.layers." + std::to_string(c.dec_layers - 1) + ".norm2", &e->mel_f, &e->mel_wg, e->bdt));
         e->mel_fold = true;
     }
     e->priors_w.resize(c.n_priors);

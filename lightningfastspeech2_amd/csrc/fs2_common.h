@@ -31,6 +31,50 @@ __host__ __device__ inline bf16 f32_to_bf16(float f) {  // round-to-nearest-even
     return r;
 }
 
+// IEEE binary16 storage, carried the same way.  Stores SATURATE: a value beyond +-65504 (an infinity included) is stored as +-65504, so
+// that one overflowing element cannot turn its whole row into NaN through the next LayerNorm; NaN stays NaN; everything else rounds to
+// nearest-even, subnormals included.  The clamp is done in fp32 in front of the convert; the host routine below (the weight conversion
+// at fs2_finalize) gives the same bits as the device's f16_sat (v_max_f32 / v_min_f32 and a NaN select) + v_cvt_f16_f32 / v_cvt_pk_f16_f32.
+struct f16 {
+    unsigned short v;
+};
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+static constexpr float kF16Max = 65504.f;
+
+__host__ __device__ inline float f16_to_f32(f16 x) {
+    union { uint32_t u; float f; } c;
+    const uint32_t sign = ((uint32_t)x.v & 0x8000u) << 16, e = (x.v >> 10) & 0x1fu, m = x.v & 0x3ffu;
+    if (e == 0x1fu) { c.u = sign | 0x7f800000u | (m << 13); return c.f; }  // inf / NaN
+    if (e) { c.u = sign | ((e + 112u) << 23) | (m << 13); return c.f; }
+    c.f = (float)m * 5.9604644775390625e-8f;  // subnormal: m * 2^-24, exact
+    c.u |= sign;
+    return c.f;
+}
+__host__ __device__ inline f16 f32_to_f16_sat(float f) {  // clamp to +-65504, then round-to-nearest-even
+    union { uint32_t u; float f; } c;
+    c.f = f;
+    const uint32_t sign = (c.u >> 16) & 0x8000u;
+    uint32_t a = c.u & 0x7fffffffu;
+    f16 r;
+    if (a > 0x7f800000u) { r.v = (unsigned short)(sign | 0x7e00u | ((a >> 13) & 0x3ffu)); return r; }  // NaN (quiet)
+    if (a >= 0x477fe000u) { r.v = (unsigned short)(sign | 0x7bffu); return r; }  // |f| >= 65504: the largest finite value
+    if (a < 0x38800000u) {  // below 2^-14: subnormal (or zero) in binary16, a multiple of 2^-24
+        if (a < 0x33000000u) { r.v = (unsigned short)sign; return r; }  // < 2^-25: rounds to zero (2^-25 itself is a tie to even = 0)
+        const uint32_t e = a >> 23, man = (a & 0x7fffffu) | 0x800000u;
+        const uint32_t sh = 126u - e;  // 14 .. 24: man * 2^(e - 150) / 2^-24 = man >> sh
+        const uint32_t q = man >> sh, rem = man & ((1u << sh) - 1u), half = 1u << (sh - 1);
+        r.v = (unsigned short)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+        return r;
+    }
+    a += 0xfffu + ((a >> 13) & 1u);  // (below 65504 - half an ulp no carry reaches the infinity pattern: 65520 and up were clamped)
+    const uint32_t h = ((a >> 13) - (112u << 10));
+    r.v = (unsigned short)(sign | (h > 0x7bffu ? 0x7bffu : h));
+    return r;
+}
+// The clamp of a store, in fp32, in front of the convert.  fminf / fmaxf alone would hand back the bound for a NaN: the select keeps it.
+__host__ __device__ inline float f16_sat(float x) { return x != x ? x : fminf(fmaxf(x, -kF16Max), kF16Max); }
+
 template <typename T> struct Num;
 template <> struct Num<float> {
     __host__ __device__ static inline float to_f32(float x) { return x; }
@@ -52,6 +96,27 @@ template <> struct Num<bf16> {
     static constexpr int kPer16B = 8;
 };
 
+template <> struct Num<f16> {
+    __host__ __device__ static inline float to_f32(f16 x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return (float)*(const _Float16*)&x.v;  // v_cvt_f32_f16
+#else
+        return f16_to_f32(x);
+#endif
+    }
+    __host__ __device__ static inline f16 from_f32(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        f16 r;
+        const _Float16 h = (_Float16)f16_sat(x);  // v_cvt_f16_f32 (RNE)
+        r.v = *(const unsigned short*)&h;
+        return r;
+#else
+        return f32_to_f16_sat(x);
+#endif
+    }
+    static constexpr int kPer16B = 8;
+};
+
 // 16-byte vector <-> fp32 lanes
 template <typename T> struct Vec16;
 template <> struct Vec16<float> {
@@ -63,6 +128,7 @@ template <> struct Vec16<float> {
     __device__ static inline uint4 pack(const float* f) {
         return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
     }
+    __device__ static inline uint4 pack_bounded(const float* f) { return pack(f); }
 };
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
@@ -71,6 +137,47 @@ __device__ inline uint32_t pack_bf16x2(float lo, float hi) {  // v_cvt_pk_bf16_f
     const bf16x2_t v = __builtin_convertvector(f, bf16x2_t);
     return *(const uint32_t*)&v;
 }
+__device__ inline uint32_t pack_f16x2(float lo, float hi) {  // saturate (f16_sat), then v_cvt_pk_f16_f32 (RNE)
+    const f32x2_t f = {f16_sat(lo), f16_sat(hi)};
+    const f16x2_t v = __builtin_convertvector(f, f16x2_t);
+    return *(const uint32_t*)&v;
+}
+// Two 16-bit values of storage type T in one 32-bit word <-> fp32 (the kernels' 8 / 16-byte epilogue stores and residual loads)
+template <typename T> __device__ inline uint32_t pack2(float lo, float hi);
+template <> __device__ inline uint32_t pack2<bf16>(float lo, float hi) { return pack_bf16x2(lo, hi); }
+template <> __device__ inline uint32_t pack2<f16>(float lo, float hi) { return pack_f16x2(lo, hi); }
+template <typename T> __device__ inline float unpack_lo(uint32_t u);
+template <typename T> __device__ inline float unpack_hi(uint32_t u);
+template <> __device__ inline float unpack_lo<bf16>(uint32_t u) { return __uint_as_float(u << 16); }
+template <> __device__ inline float unpack_hi<bf16>(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+template <> __device__ inline float unpack_lo<f16>(uint32_t u) { return (float)(*(const f16x2_t*)&u)[0]; }  // v_cvt_f32_f16
+template <> __device__ inline float unpack_hi<f16>(uint32_t u) { return (float)(*(const f16x2_t*)&u)[1]; }  // ... of the high half (SDWA / op_sel)
+// (float has no packed form and no specialisation: the primary templates are declared only, so that the sizeof(T) == 4 side of an
+//  `if constexpr` inside a generic lambda still parses, and a call that survived into code would not link)
+template <> struct Vec16<f16> {
+    static constexpr int N = 8;
+    __device__ static inline void unpack(const uint4& u, float* f) {
+        f[0] = unpack_lo<f16>(u.x); f[1] = unpack_hi<f16>(u.x);
+        f[2] = unpack_lo<f16>(u.y); f[3] = unpack_hi<f16>(u.y);
+        f[4] = unpack_lo<f16>(u.z); f[5] = unpack_hi<f16>(u.z);
+        f[6] = unpack_lo<f16>(u.w); f[7] = unpack_hi<f16>(u.w);
+    }
+    __device__ static inline uint4 pack(const float* f) {
+        return make_uint4(pack_f16x2(f[0], f[1]), pack_f16x2(f[2], f[3]),
+                          pack_f16x2(f[4], f[5]), pack_f16x2(f[6], f[7]));
+    }
+    // values known to lie inside the binary16 range (the online softmax's numerators, p <= 2^6): the plain convert, no clamp
+    __device__ static inline uint4 pack_bounded(const float* f) {
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f32x2_t v = {f[2 * j], f[2 * j + 1]};
+            const f16x2_t h = __builtin_convertvector(v, f16x2_t);
+            w[j] = *(const uint32_t*)&h;
+        }
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    }
+};
 template <> struct Vec16<bf16> {
     static constexpr int N = 8;
     __device__ static inline void unpack(const uint4& u, float* f) {
@@ -83,6 +190,7 @@ template <> struct Vec16<bf16> {
         return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]),
                           pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
     }
+    __device__ static inline uint4 pack_bounded(const float* f) { return pack(f); }  // (bf16 has fp32's range: nothing to clamp)
 };
 
 // Physical 16-byte slot of logical slot L in row `row` of an LDS operand slab with ns slots per row
@@ -186,6 +294,12 @@ template <> struct Mma16<bf16> {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&r, *(const bf16x8_t*)&c, acc, 0, 0, 0);
     }
 };
+template <> struct Mma16<f16> {
+    static constexpr int K_PER_CHUNK = 32;  // same chunk and fragment map as bf16
+    __device__ static inline void step(const uint4& r, const uint4& c, f32x4_t& acc) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8_t*)&r, *(const f16x8_t*)&c, acc, 0, 0, 0);
+    }
+};
 template <> struct Mma16<float> {
     static constexpr int K_PER_CHUNK = 16;  // 4 groups x 4 floats
     __device__ static inline void step(const uint4& r, const uint4& c, f32x4_t& acc) {
@@ -203,6 +317,12 @@ template <> struct Mma32<bf16> {
     static constexpr int K_PER_CHUNK = 16;  // 2 groups x 8
     __device__ static inline void step(const uint4& r, const uint4& c, f32x16_t& acc) {
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8_t*)&r, *(const bf16x8_t*)&c, acc, 0, 0, 0);
+    }
+};
+template <> struct Mma32<f16> {
+    static constexpr int K_PER_CHUNK = 16;
+    __device__ static inline void step(const uint4& r, const uint4& c, f32x16_t& acc) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8_t*)&r, *(const f16x8_t*)&c, acc, 0, 0, 0);
     }
 };
 template <> struct Mma32<float> {

@@ -7,6 +7,14 @@
 
 namespace fs2 {
 
+// The storage dtypes (what a tensor's elements are; the FS2_MIXED* / FS2_F32_X3 values are engine modes, not element types) and
+// their element size.  Every launcher sizes by elem_bytes and picks its instantiation by the exact dtype: a `float` instantiation is
+// reached with FS2_F32 only, never as "everything that is not bf16".
+inline bool is_16bit(int dt) { return dt == FS2_BF16 || dt == FS2_F16; }
+inline bool is_storage_dtype(int dt) { return dt == FS2_F32 || is_16bit(dt); }
+inline bool is_f32_or_bf16(int dt) { return dt == FS2_F32 || dt == FS2_BF16; }  // what the operators without an f16 form take
+inline size_t elem_bytes(int dt) { return is_16bit(dt) ? 2 : 4; }
+
 // A/B switches of the launchers (kernel family, tile order, which fused form a launch takes).  NOT process state: an engine owns one
 // (fs2_set_tuning, copied by fs2_clone), the operator-level entry points (fs2_op_*: tests, the training step) use the CALLING
 // THREAD's (fs2_op_set_gemm_variant -> op_tuning()).  Every launcher reads the one its arguments point at (Args::tune; null = the
@@ -104,12 +112,12 @@ int launch_split_k_reduce(const float* part, void* out, size_t n, int ksplit, in
 // the split a long-K, few-tile GEMM / conv is worth (1 = none): tools/bench_ops.py dgrad
 int gemm_splitk_choice(int M, int N, int Cin, int taps, int S, int in_dtype);
 bool gemm_wres_supported(const GemmArgs& a, int in_dtype, int out_dtype, bool force);
-int launch_gemm_wres(const GemmArgs& a, hipStream_t stream);
+int launch_gemm_wres(const GemmArgs& a, int dtype, hipStream_t stream);  // dtype: FS2_BF16 / FS2_F16, in and out
 // gemm_persist.hip: the slab kernel's persistent form (one workgroup per CU walks its tiles; bit-identical results)
 bool gemm_persist_supported(const GemmArgs& a, int in_dtype, int out_dtype, int mi);
 bool gemm_head_supported(const GemmArgs& a, int in_dtype, int out_dtype);  // can this launch take GemmArgs::head_out (persistent kernel, switch on)
 bool gemm_persist_pays(const GemmArgs& a, int mi);
-int launch_gemm_persist(const GemmArgs& a, int mi, hipStream_t stream);
+int launch_gemm_persist(const GemmArgs& a, int dtype, int mi, hipStream_t stream);  // dtype: FS2_BF16 / FS2_F16, in and out
 
 struct AttnArgs {
     const void* qkv;        // (B*S, 3H): [q | k | v] columns, head h at h*d
@@ -143,7 +151,7 @@ struct AttnOutArgs {
     float scale_log2e, eps;
 };
 bool attn_out_ln_supported(int dtype, int H, int heads, int S);
-int launch_attn_out_ln(const AttnOutArgs& a, hipStream_t stream);
+int launch_attn_out_ln(const AttnOutArgs& a, int dtype, hipStream_t stream);  // dtype: FS2_BF16 / FS2_F16 (qkv, w, res, out)
 // Recomputing (flash) backward of the same attention, bf16, head dim 128 (attention_bwd.hip): dqkv (B*S, 3H) from dout (B*S, H),
 // the forward's qkv / lse2 and delta = fs2 attn_delta(dout, out).  Two launches: (dK, dV) per key block, dQ per query block.
 struct AttnBwdArgs {

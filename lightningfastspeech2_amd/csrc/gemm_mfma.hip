@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void gemm_conv_kernel(GemmArgs p) {
                 if constexpr (sizeof(OutT) == 4) {
                     *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
                 } else {
-                    *(uint2*)dst = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+                    *(uint2*)dst = make_uint2(pack2<OutT>(v[0], v[1]), pack2<OutT>(v[2], v[3]));
                 }
             } else {
 #pragma unroll
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(512) void gemm_conv_glds_kernel(GemmArgs p) {
                 if constexpr (sizeof(OutT) == 4) {
                     *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
                 } else {
-                    *(uint2*)dst = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+                    *(uint2*)dst = make_uint2(pack2<OutT>(v[0], v[1]), pack2<OutT>(v[2], v[3]));
                 }
             } else {
 #pragma unroll
@@ -710,8 +710,8 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                             const unsigned w4[4] = {rq[gi][j].x, rq[gi][j].y, rq[gi][j].z, rq[gi][j].w};
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                acc[2 * j + (e >> 1)][g0 + gi][(2 * e) & 3] = __uint_as_float(w4[e] << 16);
-                                acc[2 * j + (e >> 1)][g0 + gi][(2 * e + 1) & 3] = __uint_as_float(w4[e] & 0xffff0000u);
+                                acc[2 * j + (e >> 1)][g0 + gi][(2 * e) & 3] = unpack_lo<T>(w4[e]);
+                                acc[2 * j + (e >> 1)][g0 + gi][(2 * e + 1) & 3] = unpack_hi<T>(w4[e]);
                             }
                         }
                 }
@@ -848,8 +848,8 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                             rv[0] = q.x; rv[1] = q.y; rv[2] = q.z; rv[3] = q.w;
                         } else {
                             const uint2 q = *(const uint2*)(R + (rowbase + t) * p.ldc + n);
-                            rv[0] = __uint_as_float(q.x << 16); rv[1] = __uint_as_float(q.x & 0xffff0000u);
-                            rv[2] = __uint_as_float(q.y << 16); rv[3] = __uint_as_float(q.y & 0xffff0000u);
+                            rv[0] = unpack_lo<T>(q.x); rv[1] = unpack_hi<T>(q.x);
+                            rv[2] = unpack_lo<T>(q.y); rv[3] = unpack_hi<T>(q.y);
                         }
 #pragma unroll
                         for (int r = 0; r < 4; ++r) acc[ni][mi][r] += rv[r];
@@ -877,8 +877,8 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                                 *(float4*)dst = make_float4(a0[0], a0[1], a0[2], a0[3]);
                                 *(float4*)(dst + 4) = make_float4(a1[0], a1[1], a1[2], a1[3]);
                             } else {
-                                *(uint4*)dst = make_uint4(pack_bf16x2(a0[0], a0[1]), pack_bf16x2(a0[2], a0[3]),
-                                                          pack_bf16x2(a1[0], a1[1]), pack_bf16x2(a1[2], a1[3]));
+                                *(uint4*)dst = make_uint4(pack2<OutT>(a0[0], a0[1]), pack2<OutT>(a0[2], a0[3]),
+                                                          pack2<OutT>(a1[0], a1[1]), pack2<OutT>(a1[2], a1[3]));
                             }
                         } else {
 #pragma unroll
@@ -965,8 +965,8 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                             *(float4*)dst = make_float4(y[0], y[1], y[2], y[3]);
                             *(float4*)(dst + 4) = make_float4(y[4], y[5], y[6], y[7]);
                         } else {
-                            *(uint4*)dst = make_uint4(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]),
-                                                      pack_bf16x2(y[4], y[5]), pack_bf16x2(y[6], y[7]));
+                            *(uint4*)dst = make_uint4(pack2<OutT>(y[0], y[1]), pack2<OutT>(y[2], y[3]),
+                                                      pack2<OutT>(y[4], y[5]), pack2<OutT>(y[6], y[7]));
                         }
                     } else {
 #pragma unroll
@@ -1086,8 +1086,8 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                         const unsigned w4[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            gv[2 * e] = __uint_as_float(w4[e] << 16);
-                            gv[2 * e + 1] = __uint_as_float(w4[e] & 0xffff0000u);
+                            gv[2 * e] = unpack_lo<OutT>(w4[e]);
+                            gv[2 * e + 1] = unpack_hi<OutT>(w4[e]);
                         }
                     }
 #pragma unroll
@@ -1126,8 +1126,8 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                     *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
                     *(float4*)(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
                 } else {
-                    *(uint4*)dst = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]),
-                                              pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+                    *(uint4*)dst = make_uint4(pack2<OutT>(v[0], v[1]), pack2<OutT>(v[2], v[3]),
+                                              pack2<OutT>(v[4], v[5]), pack2<OutT>(v[6], v[7]));
                 }
             } else {
 #pragma unroll
@@ -1171,8 +1171,8 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                             *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
                             *(float4*)(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
                         } else {
-                            *(uint4*)dst = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]),
-                                                      pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+                            *(uint4*)dst = make_uint4(pack2<OutT>(v[0], v[1]), pack2<OutT>(v[2], v[3]),
+                                                      pack2<OutT>(v[4], v[5]), pack2<OutT>(v[6], v[7]));
                         }
                     } else {
 #pragma unroll
@@ -1275,6 +1275,7 @@ static int launch_slab_do(const GemmArgs& a, int in_dtype, int out_dtype, bool s
             if (in_dtype == FS2_F32 && out_dtype == FS2_F32)
                 return sp ? launch_slab_t<float, float, MI, true, true>(a, stream) : launch_slab_t<float, float, MI, true>(a, stream);
             if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_slab_t<bf16, bf16, MI, true>(a, stream);
+            if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_slab_t<f16, f16, MI, true>(a, stream);
         }
         return FS2_ERR_SHAPE;
     }
@@ -1284,6 +1285,7 @@ static int launch_slab_do(const GemmArgs& a, int in_dtype, int out_dtype, bool s
             if (in_dtype == FS2_F32 && out_dtype == FS2_F32)
                 return sp ? launch_slab_t<float, float, MI, false, true, true>(a, stream) : launch_slab_t<float, float, MI, false, false, true>(a, stream);
             if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_slab_t<bf16, bf16, MI, false, false, true>(a, stream);
+            if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_slab_t<f16, f16, MI, false, false, true>(a, stream);
         }
         return FS2_ERR_SHAPE;
     }
@@ -1291,6 +1293,8 @@ static int launch_slab_do(const GemmArgs& a, int in_dtype, int out_dtype, bool s
         return sp ? launch_slab_t<float, float, MI, false, true>(a, stream) : launch_slab_t<float, float, MI, false>(a, stream);
     if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_slab_t<bf16, bf16, MI, false>(a, stream);
     if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_slab_t<bf16, float, MI, false>(a, stream);
+    if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_slab_t<f16, f16, MI, false>(a, stream);
+    if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_slab_t<f16, float, MI, false>(a, stream);
     return FS2_ERR_SHAPE;
 }
 
@@ -1326,11 +1330,14 @@ static int launch_t(const GemmArgs& a, hipStream_t stream) {
 static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream, bool* fused);
 
 int launch_gemm(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream) {
+    if (!is_storage_dtype(in_dtype) || !is_storage_dtype(out_dtype)) return FS2_ERR_ARG;
+    // f16 operands: the forward's epilogues only (no dropout, gate, pre-norm tape, split-K, head sums: the training step's and the predictors')
+    if ((in_dtype == FS2_F16 || out_dtype == FS2_F16) && (a.drop_p > 0.f || a.gate || a.z_out || a.ksplit > 1 || a.head_out || a.C_lo)) return FS2_ERR_ARG;
     const Tuning& tn = tuning_of(a.tune);
     const int g_gemm_variant = tn.gemm_variant, g_gemm_wres = tn.gemm_wres;
     if (a.head_out) {  // head sums instead of the rows: the persistent kernel's deferred epilogue only (callers ask gemm_head_supported first)
         if (a.ln_g || !gemm_head_supported(a, in_dtype, out_dtype)) return FS2_ERR_SHAPE;
-        return launch_gemm_persist(a, 6, stream);
+        return launch_gemm_persist(a, in_dtype, 6, stream);
     }
     if (!a.ln_g && a.drop_p > 0.f) {  // the plain store's dropout: slab kernel, behind a ReLU (the FFN's hidden tensor)
         if (!a.relu || a.gate || a.stats_out || a.epi_res || a.ksplit > 1 || a.zero_rows || g_gemm_variant != 0 || a.N < 192 || a.M % a.S ||
@@ -1340,7 +1347,7 @@ int launch_gemm(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stre
     }
     if (!a.ln_g) {
         // K = 256 bf16: the column tile's weights live in registers, row tiles stream (gemm_wres.hip; bit-identical results)
-        if (g_gemm_wres && g_gemm_variant == 0 && a.ksplit <= 1 && gemm_wres_supported(a, in_dtype, out_dtype, g_gemm_wres == 2)) return launch_gemm_wres(a, stream);
+        if (g_gemm_wres && g_gemm_variant == 0 && a.ksplit <= 1 && gemm_wres_supported(a, in_dtype, out_dtype, g_gemm_wres == 2)) return launch_gemm_wres(a, in_dtype, stream);
         return launch_gemm_plain(a, in_dtype, out_dtype, stream, nullptr);
     }
     // fused row epilogue requested: try the slab kernel (whole rows per workgroup), else GEMM -> ln_tmp
@@ -1373,13 +1380,18 @@ static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hip
     const int g_gemm_variant = tn_.gemm_variant;
     const bool g_split_f32 = tn_.split_f32 != 0;
     if (a.M <= 0 || a.N <= 0) return FS2_OK;
-    const int ke = in_dtype == FS2_BF16 ? 64 : 32;
-    const int e16 = in_dtype == FS2_BF16 ? 8 : 4;
+    const int ke = 128 / (int)elem_bytes(in_dtype);
+    const int e16 = 16 / (int)elem_bytes(in_dtype);
     if (a.K % ke || a.Cin % ke || a.ldx % e16 || a.K != a.taps * a.Cin) return FS2_ERR_SHAPE;
     if (a.ldc % 4) return FS2_ERR_SHAPE;
     if (a.rs_stats && a.N < 192) {  // a narrow head behind a folded LayerNorm (the mel Linear): 128x128 kernel, bf16 operands
-        if (fused || a.relu || a.gate || a.stats_out || a.epi_res || a.C_lo || a.ksplit > 1 || a.drop_p > 0.f || !a.rs_wg || a.taps != 1 || in_dtype != FS2_BF16)
+        if (fused || a.relu || a.gate || a.stats_out || a.epi_res || a.C_lo || a.ksplit > 1 || a.drop_p > 0.f || !a.rs_wg || a.taps != 1 || !is_16bit(in_dtype))
             return FS2_ERR_SHAPE;
+        if (in_dtype == FS2_F16) {
+            if (out_dtype == FS2_F32) return a.zero_rows ? launch_t<f16, float, true>(a, stream) : launch_t<f16, float>(a, stream);
+            if (out_dtype == FS2_F16 && !a.zero_rows) return launch_t<f16, f16>(a, stream);
+            return FS2_ERR_SHAPE;
+        }
         if (out_dtype == FS2_F32) return a.zero_rows ? launch_t<bf16, float, true>(a, stream) : launch_t<bf16, float>(a, stream);
         if (out_dtype == FS2_BF16 && !a.zero_rows) return launch_t<bf16, bf16>(a, stream);
         return FS2_ERR_SHAPE;
@@ -1388,12 +1400,13 @@ static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hip
         if (fused) return FS2_ERR_SHAPE;
         if (in_dtype == FS2_F32 && out_dtype == FS2_F32) return launch_t<float, float, true>(a, stream);
         if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_t<bf16, float, true>(a, stream);
+        if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_t<f16, float, true>(a, stream);
         return FS2_ERR_SHAPE;
     }
     if (a.rs_stats && (fused || a.relu || a.gate || a.stats_out || a.epi_res || a.zero_rows || a.C_lo || a.ksplit > 1 || a.drop_p > 0.f || g_gemm_variant == 1 ||
-                       g_gemm_variant == 2 || !a.rs_wg || !(a.M % a.S == 0 && (a.taps & 1)) || a.N < 192 || in_dtype != FS2_BF16 ||
-                       out_dtype != FS2_BF16))
-        return FS2_ERR_SHAPE;  // the row-scaled product lives in the slab / persistent kernels' plain bf16 epilogue only
+                       g_gemm_variant == 2 || !a.rs_wg || !(a.M % a.S == 0 && (a.taps & 1)) || a.N < 192 || !is_16bit(in_dtype) ||
+                       out_dtype != in_dtype))
+        return FS2_ERR_SHAPE;  // the row-scaled product lives in the slab / persistent kernels' plain 16-bit epilogue only
     if (a.gate && (fused || a.relu || a.stats_out || a.epi_res || g_gemm_variant != 0 || a.N < 192 || a.M % a.S || !(a.taps & 1) ||
                    in_dtype != out_dtype))
         return FS2_ERR_SHAPE;  // the gated store lives in the slab kernel's plain epilogue only
@@ -1426,6 +1439,8 @@ static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hip
         if (in_dtype == FS2_F32 && out_dtype == FS2_F32) return launch_glds_t<float, float>(a, stream);
         if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_glds_t<bf16, bf16>(a, stream);
         if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_glds_t<bf16, float>(a, stream);
+        if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_glds_t<f16, f16>(a, stream);
+        if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_glds_t<f16, float>(a, stream);
         return FS2_ERR_SHAPE;
     }
     if (variant == 0 && slab_ok && a.N >= 192) {
@@ -1455,7 +1470,7 @@ static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hip
             // more tiles than CUs: one workgroup per CU walks them, the next tile's first operands under this tile's epilogue
             // (gemm_persist.hip; same tile height, same arithmetic per element - bit-identical)
             if (!fused && tn_.gemm_persist && gemm_persist_supported(a, in_dtype, out_dtype, best) && gemm_persist_pays(a, best))
-                return launch_gemm_persist(a, best, stream);
+                return launch_gemm_persist(a, in_dtype, best, stream);
             if (fused) *fused = true;
             if (best == 1) return launch_slab<1>(a, in_dtype, out_dtype, stream);
             if (best == 2) return launch_slab<2>(a, in_dtype, out_dtype, stream);
@@ -1469,6 +1484,8 @@ static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hip
     if (in_dtype == FS2_F32 && out_dtype == FS2_F32) return launch_t<float, float>(a, stream);
     if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_t<bf16, bf16>(a, stream);
     if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_t<bf16, float>(a, stream);
+    if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_t<f16, f16>(a, stream);
+    if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_t<f16, float>(a, stream);
     return FS2_ERR_SHAPE;
 }
 
@@ -1515,10 +1532,10 @@ __global__ __launch_bounds__(256) void split_k_reduce_kernel(const float* __rest
         uint2* o = (uint2*)(out + i);
         if (accumulate) {
             const uint2 c = *o;
-            a.x += __uint_as_float(c.x << 16); a.y += __uint_as_float(c.x & 0xffff0000u);
-            a.z += __uint_as_float(c.y << 16); a.w += __uint_as_float(c.y & 0xffff0000u);
+            a.x += unpack_lo<OutT>(c.x); a.y += unpack_hi<OutT>(c.x);
+            a.z += unpack_lo<OutT>(c.y); a.w += unpack_hi<OutT>(c.y);
         }
-        *o = make_uint2(pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w));
+        *o = make_uint2(pack2<OutT>(a.x, a.y), pack2<OutT>(a.z, a.w));
     }
 }
 
@@ -1535,7 +1552,8 @@ int launch_split_k_reduce(const float* part, void* out, size_t n, int ksplit, in
 // leaves every workgroup streaming the whole K x 256 weight panel at the CU's ~64 GB/s ingest rate with half the CUs idle
 // (130 us at C2).  Split over K so that 128-row tiles fill the chip once: 1/ksplit of the panel per workgroup.
 int gemm_splitk_choice(int M, int N, int Cin, int taps, int S, int in_dtype) {
-    const int ke = in_dtype == FS2_BF16 ? 64 : 32;
+    if (!is_f32_or_bf16(in_dtype)) return 1;  // split-K is the training step's
+    const int ke = 128 / (int)elem_bytes(in_dtype);
     if (taps < 1 || !(taps & 1) || N < 192 || Cin % ke || (long)taps * Cin < 2048) return 1;
     if (taps == 1) S = M;
     if (S <= 0 || M % S) return 1;

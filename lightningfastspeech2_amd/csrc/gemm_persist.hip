@@ -47,12 +47,12 @@ template <int I> struct IntCP { static constexpr int value = I; };
 // HEAD (deferred epilogue only; GemmArgs::head_out): the tile's rows are NOT stored - the consumer is a Linear(N, 1) head behind the
 // LayerNorm, and sum_n LN(v)[n] w[n] = rstd (sum_n v[n] gw[n] - mean sum_n gw[n]) + const with gw = gamma * w.  The epilogue leaves
 // the row statistics as always plus sum_n v[n] gw[n] over the tile's columns; launch_head_finish makes the prediction of them.
-template <int MI, bool DEFER, bool RS = false, bool HEAD = false>
+template <typename T, int MI, bool DEFER, bool RS = false, bool HEAD = false>  // T = bf16 or f16 (in and out)
 __global__ __launch_bounds__(512) void gemm_persist_kernel(GemmArgs p, int ntiles) {
     static_assert(!(RS && DEFER), "the row-scaled product is a plain-epilogue form");
     static_assert(!HEAD || DEFER, "the head sums ride the deferred-LayerNorm epilogue");
 #if defined(__HIP_DEVICE_COMPILE__)
-    using T = bf16;
+    static_assert(sizeof(T) == 2, "16-bit operands");
     constexpr int BMs = MI * 32;
     constexpr int GROUPS = BMs / 8;  // 8-row (1 KiB) DMA groups
     constexpr int SI = (GROUPS + 7) / 8;
@@ -274,8 +274,8 @@ __global__ __launch_bounds__(512) void gemm_persist_kernel(GemmArgs p, int ntile
                                 const unsigned w4[4] = {rq[gi][j].x, rq[gi][j].y, rq[gi][j].z, rq[gi][j].w};
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
-                                    acc[2 * j + (e >> 1)][gi][(2 * e) & 3] = __uint_as_float(w4[e] << 16);
-                                    acc[2 * j + (e >> 1)][gi][(2 * e + 1) & 3] = __uint_as_float(w4[e] & 0xffff0000u);
+                                    acc[2 * j + (e >> 1)][gi][(2 * e) & 3] = unpack_lo<T>(w4[e]);
+                                    acc[2 * j + (e >> 1)][gi][(2 * e + 1) & 3] = unpack_hi<T>(w4[e]);
                                 }
                             }
                         if (rnorm) {
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(512) void gemm_persist_kernel(GemmArgs p, int ntile
                         }
                         T* dst = (T*)((char*)C + (unsigned)(t * p.ldc + n) * (unsigned)sizeof(T));
                         if (decltype(full_c)::value || n + 7 < p.N) {
-                            *(uint4*)dst = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+                            *(uint4*)dst = make_uint4(pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7]));
                         } else {
 #pragma unroll
                             for (int r = 0; r < 8; ++r) if (n + r < p.N) dst[r] = Num<T>::from_f32(v[r]);
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(512) void gemm_persist_kernel(GemmArgs p, int ntile
                         if (!HEAD && (ROWS || t < S) && (FULL || n < p.N)) {
                             T* dst = (T*)((char*)C + (unsigned)(t * p.ldc + n) * (unsigned)sizeof(T));
                             if (FULL || n + 7 < p.N) {
-                                *(uint4*)dst = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+                                *(uint4*)dst = make_uint4(pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7]));
                             } else {
 #pragma unroll
                                 for (int r = 0; r < 8; ++r) if (n + r < p.N) dst[r] = Num<T>::from_f32(v[r]);
@@ -518,7 +518,8 @@ __global__ __launch_bounds__(512) void gemm_persist_kernel(GemmArgs p, int ntile
 
 // The tile height comes from the slab launcher's cost model (mi); this only says whether the persistent form can run the launch.
 bool gemm_persist_supported(const GemmArgs& a, int in_dtype, int out_dtype, int mi) {
-    if (in_dtype != FS2_BF16 || out_dtype != FS2_BF16) return false;
+    if (!is_16bit(in_dtype) || out_dtype != in_dtype) return false;
+    if (in_dtype == FS2_F16 && a.head_out) return false;  // the head sums are the (bf16) predictors'
     if (a.ln_g || a.dot_w || a.z_out || a.res || a.gate || a.zero_rows || a.C_lo || a.split || a.w_presplit || a.ksplit > 1 || a.drop_p > 0.f) return false;
     if (a.rs_stats && (a.relu || a.stats_out || a.epi_res || !a.rs_wg)) return false;
     if (!a.bias) return false;
@@ -561,25 +562,32 @@ bool gemm_persist_pays(const GemmArgs& a, int mi) {
     return tiles > persist_cus();
 }
 
-template <int MI, bool DEFER, bool RS = false, bool HEAD = false>
+template <typename T, int MI, bool DEFER, bool RS = false, bool HEAD = false>
 static int launch_persist_t(const GemmArgs& a, hipStream_t stream) {
     const int BMs = MI * 32;
     const int tiles = (a.M / a.S) * ((a.S + BMs - 1) / BMs) * ((a.N + PR_BN - 1) / PR_BN);
     int grid = persist_cus();
     if (grid > ((tiles + 7) & ~7)) grid = (tiles + 7) & ~7;
-    hipLaunchKernelGGL((gemm_persist_kernel<MI, DEFER, RS, HEAD>), dim3(grid), dim3(512), 0, stream, a, tiles);
+    hipLaunchKernelGGL((gemm_persist_kernel<T, MI, DEFER, RS, HEAD>), dim3(grid), dim3(512), 0, stream, a, tiles);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
-int launch_gemm_persist(const GemmArgs& a_in, int mi, hipStream_t stream) {
+template <typename T>
+static int launch_persist_dt(const GemmArgs& a, int mi, hipStream_t stream) {
+    const bool defer = a.stats_out || a.epi_res;
+    if (defer) return launch_persist_t<T, 6, true>(a, stream);
+    if (a.rs_stats) return mi == 8 ? launch_persist_t<T, 8, false, true>(a, stream) : launch_persist_t<T, 6, false, true>(a, stream);
+    if (mi == 8) return launch_persist_t<T, 8, false>(a, stream);
+    return launch_persist_t<T, 6, false>(a, stream);
+}
+
+int launch_gemm_persist(const GemmArgs& a_in, int dtype, int mi, hipStream_t stream) {
     GemmArgs a = a_in;
     if (a.taps == 1) a.S = a.M;
-    const bool defer = a.stats_out || a.epi_res;
-    if (defer && a.head_out) return launch_persist_t<6, true, false, true>(a, stream);
-    if (defer) return launch_persist_t<6, true>(a, stream);
-    if (a.rs_stats) return mi == 8 ? launch_persist_t<8, false, true>(a, stream) : launch_persist_t<6, false, true>(a, stream);
-    if (mi == 8) return launch_persist_t<8, false>(a, stream);
-    return launch_persist_t<6, false>(a, stream);
+    if (dtype == FS2_F16) return a.head_out ? FS2_ERR_SHAPE : launch_persist_dt<f16>(a, mi, stream);
+    if (dtype != FS2_BF16) return FS2_ERR_ARG;
+    if ((a.stats_out || a.epi_res) && a.head_out) return launch_persist_t<bf16, 6, true, false, true>(a, stream);
+    return launch_persist_dt<bf16>(a, mi, stream);
 }
 
 }  // namespace fs2

@@ -40,6 +40,7 @@ __device__ unsigned long long g_wres_stamps[2][64];
 #define WRES_STAMP(i) do { } while (0)
 #endif
 
+template <typename T>  // bf16 or f16: 2-byte operands, same fragment maps
 __global__ __launch_bounds__(512) void gemm_wres_kernel(GemmArgs p, int ncol, int nrg, int tiles) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // two activation tiles (first: the weight staging area).  Separate objects: hipcc tracks pending LDS-DMA per object and would
@@ -142,14 +143,14 @@ __global__ __launch_bounds__(512) void gemm_wres_kernel(GemmArgs p, int ncol, in
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
 #pragma unroll
-                for (int mi = 0; mi < WR_MI; ++mi) Mma16<bf16>::step(fw[ks][ni], fx[ks & 1][mi], acc[ni][mi]);
+                for (int mi = 0; mi < WR_MI; ++mi) Mma16<T>::step(fw[ks][ni], fx[ks & 1][mi], acc[ni][mi]);
                 if (ni == 0) side(ks);
             }
         }
     };
     auto store_piece = [&](int t, int mi, int j, const uint4& q) {
         const int m = t * WR_RT + wm * (WR_MI * 16) + mi * 16 + fr;
-        if (m < p.M) *(uint4*)((bf16*)p.C + (size_t)m * p.ldc + n0 + wn * 64 + j * 32 + fg * 8) = q;
+        if (m < p.M) *(uint4*)((T*)p.C + (size_t)m * p.ldc + n0 + wn * 64 + j * 32 + fg * 8) = q;
     };
     using B0 = std::integral_constant<int, 0>;
     using B1 = std::integral_constant<int, 1>;
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(512) void gemm_wres_kernel(GemmArgs p, int ncol, in
                     v[r] = acc[2 * j + (r >> 2)][mi][r & 3] + bv[r];
                     if (p.relu) v[r] = fmaxf(v[r], 0.f);
                 }
-                store_piece(t, mi, j, make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])));
+                store_piece(t, mi, j, make_uint4(pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])));
             }
         }
     };
@@ -221,14 +222,16 @@ bool gemm_wres_supported(const GemmArgs& a, int in_dtype, int out_dtype, bool fo
         const int tiles = (a.M + WR_RT - 1) / WR_RT;
         if (tiles < 3 * wres_row_groups(a.N / 256, tiles)) return false;
     }
-    return in_dtype == FS2_BF16 && out_dtype == FS2_BF16 && a.taps == 1 && a.K == WR_K && a.Cin == WR_K && a.N >= 256 && a.N % 256 == 0 &&
+    return is_16bit(in_dtype) && out_dtype == in_dtype && a.taps == 1 && a.K == WR_K && a.Cin == WR_K && a.N >= 256 && a.N % 256 == 0 &&
            a.N <= 2048 && a.M > 0 && !a.res && !a.ln_g && !a.dot_w && !a.z_out && !a.epi_res && !a.stats_out && !a.gate && !a.zero_rows &&
            !a.split && !a.rs_stats && a.ldx % 8 == 0 && a.ldc % 8 == 0 && (size_t)a.M * a.ldx * 2 < 0xFFFFF000ull && (size_t)a.M * a.ldc * 2 < 0xFFFFF000ull;
 }
 
-int launch_gemm_wres(const GemmArgs& a, hipStream_t stream) {
+int launch_gemm_wres(const GemmArgs& a, int dtype, hipStream_t stream) {
+    if (!is_16bit(dtype)) return FS2_ERR_ARG;
     const int ncol = a.N / 256, tiles = (a.M + WR_RT - 1) / WR_RT, nrg = wres_row_groups(ncol, tiles);
-    hipLaunchKernelGGL(gemm_wres_kernel, dim3((unsigned)(nrg * ncol)), dim3(512), 0, stream, a, ncol, nrg, tiles);
+    if (dtype == FS2_F16) hipLaunchKernelGGL(gemm_wres_kernel<f16>, dim3((unsigned)(nrg * ncol)), dim3(512), 0, stream, a, ncol, nrg, tiles);
+    else hipLaunchKernelGGL(gemm_wres_kernel<bf16>, dim3((unsigned)(nrg * ncol)), dim3(512), 0, stream, a, ncol, nrg, tiles);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 

@@ -17,12 +17,21 @@ template <> __device__ inline void load4<bf16>(const bf16* p, float* f) {
     f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
     f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
 }
+template <> __device__ inline void load4<f16>(const f16* p, float* f) {
+    const uint2 v = *(const uint2*)p;
+    f[0] = unpack_lo<f16>(v.x); f[1] = unpack_hi<f16>(v.x);
+    f[2] = unpack_lo<f16>(v.y); f[3] = unpack_hi<f16>(v.y);
+}
 template <typename T> __device__ inline void store4(T* p, const float* f);
 template <> __device__ inline void store4<float>(float* p, const float* f) {
     *(float4*)p = make_float4(f[0], f[1], f[2], f[3]);
 }
 template <> __device__ inline void store4<bf16>(bf16* p, const float* f) {
     *(uint2*)p = make_uint2(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]));
+}
+
+template <> __device__ inline void store4<f16>(f16* p, const float* f) {
+    *(uint2*)p = make_uint2(pack_f16x2(f[0], f[1]), pack_f16x2(f[2], f[3]));
 }
 
 // =============================================================================================
@@ -110,6 +119,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LayerNormArgs p) {
 }
 
 int launch_layernorm(const LayerNormArgs& a, int dtype, hipStream_t stream) {
+    if (!is_storage_dtype(dtype) || (dtype == FS2_F16 && a.drop_p > 0.f)) return FS2_ERR_ARG;
     if (a.M <= 0) return FS2_OK;
     if (a.H % 4 || a.H > 1024) return FS2_ERR_SHAPE;
     const int nv = (a.H + 255) / 256;
@@ -117,6 +127,7 @@ int launch_layernorm(const LayerNormArgs& a, int dtype, hipStream_t stream) {
 #define FS2_LN(NVV)                                                                                     \
     if (nv == NVV) {                                                                                    \
         if (dtype == FS2_BF16) hipLaunchKernelGGL((layernorm_kernel<bf16, NVV>), grid, block, 0, stream, a); \
+        else if (dtype == FS2_F16) hipLaunchKernelGGL((layernorm_kernel<f16, NVV>), grid, block, 0, stream, a); \
         else hipLaunchKernelGGL((layernorm_kernel<float, NVV>), grid, block, 0, stream, a);             \
     }
     FS2_LN(1) FS2_LN(2) FS2_LN(3) FS2_LN(4)
@@ -193,6 +204,12 @@ template <> __device__ inline void load4v<bf16>(const bf16* p, dw_f2& a, dw_f2& 
     const uint2 v = *(const uint2*)p;
     a = dw_f2{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u)};
     b = dw_f2{__uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u)};
+}
+
+template <> __device__ inline void load4v<f16>(const f16* p, dw_f2& a, dw_f2& b) {
+    const uint2 v = *(const uint2*)p;
+    a = dw_f2{unpack_lo<f16>(v.x), unpack_hi<f16>(v.x)};
+    b = dw_f2{unpack_lo<f16>(v.y), unpack_hi<f16>(v.y)};
 }
 
 // Workgroup = 256 rows x 64 channels of one utterance; a thread owns 16 consecutive rows x 4 channels.  The
@@ -386,13 +403,16 @@ int dwconv_tile_rows(int B, int S, int C) {  // 256 rows where that fills the ch
 }
 int launch_dwconv(const DwConvArgs& a, int dtype, hipStream_t stream) {
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
+    if (!is_storage_dtype(dtype) || (dtype == FS2_F16 && a.flip)) return FS2_ERR_ARG;  // (flip: the training step's data gradient)
     if (a.k < 1 || a.k > DW_KMAX || a.C % 4) return FS2_ERR_SHAPE;
-    const int tr = dtype == FS2_BF16 ? dwconv_tile_rows(a.B, a.S, a.C) : 256;
+    const int tr = is_16bit(dtype) ? dwconv_tile_rows(a.B, a.S, a.C) : 256;
     const dim3 grid((a.S + tr - 1) / tr, (a.C + DW_CT - 1) / DW_CT, a.B), block(256);
     switch (dwconv_tap_chunk(a.k)) {
 #define FS2_DW(TC)                                                                                                     \
     case TC:                                                                                                           \
-        if (dtype != FS2_BF16) hipLaunchKernelGGL((dwconv_kernel<float, TC>), grid, block, 0, stream, a);               \
+        if (dtype == FS2_F32) hipLaunchKernelGGL((dwconv_kernel<float, TC>), grid, block, 0, stream, a);                \
+        else if (dtype == FS2_F16 && tr == 256) hipLaunchKernelGGL((dwconv_kernel<f16, TC, 256>), grid, block, 0, stream, a); \
+        else if (dtype == FS2_F16) hipLaunchKernelGGL((dwconv_kernel<f16, TC, 128>), grid, block, 0, stream, a);        \
         else if (tr == 256) hipLaunchKernelGGL((dwconv_kernel<bf16, TC, 256>), grid, block, 0, stream, a);              \
         else hipLaunchKernelGGL((dwconv_kernel<bf16, TC, 128>), grid, block, 0, stream, a);                             \
         break;
@@ -432,6 +452,7 @@ __global__ __launch_bounds__(256) void embed_kernel(EmbedArgs p) {
 }
 
 int launch_embed(const EmbedArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // a kernel of the front: fp32 or bf16 rows
     if (a.B * a.L <= 0) return FS2_OK;
     if (a.H % 4) return FS2_ERR_SHAPE;
     const dim3 grid((a.B * a.L + 3) / 4), block(256);
@@ -630,8 +651,9 @@ __global__ __launch_bounds__(256) void regulate_kernel(RegulateArgs p) {
 }
 
 int launch_regulate(const RegulateArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // a kernel of the front: fp32 or bf16 rows
     if (a.B <= 0 || a.T <= 0) return FS2_OK;
-    const int esz = dtype == FS2_BF16 ? 2 : 4;
+    const int esz = (int)elem_bytes(dtype);
     if ((a.H * esz) % 16) return FS2_ERR_SHAPE;
     const dim3 grid((a.T + 4 * RG_ROWS - 1) / (4 * RG_ROWS), a.B), block(256);
     if (dtype == FS2_BF16) hipLaunchKernelGGL(regulate_kernel<bf16>, grid, block, 0, stream, a);
@@ -750,6 +772,7 @@ __global__ __launch_bounds__(256) void bucket_embed_kernel(BucketArgs p) {
 }
 
 int launch_bucket_embed(const BucketArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // a kernel of the front: fp32 or bf16 rows
     if (a.B * a.T <= 0) return FS2_OK;
     if (a.H % 4) return FS2_ERR_SHAPE;
     const dim3 grid((a.B * a.T + 4 * BE_ROWS - 1) / (4 * BE_ROWS)), block(256);
@@ -826,6 +849,7 @@ __global__ __launch_bounds__(256) void cwt_recompose_kernel(CwtArgs p) {
 }
 
 int launch_cwt_head(const CwtArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // a kernel of the front: fp32 or bf16 rows
     if (a.B <= 0 || a.T <= 0) return FS2_OK;
     if (dtype == FS2_BF16) hipLaunchKernelGGL(cwt_mean_std_kernel<bf16>, dim3(a.B), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(cwt_mean_std_kernel<float>, dim3(a.B), dim3(256), 0, stream, a);

@@ -385,6 +385,7 @@ int voc_steps_padded(int taps, int cin_pad, int dtype) {
 }
 
 int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32 or bf16
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
     if (a.wn != 1 && a.wn != 2 && a.wn != 4 && a.wn != 8) return FS2_ERR_SHAPE;
     if (a.cin_pad < 32 || (a.cin_pad & (a.cin_pad - 1)) || a.cin > a.cin_pad || a.cin % 4) return FS2_ERR_SHAPE;

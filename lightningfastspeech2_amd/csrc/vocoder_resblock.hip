@@ -445,6 +445,7 @@ static size_t rb_lds_bytes(const VocResblockArgs& a, int nw, int mi16, int esz) 
 // is taken when >= 85 % of its rows are useful: 3-9 % faster than the 8-wave full-height tile on the 32/64-
 // channel stages and on the 128-channel k=7 pairs, equal elsewhere (repeated A/B runs).
 int voc_resblock_mi16(const VocResblockArgs& a, int dtype) {
+    if (!is_f32_or_bf16(dtype)) return 0;
     const int g_voc_fused_resblock = tuning_of(a.tune).voc_fused_resblock;
     if (!g_voc_fused_resblock || (g_voc_fused_resblock == 2 && a.npairs != 1)) return 0;
     const int esz = dtype == FS2_BF16 ? 2 : 4;
@@ -497,6 +498,7 @@ static int rb_launch_t(const VocResblockArgs& a, size_t smem, hipStream_t stream
 }
 
 int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t stream) {
+    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32 or bf16
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
     const int cfg = voc_resblock_mi16(a, dtype);
     if (!cfg) return FS2_ERR_SHAPE;

@@ -25,8 +25,11 @@ from .config import Fs2Config
 # "mixed": fp32 for everything a discrete decision hangs on (encoder, durations, variance predictors / buckets),
 # bf16 for the decoder + mel head (include/fs2.h: FS2_MIXED)
 # "mixed3": the same with the front's matrix products as bf16 x 3 split products of the fp32 operands (FS2_MIXED_X3)
+# "mixed16": "mixed3"'s front, launch for launch (the same durations and buckets, bit for bit), with the decoder's stored tensors and
+# matrix operands in IEEE binary16 instead of bf16 (FS2_MIXED_F16_X3): three more mantissa bits at the same MFMA rate, ~8x closer
+# to the fp32 mel; stores saturate at +-65504 (include/fs2.h: FS2_F16).  Every output tensor is fp32, as in all modes.
 _PRECISIONS = {"fp32": _lib.FS2_F32, "f32": _lib.FS2_F32, "bf16": _lib.FS2_BF16, "mixed": _lib.FS2_MIXED,
-               "mixed3": _lib.FS2_MIXED_X3, "fp32x3": _lib.FS2_F32_X3}
+               "mixed3": _lib.FS2_MIXED_X3, "fp32x3": _lib.FS2_F32_X3, "mixed16": _lib.FS2_MIXED_F16_X3}
 # "fp32x3": the fp32 mode's storage, attention, LayerNorm, heads and decision logic with EVERY GEMM / conv as bf16 x 3 split products
 # (FS2_F32_X3): ~1e-5 on the mel against "fp32" at about half its time
 
