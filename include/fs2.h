@@ -55,9 +55,10 @@ enum fs2_dtype {
     FS2_F16 = 5,      /* storage / operator dtype: IEEE binary16 operands, fp32 accumulate.  Stores SATURATE: a value beyond +-65504 (an
                          infinity included) is stored as +-65504, NaN stays NaN, everything else rounds to nearest-even (subnormals
                          included) - on the device and in fs2_finalize's weight conversion alike.  Taken by fs2_op_gemm / _gemm_add /
-                         _gemm_ln / _gemm_stats / _gemm_rowscale_dt, fs2_op_attention (+ _scratch_bytes), fs2_op_attn_out_ln, fs2_op_layernorm, fs2_op_dwconv and
-                         fs2_op_convert; every other operator (the training step's, bgemm, the attention backward, the predictor,
-                         the row kernels of the front, the vocoder) answers FS2_ERR_ARG / FS2_ERR_SHAPE, a *_supported query 0 */
+                         _gemm_ln / _gemm_stats / _gemm_rowscale_dt, fs2_op_attention (+ _scratch_bytes), fs2_op_attn_out_ln, fs2_op_layernorm, fs2_op_dwconv,
+                         fs2_op_convert and the vocoder (fs2_voc_config.dtype); every other operator (the training step's, bgemm, the
+                         attention backward, the predictor, the row kernels of the front) answers FS2_ERR_ARG / FS2_ERR_SHAPE, a
+                         *_supported query 0 */
     FS2_MIXED_F16_X3 = 6 /* engine mode: MIXED_X3's front, launch for launch; the back (decoder stack, the mel Linear's operands) in F16 */
 };
 
@@ -614,7 +615,11 @@ int fs2_op_cwt_head(int32_t dtype, const void* out_conv, const float* spec, int3
 #define FS2_VOC_MAX_KERNELS 4
 typedef struct fs2_voc_config {
     int32_t abi_version;      /* FS2_ABI_VERSION */
-    int32_t dtype;            /* fs2_dtype */
+    int32_t dtype;            /* FS2_F32 (parity mode, fp32 MFMA), FS2_BF16 (throughput mode) or FS2_F16: bf16's kernels, tiles and byte
+                                 counts with every stored tensor - the packed weights, the mel at conv_pre's slab fill, the streams
+                                 between launches, the LDS slabs of the resident resblocks, the stage means - in IEEE binary16 under
+                                 FS2_F16's storage rule (saturating stores).  Accumulation, biases, the 1 / n_kernels scale, conv_post,
+                                 tanh and the wav are fp32 in all three.  The engine modes (FS2_MIXED*, FS2_F32_X3) are FS2_ERR_ARG. */
     int32_t n_mels;           /* 80 */
     int32_t initial_channel;  /* upsample_initial_channel (config.json:13); halves per stage, multiples of 32 */
     int32_t n_stages;

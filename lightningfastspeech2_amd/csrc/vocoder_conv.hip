@@ -24,6 +24,7 @@ namespace {
 
 template <typename T> struct VocT;
 template <> struct VocT<bf16> { static constexpr int KE = 32; };   // elements per 64-byte k-step
+template <> struct VocT<f16> { static constexpr int KE = 32; };
 template <> struct VocT<float> { static constexpr int KE = 16; };
 
 // 0 < slope <= 1.  The bare instruction: fmaxf puts a canonicalising v_max(v, v) in front of every value that did not
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(512) void vocoder_conv_kernel(VocConvArgs p) {
 #pragma unroll
                     for (int e = 0; e < E16; ++e) f[e] = lrelu(f[e], p.in_slope);
                 }
-                *(uint4*)(slab + i * rowb + (swz.slot(s, i) << 4)) = Vec16<T>::pack(f);
+                *(uint4*)(slab + i * rowb + (swz.slot(s, i) << 4)) = Vec16<T>::pack(f);  // fp32 mel: the clamping pack (f16)
             }
         } else {
             const T* xb = (const T*)p.x + ubase * p.cin;
@@ -130,7 +131,8 @@ __global__ __launch_bounds__(512) void vocoder_conv_kernel(VocConvArgs p) {
                         Vec16<T>::unpack(raw[u], f);
 #pragma unroll
                         for (int e = 0; e < E16; ++e) f[e] = lrelu(f[e], p.in_slope);
-                        raw[u] = Vec16<T>::pack(f);
+                        // read from storage type T and scaled by 0 < slope <= 1 only: inside T's range, no clamp (f16)
+                        raw[u] = Vec16<T>::pack_bounded(f);
                     }
                     *(uint4*)(slab + dst[u]) = raw[u];
                 }
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(512) void vocoder_conv_kernel(VocConvArgs p) {
             if (t < len) {
                 uint4* dst = (uint4*)(outb + ((unsigned)t * rown + nb0));
 #pragma unroll
-                for (int q = 0; q < NP; ++q) dst[q] = Vec16<T>::pack(v + q * E16);
+                for (int q = 0; q < NP; ++q) dst[q] = Vec16<T>::pack(v + q * E16);  // fp32 accumulator: the clamping pack (f16)
             }
         }
     }
@@ -380,26 +382,32 @@ static int voc_launch_t(const VocConvArgs& a, size_t smem, hipStream_t stream) {
 }
 
 int voc_steps_padded(int taps, int cin_pad, int dtype) {
-    const int ke = dtype == FS2_BF16 ? 32 : 16;
+    const int ke = is_16bit(dtype) ? 32 : 16;
     return (taps * (cin_pad / ke) + 3) & ~3;
 }
 
 int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream) {
-    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32 or bf16
+    if (!is_storage_dtype(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32, bf16 or binary16
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
     if (a.wn != 1 && a.wn != 2 && a.wn != 4 && a.wn != 8) return FS2_ERR_SHAPE;
     if (a.cin_pad < 32 || (a.cin_pad & (a.cin_pad - 1)) || a.cin > a.cin_pad || a.cin % 4) return FS2_ERR_SHAPE;
     if (!a.post && (a.n % 32 || a.n % (a.wn * 32))) return FS2_ERR_SHAPE;
-    if (!a.in_fp32 && a.cin % (dtype == FS2_BF16 ? 8 : 4)) return FS2_ERR_SHAPE;
+    if (!a.in_fp32 && a.cin % (is_16bit(dtype) ? 8 : 4)) return FS2_ERR_SHAPE;
     if (a.shift_from % 32 || a.shift_from < 0 || a.shift_from >= (a.post ? 1 : a.n)) return FS2_ERR_SHAPE;
     size_t smem = 0;
-    const int mi = voc_pick_mi16(a, dtype == FS2_BF16 ? 2 : 4, &smem);
+    const int mi = voc_pick_mi16(a, (int)elem_bytes(dtype), &smem);
     if (!mi) return FS2_ERR_SHAPE;
     if (dtype == FS2_BF16) {
         if (mi == 14) return voc_launch_t<bf16, 14>(a, smem, stream);
         if (mi == 8) return voc_launch_t<bf16, 8>(a, smem, stream);
         if (mi == 4) return voc_launch_t<bf16, 4>(a, smem, stream);
         return voc_launch_t<bf16, 2>(a, smem, stream);
+    }
+    if (dtype == FS2_F16) {  // bf16's tiles, LDS sizes and grids: the two differ in Vec16 / Mma16 only
+        if (mi == 14) return voc_launch_t<f16, 14>(a, smem, stream);
+        if (mi == 8) return voc_launch_t<f16, 8>(a, smem, stream);
+        if (mi == 4) return voc_launch_t<f16, 4>(a, smem, stream);
+        return voc_launch_t<f16, 2>(a, smem, stream);
     }
     if (mi == 14) return voc_launch_t<float, 14>(a, smem, stream);
     if (mi == 8) return voc_launch_t<float, 8>(a, smem, stream);

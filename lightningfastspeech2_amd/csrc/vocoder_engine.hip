@@ -103,7 +103,7 @@ int next_pow2(int x) {
 // fragment order [n-tile][step][wn][2][64] x 16 B as fp32 staging
 void frag_order(int dt, const std::vector<float>& W, int n, int cin, int cin_pad, int taps, int wn_cols, bool post,
                 std::vector<float>* stage) {
-    const int KE = dt == FS2_BF16 ? 32 : 16, e16 = dt == FS2_BF16 ? 8 : 4;
+    const int KE = is_16bit(dt) ? 32 : 16, e16 = 16 / (int)elem_bytes(dt);
     const int nkc = cin_pad / KE, nsteps4 = voc_steps_padded(taps, cin_pad, dt);
     const int ntiles = post ? 1 : n / (wn_cols * 32);
     const size_t nfrag = (size_t)ntiles * nsteps4 * wn_cols * 2 * 64;
@@ -132,7 +132,10 @@ int upload_frags(fs2_vocoder* v, const std::vector<float>& stage, void** out) {
         VHIP(v, hipMemcpy(*out, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
     } else {
         std::vector<unsigned short> h(stage.size());
-        for (size_t i = 0; i < stage.size(); ++i) h[i] = f32_to_bf16(stage[i]).v;
+        if (v->dt == FS2_F16)
+            for (size_t i = 0; i < stage.size(); ++i) h[i] = f32_to_f16_sat(stage[i]).v;  // the storage rule of a device store
+        else
+            for (size_t i = 0; i < stage.size(); ++i) h[i] = f32_to_bf16(stage[i]).v;
         VCHK(vdev_alloc(v, out, h.size() * 2));
         VHIP(v, hipMemcpy(*out, h.data(), h.size() * 2, hipMemcpyHostToDevice));
     }
@@ -241,11 +244,11 @@ int fs2_voc_create(const fs2_voc_config* cfg, fs2_vocoder** out) {
     if (cfg->n_stages < 1 || cfg->n_stages > FS2_VOC_MAX_STAGES || cfg->n_kernels < 1 || cfg->n_kernels > FS2_VOC_MAX_KERNELS)
         return FS2_ERR_SHAPE;
     if (cfg->n_mels < 4 || cfg->n_mels % 4 || (cfg->initial_channel >> cfg->n_stages) % 32) return FS2_ERR_SHAPE;
-    if (cfg->dtype != FS2_F32 && cfg->dtype != FS2_BF16) return FS2_ERR_ARG;
+    if (!is_storage_dtype(cfg->dtype)) return FS2_ERR_ARG;  // FS2_F32, FS2_BF16 or FS2_F16: the engine modes are not storage types
     fs2_vocoder* v = new fs2_vocoder();
     v->cfg = *cfg;
     v->dt = cfg->dtype;
-    v->esz = cfg->dtype == FS2_BF16 ? 2 : 4;
+    v->esz = elem_bytes(cfg->dtype);
     const int C0 = cfg->initial_channel;
     v->spec["conv_pre.weight"] = {C0, cfg->n_mels, 7};
     v->spec["conv_pre.bias"] = {C0};

@@ -25,6 +25,7 @@ namespace fs2 {
 namespace {
 template <typename T> struct RbT;
 template <> struct RbT<bf16> { static constexpr int KE = 32; };
+template <> struct RbT<f16> { static constexpr int KE = 32; };
 template <> struct RbT<float> { static constexpr int KE = 16; };
 // 0 < slope <= 1: LeakyReLU(v) = max(v, slope*v), its inverse = min(a, a/slope).  fmaxf / fminf put a
 // canonicalising v_max(v, v) in front of every value that did not come out of an arithmetic instruction (MFMA
@@ -155,7 +156,8 @@ __global__ __launch_bounds__(NW * 64, 2) void vocoder_resblock_kernel(VocResbloc
                 float f[E16];
                 Vec16<T>::unpack(raw[u], f);
                 rb_lrelu_n<E16>(f, p.slope);
-                *(uint4*)(slabX + dst[u]) = Vec16<T>::pack(f);
+                // read from storage type T and scaled by 0 < slope <= 1 only: inside T's range, no clamp (f16)
+                *(uint4*)(slabX + dst[u]) = Vec16<T>::pack_bounded(f);
             }
         }
         }
@@ -328,6 +330,8 @@ __global__ __launch_bounds__(NW * 64, 2) void vocoder_resblock_kernel(VocResbloc
             }
         } else {
             // + residual, recovered from the activated copy; all of this wave's rows of X are requested first
+            // (f16: a / slope may leave the binary16 range - it lives in fp32 only and is stored after the add, through the
+            //  clamping pack like every other accumulator in this kernel)
             uint4 xa[MC][SPL];
             auto fetch = [&](int m) {  // at the head of every chunk of MC fragments
 #pragma unroll
@@ -445,10 +449,10 @@ static size_t rb_lds_bytes(const VocResblockArgs& a, int nw, int mi16, int esz) 
 // is taken when >= 85 % of its rows are useful: 3-9 % faster than the 8-wave full-height tile on the 32/64-
 // channel stages and on the 128-channel k=7 pairs, equal elsewhere (repeated A/B runs).
 int voc_resblock_mi16(const VocResblockArgs& a, int dtype) {
-    if (!is_f32_or_bf16(dtype)) return 0;
+    if (!is_storage_dtype(dtype)) return 0;
     const int g_voc_fused_resblock = tuning_of(a.tune).voc_fused_resblock;
     if (!g_voc_fused_resblock || (g_voc_fused_resblock == 2 && a.npairs != 1)) return 0;
-    const int esz = dtype == FS2_BF16 ? 2 : 4;
+    const int esz = (int)elem_bytes(dtype);
     if (a.C != 32 && a.C != 64 && a.C != 128) return 0;
     if (a.wn != a.C / 32 || !(a.taps & 1) || (a.npairs != 1 && a.npairs != 3)) return 0;
     // a whole block per launch pays while a conv's K loop is short (<= 7 steps of 32 channels): measured 5-15 %
@@ -498,15 +502,19 @@ static int rb_launch_t(const VocResblockArgs& a, size_t smem, hipStream_t stream
 }
 
 int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t stream) {
-    if (!is_f32_or_bf16(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32 or bf16
+    if (!is_storage_dtype(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32, bf16 or binary16
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
     const int cfg = voc_resblock_mi16(a, dtype);
     if (!cfg) return FS2_ERR_SHAPE;
     const int nw = cfg / 100, mi = cfg % 100;
-    const size_t smem = rb_lds_bytes(a, nw, mi, dtype == FS2_BF16 ? 2 : 4);
+    const size_t smem = rb_lds_bytes(a, nw, mi, (int)elem_bytes(dtype));
     if (dtype == FS2_BF16) {
         if (nw == 4) return rb_launch_t<bf16, 8, 4>(a, smem, stream);
         return mi == 8 ? rb_launch_t<bf16, 8, 8>(a, smem, stream) : rb_launch_t<bf16, 4, 8>(a, smem, stream);
+    }
+    if (dtype == FS2_F16) {  // bf16's tiles, LDS sizes and grids
+        if (nw == 4) return rb_launch_t<f16, 8, 4>(a, smem, stream);
+        return mi == 8 ? rb_launch_t<f16, 8, 8>(a, smem, stream) : rb_launch_t<f16, 4, 8>(a, smem, stream);
     }
     if (nw == 4) return rb_launch_t<float, 8, 4>(a, smem, stream);
     return mi == 8 ? rb_launch_t<float, 8, 8>(a, smem, stream) : rb_launch_t<float, 4, 8>(a, smem, stream);

@@ -153,16 +153,26 @@ def _bind(lib):
     return lib
 
 
+_PRECISIONS = {"bf16": _lib.FS2_BF16, "fp32": _lib.FS2_F32, "fp16": _lib.FS2_F16}
+
+
 class HifiGan:
     """Device-resident generator.  ``state_dict`` may be the checkpoint form (weight_g / weight_v) or
-    plain weights; names are the reference generator's own."""
+    plain weights; names are the reference generator's own.
+
+    ``precision``: "fp32" (parity mode, fp32 MFMA), "bf16" (throughput mode, the default) or "fp16": bf16's kernels, tiles and
+    byte counts with every stored tensor (weights, the mel slab, the streams between launches, the stage means) in IEEE binary16
+    - three more mantissa bits; stores saturate at +-65504.  Accumulation, biases, tanh and the wav are fp32 in all three."""
 
     def __init__(self, cfg: HifiGanConfig, state_dict, precision: str = "bf16", device="cuda:0"):
         self.cfg, self.device = cfg, torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the HiFi-GAN generator runs on an MI355X only (no CPU fallback)")
         self.lib = _bind(_lib.load())
-        self.dtype = {"bf16": _lib.FS2_BF16, "fp32": _lib.FS2_F32}[precision]
+        if precision not in _PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
+        self.precision = precision
+        self.dtype = _PRECISIONS[precision]
         self.handle = C.c_void_p()
         cc = _config_to_c(cfg, self.dtype)
         with torch.cuda.device(self.device):  # no global set_device: the reference Synthesiser has no such side effect
@@ -229,7 +239,7 @@ class HifiGan:
 class Synthesiser:
     """Drop-in for ``litfass.third_party.hifigan.Synthesiser`` (__init__.py:19-43): ``synth(mel)`` with
     mel ``(T, num_mels)`` returns int16 numpy ``(1, T*hop)``.  ``checkpoint`` is the path of a
-    ``generator_*.pth.tar`` (``{"generator": state_dict}``) or a state_dict."""
+    ``generator_*.pth.tar`` (``{"generator": state_dict}``) or a state_dict.  ``precision`` is HifiGan's ("bf16", "fp16", "fp32")."""
 
     def __init__(self, device="cuda:0", model="universal", checkpoint=None, config: Optional[HifiGanConfig] = None,
                  precision: str = "bf16"):

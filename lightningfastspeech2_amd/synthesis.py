@@ -34,7 +34,8 @@ class SpeechGenerator:
     """``generate_samples(batch)`` -> ``{"fs", "audios"[, "durations"]}`` like the reference's
     (generator.py:151-223): ``audios`` is a list of float32 arrays, one per utterance, each the
     int16-quantised generator output rescaled by 1/32767 exactly as the reference does
-    (Synthesiser.__call__ then int16_samples_to_float32)."""
+    (Synthesiser.__call__ then int16_samples_to_float32).  Either object carries its own precision: the reference's mel and the
+    reference's waveform at 16-bit speed are ``FastSpeech2(precision="mixed16")`` with ``HifiGan(precision="fp16")``."""
 
     def __init__(self, model: FastSpeech2, vocoder: HifiGan, g2p_model=None):
         self.model, self.synth, self.g2p = model, vocoder, g2p_model

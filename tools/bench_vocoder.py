@@ -2,7 +2,10 @@
 """Benchmark of the HiFi-GAN generator on the mel forward's own output shape:
 B utterances x T frames of synthetic mel -> B x T*256 samples, inputs resident in HBM.
 
-    python tools/bench_vocoder.py [--batch 32 --frames 1536 --steps 5 --warmup 2 --precision bf16]
+    python tools/bench_vocoder.py [--batch 32 --frames 1536 --steps 5 --warmup 2 --precision bf16|fp16|fp32]
+
+With --compare bf16,fp16 the listed precisions run ALTERNATING in one process, --loops timed loops of --steps passes each, and
+every precision gets one JSON line with its fastest loop and all of them (boxes differ by ~8 %: only figures of one run compare).
 
 Prints ONE JSON line: samples/s and mel-frames/s of the whole batch, the aggregate MFMA roofline
 (algorithmic FLOPs of every conv in Generator.forward / wall time per pass) and a CPU baseline (the
@@ -22,7 +25,7 @@ import torch
 
 from lightningfastspeech2_amd.hifigan import HifiGan, HifiGanConfig, synth_state_dict
 
-MFMA_PEAK = {"bf16": 2.5e15, "fp32": 157.3e12}
+MFMA_PEAK = {"bf16": 2.5e15, "fp16": 2.5e15, "fp32": 157.3e12}
 
 
 def flops_per_frame(cfg):
@@ -38,13 +41,41 @@ def flops_per_frame(cfg):
     return fl
 
 
+def compare(a, cfg, sd, mel):
+    """the precisions of --compare in turn, --loops times: ms per pass of every loop, the fastest and the spread"""
+    from lightningfastspeech2_amd import _lib
+    modes = [m for m in a.compare.split(",") if m]
+    gens = {m: HifiGan(cfg, sd, precision=m) for m in modes}
+    for g in gens.values():
+        for _ in range(a.warmup):
+            g.synthesize(mel)
+    loops = {m: [] for m in modes}
+    for _ in range(a.loops):
+        for m in modes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                wav = gens[m].synthesize(mel)
+            torch.cuda.synchronize()
+            loops[m].append((time.perf_counter() - t0) / a.steps * 1e3)
+            assert bool(torch.isfinite(wav).all())
+    for m in modes:
+        t = loops[m]
+        print(json.dumps({"tool": "bench_vocoder --compare", "dtype": m, "ms_per_pass": round(min(t), 4), "loops_ms": [round(x, 4) for x in t],
+                          "spread": round((max(t) - min(t)) / min(t), 4), "batch": a.batch, "frames": a.frames, "steps": a.steps,
+                          "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "library": os.path.basename(os.path.dirname(_lib.LIB_PATH))
+                          if os.environ.get("FS2_LIB") else "in-tree"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=1536)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
+    ap.add_argument("--compare", default="", help="comma list of precisions run alternating in one process (no roofline / CPU legs)")
+    ap.add_argument("--loops", type=int, default=5, help="--compare: timed loops per precision")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=192)
     ap.add_argument("--no-fused-resblock", action="store_true", help="A/B: narrow-stage resblocks conv by conv")
@@ -53,13 +84,15 @@ def main():
     a = ap.parse_args()
     cfg = HifiGanConfig()
     sd = synth_state_dict(cfg, 0)
-    g = HifiGan(cfg, sd, precision=a.precision)
     from lightningfastspeech2_amd import _lib
     if a.lds_limit:
         _lib.load().fs2_op_set_vocoder_lds_limit(a.lds_limit)
     _lib.load().fs2_op_set_vocoder_fused_resblock(0 if a.no_fused_resblock else a.fused_mode)
     rs = np.random.RandomState(1234)
     mel = torch.from_numpy((rs.standard_normal((a.batch, a.frames, 80)) * 1.5 - 4.0).astype(np.float32)).cuda()
+    if a.compare:
+        return compare(a, cfg, sd, mel)
+    g = HifiGan(cfg, sd, precision=a.precision)
     for _ in range(a.warmup):
         wav = g.synthesize(mel)
     torch.cuda.synchronize()
