@@ -558,6 +558,23 @@ int fs2_op_dropout(int32_t dtype, const void* x, void* y, size_t n, float p, uin
  * last LayerNorm and the Linear (otherwise fs2_op_layernorm's fused head does it) */
 int fs2_op_row_dot(int32_t dtype, const void* y, const float* w, const float* b, const uint8_t* mask, float* pred, int64_t M,
                    int32_t H, void* hip_stream);
+/* CWT head of a VariancePredictor in training (model.py:413-415, 505-520), one pass over out_conv (B*S, F) in `dtype`
+ * (FS2_F32 / FS2_BF16; F a multiple of 64, 64..1024; anything else is FS2_ERR_ARG):
+ *   spec_out (B*S, 10) = mask ? 0 : out_conv w10^T + b10;  ybar_out (B, F) = mean over ALL S rows of an utterance (pads included);
+ *   mean_std_out (B, 2) = ybar ms_w^T + ms_b.
+ * Column sums by per-workgroup partials in ws (fs2_op_cwt_head_train_ws_bytes), added in a fixed order; fp32 accumulation. */
+size_t fs2_op_cwt_head_train_ws_bytes(int32_t B, int32_t S, int32_t F);
+int fs2_op_cwt_head_train(int32_t dtype, const void* out_conv, const float* w10, const float* b10, const float* ms_w, const float* ms_b,
+                          const uint8_t* mask, float* spec_out, float* ybar_out, float* mean_std_out, float* ws, int32_t B, int32_t S,
+                          int32_t F, void* hip_stream);
+/* ... and its backward, one pass again: dy (B*S, F) in `dtype` = dspec w10 + (1 / S) dms[b] ms_w (pad rows, whose dspec is 0, get the
+ * second term too);  g_w10 (10, F) += dspec^T out_conv,  g_b10 (10) += column sums of dspec  (per-workgroup partials in ws, added
+ * in workgroup order);  g_ms_w (2, F) += dms^T ybar,  g_ms_b (2) += column sums of dms.  Same inputs, same bits.
+ * ws: fs2_op_cwt_head_bwd_ws_bytes, zero before its first use (it starts with a fs2_op_col_sum workspace, whose counters so keep one address for every shape). */
+size_t fs2_op_cwt_head_bwd_ws_bytes(int32_t B, int32_t S, int32_t F);
+int fs2_op_cwt_head_bwd(int32_t dtype, const void* out_conv, const float* dspec, const float* dms, const float* ybar, const float* w10,
+                        const float* ms_w, void* dy, float* g_w10, float* g_b10, float* g_ms_w, float* g_ms_b, float* ws, int32_t B,
+                        int32_t S, int32_t F, void* hip_stream);
 /* depth-wise Conv1d (model.py:75-81, 545-551) backward: data gradient = the same conv with the taps reversed and no bias;
  * weight / bias gradient as per-chunk partials part (fs2_op_dwconv_wgrad_parts(B, S), C * (k + 1)): [c * k + j] then [C * k + c],
  * reduced with fs2_op_col_sum into the adjacent (C, k) weight and (C) bias gradients */

@@ -212,6 +212,12 @@ def load():
     lib.fs2_op_bucket_embed_utt.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]
     lib.fs2_op_dropout.argtypes = [i32, vp, vp, sz, f32, C.c_uint64, C.c_uint64, vp]
     lib.fs2_op_row_dot.argtypes = [i32, vp, vp, vp, vp, vp, C.c_int64, i32, vp]
+    lib.fs2_op_cwt_head_train_ws_bytes.restype = sz
+    lib.fs2_op_cwt_head_train_ws_bytes.argtypes = [i32, i32, i32]
+    lib.fs2_op_cwt_head_train.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.fs2_op_cwt_head_bwd_ws_bytes.restype = sz
+    lib.fs2_op_cwt_head_bwd_ws_bytes.argtypes = [i32, i32, i32]
+    lib.fs2_op_cwt_head_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fs2_op_dwconv_dgrad.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.fs2_op_dwconv_wgrad_parts.restype = i32
     lib.fs2_op_dwconv_wgrad_parts.argtypes = [i32, i32]

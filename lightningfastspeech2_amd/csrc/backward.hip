@@ -883,9 +883,246 @@ __global__ __launch_bounds__(256) void unfold_conv2_g_kernel(UnfoldConv2Args p) 
     if (tid == 0) p.dbg[f] += red[0][UF_GS];
 }
 
+// ---- CWT head of a VariancePredictor in training (model.py:413-415, 505-520) ------------------------------------------
+// spec[r] = mask[r] ? 0 : W10 y[r] + b10 (ten dots per row), ybar[b] = mean over ALL S rows of utterance b (pads included, as
+// torch.mean(out_conv, axis=1) has it), mean_std[b] = Wms ybar[b] + bms; and the backward of the three.  Both are ONE pass over
+// y = out_conv (B*S, F): a workgroup owns CWT_ROWS rows of one utterance, a wave a row at a time, a lane 4 consecutive columns of
+// every 256-column chunk (8- / 16-byte accesses: a row of 256 bf16 is 512 B, so all 64 lanes load), W10 in LDS, the dots by
+// wave_sum.  What crosses workgroups (column sums of y; dspec^T y and the column sums of dspec) leaves as one partial per
+// workgroup and is added in workgroup order by a second launch: no atomics, bit-equal reruns.
+constexpr int CWT_J = 10;      // wavelet scales: Linear(filter, 10), model.py:508
+constexpr int CWT_ROWS = 64;
+constexpr int CWT_MAXC = 4;    // 256-column chunks: F <= 1024
+
+template <int NC>
+__device__ inline void cwt_load_w10(float (*wsh)[256 * NC], const float* w10, int F) {
+    for (int i = threadIdx.x; i < CWT_J * 256 * NC; i += 256) {
+        const int q = i / (256 * NC), c = i % (256 * NC);
+        wsh[q][c] = c < F ? w10[q * F + c] : 0.f;
+    }
+    __syncthreads();
+}
+
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void cwt_head_train_kernel(CwtHeadTrainArgs p) {
+    __shared__ float wsh[CWT_J][256 * NC];
+    __shared__ float red[4][256 * NC];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int b = blockIdx.y, F = p.F;
+    cwt_load_w10<NC>(wsh, p.w10, F);
+    float cs[NC][4];
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cs[j][e] = 0.f;
+    const int r0 = blockIdx.x * CWT_ROWS, r1 = min(p.S, r0 + CWT_ROWS);
+    const T* y = (const T*)p.out_conv + (long)b * p.S * F;
+    for (int r = r0 + wid; r < r1; r += 4) {
+        const long row = (long)b * p.S + r;
+        float d[CWT_J];
+#pragma unroll
+        for (int q = 0; q < CWT_J; ++q) d[q] = 0.f;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const int c = j * 256 + lane * 4;
+            if (c < F) {
+                float v[4];
+                ld4<T>(y + (long)r * F + c, v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) cs[j][e] += v[e];
+#pragma unroll
+                for (int q = 0; q < CWT_J; ++q) {
+                    const float4 w = *(const float4*)&wsh[q][c];
+                    d[q] = fmaf(v[0], w.x, fmaf(v[1], w.y, fmaf(v[2], w.z, fmaf(v[3], w.w, d[q]))));
+                }
+            }
+        }
+        float o = 0.f;
+#pragma unroll
+        for (int q = 0; q < CWT_J; ++q) {
+            const float s = wave_sum(d[q]);
+            if (lane == q) o = s;
+        }
+        if (lane < CWT_J) p.spec[row * CWT_J + lane] = p.mask[row] ? 0.f : o + p.b10[lane];
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[wid][j * 256 + lane * 4 + e] = cs[j][e];
+    __syncthreads();
+    float* part = p.ws + ((long)b * gridDim.x + blockIdx.x) * F;
+    for (int c = threadIdx.x; c < F; c += 256) part[c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+}
+
+// one workgroup per utterance: the chunk partials in chunk order -> ybar, then the 2-wide Linear
+__global__ __launch_bounds__(256) void cwt_head_finish_kernel(CwtHeadTrainArgs p, int nchunk) {
+    __shared__ float sh[2][4];
+    const int b = blockIdx.x, tid = threadIdx.x, F = p.F;
+    float d0 = 0.f, d1 = 0.f;
+    for (int c = tid; c < F; c += 256) {
+        float s = 0.f;
+        for (int k = 0; k < nchunk; ++k) s += p.ws[((long)b * nchunk + k) * F + c];
+        const float m = s / (float)p.S;
+        p.ybar[(long)b * F + c] = m;
+        d0 = fmaf(m, p.ms_w[c], d0);
+        d1 = fmaf(m, p.ms_w[F + c], d1);
+    }
+    d0 = wave_sum(d0);
+    d1 = wave_sum(d1);
+    if ((tid & 63) == 0) { sh[0][tid >> 6] = d0; sh[1][tid >> 6] = d1; }
+    __syncthreads();
+    if (tid < 2) p.mean_std[2 * b + tid] = ((sh[tid][0] + sh[tid][1]) + (sh[tid][2] + sh[tid][3])) + p.ms_b[tid];
+}
+
+// dy[r] = sum_q dspec[r][q] W10[q] + (1 / S) sum_k dms[b][k] Wms[k]  (pad rows: dspec = 0, the second term stays);
+// part[workgroup] = (dspec^T y | column sums of dspec) over the workgroup's rows, row stride ld
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void cwt_head_bwd_kernel(CwtHeadBwdArgs p, int ld) {
+    __shared__ float wsh[CWT_J][256 * NC];
+    __shared__ float red[4][256 * NC];
+    __shared__ float redb[4][CWT_J];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int b = blockIdx.y, F = p.F;
+    cwt_load_w10<NC>(wsh, p.w10, F);
+    float gw[CWT_J][NC][4], gb[CWT_J], ms[NC][4];
+    const float m0 = p.dms[2 * b], m1 = p.dms[2 * b + 1], invS = 1.f / (float)p.S;
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = j * 256 + lane * 4 + e;
+            ms[j][e] = c < F ? (m0 * p.ms_w[c] + m1 * p.ms_w[F + c]) * invS : 0.f;
+#pragma unroll
+            for (int q = 0; q < CWT_J; ++q) gw[q][j][e] = 0.f;
+        }
+#pragma unroll
+    for (int q = 0; q < CWT_J; ++q) gb[q] = 0.f;
+    const int r0 = blockIdx.x * CWT_ROWS, r1 = min(p.S, r0 + CWT_ROWS);
+    const T* y = (const T*)p.out_conv + (long)b * p.S * F;
+    T* dy = (T*)p.dy + (long)b * p.S * F;
+    for (int r = r0 + wid; r < r1; r += 4) {
+        const float* dsr = p.dspec + ((long)b * p.S + r) * CWT_J;
+        float ds[CWT_J];
+#pragma unroll
+        for (int q = 0; q < CWT_J; ++q) {
+            ds[q] = dsr[q];
+            gb[q] += ds[q];
+        }
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const int c = j * 256 + lane * 4;
+            if (c < F) {
+                float v[4], o[4];
+                ld4<T>(y + (long)r * F + c, v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = ms[j][e];
+#pragma unroll
+                for (int q = 0; q < CWT_J; ++q) {
+                    const float4 w = *(const float4*)&wsh[q][c];
+                    o[0] = fmaf(ds[q], w.x, o[0]); o[1] = fmaf(ds[q], w.y, o[1]);
+                    o[2] = fmaf(ds[q], w.z, o[2]); o[3] = fmaf(ds[q], w.w, o[3]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) gw[q][j][e] = fmaf(ds[q], v[e], gw[q][j][e]);
+                }
+                st4<T>(dy + (long)r * F + c, o);
+            }
+        }
+    }
+    float* part = p.ws + ((long)b * gridDim.x + blockIdx.x) * ld;
+#pragma unroll
+    for (int q = 0; q < CWT_J; ++q) {
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) red[wid][j * 256 + lane * 4 + e] = gw[q][j][e];
+        __syncthreads();
+        for (int c = threadIdx.x; c < F; c += 256) part[q * F + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+        __syncthreads();
+    }
+    if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < CWT_J; ++q) redb[wid][q] = gb[q];
+    __syncthreads();
+    if (threadIdx.x < CWT_J) {
+        const int q = threadIdx.x;
+        part[CWT_J * F + q] = (redb[0][q] + redb[1][q]) + (redb[2][q] + redb[3][q]);
+    }
+}
+
+// g_ms_w[k][c] += sum_b dms[b][k] ybar[b][c];  g_ms_b[k] += sum_b dms[b][k]   (utterances in order)
+__global__ __launch_bounds__(256) void cwt_ms_grad_kernel(CwtHeadBwdArgs p) {
+    const int i = blockIdx.x * 256 + threadIdx.x, F = p.F;
+    if (i < 2 * F) {
+        const int k = i / F, c = i % F;
+        float a = 0.f;
+        for (int b = 0; b < p.B; ++b) a = fmaf(p.dms[2 * b + k], p.ybar[(long)b * F + c], a);
+        p.g_ms_w[i] += a;
+    }
+    if (i < 2) {
+        float a = 0.f;
+        for (int b = 0; b < p.B; ++b) a += p.dms[2 * b + i];
+        p.g_ms_b[i] += a;
+    }
+}
+
 inline int ok() { return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP; }
 
 }  // namespace
+
+static bool cwt_shape_ok(int B, int S, int F, int dtype) {
+    return is_f32_or_bf16(dtype) && B > 0 && B <= 65535 && S > 0 && F >= 64 && F <= 256 * CWT_MAXC && F % 64 == 0;
+}
+static int cwt_chunks(int S) { return (S + CWT_ROWS - 1) / CWT_ROWS; }
+static int cwt_part_ld(int F) { return CWT_J * F + 16; }  // (dspec^T y | column sums of dspec | pad): rows stay 16-byte aligned
+// the backward's workspace: the fs2_op_col_sum workspace FIRST (its ticket counters stay at one address whatever the shape, so a
+// buffer shared between shapes keeps them zero), the workgroup partials behind it, 16-byte aligned
+static size_t cwt_cs_floats(int nblk, int F) { return (col_sum_ws_bytes(nblk, CWT_J * F + CWT_J, 0) / sizeof(float) + 3) / 4 * 4; }
+
+size_t cwt_head_train_ws_bytes(int B, int S, int F) {
+    if (B <= 0 || S <= 0 || F <= 0) return 0;
+    return (size_t)B * cwt_chunks(S) * F * sizeof(float);
+}
+int launch_cwt_head_train(const CwtHeadTrainArgs& a, int dtype, hipStream_t stream) {
+    if (!cwt_shape_ok(a.B, a.S, a.F, dtype)) return FS2_ERR_ARG;
+    if (!a.out_conv || !a.w10 || !a.b10 || !a.ms_w || !a.ms_b || !a.mask || !a.spec || !a.ybar || !a.mean_std || !a.ws) return FS2_ERR_ARG;
+    const int nchunk = cwt_chunks(a.S), nc = (a.F + 255) / 256;
+    const dim3 g(nchunk, a.B);
+#define FS2_CWT(T, NC) hipLaunchKernelGGL((cwt_head_train_kernel<T, NC>), g, dim3(256), 0, stream, a)
+    if (dtype == FS2_F32) { if (nc == 1) FS2_CWT(float, 1); else if (nc == 2) FS2_CWT(float, 2); else if (nc == 3) FS2_CWT(float, 3); else FS2_CWT(float, 4); }
+    else { if (nc == 1) FS2_CWT(bf16, 1); else if (nc == 2) FS2_CWT(bf16, 2); else if (nc == 3) FS2_CWT(bf16, 3); else FS2_CWT(bf16, 4); }
+#undef FS2_CWT
+    hipLaunchKernelGGL(cwt_head_finish_kernel, dim3(a.B), dim3(256), 0, stream, a, nchunk);
+    return ok();
+}
+
+size_t cwt_head_bwd_ws_bytes(int B, int S, int F) {
+    if (B <= 0 || S <= 0 || F <= 0) return 0;
+    const long nblk = (long)B * cwt_chunks(S);
+    if (nblk > 0x7fffffffL / cwt_part_ld(F)) return 0;
+    return cwt_cs_floats((int)nblk, F) * sizeof(float) + (size_t)nblk * cwt_part_ld(F) * sizeof(float);
+}
+int launch_cwt_head_bwd(const CwtHeadBwdArgs& a, int dtype, hipStream_t stream) {
+    if (!cwt_shape_ok(a.B, a.S, a.F, dtype) || !cwt_head_bwd_ws_bytes(a.B, a.S, a.F)) return FS2_ERR_ARG;
+    if (!a.out_conv || !a.dspec || !a.dms || !a.ybar || !a.w10 || !a.ms_w || !a.dy || !a.g_w10 || !a.g_b10 || !a.g_ms_w || !a.g_ms_b || !a.ws)
+        return FS2_ERR_ARG;
+    const int nchunk = cwt_chunks(a.S), nc = (a.F + 255) / 256, ld = cwt_part_ld(a.F), nblk = a.B * nchunk;
+    const dim3 g(nchunk, a.B);
+    float* const cs_ws = a.ws;
+    CwtHeadBwdArgs k = a;
+    k.ws = a.ws + cwt_cs_floats(nblk, a.F);  // the partials
+#define FS2_CWT(T, NC) hipLaunchKernelGGL((cwt_head_bwd_kernel<T, NC>), g, dim3(256), 0, stream, k, ld)
+    if (dtype == FS2_F32) { if (nc == 1) FS2_CWT(float, 1); else if (nc == 2) FS2_CWT(float, 2); else if (nc == 3) FS2_CWT(float, 3); else FS2_CWT(float, 4); }
+    else { if (nc == 1) FS2_CWT(bf16, 1); else if (nc == 2) FS2_CWT(bf16, 2); else if (nc == 3) FS2_CWT(bf16, 3); else FS2_CWT(bf16, 4); }
+#undef FS2_CWT
+    hipLaunchKernelGGL(cwt_ms_grad_kernel, dim3((2 * a.F + 255) / 256), dim3(256), 0, stream, a);
+    if (hipGetLastError() != hipSuccess) return FS2_ERR_HIP;
+    // the workgroup partials, in workgroup order, ADDED to (g_w10 | g_b10)
+    ColSumArgs cs{k.ws, a.g_w10, cs_ws, nblk, CWT_J * a.F + CWT_J, ld, 0, 1, 1.f};
+    cs.out2 = a.g_b10;
+    cs.n1 = CWT_J * a.F;
+    cs.accumulate2 = 1;
+    return launch_col_sum(cs, FS2_F32, stream);
+}
 
 int launch_dropout(const DropoutArgs& a, int dtype, hipStream_t stream) {
     if (!(a.p >= 0.f && a.p < 1.f)) return FS2_ERR_ARG;

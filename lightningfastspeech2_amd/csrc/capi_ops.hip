@@ -594,6 +594,20 @@ int fs2_op_row_dot(int32_t dtype, const void* y, const float* w, const float* b,
     RowDotArgs a{y, w, b, mask, pred, (long)M, H};
     return launch_row_dot(a, dtype, (hipStream_t)stream);
 }
+size_t fs2_op_cwt_head_train_ws_bytes(int32_t B, int32_t S, int32_t F) { return cwt_head_train_ws_bytes(B, S, F); }
+int fs2_op_cwt_head_train(int32_t dtype, const void* out_conv, const float* w10, const float* b10, const float* ms_w, const float* ms_b,
+                          const uint8_t* mask, float* spec_out, float* ybar_out, float* mean_std_out, float* ws, int32_t B, int32_t S,
+                          int32_t F, void* stream) {
+    CwtHeadTrainArgs a{out_conv, w10, b10, ms_w, ms_b, mask, spec_out, ybar_out, mean_std_out, ws, B, S, F};
+    return launch_cwt_head_train(a, dtype, (hipStream_t)stream);
+}
+size_t fs2_op_cwt_head_bwd_ws_bytes(int32_t B, int32_t S, int32_t F) { return cwt_head_bwd_ws_bytes(B, S, F); }
+int fs2_op_cwt_head_bwd(int32_t dtype, const void* out_conv, const float* dspec, const float* dms, const float* ybar, const float* w10,
+                        const float* ms_w, void* dy, float* g_w10, float* g_b10, float* g_ms_w, float* g_ms_b, float* ws, int32_t B,
+                        int32_t S, int32_t F, void* stream) {
+    CwtHeadBwdArgs a{out_conv, dspec, dms, ybar, w10, ms_w, dy, g_w10, g_b10, g_ms_w, g_ms_b, ws, B, S, F};
+    return launch_cwt_head_bwd(a, dtype, (hipStream_t)stream);
+}
 int fs2_op_dwconv_dgrad(int32_t dtype, const void* dy, const float* w, void* dx, int32_t B, int32_t S, int32_t C, int32_t k,
                         void* stream) {
     DwConvArgs a{dy, w, nullptr, dx, B, S, C, k, (k - 1) / 2};

@@ -602,6 +602,42 @@ struct RowDotArgs {    // pred[m] = mask[m] ? 0 : y[m] . w + b[0]
 };
 int launch_row_dot(const RowDotArgs& a, int dtype, hipStream_t stream);
 
+// CWT head of a VariancePredictor in training (model.py:413-415, 505-520): spec = Linear(F, 10)(out_conv) (0 at pad rows),
+// ybar = time mean of out_conv over ALL S rows, mean_std = mean_std_linear(ybar); and its backward.
+struct CwtHeadTrainArgs {
+    const void* out_conv;   // (B*S, F) launch dtype
+    const float* w10;       // (10, F)
+    const float* b10;       // (10)
+    const float* ms_w;      // (2, F)
+    const float* ms_b;      // (2)
+    const uint8_t* mask;    // (B*S) 1 = pad
+    float* spec;            // (B*S, 10)
+    float* ybar;            // (B, F)
+    float* mean_std;        // (B, 2)
+    float* ws;              // cwt_head_train_ws_bytes
+    int B, S, F;
+};
+size_t cwt_head_train_ws_bytes(int B, int S, int F);
+int launch_cwt_head_train(const CwtHeadTrainArgs& a, int dtype, hipStream_t stream);
+
+struct CwtHeadBwdArgs {
+    const void* out_conv;   // (B*S, F) launch dtype
+    const float* dspec;     // (B*S, 10), 0 at pad rows
+    const float* dms;       // (B, 2)
+    const float* ybar;      // (B, F)
+    const float* w10;       // (10, F)
+    const float* ms_w;      // (2, F)
+    void* dy;               // (B*S, F) launch dtype
+    float* g_w10;           // (10, F)  +=
+    float* g_b10;           // (10)     +=
+    float* g_ms_w;          // (2, F)   +=
+    float* g_ms_b;          // (2)      +=
+    float* ws;              // cwt_head_bwd_ws_bytes
+    int B, S, F;
+};
+size_t cwt_head_bwd_ws_bytes(int B, int S, int F);
+int launch_cwt_head_bwd(const CwtHeadBwdArgs& a, int dtype, hipStream_t stream);
+
 struct TransposeWeightArgs {   // dst (Cin, taps*N) [ci][j'*N + n] = src (N, taps*Cin) [n][(taps-1-j')*Cin + ci]
     const void* src;
     void* dst;

@@ -14,13 +14,14 @@ no CPU path - without libfs2_hip.so the constructor raises.
 
 Covered: dense and depth-wise convolution variants of every block (C1-C5 of BASELINE.json, the reference's class defaults
 and the test-size configs; the depth-wise layer's conv2 pair is trained through its folded (H, F) map), frame-level
-'none' variances, 'l1' / 'mse' losses; precision "fp32" (exact fp32 MFMA, the parity mode) or "bf16" (bf16 activations,
+'none' and phone-level / CWT variances, 'l1' / 'mse' losses; precision "fp32" (exact fp32 MFMA, the parity mode) or "bf16" (bf16 activations,
 activation gradients and GEMM operands on the bf16 MFMA with fp32 accumulation; fp32 master weights, weight gradients,
 Adam moments, LayerNorm / softmax statistics and losses - what the reference's `--precision 16` recipe does with fp16).
 Dropout: every nn.Dropout site of the reference in training mode (encoder / decoder incl. the attention weights and both positional encodings, variance / duration predictors)
 with a counter-based mask that is regenerated, not stored; 0 by default, which is what the parity fixtures pin (the
-reference's masks come from torch's random stream and cannot be reproduced).  Priors (PriorEmbedding) are trained.  Rejected loudly:
-phone-level / CWT variances, stochastic durations.
+reference's masks come from torch's random stream and cannot be reproduced).  Priors (PriorEmbedding) are trained.  Variances at either level
+("frame" / "phone") with either transform ("none" / "cwt": the 10-scale spectrogram head + the utterance-level mean / std head,
+teacher-forced with the raw signal).  Rejected loudly: soft-DTW on a CWT spectrogram, stochastic durations.
 """
 from __future__ import annotations
 
@@ -380,9 +381,18 @@ class Trainer:
                  duration_loss="mse", loss_alphas=None, precision="fp32", encoder_dropout=0.0, decoder_dropout=0.0,
                  variance_dropout=0.0, duration_dropout=0.0, seed=0, attention="auto", device="cuda:0",
                  soft_dtw_gamma=0.01, soft_dtw_chunk_size=256):
-        if any(l != "frame" for l in cfg.variance_levels[:len(cfg.variances)]) or any(cfg.is_cwt(i) for i in range(len(cfg.variances))):
-            # (the reference cannot train the CWT head either: loss.py:141,148 read self.mse_loss, which its __init__ never sets)
-            raise NotImplementedError("training step: frame-level 'none' variances only")
+        # any mix of variance levels ("frame" / "phone") and transforms ("none" / "cwt"), as VarianceAdaptor.forward takes them
+        # (model.py:276-333).  The reference's own FastSpeech2Loss reads self.mse_loss for a CWT variance's mean / std terms
+        # (loss.py:141,148) and never sets it; plain nn.MSELoss() over the B utterance values is what the name stands for, and what
+        # the fixtures were produced with (tools/gen_golden_train_variances.py).
+        for i, v in enumerate(cfg.variances):
+            # Fs2Config has already checked the level and transform names; the CWT head operators take these widths only
+            if cfg.is_cwt(i) and (cfg.variance_filter_size % 64 or not 64 <= cfg.variance_filter_size <= 1024):
+                raise ValueError(f"variance_filter_size = {cfg.variance_filter_size}: the CWT head of {v!r} trains with a multiple "
+                                 f"of 64 up to 1024")
+            if cfg.is_cwt(i) and variance_losses is not None and variance_losses[i] == "soft_dtw":
+                # soft-DTW over a (B, S, 10) spectrogram is defined (loss.py:59-78) but has no fixture and no user: not built
+                raise NotImplementedError(f"training step: 'soft_dtw' on the CWT variance {v!r} ('l1' / 'mse' on its spectrogram)")
         if precision not in _PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
         self.cfg, self.precision = cfg, precision
@@ -772,7 +782,9 @@ class Trainer:
         return dx
 
     # ---- VariancePredictor (model.py:482-561, dense) ----
-    def _predictor_fwd(self, x, prefix, nlayers, filt, k, B, S, mask, dw=False, pd=0.0):
+    def _predictor_fwd(self, x, prefix, nlayers, filt, k, B, S, mask, dw=False, pd=0.0, cwt=None):
+        """cwt: the VarianceEncoder's prefix when the predictor ends in the CWT head (Linear(filter, 10) + mean_std_linear on the time
+        mean of the last layer's output, model.py:413-415,508): pred is then (spec (M, 10), mean_std (B, 2)), both fp32."""
         o, P, W, H = self.ops, self.P, self.W, self.cfg.hidden
         M = B * S
         tape, y, cin = [], x, H
@@ -794,7 +806,7 @@ class Trainer:
                 continue
             if not dw:
                 c = o.gemm(y, W[f"{p}.0.module.weight"], P[f"{p}.0.module.bias"], M, filt, cin, taps=k, S=S, relu=True)
-            fused_head = last and pd <= 0
+            fused_head = last and pd <= 0 and cwt is None
             kd = None
             if pd > 0:  # VarianceConvolutionLayer ends in nn.Dropout (model.py:539,557): inside the LayerNorm launch
                 kd = o.site()
@@ -810,18 +822,36 @@ class Trainer:
                 else:
                     yn, pred = o.layernorm(c, None, P[f"{p}.2.weight"], P[f"{p}.2.bias"], M, filt)
                 kd = o.site()
-            if last and pd > 0:
+            if last and pd > 0 and cwt is None:
                 pred = o.empty(M)
                 o.ck(o.lib.fs2_op_row_dot(o.dt, _p(yn), _p(P[f"{prefix}.linear.weight"]), _p(P[f"{prefix}.linear.bias"]), _p(mask), _p(pred),
                                           M, filt, o.st()), "row_dot")
             tape.append({"xin": y, "c": c, "cin": cin, "u": u, "kd": kd})
             y, cin = yn, filt
-        return pred, {"layers": tape, "y": y, "pd": pd}
+        ybar = None
+        if cwt is not None:  # out_conv = y (behind the last layer's Dropout): ten dots per row + the utterance mean, one pass
+            spec, ybar, ms = o.empty(M, 10), o.empty(B, filt), o.empty(B, 2)
+            ws = o.ws("cwt_head", int(o.lib.fs2_op_cwt_head_train_ws_bytes(B, S, filt)))
+            o.ck(o.lib.fs2_op_cwt_head_train(o.dt, _p(y), _p(P[f"{prefix}.linear.weight"]), _p(P[f"{prefix}.linear.bias"]),
+                                             _p(P[f"{cwt}.mean_std_linear.weight"]), _p(P[f"{cwt}.mean_std_linear.bias"]), _p(mask),
+                                             _p(spec), _p(ybar), _p(ms), _p(ws), B, S, filt, o.st()), "cwt_head_train")
+            pred = (spec, ms)
+        return pred, {"layers": tape, "y": y, "pd": pd, "ybar": ybar}
 
-    def _predictor_bwd(self, dpred, t, prefix, nlayers, filt, k, B, S, dx_out, dw=False):
-        """dpred (M) -> gradients of the predictor's parameters, and dx_out (M, H) += d/dx."""
+    def _predictor_bwd(self, dpred, t, prefix, nlayers, filt, k, B, S, dx_out, dw=False, cwt=None):
+        """dpred (M) - with the CWT head (cwt = the VarianceEncoder's prefix) the pair (dspec (M, 10), dmean_std (B, 2)) - ->
+        gradients of the predictor's parameters, and dx_out (M, H) += d/dx."""
         o, P, W, G = self.ops, self.P, self.W, self.G
         M = B * S
+        if cwt is not None:
+            dspec, dms = dpred
+            dy = o.act(M, filt)
+            ws = o.ws("cwt_head_bwd", int(o.lib.fs2_op_cwt_head_bwd_ws_bytes(B, S, filt)))
+            o.ck(o.lib.fs2_op_cwt_head_bwd(o.dt, _p(t["y"]), _p(dspec), _p(dms), _p(t["ybar"]), _p(P[f"{prefix}.linear.weight"]),
+                                           _p(P[f"{cwt}.mean_std_linear.weight"]), _p(dy), _p(G[f"{prefix}.linear.weight"]),
+                                           _p(G[f"{prefix}.linear.bias"]), _p(G[f"{cwt}.mean_std_linear.weight"]),
+                                           _p(G[f"{cwt}.mean_std_linear.bias"]), _p(ws), B, S, filt, o.st()), "cwt_head_bwd")
+            return self._predictor_layers_bwd(dy, t, prefix, nlayers, filt, k, B, S, dx_out, dw)
         # pred = y . w + b  (masked rows carry dpred = 0 already): dw = sum_m dpred[m] y[m] as a row-weighted column sum (fp32
         # weights; as a 1 x filt x M product on the 128 x 128 GEMM tile it took 51 us per head)
         dpred32 = dpred
@@ -835,6 +865,12 @@ class Trainer:
         o.col_sum(dpred, G[f"{prefix}.linear.bias"], M, 1)
         dy = o.act(M, filt)
         o.bgemm(dpred, W[f"{prefix}.linear.weight"], dy, M=M, N=filt, K=1, sAm=1, sAk=1, sBk=filt, sBn=1, ldc=filt)
+        self._predictor_layers_bwd(dy, t, prefix, nlayers, filt, k, B, S, dx_out, dw)
+
+    def _predictor_layers_bwd(self, dy, t, prefix, nlayers, filt, k, B, S, dx_out, dw):
+        """dy (M, filt) = the gradient of the last layer's output -> the conv layers' gradients, dx_out (M, H) += d/dx"""
+        o, P, W, G = self.ops, self.P, self.W, self.G
+        M = B * S
         for j in reversed(range(nlayers)):
             p = f"{prefix}.layers.{j}.layers"
             lt = t["layers"][j]
@@ -908,12 +944,28 @@ class Trainer:
         T = int(mel_t.shape[1])
         if tuple(dur_t.shape) != (B, L):
             raise ValueError(f"duration must be {(B, L)}, got {tuple(dur_t.shape)}")
-        var_t = {}
-        for v in cfg.variances:
-            t = batch[f"variances_{v}"].to(dev, torch.float32).contiguous()
-            if tuple(t.shape) != (B, T):
-                raise ValueError(f"variances_{v} must be {(B, T)}, got {tuple(t.shape)}")
-            var_t[v] = t
+        nv = len(cfg.variances)
+        phone_vis = [vi for vi in range(nv) if cfg.is_phone_level(vi)]
+        frame_vis = [vi for vi in range(nv) if not cfg.is_phone_level(vi)]
+
+        def target(key, shape):
+            if key not in batch:
+                raise ValueError(f"the batch has no {key} (must be {shape})")
+            t = batch[key]
+            t = (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))).to(dev, torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{key} must be {shape}, got {tuple(t.shape)}")
+            return t
+        var_t, cwt_t = {}, {}
+        for vi, v in enumerate(cfg.variances):
+            S_ = L if cfg.is_phone_level(vi) else T  # a phone-level variance is (B, L), model.py:276-294
+            if cfg.is_cwt(vi):  # teacher-forced with the raw signal, bucketised as log(signal) (model.py:418-419): torch.log on the
+                # device tensor, as the inference path takes it (model.py of this package), so both paths pick the same buckets
+                var_t[v] = torch.log(target(f"variances_{v}_signal", (B, S_)))
+                cwt_t[v] = (target(f"variances_{v}_spectrogram", (B, S_, 10)), target(f"variances_{v}_mean", (B,)),
+                            target(f"variances_{v}_std", (B,)))
+            else:
+                var_t[v] = target(f"variances_{v}", (B, S_))
         pe = self.buffers["positional_encoding.pe"]
         with torch.cuda.device(dev):
             # ---------------- forward ----------------
@@ -957,6 +1009,26 @@ class Trainer:
             dur_pred, dur_tape = self._predictor_fwd(x, "variance_adaptor.duration_predictor", cfg.duration_nlayers,
                                                      cfg.duration_filter_size, cfg.duration_kernel_size, B, L, src_mask,
                                                      dw=cfg.duration_depthwise_conv, pd=self.p_dur)
+            var_pred, var_tape, var_idx = {}, {}, {}
+
+            def variance_fwd(vi, xa, S_, mask, pe_, spk_):
+                """VarianceEncoder.forward with its target (model.py:409-422): the prediction, and xa + Emb[bucketize(target)]"""
+                v = cfg.variances[vi]
+                pfx = f"variance_adaptor.encoders.{v}"
+                var_pred[v], var_tape[v] = self._predictor_fwd(xa, f"{pfx}.predictor", cfg.variance_nlayers[vi], cfg.variance_filter_size,
+                                                               cfg.variance_kernel_size[vi], B, S_, mask, dw=cfg.variance_depthwise_conv,
+                                                               pd=self.p_var[vi], cwt=pfx if cfg.is_cwt(vi) else None)
+                idx = o.empty(B * S_, dtype=torch.int32)
+                xn = o.act(B * S_, H)
+                st_ = {"std": 1.0, "mean": 0.0} if cfg.is_cwt(vi) else cfg.stats[v]  # log(signal) is bucketised as it is
+                o.ck(o.lib.fs2_op_bucket_embed_target(o.dt, _p(xa), _p(var_t[v]), _p(self.buffers[f"{pfx}.bins"]), _p(P[f"{pfx}.embedding.weight"]),
+                                                      cfg.variance_nbins, C.c_float(st_["std"]), C.c_float(st_["mean"]), pe_, spk_, _p(xn), _p(idx),
+                                                      B, S_, H, o.st()), "bucket_embed_target")
+                var_idx[v] = idx
+                return xn
+            # the duration predictor saw x as it is here; the phone-level variances follow in order, each on x + the earlier embeddings
+            for vi in phone_vis:
+                x = variance_fwd(vi, x, L, src_mask, None, None)
             forced = dur_t.to(torch.int32)
             dur, cum, totals, guard = (o.empty(B, L, dtype=torch.int32), o.empty(B, L, dtype=torch.int32),
                                        o.empty(B, dtype=torch.int32), o.empty(B, dtype=torch.int32))
@@ -964,25 +1036,11 @@ class Trainer:
             xr = o.act(B * T, H)
             tgt_mask = o.empty(B, T, dtype=torch.uint8)
             o.ck(o.lib.fs2_op_regulate(o.dt, _p(x), _p(cum), _p(totals), _p(xr), _p(tgt_mask), B, L, T, H, o.st()), "regulate")
-            var_pred, var_tape, var_idx = {}, {}, {}
             xa = xr
-            nv = len(cfg.variances)
-            for vi, v in enumerate(cfg.variances):
-                pfx = f"variance_adaptor.encoders.{v}"
-                var_pred[v], var_tape[v] = self._predictor_fwd(xa, f"{pfx}.predictor", cfg.variance_nlayers[vi], cfg.variance_filter_size,
-                                                               cfg.variance_kernel_size[vi], B, T, tgt_mask, dw=cfg.variance_depthwise_conv,
-                                                               pd=self.p_var[vi])
-                idx = o.empty(B * T, dtype=torch.int32)
-                xn = o.act(B * T, H)
-                last = vi == nv - 1
-                st_ = cfg.stats[v]
-                o.ck(o.lib.fs2_op_bucket_embed_target(o.dt, _p(xa), _p(var_t[v]), _p(self.buffers[f"{pfx}.bins"]), _p(P[f"{pfx}.embedding.weight"]),
-                                                      cfg.variance_nbins, C.c_float(st_["std"]), C.c_float(st_["mean"]),
-                                                      _p(pe) if last else None, _p(spk) if (last and not pe_drop) else None, _p(xn), _p(idx),
-                                                      B, T, H, o.st()), "bucket_embed_target")
-                var_idx[v] = idx
-                xa = xn
-            if nv == 0:
+            for vi in frame_vis:  # the last frame-level embedding launch also adds pe (and spk)
+                last = vi == frame_vis[-1]
+                xa = variance_fwd(vi, xa, T, tgt_mask, _p(pe) if last else None, _p(spk) if (last and not pe_drop) else None)
+            if not frame_vis:
                 xn = o.act(B * T, H)
                 o.ck(o.lib.fs2_op_bucket_embed(o.dt, _p(xa), None, None, None, 0, C.c_float(1), C.c_float(0), _p(pe),
                                                None if pe_drop else _p(spk), _p(xn), None, B, T, H, o.st()), "pe_spk")
@@ -1001,14 +1059,33 @@ class Trainer:
             # ---------------- losses + their gradients (loss.py:83-213) ----------------
             losses = {}
             dvar = {}
-            for v, kind in zip(cfg.variances, self.variance_losses):
-                stat, dvar[v] = self._loss(v, var_pred[v], var_t[v], 0, tgt_mask, B * T, 1, kind)
-                losses[v] = stat[0]
+            alpha_of = {}
+            for vi, (v, kind) in enumerate(zip(cfg.variances, self.variance_losses)):
+                S_, mask = (L, src_mask) if cfg.is_phone_level(vi) else (T, tgt_mask)  # loss.py:123-130
+                if not cfg.is_cwt(vi):
+                    stat, dvar[v] = self._loss(v, var_pred[v], var_t[v], 0, mask, B * S_, 1, kind)
+                    losses[v] = stat[0]
+                    alpha_of[v] = self.loss_alphas[v]
+                    continue
+                # loss.py:133-154: the masked loss on the spectrogram, plain MSE over the B utterance values of mean and std
+                (spec, ms), (spec_t, mean_t, std_t) = var_pred[v], cwt_t[v]
+                stat, dspec = self._loss(v, spec, spec_t, 0, mask, B * S_, 10, kind)
+                losses[f"{v}_cwt"] = stat[0]
+                every = torch.zeros(B, dtype=torch.uint8, device=dev)
+                dms = o.empty(B, 2)
+                for col, (nm, tt) in enumerate((("mean", mean_t), ("std", std_t))):
+                    stat, d = self._loss(v, ms[:, col].contiguous(), tt, 0, every, B, 1, "mse")
+                    losses[f"{v}_{nm}"] = stat[0]
+                    dms[:, col] = d
+                dvar[v] = (dspec, dms)
+                for sfx in ("cwt", "mean", "std"):
+                    alpha_of[f"{v}_{sfx}"] = self.loss_alphas[v]  # loss.py:51-55
             stat, dmel = self._loss("mel", mel, mel_t, 0, tgt_mask, B * T, cfg.n_mels, self.mel_loss)
             losses["mel"] = stat[0]
             stat, ddur = self._loss("duration", dur_pred, dur_t, 1, src_mask, B * L, 1, self.duration_loss)
             losses["duration"] = stat[0]
-            losses["total"] = sum(v * self.loss_alphas[k] for k, v in losses.items())
+            alpha_of.update(mel=self.loss_alphas["mel"], duration=self.loss_alphas["duration"])
+            losses["total"] = sum(v * alpha_of[k] for k, v in losses.items())
             # ---------------- backward ----------------
             dmel = o.to_act(dmel)
             o.wgrad(dmel, y, G["linear.weight"], G["linear.bias"], B * T, cfg.n_mels, H)
@@ -1019,14 +1096,23 @@ class Trainer:
             dspk = torch.zeros(B, H, device=dev)
             o.col_sum(dy, dspk, B * T, H, seg=T)  # decoder input = dropout(adaptor out + pe) + spk (fastspeech2.py:705-718)
             dx = o.dropout(dy, self.p_enc, k_pe_dec)
-            for vi in reversed(range(nv)):
+            def variance_bwd(vi, d, S_):
+                """d = the gradient of x + embedding: scattered into the embedding table (a leaf: side stream), then d += the
+                predictor's d/dx - x reached both the sum and the predictor"""
                 v = cfg.variances[vi]
                 pfx = f"variance_adaptor.encoders.{v}"
-                o.on_side((dx,), lambda: o.scatter_rows(dx, var_idx[v], None, G[f"{pfx}.embedding.weight"], B * T, H, cfg.variance_nbins, -1))
+                o.on_side((d,), lambda: o.scatter_rows(d, var_idx[v], None, G[f"{pfx}.embedding.weight"], B * S_, H, cfg.variance_nbins, -1))
                 self._predictor_bwd(dvar[v], var_tape[v], f"{pfx}.predictor", cfg.variance_nlayers[vi], cfg.variance_filter_size,
-                                    cfg.variance_kernel_size[vi], B, T, dx, dw=cfg.variance_depthwise_conv)
+                                    cfg.variance_kernel_size[vi], B, S_, d, dw=cfg.variance_depthwise_conv,
+                                    cwt=pfx if cfg.is_cwt(vi) else None)
+            for vi in reversed(frame_vis):
+                variance_bwd(vi, dx, T)
             dxe = o.act(B * L, H)
             o.ck(o.lib.fs2_op_regulate_bwd(o.dt, _p(dx), _p(cum), _p(dxe), B, L, T, H, o.st()), "regulate_bwd")
+            # the phone-level tape, all residual adds onto dxe in ONE order (bit-equal reruns): the regulator's segment sums, then the
+            # phone-level variances last to first, then the duration predictor (which saw the encoder output before any of them)
+            for vi in reversed(phone_vis):
+                variance_bwd(vi, dxe, L)
             self._predictor_bwd(ddur, dur_tape, "variance_adaptor.duration_predictor", cfg.duration_nlayers, cfg.duration_filter_size,
                                 cfg.duration_kernel_size, B, L, dxe, dw=cfg.duration_depthwise_conv)
             if cfg.priors:
@@ -1049,7 +1135,11 @@ class Trainer:
         o.join_side()  # the weight gradients of this micro-step are in the flat buffer before anything reads it
         self._accum += 1
         self.last = {"mel": mel.view(B, T, cfg.n_mels), "duration_prediction": dur_pred.view(B, L), "tgt_mask": tgt_mask.bool(),
-                     "src_mask": src_mask.bool(), **{f"variances_{v}": var_pred[v].view(B, T) for v in cfg.variances}}
+                     "src_mask": src_mask.bool()}
+        for vi, v in enumerate(cfg.variances):  # a CWT variance hands back what the reference's teacher-forced call does (model.py:443-451)
+            S_ = L if cfg.is_phone_level(vi) else T
+            self.last[f"variances_{v}"] = ({"spectrogram": var_pred[v][0].view(B, S_, 10), "mean": var_pred[v][1][:, 0],
+                                            "std": var_pred[v][1][:, 1]} if cfg.is_cwt(vi) else var_pred[v].view(B, S_))
         return losses
 
     def optimizer_step(self, group=None):
