@@ -243,7 +243,7 @@ int fs2_profile_read(fs2_engine* e, int32_t kernel_class, double* total_ms, int6
  * (defaults at fs2_create; fs2_set_tuning changes one; fs2_clone copies them) and never looks at a thread's.  An undefined value is
  * FS2_ERR_ARG.  Every non-default form is pinned bit-identical (or within a stated tolerance) to the default by a test.
  *   0       auto (by problem size)
- *   1       128x128 register-staged GEMM      2       128x256 LDS-DMA ring GEMM
+ *   1       128x128 register-staged GEMM      (2, the 128x256 LDS-DMA ring GEMM, is retired: FS2_ERR_ARG; tools/probes/gemm_forms)
  *   3/4/5   slab kernel, 128/192/256-row tiles   6/7   slab kernel, 32/64-row tiles
  *   200/201/202 slab kernel tile order: plain / XCD-contiguous (default) / XCD-contiguous with column-tile PAIRS per XCD where the launch
  *           has 4, 8 or 16 column tiles and a weight panel larger than an XCD's L2 (the decoder FFN conv1: 109 MB fetched instead of 139,
@@ -325,6 +325,15 @@ int fs2_op_head_finish(const float* parts, const float* dots, int32_t nparts, in
  * workgroups of ONE launch into fp32 planes part (ksplit, M, N), a second launch adds the planes in order:
  * c (out_dtype) = [c +] sum_s part[s].  No bias / ReLU.  FS2_ERR_SHAPE when the shape does not run on the slab kernel. */
 int fs2_op_gemm_splitk_choice(int32_t dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S);
+/* Which kernel a GEMM / conv request would run on under the calling thread's switches: host arithmetic, no GPU needed (the routing
+ * of every fs2_op_gemm* entry and of the engine is this function's).  present: one bit per optional member of the request, from bit 0:
+ * bias, res, ln_g, dot_w, z_out, ln_tmp, stats_out, epi_res, gate, drop_p > 0, rs_stats + rs_wg, head_out + head_gw, zero_rows, C_lo,
+ * split, w_presplit, relu.  bias_aligned: the bias pointer is 16-byte aligned.  Returns -status where the request is refused, else
+ * family | mi << 4 | flags << 8 | two_launch << 16 with family 0 nothing to do / 1 128x128 / 2 slab / 3 persistent / 4 weight-resident,
+ * mi = tile rows / 32 (slab, persistent), flags bit 0-5 = the slab kernel's LN, SPLIT, DEFER, XPRE, the 128x128 kernel's zero_rows form,
+ * weights packed on the fly; two_launch = a LayerNorm request served as GEMM into ln_tmp + the LayerNorm kernel. */
+int32_t fs2_op_gemm_route(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
+                          uint32_t present, int32_t bias_aligned);
 int fs2_op_gemm_splitk(int32_t dtype, int32_t out_dtype, const void* x, const void* w, void* c, float* part, int32_t M, int32_t N,
                        int32_t Cin, int32_t taps, int32_t S, int32_t ksplit, int32_t accumulate, void* hip_stream);
 /* ... with the ReLU (and dropout) backward of a data-gradient product folded into the store: c = gate > 0 ? scale * (x w^T + bias)

@@ -56,7 +56,7 @@ int apply_knob(Tuning& t, int variant) {
     else if (variant == 230 || variant == 231) t.head_sums = variant - 230;           // predictor head from a normalise pass / from the last GEMM's epilogue sums (default)
     else if (variant == 220 || variant == 221) t.gemm_persist = variant - 220;         // multi-round bf16 pointwise launches one tile per workgroup / on the persistent kernel (default)
     else if (variant >= 200 && variant <= 202) t.slab_xcd_remap = variant - 200;       // slab kernel tile order plain / XCD-contiguous (default) / + column pairs per XCD for wide weight panels
-    else if (variant >= 0 && variant <= 7) t.gemm_variant = variant;                    // kernel family / forced tile height of the forward GEMM launcher (gemm_mfma.hip: launch_gemm)
+    else if (variant >= 0 && variant <= 7 && variant != 2) t.gemm_variant = variant;    // kernel family / forced tile height of the forward GEMM launcher (gemm_mfma.hip: route_gemm; 2 was the 128x256 DMA ring: tools/probes/gemm_forms)
     else ok = 0;
     if (!ok) return FS2_ERR_ARG;
     ++t.gen;
@@ -67,6 +67,15 @@ Tuning& op_tuning() {
     return t;
 }
 }  // namespace fs2
+
+// one GEMM / "same"-padded conv request in the operators' layout: x (M, Cin) and c (M, N) dense, w (N, taps * Cin)
+static GemmArgs gemm_args(const void* x, const void* w, const float* bias, void* c, int M, int N, int Cin, int taps, int S, int relu) {
+    GemmArgs a;
+    a.X = x; a.W = w; a.bias = bias; a.C = c;
+    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
+    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = relu;
+    return a;
+}
 
 extern "C" {
 
@@ -151,20 +160,14 @@ int fs2_op_set_gemm_variant(int32_t variant) { return fs2::apply_knob(fs2::op_tu
 
 int fs2_op_gemm(int32_t dtype, int32_t out_dtype, const void* x, const void* w, const float* bias, void* c,
                 int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t relu, void* stream) {
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = c;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = relu;
+    GemmArgs a = gemm_args(x, w, bias, c, M, N, Cin, taps, S, relu);
     return launch_gemm(a, dtype, out_dtype, (hipStream_t)stream);
 }
 
 int fs2_op_gemm_relu_dropout(int32_t dtype, const void* x, const void* w, const float* bias, void* c, int32_t M, int32_t N, int32_t Cin,
                              int32_t taps, int32_t S, float p, uint64_t seed, uint64_t key, void* stream) {
     if (!(p > 0.f && p < 1.f)) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = c;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = 1;
+    GemmArgs a = gemm_args(x, w, bias, c, M, N, Cin, taps, S, 1);
     a.drop_p = p; a.drop_seed = seed; a.drop_key = key;
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
 }
@@ -172,10 +175,7 @@ int fs2_op_gemm_relu_dropout(int32_t dtype, const void* x, const void* w, const 
 int fs2_op_gemm_add(int32_t dtype, const void* x, const void* w, const float* bias, const void* addend, void* c, int32_t M, int32_t N,
                     int32_t Cin, int32_t taps, int32_t S, void* stream) {
     if (!addend) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = c;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = 0;
+    GemmArgs a = gemm_args(x, w, bias, c, M, N, Cin, taps, S, 0);
     a.epi_res = addend;  // the slab kernel's residual epilogue without statistics: the accumulators start AT the addend
     if (N < 192 || M % S || !(taps & 1)) return FS2_ERR_SHAPE;  // slab kernel only
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
@@ -187,10 +187,7 @@ int fs2_op_gemm_add(int32_t dtype, const void* x, const void* w, const float* bi
 int fs2_op_gemm_stats(int32_t dtype, const void* x, const void* w, const float* bias, const void* res, void* c, float* stats, int32_t M,
                       int32_t N, int32_t Cin, int32_t relu, void* stream) {
     if (!x || !w || !c || !stats) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = c;
-    a.M = M; a.N = N; a.K = Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = 1; a.pad = 0; a.S = M; a.relu = relu;
+    GemmArgs a = gemm_args(x, w, bias, c, M, N, Cin, 1, M, relu);
     a.epi_res = res; a.stats_out = stats; a.ln_eps = 1e-5f;
     if (N < 192) return FS2_ERR_SHAPE;  // slab / persistent kernels only
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
@@ -205,10 +202,7 @@ int fs2_op_gemm_rowscale_dt(int32_t dtype, int32_t out_dtype, const void* x, con
                             const float* wg, void* c, int32_t M, int32_t N, int32_t Cin, void* stream) {
     if (!x || !w || !bias || !rowstats || !wg || !c) return FS2_ERR_ARG;
     if (!is_16bit(dtype)) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = c;
-    a.M = M; a.N = N; a.K = Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = 1; a.pad = 0; a.S = M; a.relu = 0;
+    GemmArgs a = gemm_args(x, w, bias, c, M, N, Cin, 1, M, 0);
     a.rs_stats = rowstats; a.rs_wg = wg;
     return launch_gemm(a, dtype, out_dtype, (hipStream_t)stream);
 }
@@ -218,10 +212,7 @@ int fs2_op_rowstats_finish(const float* parts, int32_t nparts, int32_t ncols, fl
 int fs2_op_gemm_head(const void* x, const void* w, const float* bias, const float* head_gw, float* stats_out, float* head_out, int32_t M,
                      int32_t N, int32_t Cin, int32_t relu, void* stream) {
     if (!x || !w || !bias || !head_gw || !stats_out || !head_out) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = nullptr;
-    a.M = M; a.N = N; a.K = Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = 1; a.pad = 0; a.S = M; a.relu = relu;
+    GemmArgs a = gemm_args(x, w, bias, nullptr, M, N, Cin, 1, M, relu);
     a.stats_out = stats_out; a.head_gw = head_gw; a.head_out = head_out; a.ln_eps = 1e-5f;
     return launch_gemm(a, FS2_BF16, FS2_BF16, (hipStream_t)stream);
 }
@@ -234,13 +225,39 @@ int fs2_op_gemm_splitk_choice(int32_t dtype, int32_t M, int32_t N, int32_t Cin, 
     return gemm_splitk_choice(M, N, Cin, taps, S, dtype);
 }
 
+// Which kernel the forward GEMM launcher would take for a request, under the calling thread's tuning: host arithmetic, no GPU.
+int32_t fs2_op_gemm_route(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
+                          uint32_t present, int32_t bias_aligned) {
+    static float dummy[8];  // only the members' presence and the bias pointer's alignment are looked at
+    void* p = (void*)(((uintptr_t)dummy + 15) & ~(uintptr_t)15);
+    GemmArgs a = gemm_args(p, p, nullptr, p, M, N, Cin, taps, S, (present & GF_RELU) != 0);
+    a.ksplit = ksplit;
+    if (present & GF_BIAS) a.bias = (const float*)p + (bias_aligned ? 0 : 1);
+    if (present & GF_RES) a.res = p;
+    if (present & GF_LN) { a.ln_g = (const float*)p; a.ln_b = (const float*)p; }
+    if (present & GF_DOT) a.dot_w = (const float*)p;
+    if (present & GF_ZOUT) a.z_out = p;
+    if (present & GF_LNTMP) a.ln_tmp = p;
+    if (present & GF_STATS) a.stats_out = (float*)p;
+    if (present & GF_EPIRES) a.epi_res = p;
+    if (present & GF_GATE) a.gate = p;
+    if (present & GF_DROP) a.drop_p = 0.1f;
+    if (present & GF_RS) { a.rs_stats = (const float*)p; a.rs_wg = (const float*)p; }
+    if (present & GF_HEAD) { a.head_out = (float*)p; a.head_gw = (const float*)p; }
+    if (present & GF_ZR) a.zero_rows = (const uint8_t*)p;
+    if (present & GF_CLO) a.C_lo = p;
+    if (present & GF_SPLIT) a.split = 1;
+    if (present & GF_WPRE) a.w_presplit = 1;
+    const GemmRoute r = route_gemm(a, dtype, out_dtype);
+    if (r.status != FS2_OK) return -r.status;
+    return r.family | r.mi << 4 | (r.ln ? 1 : 0) << 8 | (r.split ? 1 : 0) << 9 | (r.defer ? 1 : 0) << 10 | (r.xpre ? 1 : 0) << 11 |
+           (r.zr ? 1 : 0) << 12 | (r.presplit ? 1 : 0) << 13 | (r.two_launch ? 1 : 0) << 16;
+}
+
 int fs2_op_gemm_splitk(int32_t dtype, int32_t out_dtype, const void* x, const void* w, void* c, float* part, int32_t M, int32_t N,
                        int32_t Cin, int32_t taps, int32_t S, int32_t ksplit, int32_t accumulate, void* stream) {
     if (ksplit < 2 || !part) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = nullptr; a.C = part;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = 0;
+    GemmArgs a = gemm_args(x, w, nullptr, part, M, N, Cin, taps, S, 0);
     a.ksplit = ksplit;
     const int r = launch_gemm(a, dtype, FS2_F32, (hipStream_t)stream);
     if (r != FS2_OK) return r;
@@ -250,10 +267,7 @@ int fs2_op_gemm_splitk(int32_t dtype, int32_t out_dtype, const void* x, const vo
 int fs2_op_gemm_gated(int32_t dtype, const void* x, const void* w, const float* bias, const void* gate, float scale, void* c, int32_t M,
                       int32_t N, int32_t Cin, int32_t taps, int32_t S, void* stream) {
     if (!gate) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = c;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = 0;
+    GemmArgs a = gemm_args(x, w, bias, c, M, N, Cin, taps, S, 0);
     a.gate = gate; a.gate_scale = scale;
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
 }
@@ -262,10 +276,7 @@ int fs2_op_gemm_ln(int32_t dtype, const void* x, const void* w, const float* bia
                    const float* ln_g, const float* ln_b, const float* dot_w, float dot_b, const uint8_t* mask,
                    float* pred, void* y, void* tmp, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S,
                    int32_t relu, void* stream) {
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = y;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = relu;
+    GemmArgs a = gemm_args(x, w, bias, y, M, N, Cin, taps, S, relu);
     a.res = res; a.ln_g = ln_g; a.ln_b = ln_b; a.dot_w = dot_w; a.dot_b = dot_b; a.mask = mask; a.pred = pred;
     a.ln_tmp = tmp;
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
@@ -275,10 +286,7 @@ int fs2_op_gemm_ln_tape(int32_t dtype, const void* x, const void* w, const float
                         const float* ln_b, void* y, void* z_out, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S,
                         int32_t relu, void* stream) {
     if (!x || !w || !ln_g || !ln_b || !y || !z_out) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = y;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = relu;
+    GemmArgs a = gemm_args(x, w, bias, y, M, N, Cin, taps, S, relu);
     a.res = res; a.ln_g = ln_g; a.ln_b = ln_b; a.z_out = z_out;
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
 }
@@ -288,10 +296,7 @@ int fs2_op_gemm_ln_tape_dropout(int32_t dtype, const void* x, const void* w, con
                                 int32_t relu, float p, uint64_t seed, uint64_t key, void* stream) {
     if (!x || !w || !ln_g || !ln_b || !y || !z_out) return FS2_ERR_ARG;
     if (!(p >= 0.f && p < 1.f)) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = y;
-    a.M = M; a.N = N; a.K = taps * Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = taps; a.pad = (taps - 1) / 2; a.S = S; a.relu = relu;
+    GemmArgs a = gemm_args(x, w, bias, y, M, N, Cin, taps, S, relu);
     a.res = res; a.ln_g = ln_g; a.ln_b = ln_b; a.z_out = z_out;
     a.drop_p = p; a.drop_seed = seed; a.drop_key = key;
     return launch_gemm(a, dtype, dtype, (hipStream_t)stream);
@@ -366,10 +371,8 @@ int fs2_op_attention_x3(const float* qkv, const uint8_t* key_pad_mask, float* ou
 int fs2_op_gemm_split_out(const void* x, const void* w, const float* bias, void* c_hi, void* c_lo, int32_t M, int32_t N, int32_t Cin,
                           int32_t split, void* stream) {
     if (!x || !w || !c_hi || !c_lo) return FS2_ERR_ARG;
-    GemmArgs a;
-    a.X = x; a.W = w; a.bias = bias; a.C = c_hi; a.C_lo = c_lo;
-    a.M = M; a.N = N; a.K = Cin; a.ldx = Cin; a.ldc = N;
-    a.Cin = Cin; a.taps = 1; a.pad = 0; a.S = M; a.relu = 0; a.split = split != 0;
+    GemmArgs a = gemm_args(x, w, bias, c_hi, M, N, Cin, 1, M, 0);
+    a.C_lo = c_lo; a.split = split != 0;
     return launch_gemm(a, FS2_F32, FS2_F32, (hipStream_t)stream);
 }
 

@@ -1291,7 +1291,7 @@ int fs2_finalize(fs2_engine* e) {
         CHK(up_vec(e, p + ".embedding.weight", &e->vars[v].emb));
     }
     CHK(make_conv(e, "linear.weight", "linear.bias", &e->mel, e->bdt));
-    // (the row-scaled product with an fp32 store exists for narrow heads only - launch_gemm_plain: N < 192 -; a wider mel head keeps the
+    // (the row-scaled product with an fp32 store exists for narrow heads only - route_gemm's GF_RS_NARROW row: N < 192 -; a wider mel head keeps the
     //  normalise-only pass + the plain mel GEMM)
     if (H > 256 && c.dec_layers > 0 && c.dec_depthwise && is_16bit(e->bdt) && c.n_mels < 192) {
         // mel = Linear(LN2_last(v2)) evaluated on v2

@@ -21,7 +21,7 @@ inline size_t elem_bytes(int dt) { return is_16bit(dt) ? 2 : 4; }
 // calling thread's).  Defaults are what measured fastest; every non-default value is kept for A/B or for the tests that pin two
 // forms against each other.  (Until r05 these were ~20 process-wide ints read unsynchronised by every engine and pipeline thread.)
 struct Tuning {
-    int gemm_variant = 0;      // 0 auto; 1 128x128 register-staged; 2 128x256 DMA ring; 3/4/5 slab kernel 128/192/256-row tiles; 6/7 32/64-row
+    int gemm_variant = 0;      // 0 auto; 1 128x128 register-staged; 3/4/5 slab kernel 128/192/256-row tiles; 6/7 32/64-row
     int gemm_wres = 1;         // bf16 K = 256 plain GEMMs on the weight-resident kernel: 0 never, 1 where it pays, 2 wherever it applies
     int head_sums = 1;         // wide predictors: last LayerNorm + Linear head from the last GEMM's epilogue sums (GemmArgs::head_out) / a normalise pass
     int gemm_persist = 1;      // bf16 pointwise launches of more tiles than CUs on the persistent kernel (gemm_persist.hip)
@@ -101,7 +101,34 @@ struct GemmArgs {
     int ksplit = 0;                 // > 1: split-K on the slab kernel (plain epilogue, fp32 out, no bias / ReLU / gate): split s sums the channel
                                     // blocks [s, s + 1) * Cin / ksplit of every tap into plane s of C (ksplit, M, ldc); launch_split_k_reduce adds them
 };
-int launch_gemm(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream);
+// The optional members of a GemmArgs, one bit each: what route_gemm's feature rules are written in, and the `present` mask of
+// fs2_op_gemm_route (include/fs2.h lists the same order).
+enum GemmFeature : unsigned {
+    GF_BIAS = 1u << 0, GF_RES = 1u << 1, GF_LN = 1u << 2, GF_DOT = 1u << 3, GF_ZOUT = 1u << 4, GF_LNTMP = 1u << 5, GF_STATS = 1u << 6,
+    GF_EPIRES = 1u << 7, GF_GATE = 1u << 8, GF_DROP = 1u << 9, GF_RS = 1u << 10 /* rs_stats + rs_wg */, GF_HEAD = 1u << 11 /* head_out + head_gw */,
+    GF_ZR = 1u << 12, GF_CLO = 1u << 13, GF_SPLIT = 1u << 14, GF_WPRE = 1u << 15, GF_RELU = 1u << 16,
+};
+enum GemmFamily { GEMM_NONE = 0, GEMM_FLAT128 = 1, GEMM_SLAB = 2, GEMM_PERSIST = 3, GEMM_WRES = 4 };
+// What serves one request: decided by route_gemm from the arguments and the tuning alone (host arithmetic: no launch, no allocation),
+// executed by launch_route, which reads nothing else - so the choice can be tested without a GPU (fs2_op_gemm_route).  One input
+// is the device's: gemm_persist_pays compares the tile count with the CU count (hipDeviceGetAttribute; 256 where there is no device,
+// which is also the MI355X's), so slab-against-persistent answers hold for 256 CUs.
+struct GemmRoute {
+    int status = FS2_OK;       // != FS2_OK: nothing is launched
+    int family = GEMM_NONE;    // GEMM_NONE with FS2_OK: nothing to do (M <= 0)
+    int mi = 0;                // slab / persistent kernel: tile height / 32
+    int in_dtype = 0, out_dtype = 0;
+    bool ln = false, split = false, defer = false, xpre = false;  // the slab kernel's template flags
+    bool zr = false;           // the 128x128 kernel's zero_rows instantiation
+    bool two_launch = false;   // a LayerNorm request served as GEMM into ln_tmp + the LayerNorm kernel
+    bool presplit = false;     // split arithmetic on plain fp32 weights: packed on the fly for this launch
+};
+inline bool layernorm_rows_ok(int H) { return H % 4 == 0 && H <= 1024; }  // what layernorm_kernel takes (rowops.hip)
+GemmRoute route_gemm(const GemmArgs& a, int in_dtype, int out_dtype);
+int launch_route(const GemmRoute& r, const GemmArgs& a, hipStream_t stream);
+inline int launch_gemm(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream) {
+    return launch_route(route_gemm(a, in_dtype, out_dtype), a, stream);
+}
 // fp32 (N, K) weights, K % 32 == 0 -> the split arithmetic's load-time format, same size: per row and 32-channel chunk (128 bytes)
 // 16-byte slot s < 4 = bf16 heads of channels [4s, 4s + 4) and [16 + 4s, 16 + 4s + 4) of the chunk, slot 4 + s = their tails
 // (x = hi + lo up to 2^-17 |x|; the values split_bf16x3 produces).  Once per weight tensor, at fs2_finalize.

@@ -168,181 +168,6 @@ __global__ __launch_bounds__(256) void gemm_conv_kernel(GemmArgs p) {
 }
 
 // =================================================================================================
-// Large-problem variant: 128 (x rows) x 256 (W rows) per 512-thread workgroup (8 waves as 2 x 4,
-// each again a 64x64 patch), operands streamed global -> LDS by DMA (global_load_lds, 16 B per lane,
-// no staging registers, XOR swizzle applied on the source address) through a 3-stage ring:
-// chunk kc+2 is in flight while chunk kc is multiplied, with a counted vmcnt (never 0 in the steady
-// state) and one raw s_barrier per chunk (cdna_hip_programming.md §5 "Pipelining across barriers").
-// Rows that must read as zero (conv halo outside the utterance, M/N tails) are DMA'd from a zero
-// page.  All LDS lives in ONE extern array (a second __shared__ object would make hipcc drain
-// vmcnt before every ds_read).
-// =================================================================================================
-static constexpr int G2_BM = 128, G2_BN = 256;  // 3 LDS stages
-static constexpr int G2_XB = G2_BM * ROWB;        // 16 KiB
-static constexpr int G2_WB = G2_BN * ROWB;        // 32 KiB
-static constexpr int G2_STAGE = G2_XB + G2_WB;    // 48 KiB
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];
-
-__device__ inline void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <typename T, typename OutT>
-__global__ __launch_bounds__(512) void gemm_conv_glds_kernel(GemmArgs p) {
-    // one array PER STAGE: hipcc tracks pending LDS-DMA writes per LDS object, so ds_reads of the
-    // stage being multiplied do not wait for the DMAs still filling the other two
-    __shared__ __attribute__((aligned(16))) unsigned char st0[G2_STAGE];  // [X 16K | W 32K]
-    __shared__ __attribute__((aligned(16))) unsigned char st1[G2_STAGE];
-    __shared__ __attribute__((aligned(16))) unsigned char st2[G2_STAGE];
-    constexpr int E16 = Num<T>::kPer16B;
-    constexpr int KE = ROWB / (int)sizeof(T);
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tiles_n = (p.N + G2_BN - 1) / G2_BN;
-    const int bm = blockIdx.x / tiles_n, bn = blockIdx.x % tiles_n;
-    const int m0 = bm * G2_BM, n0 = bn * G2_BN;
-    const T* __restrict__ X = (const T*)p.X;
-    const T* __restrict__ W = (const T*)p.W;
-
-    // DMA assignment: a wave instruction moves 64 x 16 B = 8 LDS rows.  X: 2 per wave, W: 4.
-    // Exactly 6 DMA instructions per chunk per wave, unconditionally (the counted vmcnt below
-    // relies on it): lanes whose row must read as zero point at the zero page instead of branching.
-    int xt[2];            // row position inside its utterance (0 for plain GEMMs: always in range)
-    uintptr_t xmask[2];   // all ones if row < M
-    uintptr_t xaddr[2];   // byte address of (row, logical slot) at tap shift 0, channel 0
-    uintptr_t waddr[4];   // byte address of (n, logical slot) at k = 0, or the zero page
-    uintptr_t wstep[4];   // K advance in bytes (0 for zero-page lanes)
-    const uintptr_t zaddr = (uintptr_t)g_zero_page;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int P = (i * 8 + wave) * 64 + lane, row = P >> 3, ps = P & 7;
-        const int m = m0 + row;
-        xmask[i] = (uintptr_t)0 - (uintptr_t)(m < p.M);
-        xt[i] = (p.taps > 1) ? (m % p.S) : 0;
-        xaddr[i] = (uintptr_t)(X + (size_t)m * p.ldx + (ps ^ (row & 7)) * E16);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int P = (i * 8 + wave) * 64 + lane, row = P >> 3, ps = P & 7;
-        const int n = n0 + row;
-        const uintptr_t in = (uintptr_t)0 - (uintptr_t)(n < p.N);
-        waddr[i] = ((uintptr_t)(W + (size_t)n * p.K + (ps ^ (row & 7)) * E16) & in) | (zaddr & ~in);
-        wstep[i] = (uintptr_t)(KE * sizeof(T)) & in;
-    }
-    const int nk = p.K / KE;
-    const int Seff = p.taps > 1 ? p.S : 1;
-    int is_tap = 0, is_c0 = 0;  // (tap, channel offset) of the next chunk to be issued, in issue order
-    const ptrdiff_t row_bytes = (ptrdiff_t)p.ldx * (ptrdiff_t)sizeof(T);
-
-    auto issue = [&](unsigned char* sx) {  // chunks are issued strictly in order 0, 1, 2, ...
-        const int shift = is_tap - p.pad;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int t = xt[i] + shift;
-            const uintptr_t ok = xmask[i] & ((uintptr_t)0 - (uintptr_t)((t >= 0) & (t < Seff)));
-            const uintptr_t a = xaddr[i] + (uintptr_t)(shift * row_bytes + is_c0 * (ptrdiff_t)sizeof(T));
-            glds16((const void*)((a & ok) | (zaddr & ~ok)), sx + (i * 8 + wave) * 1024);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            glds16((const void*)waddr[i], sx + G2_XB + (i * 8 + wave) * 1024);
-            waddr[i] += wstep[i];
-        }
-        is_c0 += KE;
-        if (is_c0 == p.Cin) { is_c0 = 0; ++is_tap; }
-    };
-
-    f32x4_t acc[4][4];  // [ni][mi]
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-    const int wm = wave >> 2, wn = wave & 3;
-    const int fr = lane & 15, fg = lane >> 4;
-
-    auto compute = [&](const unsigned char* bx) {
-        const unsigned char* bw = bx + G2_XB;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            uint4 fw[4], fx[4];
-            const int slot = ks * 4 + fg;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                fw[i] = *(const uint4*)(bw + swz(wn * 64 + i * 16 + fr, slot));
-                fx[i] = *(const uint4*)(bx + swz(wm * 64 + i * 16 + fr, slot));
-            }
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) Mma16<T>::step(fw[ni], fx[mi], acc[ni][mi]);
-        }
-    };
-    // one pipeline step: chunk kc (in `cur`) has landed once at most the 6 DMAs of chunk kc+1 are
-    // still outstanding; the barrier also frees the stage chunk kc-1 was multiplied from, which is
-    // where chunk kc+2 goes
-#define FS2_G2_STEP(cur, nxt2, kcv)                                                   \
-    {                                                                                 \
-        if ((kcv) + 1 < nk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");           \
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          \
-        __builtin_amdgcn_s_barrier();                                                 \
-        if ((kcv) + 2 < nk) issue(nxt2);                                               \
-        compute(cur);                                                                 \
-    }
-    issue(st0);
-    if (nk > 1) issue(st1);
-    for (int kc = 0; kc < nk; kc += 3) {
-        FS2_G2_STEP(st0, st2, kc)
-        if (kc + 1 < nk) FS2_G2_STEP(st1, st0, kc + 1)
-        if (kc + 2 < nk) FS2_G2_STEP(st2, st1, kc + 2)
-    }
-#undef FS2_G2_STEP
-
-    OutT* __restrict__ C = (OutT*)p.C;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-        const int n = n0 + wn * 64 + ni * 16 + fg * 4;
-        if (n >= p.N) continue;
-        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (p.bias) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (n + r < p.N) bv[r] = p.bias[n + r];
-        }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-            const int m = m0 + wm * 64 + mi * 16 + fr;
-            if (m >= p.M) continue;
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = acc[ni][mi][r] + bv[r];
-                if (p.relu) v[r] = fmaxf(v[r], 0.f);
-            }
-            OutT* dst = C + (size_t)m * p.ldc + n;
-            if (n + 3 < p.N) {
-                if constexpr (sizeof(OutT) == 4) {
-                    *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-                    *(uint2*)dst = make_uint2(pack2<OutT>(v[0], v[1]), pack2<OutT>(v[2], v[3]));
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) if (n + r < p.N) dst[r] = Num<OutT>::from_f32(v[r]);
-            }
-        }
-    }
-}
-
-template <typename T, typename OutT>
-static int launch_glds_t(const GemmArgs& a, hipStream_t stream) {
-    const int tiles = ((a.M + G2_BM - 1) / G2_BM) * ((a.N + G2_BN - 1) / G2_BN);
-    hipLaunchKernelGGL((gemm_conv_glds_kernel<T, OutT>), dim3(tiles), dim3(512), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
-}
-
-// =================================================================================================
 // Slab kernel: (MI*32) rows of ONE utterance x 256 output channels per 512-thread workgroup
 // (8 waves as 2 x 4, wave patch (MI*16) x 64).  For a k-tap conv the x operand of all taps is the
 // same (rows + k - 1) x 64-channel slab: it is DMA'd into LDS ONCE per channel block and the taps
@@ -1228,7 +1053,7 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
 #endif
 }
 
-template <typename T, typename OutT, int MI, bool LN, bool SPLIT = false, bool DEFER = false>
+template <typename T, typename OutT, int MI, bool LN, bool SPLIT = false, bool DEFER = false, bool XPRE = false>
 static int launch_slab_t(const GemmArgs& a0, hipStream_t stream) {
     GemmArgs a = a0;
     a.xcd_remap = tuning_of(a0.tune).slab_xcd_remap;
@@ -1239,16 +1064,9 @@ static int launch_slab_t(const GemmArgs& a0, hipStream_t stream) {
                         (size_t)a.N * a.K * sizeof(T) > (size_t)3 << 20;
         if (!ok) a.xcd_remap = 1;
     }
-    if constexpr (SPLIT) {  // conv launches of the split arithmetic: the slab is split in place when it lands
-        if (a.taps > 1) {
-            const int tiles = (a.M / a.S) * ((a.S + BMs - 1) / BMs) * ((a.N + S_BN - 1) / S_BN) * (a.ksplit > 1 ? a.ksplit : 1);
-            hipLaunchKernelGGL((gemm_conv_slab_kernel<T, OutT, MI, LN, SPLIT, DEFER, true>), dim3(tiles), dim3(512), 0, stream, a);
-            return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
-        }
-    }
     if (a.taps == 1) a.S = a.M;  // plain GEMM: one "utterance" of M rows
     const int tiles = (a.M / a.S) * ((a.S + BMs - 1) / BMs) * ((a.N + S_BN - 1) / S_BN) * (a.ksplit > 1 ? a.ksplit : 1);
-    hipLaunchKernelGGL((gemm_conv_slab_kernel<T, OutT, MI, LN, SPLIT, DEFER>), dim3(tiles), dim3(512), 0, stream, a);
+    hipLaunchKernelGGL((gemm_conv_slab_kernel<T, OutT, MI, LN, SPLIT, DEFER, XPRE>), dim3(tiles), dim3(512), 0, stream, a);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
@@ -1267,51 +1085,6 @@ static int presplit_on_the_fly(GemmArgs& a, hipStream_t stream, void** tmp) {
     return r;
 }
 
-template <int MI>
-static int launch_slab_do(const GemmArgs& a, int in_dtype, int out_dtype, bool sp, hipStream_t stream) {
-    if (a.ln_g) {  // fused LayerNorm epilogue: whole rows per workgroup (N <= 256), tile heights up to 192
-        if constexpr (MI <= 6) {
-            if (a.N > S_BN) return FS2_ERR_SHAPE;
-            if (in_dtype == FS2_F32 && out_dtype == FS2_F32)
-                return sp ? launch_slab_t<float, float, MI, true, true>(a, stream) : launch_slab_t<float, float, MI, true>(a, stream);
-            if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_slab_t<bf16, bf16, MI, true>(a, stream);
-            if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_slab_t<f16, f16, MI, true>(a, stream);
-        }
-        return FS2_ERR_SHAPE;
-    }
-    if (a.stats_out || a.epi_res) {  // deferred-LayerNorm epilogue (tile heights up to 192: the 256-row form spills)
-        if (a.epi_res && a.relu) return FS2_ERR_SHAPE;  // the residual rides in the accumulators' initial value: no activation in between
-        if constexpr (MI <= 6) {
-            if (in_dtype == FS2_F32 && out_dtype == FS2_F32)
-                return sp ? launch_slab_t<float, float, MI, false, true, true>(a, stream) : launch_slab_t<float, float, MI, false, false, true>(a, stream);
-            if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_slab_t<bf16, bf16, MI, false, false, true>(a, stream);
-            if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_slab_t<f16, f16, MI, false, false, true>(a, stream);
-        }
-        return FS2_ERR_SHAPE;
-    }
-    if (in_dtype == FS2_F32 && out_dtype == FS2_F32)
-        return sp ? launch_slab_t<float, float, MI, false, true>(a, stream) : launch_slab_t<float, float, MI, false>(a, stream);
-    if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_slab_t<bf16, bf16, MI, false>(a, stream);
-    if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_slab_t<bf16, float, MI, false>(a, stream);
-    if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_slab_t<f16, f16, MI, false>(a, stream);
-    if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_slab_t<f16, float, MI, false>(a, stream);
-    return FS2_ERR_SHAPE;
-}
-
-template <int MI>
-static int launch_slab(const GemmArgs& a_in, int in_dtype, int out_dtype, hipStream_t stream) {
-    GemmArgs a = a_in;
-    const bool sp = a.split || tuning_of(a.tune).split_f32;
-    void* tmp = nullptr;
-    if (in_dtype == FS2_F32 && out_dtype == FS2_F32 && sp && !a.w_presplit) {
-        const int r = presplit_on_the_fly(a, stream, &tmp);
-        if (r != FS2_OK) { if (tmp) (void)hipFreeAsync(tmp, stream); return r; }
-    }
-    const int r = launch_slab_do<MI>(a, in_dtype, out_dtype, sp, stream);
-    if (tmp) (void)hipFreeAsync(tmp, stream);  // behind the launch that reads it, in stream order
-    return r;
-}
-
 template <typename T, typename OutT, bool ZR = false>
 static int launch_t(const GemmArgs& a, hipStream_t stream) {
     static bool attr_set = false;
@@ -1327,166 +1100,267 @@ static int launch_t(const GemmArgs& a, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
-static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream, bool* fused);
+// ---- the (in, out) storage dtype pairs, once ------------------------------------------------------------------------------------
+// A kernel family's epilogue accepts a SET of pairs; the router tests membership, the launcher turns the pair into <T, OutT> and
+// instantiates the members of the set only.
+enum : unsigned {
+    DT_F32 = 1, DT_BF16 = 2, DT_F16 = 4, DT_BF16_F32 = 8, DT_F16_F32 = 16,
+    DT_SAME = DT_F32 | DT_BF16 | DT_F16,            // the slab kernel's LayerNorm and deferred epilogues
+    DT_ALL = DT_SAME | DT_BF16_F32 | DT_F16_F32,    // its plain epilogue; the 128x128 kernel
+    DT_TO_F32 = DT_F32 | DT_BF16_F32 | DT_F16_F32,  // the 128x128 kernel's zero_rows form (the mel head)
+};
+static unsigned dtype_pair(int in, int out) {
+    if (in == FS2_F32) return out == FS2_F32 ? DT_F32 : 0;
+    if (in == FS2_BF16) return out == FS2_BF16 ? DT_BF16 : out == FS2_F32 ? DT_BF16_F32 : 0;
+    if (in == FS2_F16) return out == FS2_F16 ? DT_F16 : out == FS2_F32 ? DT_F16_F32 : 0;
+    return 0;
+}
+template <typename T> struct Ty { using type = T; };
+template <unsigned SET, typename F>
+static int with_dtypes(int in, int out, F&& f) {  // f(Ty<T>, Ty<OutT>)
+    const unsigned p = dtype_pair(in, out);
+    if constexpr ((SET & DT_F32) != 0) if (p == DT_F32) return f(Ty<float>{}, Ty<float>{});
+    if constexpr ((SET & DT_BF16) != 0) if (p == DT_BF16) return f(Ty<bf16>{}, Ty<bf16>{});
+    if constexpr ((SET & DT_BF16_F32) != 0) if (p == DT_BF16_F32) return f(Ty<bf16>{}, Ty<float>{});
+    if constexpr ((SET & DT_F16) != 0) if (p == DT_F16) return f(Ty<f16>{}, Ty<f16>{});
+    if constexpr ((SET & DT_F16_F32) != 0) if (p == DT_F16_F32) return f(Ty<f16>{}, Ty<float>{});
+    return FS2_ERR_SHAPE;
+}
+static constexpr unsigned slab_dtypes(bool ln, bool defer) { return ln || defer ? DT_SAME : DT_ALL; }
+static constexpr unsigned flat_dtypes(bool zr) { return zr ? DT_TO_F32 : DT_ALL; }
 
-int launch_gemm(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream) {
-    if (!is_storage_dtype(in_dtype) || !is_storage_dtype(out_dtype)) return FS2_ERR_ARG;
-    // f16 operands: the forward's epilogues only (no dropout, gate, pre-norm tape, split-K, head sums: the training step's and the predictors')
-    if ((in_dtype == FS2_F16 || out_dtype == FS2_F16) && (a.drop_p > 0.f || a.gate || a.z_out || a.ksplit > 1 || a.head_out || a.C_lo)) return FS2_ERR_ARG;
+// ---- the route -------------------------------------------------------------------------------------------------------------------
+// Feature rules, as data: an optional member of GemmArgs that only some kernels implement has ONE row saying which families have
+// it, which other members it cannot be combined with, and what the shape / dtypes / knobs must satisfy.  A request that breaks a
+// row of a member it carries is FS2_ERR_SHAPE.  (Members without a row - bias, res, dot_w, relu, split - are every family's, or the
+// LayerNorm epilogue's, which route_gemm handles as a whole.)
+enum : unsigned {  // router-internal feature bits behind GemmFeature's
+    GF_KSPLIT = 1u << 17,
+    GF_RS_NARROW = 1u << 18,  // rs_stats with N < 192: the 128x128 kernel's form of it (GF_RS: the slab / persistent kernels')
+};
+enum : unsigned {  // conditions a row can need
+    ND_AUTO = 1u << 0, ND_NOT_FLAT = 1u << 1, ND_SLAB_KNOB = 1u << 2,  // gemm_variant: 0 (no family forced) / not 1 / 0 or a forced slab tile height (3-7)
+    ND_WIDE = 1u << 3,                                                  // N >= 192
+    ND_TILES = 1u << 4,                                                 // whole utterances and an odd tap count: what the slab kernel tiles
+    ND_SAME_DT = 1u << 5, ND_IN_F32 = 1u << 6, ND_OUT_F32 = 1u << 7, ND_IN_16 = 1u << 8,
+    ND_RELU = 1u << 9, ND_RS_WG = 1u << 10, ND_TAPS1 = 1u << 11,
+    ND_SPLIT_ON = 1u << 12,                                             // GemmArgs::split or Tuning::split_f32
+    ND_KDIV = 1u << 13,                                                 // ksplit divides the channel blocks
+};
+struct FeatureRule { unsigned feature, not_with, needs, families; };
+static constexpr unsigned FAM_FLAT = 1u << GEMM_FLAT128, FAM_SLAB = 1u << GEMM_SLAB, FAM_PERSIST = 1u << GEMM_PERSIST;
+static constexpr unsigned GF_OTHER_EPI = GF_LN | GF_STATS | GF_EPIRES;  // members of the plain epilogue exclude the other two epilogues
+static const FeatureRule kFeatureRules[] = {
+    // the plain store's dropout: behind a ReLU (the FFN's hidden tensor)
+    {GF_DROP, GF_GATE | GF_STATS | GF_EPIRES | GF_KSPLIT | GF_ZR, ND_RELU | ND_AUTO | ND_WIDE | ND_TILES | ND_SAME_DT, FAM_SLAB},
+    // a narrow head behind a folded LayerNorm (the mel Linear), 16-bit operands / the row-scaled product of the plain 16-bit epilogue
+    {GF_RS_NARROW, GF_OTHER_EPI | GF_RELU | GF_GATE | GF_CLO | GF_KSPLIT | GF_DROP, ND_RS_WG | ND_TAPS1 | ND_IN_16, FAM_FLAT},
+    {GF_RS, GF_OTHER_EPI | GF_RELU | GF_GATE | GF_CLO | GF_KSPLIT | GF_DROP, ND_RS_WG | ND_NOT_FLAT | ND_TILES | ND_IN_16 | ND_SAME_DT, FAM_SLAB | FAM_PERSIST},
+    {GF_ZR, GF_LN, 0, FAM_FLAT},  // the mel head with zeroed pad rows
+    {GF_GATE, GF_OTHER_EPI | GF_RELU, ND_AUTO | ND_WIDE | ND_TILES | ND_SAME_DT, FAM_SLAB},
+    // weights packed as heads + tails are the split arithmetic's own format
+    {GF_WPRE, GF_KSPLIT, ND_SPLIT_ON | ND_AUTO | ND_WIDE | ND_TILES | ND_IN_F32, FAM_SLAB},
+    {GF_CLO, GF_OTHER_EPI | GF_GATE | GF_KSPLIT | GF_DROP, ND_AUTO | ND_WIDE | ND_TILES | ND_IN_F32 | ND_OUT_F32, FAM_SLAB},  // head + tail store: plain fp32 epilogue
+    {GF_KSPLIT, GF_OTHER_EPI | GF_BIAS | GF_RELU | GF_GATE, ND_SLAB_KNOB | ND_WIDE | ND_TILES | ND_OUT_F32 | ND_KDIV, FAM_SLAB},  // plain fp32 store only
+    // the deferred-LayerNorm epilogue; its residual rides in the accumulators' initial value: no activation in between
+    {GF_STATS, 0, 0, FAM_SLAB | FAM_PERSIST},
+    {GF_EPIRES, GF_RELU, 0, FAM_SLAB | FAM_PERSIST},
+};
+
+struct Request { unsigned feats, have; };  // what the rules look at: the members a request carries, the conditions that hold
+static Request classify(const GemmArgs& a, int in_dtype, int out_dtype) {
     const Tuning& tn = tuning_of(a.tune);
-    const int g_gemm_variant = tn.gemm_variant, g_gemm_wres = tn.gemm_wres;
-    if (a.head_out) {  // head sums instead of the rows: the persistent kernel's deferred epilogue only (callers ask gemm_head_supported first)
-        if (a.ln_g || !gemm_head_supported(a, in_dtype, out_dtype)) return FS2_ERR_SHAPE;
-        return launch_gemm_persist(a, in_dtype, 6, stream);
+    const int v = tn.gemm_variant, ke = 128 / (int)elem_bytes(in_dtype);
+    const bool ln = a.ln_g != nullptr;  // the LayerNorm epilogue takes precedence over the deferred one, and has a dropout of its own
+    const unsigned feats = (a.bias ? GF_BIAS : 0) | (a.relu ? GF_RELU : 0) | (ln ? GF_LN : 0) | (!ln && a.stats_out ? GF_STATS : 0) |
+                           (!ln && a.epi_res ? GF_EPIRES : 0) | (!ln && a.drop_p > 0.f ? GF_DROP : 0) | (a.gate ? GF_GATE : 0) |
+                           (a.rs_stats ? (a.N < 192 ? GF_RS_NARROW : GF_RS) : 0) | (a.zero_rows ? GF_ZR : 0) | (a.C_lo ? GF_CLO : 0) |
+                           (a.w_presplit ? GF_WPRE : 0) | (a.ksplit > 1 ? GF_KSPLIT : 0);
+    const unsigned have = (v == 0 ? ND_AUTO : 0) | (v != 1 ? ND_NOT_FLAT : 0) | (v == 0 || (v >= 3 && v <= 7) ? ND_SLAB_KNOB : 0) |
+                          (a.N >= 192 ? ND_WIDE : 0) | (a.S > 0 && a.M % a.S == 0 && (a.taps & 1) ? ND_TILES : 0) |
+                          (in_dtype == out_dtype ? ND_SAME_DT : 0) | (in_dtype == FS2_F32 ? ND_IN_F32 : 0) | (out_dtype == FS2_F32 ? ND_OUT_F32 : 0) |
+                          (is_16bit(in_dtype) ? ND_IN_16 : 0) | (a.relu ? ND_RELU : 0) | (a.rs_wg ? ND_RS_WG : 0) | (a.taps == 1 ? ND_TAPS1 : 0) |
+                          (a.split || tn.split_f32 ? ND_SPLIT_ON : 0) | (a.ksplit > 1 && (a.Cin / ke) % a.ksplit == 0 ? ND_KDIV : 0);
+    return {feats, have};
+}
+// the rows of the members in `subject`: their combinations and conditions, and (family != GEMM_NONE) that the family has them
+static bool rules_hold(const Request& q, unsigned subject, int family) {
+    for (const FeatureRule& r : kFeatureRules) {
+        if (!(subject & r.feature)) continue;
+        if ((q.feats & r.not_with) || (r.needs & ~q.have)) return false;
+        if (family != GEMM_NONE && !(r.families & (1u << family))) return false;
     }
-    if (!a.ln_g && a.drop_p > 0.f) {  // the plain store's dropout: slab kernel, behind a ReLU (the FFN's hidden tensor)
-        if (!a.relu || a.gate || a.stats_out || a.epi_res || a.ksplit > 1 || a.zero_rows || g_gemm_variant != 0 || a.N < 192 || a.M % a.S ||
-            !(a.taps & 1) || in_dtype != out_dtype)
-            return FS2_ERR_SHAPE;
-        return launch_gemm_plain(a, in_dtype, out_dtype, stream, nullptr);  // (FS2_ERR_SHAPE there if it would take a flat kernel)
-    }
-    if (!a.ln_g) {
-        // K = 256 bf16: the column tile's weights live in registers, row tiles stream (gemm_wres.hip; bit-identical results)
-        if (g_gemm_wres && g_gemm_variant == 0 && a.ksplit <= 1 && gemm_wres_supported(a, in_dtype, out_dtype, g_gemm_wres == 2)) return launch_gemm_wres(a, in_dtype, stream);
-        return launch_gemm_plain(a, in_dtype, out_dtype, stream, nullptr);
-    }
-    // fused row epilogue requested: try the slab kernel (whole rows per workgroup), else GEMM -> ln_tmp
-    // followed by the stand-alone LayerNorm kernel (same arithmetic, one more HBM round trip)
-    bool fused = false;
-    if (a.z_out && a.N > S_BN) return FS2_ERR_SHAPE;  // the pre-norm store exists in the one-column-tile epilogue only
-    if (a.drop_p > 0.f && (a.N > S_BN || !a.z_out)) return FS2_ERR_SHAPE;  // the epilogue's dropout: one-column-tile fused form only (training tape)
-    if (a.N <= S_BN && in_dtype == out_dtype) {
-        const int r = launch_gemm_plain(a, in_dtype, out_dtype, stream, &fused);
-        if (r != FS2_OK || fused) return r;
-    }
-    if (a.z_out) return FS2_ERR_SHAPE;  // not fusable for this shape: the caller takes its two-launch path (nothing was launched)
-    if (!a.ln_tmp || in_dtype != out_dtype) return FS2_ERR_ARG;
-    GemmArgs g = a;
-    g.ln_g = nullptr;
-    g.C = a.ln_tmp;
-    const int r = launch_gemm_plain(g, in_dtype, out_dtype, stream, nullptr);
-    if (r != FS2_OK) return r;
-    LayerNormArgs l;
-    l.x = a.ln_tmp; l.res = a.res; l.gamma = a.ln_g; l.beta = a.ln_b; l.y = a.C;
-    l.dot_w = a.dot_w; l.dot_b = a.dot_b; l.mask = a.mask; l.pred = a.pred;
-    l.M = a.M; l.H = a.N; l.eps = a.ln_eps;
-    return launch_layernorm(l, out_dtype, stream);
+    return true;
 }
 
-// fused != nullptr: the caller wants the LN epilogue; only the slab kernel provides it.  If the slab
-// kernel is not selected, nothing is launched and *fused stays false.
-static int launch_gemm_plain(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream, bool* fused) {
-    const Tuning& tn_ = tuning_of(a.tune);
-    const int g_gemm_variant = tn_.gemm_variant;
-    const bool g_split_f32 = tn_.split_f32 != 0;
-    if (a.M <= 0 || a.N <= 0) return FS2_OK;
-    const int ke = 128 / (int)elem_bytes(in_dtype);
-    const int e16 = 16 / (int)elem_bytes(in_dtype);
-    if (a.K % ke || a.Cin % ke || a.ldx % e16 || a.K != a.taps * a.Cin) return FS2_ERR_SHAPE;
-    if (a.ldc % 4) return FS2_ERR_SHAPE;
-    if (a.rs_stats && a.N < 192) {  // a narrow head behind a folded LayerNorm (the mel Linear): 128x128 kernel, bf16 operands
-        if (fused || a.relu || a.gate || a.stats_out || a.epi_res || a.C_lo || a.ksplit > 1 || a.drop_p > 0.f || !a.rs_wg || a.taps != 1 || !is_16bit(in_dtype))
-            return FS2_ERR_SHAPE;
-        if (in_dtype == FS2_F16) {
-            if (out_dtype == FS2_F32) return a.zero_rows ? launch_t<f16, float, true>(a, stream) : launch_t<f16, float>(a, stream);
-            if (out_dtype == FS2_F16 && !a.zero_rows) return launch_t<f16, f16>(a, stream);
-            return FS2_ERR_SHAPE;
-        }
-        if (out_dtype == FS2_F32) return a.zero_rows ? launch_t<bf16, float, true>(a, stream) : launch_t<bf16, float>(a, stream);
-        if (out_dtype == FS2_BF16 && !a.zero_rows) return launch_t<bf16, bf16>(a, stream);
-        return FS2_ERR_SHAPE;
-    }
-    if (a.zero_rows) {  // the mel head with zeroed pad rows: 128x128 kernel only
-        if (fused) return FS2_ERR_SHAPE;
-        if (in_dtype == FS2_F32 && out_dtype == FS2_F32) return launch_t<float, float, true>(a, stream);
-        if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_t<bf16, float, true>(a, stream);
-        if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_t<f16, float, true>(a, stream);
-        return FS2_ERR_SHAPE;
-    }
-    if (a.rs_stats && (fused || a.relu || a.gate || a.stats_out || a.epi_res || a.zero_rows || a.C_lo || a.ksplit > 1 || a.drop_p > 0.f || g_gemm_variant == 1 ||
-                       g_gemm_variant == 2 || !a.rs_wg || !(a.M % a.S == 0 && (a.taps & 1)) || a.N < 192 || !is_16bit(in_dtype) ||
-                       out_dtype != in_dtype))
-        return FS2_ERR_SHAPE;  // the row-scaled product lives in the slab / persistent kernels' plain 16-bit epilogue only
-    if (a.gate && (fused || a.relu || a.stats_out || a.epi_res || g_gemm_variant != 0 || a.N < 192 || a.M % a.S || !(a.taps & 1) ||
-                   in_dtype != out_dtype))
-        return FS2_ERR_SHAPE;  // the gated store lives in the slab kernel's plain epilogue only
-    const int variant = g_gemm_variant;  // 0 = auto, 1 = 128x128 register-staged, 2 = 128x256 DMA ring,
-                                         // 3/4/5 = slab kernel with 128/192/256-row tiles
-    const bool slab_ok = a.M % a.S == 0 && (a.taps & 1);
+// One launch for the request as it stands.  With ln_g set the question is whether the slab kernel takes it with the LayerNorm in
+// its epilogue (whole rows per workgroup); GEMM_NONE with FS2_OK and M > 0 then means it does not.
+static GemmRoute route_one(const GemmArgs& a, int in_dtype, int out_dtype) {
+    GemmRoute r;
+    if (a.M <= 0 || a.N <= 0) return r;
+    const int ke = 128 / (int)elem_bytes(in_dtype), e16 = 16 / (int)elem_bytes(in_dtype);
+    if (a.K % ke || a.Cin % ke || a.ldx % e16 || a.K != a.taps * a.Cin || a.ldc % 4) return GemmRoute{FS2_ERR_SHAPE};
+    const Tuning& tn = tuning_of(a.tune);
+    const Request q = classify(a, in_dtype, out_dtype);
+    const bool ln = q.feats & GF_LN, defer = q.feats & (GF_STATS | GF_EPIRES), tiles_ok = q.have & ND_TILES;
+    const int variant = tn.gemm_variant;  // 0 = auto, 1 = 128x128 register-staged, 3/4/5 = slab kernel with 128/192/256-row tiles, 6/7 = 32/64-row
     const int ksp = a.ksplit > 1 ? a.ksplit : 1;
-    if (a.w_presplit && (!(a.split || g_split_f32) || variant != 0 || !slab_ok || a.N < 192 || in_dtype != FS2_F32 || a.ksplit > 1 || a.zero_rows))
-        return FS2_ERR_SHAPE;  // weights packed as heads + tails are the slab kernel's split arithmetic's own format
-    if (a.C_lo && (fused || a.gate || a.stats_out || a.epi_res || a.zero_rows || a.ksplit > 1 || a.drop_p > 0.f || variant != 0 || !slab_ok ||
-                   a.N < 192 || in_dtype != FS2_F32 || out_dtype != FS2_F32))
-        return FS2_ERR_SHAPE;  // the head + tail store lives in the slab kernel's plain fp32 epilogue only
-    if (ksp > 1 && (fused || a.bias || a.relu || a.gate || a.stats_out || a.epi_res || a.zero_rows || out_dtype != FS2_F32 || !slab_ok ||
-                    a.N < 192 || (a.Cin / ke) % ksp || (variant != 0 && (variant < 3 || variant > 7))))
-        return FS2_ERR_SHAPE;  // split-K: the slab kernel's plain fp32 store only
-    if (variant >= 6 && variant <= 7 && slab_ok) {  // 6/7 = slab kernel with 32/64-row tiles
-        if (fused) *fused = true;
-        if (variant == 6) return launch_slab<1>(a, in_dtype, out_dtype, stream);
-        return launch_slab<2>(a, in_dtype, out_dtype, stream);
-    }
-    if (variant >= 3 && variant <= 5 && slab_ok && !(fused && variant == 5)) {
-        if (fused) *fused = true;
-        if (variant == 3) return launch_slab<4>(a, in_dtype, out_dtype, stream);
-        if (variant == 4 || a.stats_out || a.epi_res) return launch_slab<6>(a, in_dtype, out_dtype, stream);
-        return launch_slab<8>(a, in_dtype, out_dtype, stream);
-    }
-    if (fused && variant != 0) return FS2_OK;  // forced non-slab kernel: caller falls back
-    if (variant == 2) {
-        if (a.stats_out || a.epi_res) return FS2_ERR_SHAPE;
-        if (in_dtype == FS2_F32 && out_dtype == FS2_F32) return launch_glds_t<float, float>(a, stream);
-        if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_glds_t<bf16, bf16>(a, stream);
-        if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_glds_t<bf16, float>(a, stream);
-        if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_glds_t<f16, f16>(a, stream);
-        if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_glds_t<f16, float>(a, stream);
-        return FS2_ERR_SHAPE;
-    }
-    if (variant == 0 && slab_ok && a.N >= 192) {
+    // A member that only the 128x128 kernel has decides the family by itself, and the slab kernel's members are then not looked at
+    // (a gate or C_lo beside zero_rows is ignored, not refused): kept as it always was, the statuses are pinned by the route test.
+    // (Every conflicting pair of members stands in one row of the table only: a new member names its conflicts in its own row.)
+    const bool flat_only = q.feats & (GF_RS_NARROW | GF_ZR);
+    const unsigned subject = flat_only ? q.feats & (GF_DROP | GF_RS_NARROW | GF_ZR) : q.feats;
+    if (!rules_hold(q, subject, GEMM_NONE)) return GemmRoute{FS2_ERR_SHAPE};
+
+    int family = GEMM_FLAT128, mi = 0;
+    if (flat_only) {
+    } else if (tiles_ok && (variant == 6 || variant == 7)) {
+        family = GEMM_SLAB; mi = variant == 6 ? 1 : 2;
+    } else if (tiles_ok && variant >= 3 && variant <= 5 && !(ln && variant == 5)) {
+        family = GEMM_SLAB; mi = variant == 3 ? 4 : (variant == 4 || defer) ? 6 : 8;
+    } else if (variant == 0 && tiles_ok && a.N >= 192) {
         // One 512-thread workgroup per CU: pick the row-tile height that minimises
         // (rounds over the 256 CUs) x (tile rows + ~40 rows' worth of prologue/epilogue), measured
         // on MI355X (tools/bench_ops.py); fall back to the flat 128x128 kernel when utterances are
         // so short that per-utterance tiles would be mostly padding.
-        const int S = a.taps == 1 ? a.M : a.S, nutt = a.M / S, tn = (a.N + S_BN - 1) / S_BN;
+        const int S = a.taps == 1 ? a.M : a.S, nutt = a.M / S, tiles_n = (a.N + S_BN - 1) / S_BN;
         int best = 0;
         long best_cost = 0, best_rows = 0;
         static const int kHeights[5] = {1, 2, 4, 6, 8};  // x32 rows; 32/64-row tiles keep small-M launches
         for (int hi = 0; hi < 5; ++hi) {                  // (the encoder's) spread over all CUs
-            const int mi = kHeights[hi];
-            if (fused && mi > 6) continue;                                    // 256-row tiles spill with the fused LayerNorm epilogue
-            if ((a.stats_out || a.epi_res) && mi > 6) continue;                // ... and with the deferred one (r04: 24 spills even without its in-epilogue residual path; selected nowhere)
-            const long bm = mi * 32, tm = (S + bm - 1) / bm;
-            const long tiles = (long)nutt * tm * tn * ksp;
+            const int h = kHeights[hi];
+            if ((ln || defer) && h > 6) continue;  // 256-row tiles spill with the fused LayerNorm epilogue and with the deferred one (r04: 24 spills even without its in-epilogue residual path; selected nowhere)
+            const long bm = h * 32, tm = (S + bm - 1) / bm;
+            const long tiles = (long)nutt * tm * tiles_n * ksp;
             long cost = ((tiles + 255) / 256) * (bm + 40);
             // long reductions (K >= 4096: the data-gradient convs of the training step, K = taps * filter): every workgroup
             // streams the whole K x 256 weight panel out of L2, and tiles x panel bytes over the ~10 TB/s the L2s deliver
             // together becomes the bound before the CUs fill - in the same units (one row of MFMA work per K) that is ~1 per
             // tile.  C5 encoder conv1 dgrad (M = 2048, N = 1024, K = 36864): 256 x 32-row tiles 500 us -> 128 x 64-row tiles.
             if (a.K / ksp >= 4096) cost = cost > tiles ? cost : tiles;
-            if (!best || cost < best_cost) { best = mi; best_cost = cost; best_rows = (long)nutt * tm * bm; }
+            if (!best || cost < best_cost) { best = h; best_cost = cost; best_rows = (long)nutt * tm * bm; }
         }
-        if (best_rows <= 2L * a.M || a.C_lo || a.w_presplit || a.rs_stats) {  // (the head + tail store / pre-split weights / row-scaled product exist in this kernel only)
+        if (best_rows <= 2L * a.M || (q.feats & (GF_CLO | GF_WPRE | GF_RS))) {  // (the head + tail store / pre-split weights / row-scaled product exist in this kernel only)
             // more tiles than CUs: one workgroup per CU walks them, the next tile's first operands under this tile's epilogue
             // (gemm_persist.hip; same tile height, same arithmetic per element - bit-identical)
-            if (!fused && tn_.gemm_persist && gemm_persist_supported(a, in_dtype, out_dtype, best) && gemm_persist_pays(a, best))
-                return launch_gemm_persist(a, in_dtype, best, stream);
-            if (fused) *fused = true;
-            if (best == 1) return launch_slab<1>(a, in_dtype, out_dtype, stream);
-            if (best == 2) return launch_slab<2>(a, in_dtype, out_dtype, stream);
-            if (best == 4) return launch_slab<4>(a, in_dtype, out_dtype, stream);
-            if (best == 6) return launch_slab<6>(a, in_dtype, out_dtype, stream);
-            return launch_slab<8>(a, in_dtype, out_dtype, stream);
+            family = !ln && tn.gemm_persist && gemm_persist_supported(a, in_dtype, out_dtype, best) && gemm_persist_pays(a, best) ? GEMM_PERSIST : GEMM_SLAB;
+            mi = best;
         }
     }
-    if (fused) return FS2_OK;  // not the slab kernel: caller falls back to GEMM + LayerNorm kernel
-    if (a.stats_out || a.epi_res || a.gate || ksp > 1 || a.drop_p > 0.f || a.rs_stats) return FS2_ERR_SHAPE;  // the deferred-LayerNorm epilogue lives in the slab kernel only
-    if (in_dtype == FS2_F32 && out_dtype == FS2_F32) return launch_t<float, float>(a, stream);
-    if (in_dtype == FS2_BF16 && out_dtype == FS2_BF16) return launch_t<bf16, bf16>(a, stream);
-    if (in_dtype == FS2_BF16 && out_dtype == FS2_F32) return launch_t<bf16, float>(a, stream);
-    if (in_dtype == FS2_F16 && out_dtype == FS2_F16) return launch_t<f16, f16>(a, stream);
-    if (in_dtype == FS2_F16 && out_dtype == FS2_F32) return launch_t<f16, float>(a, stream);
-    return FS2_ERR_SHAPE;
+    if (ln && family != GEMM_SLAB) return r;  // only the slab kernel has the LayerNorm epilogue
+    if (!rules_hold(q, subject, family)) return GemmRoute{FS2_ERR_SHAPE};
+    r.family = family; r.mi = mi;
+    if (family == GEMM_FLAT128) {
+        r.zr = q.feats & GF_ZR;
+        if (!(dtype_pair(in_dtype, out_dtype) & flat_dtypes(r.zr))) return GemmRoute{FS2_ERR_SHAPE};
+    } else if (family == GEMM_SLAB) {
+        r.ln = ln; r.defer = defer;
+        if (!(dtype_pair(in_dtype, out_dtype) & slab_dtypes(ln, defer))) return GemmRoute{FS2_ERR_SHAPE};
+        r.split = in_dtype == FS2_F32 && out_dtype == FS2_F32 && (q.have & ND_SPLIT_ON);
+        r.xpre = r.split && a.taps > 1;  // conv launches of the split arithmetic: the slab is split in place when it lands
+        r.presplit = r.split && !a.w_presplit;
+    }
+    return r;
+}
+
+static GemmRoute route_request(const GemmArgs& a, int in_dtype, int out_dtype) {
+    const auto no = [](int status) { return GemmRoute{status}; };
+    const auto on = [](int family, int mi) { GemmRoute r; r.family = family; r.mi = mi; return r; };
+    if (!is_storage_dtype(in_dtype) || !is_storage_dtype(out_dtype)) return no(FS2_ERR_ARG);
+    // f16 operands: the forward's epilogues only (no dropout, gate, pre-norm tape, split-K, head sums: the training step's and the predictors')
+    if ((in_dtype == FS2_F16 || out_dtype == FS2_F16) && (a.drop_p > 0.f || a.gate || a.z_out || a.ksplit > 1 || a.head_out || a.C_lo)) return no(FS2_ERR_ARG);
+    const Tuning& tn = tuning_of(a.tune);
+    if (a.head_out) {  // head sums instead of the rows: the persistent kernel's deferred epilogue only (callers ask gemm_head_supported first)
+        if (a.ln_g || !gemm_head_supported(a, in_dtype, out_dtype)) return no(FS2_ERR_SHAPE);
+        return on(GEMM_PERSIST, 6);
+    }
+    if (!a.ln_g) {
+        if (a.drop_p > 0.f) {
+            if (!rules_hold(classify(a, in_dtype, out_dtype), GF_DROP, GEMM_NONE)) return no(FS2_ERR_SHAPE);
+        } else if (tn.gemm_wres && tn.gemm_variant == 0 && a.ksplit <= 1 && gemm_wres_supported(a, in_dtype, out_dtype, tn.gemm_wres == 2)) {
+            // K = 256 bf16: the column tile's weights live in registers, row tiles stream (gemm_wres.hip; bit-identical results)
+            return on(GEMM_WRES, 0);
+        }
+        return route_one(a, in_dtype, out_dtype);
+    }
+    // fused row epilogue requested: the slab kernel (whole rows per workgroup, N <= 256), else GEMM -> ln_tmp followed by the
+    // stand-alone LayerNorm kernel (same arithmetic, one more HBM round trip)
+    if (a.z_out && a.N > S_BN) return no(FS2_ERR_SHAPE);  // the pre-norm store exists in the one-column-tile epilogue only
+    if (a.drop_p > 0.f && (a.N > S_BN || !a.z_out)) return no(FS2_ERR_SHAPE);  // the epilogue's dropout: one-column-tile fused form only (training tape)
+    if (a.N <= S_BN && in_dtype == out_dtype) {
+        const GemmRoute r = route_one(a, in_dtype, out_dtype);
+        if (r.status != FS2_OK || r.family != GEMM_NONE) return r;
+    }
+    if (a.z_out) return no(FS2_ERR_SHAPE);  // not fusable for this shape: the caller takes its two-launch path (nothing is launched)
+    if (!a.ln_tmp || in_dtype != out_dtype) return no(FS2_ERR_ARG);
+    GemmArgs g = a;
+    g.ln_g = nullptr;
+    g.C = a.ln_tmp;
+    GemmRoute r = route_one(g, in_dtype, out_dtype);
+    if (r.status != FS2_OK || r.family == GEMM_NONE) return r;
+    if (!layernorm_rows_ok(a.N)) return no(FS2_ERR_SHAPE);  // refused before the GEMM goes out, not behind it
+    r.two_launch = true;
+    return r;
+}
+GemmRoute route_gemm(const GemmArgs& a, int in_dtype, int out_dtype) {
+    GemmRoute r = route_request(a, in_dtype, out_dtype);
+    r.in_dtype = in_dtype; r.out_dtype = out_dtype;
+    return r;
+}
+
+// ---- the launcher: executes a route, decides nothing ------------------------------------------------------------------------------
+template <int MI, bool LN, bool DEFER>
+static int launch_slab_e(const GemmRoute& r, const GemmArgs& a, hipStream_t stream) {
+    return with_dtypes<slab_dtypes(LN, DEFER)>(r.in_dtype, r.out_dtype, [&](auto t, auto o) {
+        using T = typename decltype(t)::type;
+        using OutT = typename decltype(o)::type;
+        if constexpr (sizeof(T) == 4) {
+            if (r.xpre) return launch_slab_t<T, OutT, MI, LN, true, DEFER, true>(a, stream);
+            if (r.split) return launch_slab_t<T, OutT, MI, LN, true, DEFER>(a, stream);
+        }
+        return launch_slab_t<T, OutT, MI, LN, false, DEFER>(a, stream);
+    });
+}
+template <int MI>
+static int launch_slab_mi(const GemmRoute& r, const GemmArgs& a, hipStream_t stream) {
+    if constexpr (MI <= 6) {  // the 256-row form of the LayerNorm and deferred epilogues spills: not built, never routed
+        if (r.ln) return launch_slab_e<MI, true, false>(r, a, stream);
+        if (r.defer) return launch_slab_e<MI, false, true>(r, a, stream);
+    }
+    return launch_slab_e<MI, false, false>(r, a, stream);
+}
+template <bool ZR>
+static int launch_flat(const GemmRoute& r, const GemmArgs& a, hipStream_t stream) {
+    return with_dtypes<flat_dtypes(ZR)>(r.in_dtype, r.out_dtype, [&](auto t, auto o) {
+        return launch_t<typename decltype(t)::type, typename decltype(o)::type, ZR>(a, stream);
+    });
+}
+
+int launch_route(const GemmRoute& r, const GemmArgs& a_in, hipStream_t stream) {
+    if (r.status != FS2_OK || r.family == GEMM_NONE) return r.status;
+    GemmArgs a = a_in;
+    if (r.two_launch) { a.ln_g = nullptr; a.C = a_in.ln_tmp; }
+    void* tmp = nullptr;
+    if (r.presplit) {
+        const int st = presplit_on_the_fly(a, stream, &tmp);
+        if (st != FS2_OK) { if (tmp) (void)hipFreeAsync(tmp, stream); return st; }
+    }
+    int st;
+    if (r.family == GEMM_FLAT128) st = r.zr ? launch_flat<true>(r, a, stream) : launch_flat<false>(r, a, stream);
+    else if (r.family == GEMM_PERSIST) st = launch_gemm_persist(a, r.in_dtype, r.mi, stream);
+    else if (r.family == GEMM_WRES) st = launch_gemm_wres(a, r.in_dtype, stream);
+    else if (r.mi == 1) st = launch_slab_mi<1>(r, a, stream);
+    else if (r.mi == 2) st = launch_slab_mi<2>(r, a, stream);
+    else if (r.mi == 4) st = launch_slab_mi<4>(r, a, stream);
+    else if (r.mi == 6) st = launch_slab_mi<6>(r, a, stream);
+    else st = launch_slab_mi<8>(r, a, stream);
+    if (tmp) (void)hipFreeAsync(tmp, stream);  // behind the launch that reads it, in stream order
+    if (st != FS2_OK || !r.two_launch) return st;
+    LayerNormArgs l;
+    l.x = a_in.ln_tmp; l.res = a_in.res; l.gamma = a_in.ln_g; l.beta = a_in.ln_b; l.y = a_in.C;
+    l.dot_w = a_in.dot_w; l.dot_b = a_in.dot_b; l.mask = a_in.mask; l.pred = a_in.pred;
+    l.M = a_in.M; l.H = a_in.N; l.eps = a_in.ln_eps;
+    return launch_layernorm(l, r.out_dtype, stream);
 }
 
 bool gemm_presplit_eligible(int N, int K) { return N >= 192 && K % 32 == 0; }

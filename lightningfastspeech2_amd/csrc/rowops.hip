@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LayerNormArgs p) {
 int launch_layernorm(const LayerNormArgs& a, int dtype, hipStream_t stream) {
     if (!is_storage_dtype(dtype) || (dtype == FS2_F16 && a.drop_p > 0.f)) return FS2_ERR_ARG;
     if (a.M <= 0) return FS2_OK;
-    if (a.H % 4 || a.H > 1024) return FS2_ERR_SHAPE;
+    if (!layernorm_rows_ok(a.H)) return FS2_ERR_SHAPE;
     const int nv = (a.H + 255) / 256;
     const dim3 grid((a.M + 3) / 4), block(256);
 #define FS2_LN(NVV)                                                                                     \

@@ -171,10 +171,11 @@ def test_split_k_choice_is_a_pure_shape_function(lib):
 
 def test_knob_setter_rejects_undefined_values(lib):
     """fs2_op_set_gemm_variant takes closed ranges - a typo in FS2_GEMM_KNOBS is an error, not a silent default; the
-    switches removed in r05 (measured-slower forms: 1211, 211, 1301 / 1302, 301, 311 and their "off" values) are undefined now."""
+    switches removed in r05 (measured-slower forms: 1211, 211, 1301 / 1302, 301, 311 and their "off" values) are undefined now, and
+    so is 2 (the 128x256 DMA-ring GEMM, moved to tools/probes/gemm_forms)."""
     FS2_OK, FS2_ERR_ARG = 0, lib.fs2_op_set_gemm_variant(-1)
     assert FS2_ERR_ARG != FS2_OK
-    for bad in (1300, 1301, 1302, 1319, 1322, 1399, 1403, 1205, 1210, 1211, 1299, 1102, 1002, 910, 802, 702, 502, 310, 311, 300, 301, 210, 211, 222, 203, 250, 251, 252, 253, 8, 100000):
+    for bad in (1300, 1301, 1302, 1319, 1322, 1399, 1403, 1205, 1210, 1211, 1299, 1102, 1002, 910, 802, 702, 502, 310, 311, 300, 301, 210, 211, 222, 203, 250, 251, 252, 253, 8, 2, 100000):
         assert lib.fs2_op_set_gemm_variant(bad) == FS2_ERR_ARG, bad
     # the defaults (each is a defined value) leave the process as it was
     for ok in (0, 202, 201, 221, 230, 231, 500, 701, 801, 909, 904, 1001, 1100, 1203, 1321, 1340, 1341, 1401, 1501):

@@ -41,7 +41,7 @@ def pack_conv_weight(w):
     return w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous()
 
 
-@pytest.fixture(params=[1, 2, 3, 4, 5, 6, 7], ids=["gemm128x128", "gemm128x256dma", "slab128", "slab192", "slab256", "slab32", "slab64"])
+@pytest.fixture(params=[1, 3, 4, 5, 6, 7], ids=["gemm128x128", "slab128", "slab192", "slab256", "slab32", "slab64"])
 def gemm_variant(request):
     knob(request.param)
     yield request.param
