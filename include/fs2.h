@@ -628,6 +628,18 @@ int fs2_op_bucket_embed_target(int32_t dtype, const void* x, const float* target
 int fs2_op_cwt_head(int32_t dtype, const void* out_conv, const float* spec, int32_t ld_spec, const uint8_t* mask,
                     const float* ms_w, const float* ms_b, float* mean_std, float* pred, float* spec_out, int32_t B, int32_t T,
                     int32_t F, void* hip_stream);
+/* Waveform finishing behind the generator, one launch (what Synthesiser.__call__ and int16_samples_to_float32 do on the host,
+ * third_party/hifigan/__init__.py:39-43, synthesis/generator.py:24-33): wav (B, T * hop) fp32 device, lengths (B) int32 device frame
+ * counts (clamped to [0, T]; never read by the host) or NULL for full rows.  offsets (B + 1) int64 device, written here:
+ * offsets[b] = hop * sum(lengths[< b]), offsets[B] = the packed total.  Utterance b's first lengths[b] * hop samples land contiguously
+ * at out + offsets[b]; pads are neither read nor written, out beyond offsets[B] is left alone.  kind FS2_WAV_I16: out is int16,
+ * q = (int16)(int32)trunc(x * 32768.0f) - toward zero, low 16 bits kept, so +1.0f gives -32768 as numpy's cast does on the host;
+ * FS2_WAV_F32: out is float32, (float)q / 32767.0f, IEEE division.  out_capacity (elements) < B * T * hop is FS2_ERR_ARG: the packed
+ * total is not known to the host at launch time.  Any hop; 16 B accesses where an utterance's rows are 16 B aligned. */
+#define FS2_WAV_I16 0
+#define FS2_WAV_F32 1
+int fs2_op_wav_pack(const float* wav, const int32_t* lengths, int32_t B, int32_t T, int32_t hop, int32_t kind, void* out,
+                    int64_t out_capacity, int64_t* offsets, void* hip_stream);
 
 /* ================================================================================================
  * HiFi-GAN generator: the step right after the mel forward.  Replaces

@@ -27,6 +27,7 @@ FS2_OK = 0
 FS2_ERR_HIP, FS2_ERR_SHAPE, FS2_ERR_ARG, FS2_ERR_WEIGHT, FS2_ERR_STATE, FS2_ERR_NOMEM = 1, 2, 3, 4, 5, 6
 FS2_F32, FS2_BF16, FS2_MIXED, FS2_MIXED_X3, FS2_F32_X3 = 0, 1, 2, 3, 4
 FS2_F16, FS2_MIXED_F16_X3 = 5, 6  # IEEE binary16 storage (operators) / the engine mode built on it (include/fs2.h)
+FS2_WAV_I16, FS2_WAV_F32 = 0, 1  # fs2_op_wav_pack's output kinds
 K_CONV_GEMM, K_GEMM, K_ATTENTION, K_ROWOPS, K_DEC_FFN_CONV1, K_DEC_ATTENTION, K_ENC_MHA, K_PREDICTOR = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -237,6 +238,7 @@ def load():
     lib.fs2_op_transpose_weight_batch.argtypes = [vp, i32, C.c_int64, vp]
     lib.fs2_op_bucket_embed_target.argtypes = [i32, vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fs2_op_cwt_head.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.fs2_op_wav_pack.argtypes = [vp, vp, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
     if lib.fs2_abi_version() != FS2_ABI_VERSION:
         raise Fs2LibraryError("libfs2_hip.so ABI version mismatch")
     _lib = lib

@@ -672,5 +672,10 @@ int fs2_op_cwt_head(int32_t dtype, const void* out_conv, const float* spec, int3
     CwtArgs a{out_conv, spec, ld_spec, mask, ms_w, ms_b, mean_std, pred, spec_out, B, T, F};
     return launch_cwt_head(a, dtype, (hipStream_t)stream);
 }
+int fs2_op_wav_pack(const float* wav, const int32_t* lengths, int32_t B, int32_t T, int32_t hop, int32_t kind, void* out,
+                    int64_t out_capacity, int64_t* offsets, void* stream) {
+    WavPackArgs a{wav, lengths, out, offsets, (long long)out_capacity, B, T, hop, kind};
+    return launch_wav_pack(a, (hipStream_t)stream);
+}
 
 }  // extern "C"

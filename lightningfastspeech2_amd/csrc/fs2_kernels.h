@@ -374,6 +374,17 @@ struct CwtArgs {
 };
 int launch_cwt_head(const CwtArgs& a, int dtype, hipStream_t stream);
 
+// waveform finishing behind the generator (wav_pack.hip): quantise + pack every utterance's own samples, offsets on the device
+struct WavPackArgs {
+    const float* wav;        // (B, T*hop) fp32
+    const int32_t* lengths;  // (B) frames, clamped to [0, T], or null: full rows
+    void* out;               // int16 / float32 (kind), `capacity` elements >= B*T*hop
+    int64_t* offsets;        // (B + 1) out: hop * sum(len[<b]), [B] = the total
+    long long capacity;
+    int B, T, hop, kind;     // kind: FS2_WAV_I16 / FS2_WAV_F32
+};
+int launch_wav_pack(const WavPackArgs& a, hipStream_t stream);
+
 struct EmbedArgs {
     const int64_t* phones;  // (B, L)
     const float* table;     // (n_phones, H), row 0 == 0

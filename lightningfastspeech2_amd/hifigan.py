@@ -154,6 +154,37 @@ def _bind(lib):
 
 
 _PRECISIONS = {"bf16": _lib.FS2_BF16, "fp32": _lib.FS2_F32, "fp16": _lib.FS2_F16}
+_WAV_KINDS = {"int16": (_lib.FS2_WAV_I16, torch.int16), "float32": (_lib.FS2_WAV_F32, torch.float32)}
+
+
+def wav_pack(wav: torch.Tensor, lengths: Optional[torch.Tensor], hop: int, dtype: str = "float32",
+             out: Optional[torch.Tensor] = None):
+    """fs2_op_wav_pack (include/fs2.h) on the current stream: wav (B, T*hop) fp32 device, lengths (B,) int32 device frame counts or
+    None -> ``(packed, offsets)`` as ``HifiGan.synthesize_packed`` documents them.  ``out``: a flat device buffer of ``dtype`` with
+    at least ``B*T*hop`` elements (the total is known on the device only); a smaller one is an error."""
+    if dtype not in _WAV_KINDS:
+        raise ValueError(f"dtype must be one of {sorted(_WAV_KINDS)}, got {dtype!r}")
+    kind, tdt = _WAV_KINDS[dtype]
+    if not wav.is_cuda or wav.dtype != torch.float32 or wav.dim() != 2 or not wav.is_contiguous():
+        raise ValueError("wav must be a contiguous (B, T*hop) float32 device tensor")
+    B, S = wav.shape
+    if hop <= 0 or S % hop:
+        raise ValueError(f"wav rows of {S} samples are no multiple of hop={hop}")
+    if lengths is not None and (not lengths.is_cuda or lengths.dtype != torch.int32 or lengths.numel() != B
+                                or not lengths.is_contiguous()):
+        raise ValueError("lengths must be a contiguous (B,) int32 device tensor")
+    if out is None:
+        out = torch.empty(B * S, dtype=tdt, device=wav.device)
+    elif not out.is_cuda or out.dtype != tdt or not out.is_contiguous() or out.device != wav.device:
+        raise ValueError(f"out must be a contiguous {dtype} tensor on {wav.device}")
+    offsets = torch.empty(B + 1, dtype=torch.int64, device=wav.device)
+    lib = _lib.load()
+    with torch.cuda.device(wav.device):
+        st = lib.fs2_op_wav_pack(C.c_void_p(wav.data_ptr()), None if lengths is None else C.c_void_p(lengths.data_ptr()), B, S // hop,
+                                 hop, kind, C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(offsets.data_ptr()),
+                                 C.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream))
+    _lib.check(st, None, f"op_wav_pack (capacity {out.numel()} for {B} x {S} samples)")
+    return out, offsets
 
 
 class HifiGan:
@@ -209,14 +240,12 @@ class HifiGan:
         except Exception:
             pass
 
-    def synthesize(self, mel: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """mel (B, T, n_mels) fp32 -> wav (B, T*hop) fp32 in [-1, 1]; with ``lengths`` (B,) every
-        utterance is synthesised from its first lengths[b] frames only (samples past it are 0)."""
+    def _generate(self, mel: torch.Tensor, lengths: Optional[torch.Tensor], zero_pads: bool):
         mel = mel.to(self.device, torch.float32).contiguous()
         B, T, M = mel.shape
         if M != self.cfg.num_mels:
             raise ValueError(f"mel has {M} bins, generator wants {self.cfg.num_mels}")
-        wav = torch.zeros(B, T * self.hop, dtype=torch.float32, device=self.device)
+        wav = (torch.zeros if zero_pads else torch.empty)(B, T * self.hop, dtype=torch.float32, device=self.device)
         ld = None if lengths is None else lengths.to(self.device, torch.int32).contiguous()
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):  # arena hipMalloc + launches must hit the engine's device
@@ -224,7 +253,23 @@ class HifiGan:
                                                     None if ld is None else C.c_void_p(ld.data_ptr()), B, T,
                                                     C.c_void_p(wav.data_ptr()), stream), "synthesize")
         self._last = (B, T)
-        return wav
+        return wav, ld
+
+    def synthesize(self, mel: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mel (B, T, n_mels) fp32 -> wav (B, T*hop) fp32 in [-1, 1]; with ``lengths`` (B,) every
+        utterance is synthesised from its first lengths[b] frames only (samples past it are 0)."""
+        return self._generate(mel, lengths, True)[0]
+
+    def synthesize_packed(self, mel: torch.Tensor, lengths: Optional[torch.Tensor] = None, dtype: str = "float32",
+                          out: Optional[torch.Tensor] = None):
+        """``synthesize`` finished on the device (fs2_op_wav_pack right behind the generator, same stream): returns
+        ``(packed, offsets)``, device tensors.  ``packed`` is flat, ``B*T*hop`` elements of capacity (or the caller's ``out``);
+        utterance b's ``lengths[b]*hop`` samples are ``packed[offsets[b]:offsets[b+1]]``, ``offsets`` (B+1,) int64 and
+        ``offsets[B]`` the total - what lies beyond it is not written.  dtype "int16": the samples ``Synthesiser.__call__`` returns,
+        ``(wav * 32768.0).astype("int16")`` bit for bit; "float32": those divided by 32767 as ``int16_samples_to_float32`` does.
+        The frame counts are never read by the host."""
+        wav, ld = self._generate(mel, lengths, False)  # the pads are neither read nor written behind it: no memset
+        return wav_pack(wav, ld, self.hop, dtype, out)
 
     def debug_stage(self, stage: int) -> torch.Tensor:
         B, T = self._last
@@ -255,5 +300,6 @@ class Synthesiser:
 
     def __call__(self, mel):
         mel = torch.as_tensor(mel, dtype=torch.float32)
-        wav = self.vocoder.synthesize(mel.unsqueeze(0))  # (1, T*hop)
-        return (wav.cpu().numpy() * 32768.0).astype("int16")
+        # the cast runs on the device (fs2_op_wav_pack: numpy's own truncation and wrap, +1.0 -> -32768): 2 bytes per sample cross PCIe
+        packed, _ = self.vocoder.synthesize_packed(mel.unsqueeze(0), None, "int16")
+        return packed.cpu().numpy().reshape(1, -1)  # (1, T*hop)

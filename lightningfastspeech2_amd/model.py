@@ -608,13 +608,17 @@ class ForwardPipeline:
             done.synchronize()  # a host tensor is read by the host: the copy has landed (what .cpu() waits for in the reference's caller)
         return out
 
-    def submit(self, batch):
-        """Queue one batch; returns the list (possibly empty) of finished-in-order results that fall out of the window."""
+    def _start(self, batch):
+        """Queue one batch on the next replica; the future of ``_run``'s ``(out, done event)`` (SpeechPipeline takes these one by one)."""
         k = self.n % len(self.models)
         self.n += 1
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(self.device))
-        self.pending.append(self.pools[k].submit(self._run, k, batch, ready))
+        return self.pools[k].submit(self._run, k, batch, ready)
+
+    def submit(self, batch):
+        """Queue one batch; returns the list (possibly empty) of finished-in-order results that fall out of the window."""
+        self.pending.append(self._start(batch))
         outs = []
         # never more than in_flight behind: the host waits for the oldest.  With host outputs a result is finished only when its copy has
         # landed, which runs BESIDE the forwards (its replica is already on its next batch): the window counts one more round, so that
