@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
+from types import SimpleNamespace
 
 import torch  # noqa: F401  (must precede the dlopen below)
 
@@ -18,72 +19,104 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS2_LIB") or os.path.join(_HERE, "libfs2_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fs2.h")
 
-FS2_ABI_VERSION = 4
-FS2_MAX_LAYERS = 32
-FS2_MAX_VARIANCES = 4
-FS2_MAX_PRIORS = 8
-FS2_NAME_LEN = 32
-FS2_OK = 0
-FS2_ERR_HIP, FS2_ERR_SHAPE, FS2_ERR_ARG, FS2_ERR_WEIGHT, FS2_ERR_STATE, FS2_ERR_NOMEM = 1, 2, 3, 4, 5, 6
-FS2_F32, FS2_BF16, FS2_MIXED, FS2_MIXED_X3, FS2_F32_X3 = 0, 1, 2, 3, 4
-FS2_F16, FS2_MIXED_F16_X3 = 5, 6  # IEEE binary16 storage (operators) / the engine mode built on it (include/fs2.h)
-FS2_WAV_I16, FS2_WAV_F32 = 0, 1  # fs2_op_wav_pack's output kinds
-K_CONV_GEMM, K_GEMM, K_ATTENTION, K_ROWOPS, K_DEC_FFN_CONV1, K_DEC_ATTENTION, K_ENC_MHA, K_PREDICTOR = 0, 1, 2, 3, 4, 5, 6, 7
+
+class Fs2LibraryError(RuntimeError):
+    pass
 
 
-class Fs2ConfigC(C.Structure):
-    _fields_ = [
-        ("abi_version", C.c_int32), ("dtype", C.c_int32), ("n_phones", C.c_int32), ("hidden", C.c_int32),
-        ("n_mels", C.c_int32), ("dvec_dim", C.c_int32), ("max_frames", C.c_int32), ("pe_len", C.c_int32),
-        ("enc_layers", C.c_int32), ("enc_heads", C.c_int32), ("enc_filter", C.c_int32), ("enc_depthwise", C.c_int32),
-        ("enc_kernels", C.c_int32 * FS2_MAX_LAYERS),
-        ("dec_layers", C.c_int32), ("dec_heads", C.c_int32), ("dec_filter", C.c_int32), ("dec_depthwise", C.c_int32),
-        ("dec_kernels", C.c_int32 * FS2_MAX_LAYERS),
-        ("n_variances", C.c_int32),
-        ("var_names", (C.c_char * FS2_NAME_LEN) * FS2_MAX_VARIANCES),
-        ("var_nlayers", C.c_int32 * FS2_MAX_VARIANCES),
-        ("var_kernel", C.c_int32 * FS2_MAX_VARIANCES),
-        ("var_mean", C.c_float * FS2_MAX_VARIANCES),
-        ("var_std", C.c_float * FS2_MAX_VARIANCES),
-        ("var_filter", C.c_int32), ("var_nbins", C.c_int32), ("var_depthwise", C.c_int32),
-        ("dur_nlayers", C.c_int32), ("dur_kernel", C.c_int32), ("dur_filter", C.c_int32), ("dur_depthwise", C.c_int32),
-        ("n_priors", C.c_int32),
-        ("prior_names", (C.c_char * FS2_NAME_LEN) * FS2_MAX_PRIORS),
-        ("var_cwt", C.c_int32 * FS2_MAX_VARIANCES),
-        ("var_level", C.c_int32 * FS2_MAX_VARIANCES),
-    ]
+# The closed type table: scalars passed or stored by value, and what a pointer may point to besides a type the header declares.
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32,
+            "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_POINTEES = set(_SCALARS) | {"void", "char", "int8_t", "int16_t", "uint16_t"}
 
 
-class Fs2OutputsC(C.Structure):
-    _fields_ = [
-        ("mel", C.c_void_p), ("duration_prediction", C.c_void_p), ("duration_rounded", C.c_void_p),
-        ("src_mask", C.c_void_p), ("tgt_mask", C.c_void_p), ("variances", C.c_void_p * FS2_MAX_VARIANCES),
-        ("var_spectrogram", C.c_void_p * FS2_MAX_VARIANCES), ("var_mean_std", C.c_void_p * FS2_MAX_VARIANCES),
-    ]
+def parse_header(src: str = HEADER_PATH):
+    """include/fs2.h (a path, or header text: anything with a newline in it) -> its constants {name: int}, structs {C name:
+    ctypes.Structure} and functions {name: (restype, argtypes)}.  The header is the single source of the binding, so whatever
+    this grammar cannot type is an Fs2LibraryError naming the declaration, never a default."""
+    if "\n" not in src:
+        with open(src) as f:
+            src = f.read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
+    loose = set(re.findall(r"\b(fs2_[a-z0-9_]+)\s*\(", text))  # every name that looks declared: none may end up unbound
+    consts = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(FS2_\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", text, re.M)}
+
+    def const(word, where):
+        if word not in consts and not re.fullmatch(r"-?(0[xX][0-9a-fA-F]+|\d+)", word):
+            raise Fs2LibraryError(f"include/fs2.h: {where}: {word!r} is neither an integer nor a constant declared above it")
+        return consts[word] if word in consts else int(word, 0)
+
+    def enum(m):
+        nxt = 0
+        for item in filter(None, (s.strip() for s in m.group(1).split(","))):
+            name, _, val = (s.strip() for s in item.partition("="))
+            consts[name] = nxt = const(val, name) if val else nxt
+            nxt += 1
+        return " "
+
+    def struct(m):
+        name, fields = m.group(1), []
+        for stmt in filter(None, (s.strip() for s in m.group(2).split(";"))):
+            head = re.fullmatch(r"(?:const\s+)?(\w+)\b(.*)", stmt, re.S)
+            base, rest = head.groups() if head else (None, "")
+            for decl in rest.split(","):
+                d = re.fullmatch(r"\s*(\**)\s*(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)", decl)
+                t = d and (C.c_void_p if d.group(1) else C.c_char if base == "char" else _SCALARS.get(base))
+                if not t:
+                    raise Fs2LibraryError(f"include/fs2.h: struct {name}: field {stmt!r} is outside the binding's type table")
+                for dim in reversed(re.findall(r"\w+", d.group(3))):
+                    t = t * const(dim, f"struct {name}.{d.group(2)}")
+                fields.append((d.group(2), t))
+        structs[name] = type(name, (C.Structure,), {"_fields_": fields})
+        return " "
+
+    def ctype(decl, fn, ret=False):
+        m = re.fullmatch(r"\s*(\w+)\s*((?:\*\s*)*)(\w+)?\s*", re.sub(r"\bconst\b", " ", decl))
+        base, stars = (m.group(1), m.group(2).count("*")) if m and not (ret and m.group(3)) else (None, 0)
+        if not stars:
+            t = _SCALARS.get(base)
+        elif base == "char" and stars == 1 and re.search(r"\bconst\b", decl):
+            t = C.c_char_p
+        elif base in structs and stars == 1:
+            t = C.POINTER(structs[base])
+        elif base in opaque and stars == 2:
+            t = C.POINTER(C.c_void_p)
+        else:
+            t = C.c_void_p if base in _POINTEES or base in opaque or base in structs else None
+        if t is None and not (ret and base == "void" and not stars):
+            raise Fs2LibraryError(f"include/fs2.h: {fn}: {' '.join(decl.split())!r} is outside the binding's type table")
+        return t
+
+    text = re.sub(r"#[ \t]*ifdef[ \t]+__cplusplus.*?#[ \t]*endif", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r"\benum\s+\w*\s*\{(.*?)\}\s*;", enum, text, flags=re.S)
+    structs, funcs = {}, {}
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", struct, text, flags=re.S)
+    opaque = set(re.findall(r"\btypedef\s+struct\s+(\w+)\s+\1\s*;", text))
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s+\1\s*;", " ", text)
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(fs2_[a-z0-9_]+)\s*\(([^()]*)\)", stmt, re.S)
+        if not m:
+            raise Fs2LibraryError(f"include/fs2.h: not a prototype the binding can parse: {' '.join(stmt.split())!r}")
+        ret, name, params = m.groups()
+        funcs[name] = (ctype(ret, name, ret=True), [] if params.strip() == "void" else [ctype(p, name) for p in params.split(",")])
+    if set(funcs) != loose:
+        raise Fs2LibraryError(f"include/fs2.h: declared in a form the binding does not parse: {sorted(loose - set(funcs))}")
+    return SimpleNamespace(constants=consts, structs=structs, functions=funcs)
 
 
-class BGemmDescC(C.Structure):
-    _fields_ = [
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-        ("sAm", C.c_int64), ("sAk", C.c_int64), ("sBk", C.c_int64), ("sBn", C.c_int64), ("ldc", C.c_int64),
-        ("nb1", C.c_int32), ("nb2", C.c_int32),
-        ("sA1", C.c_int64), ("sA2", C.c_int64), ("sB1", C.c_int64), ("sB2", C.c_int64), ("sC1", C.c_int64), ("sC2", C.c_int64),
-        ("alpha", C.c_float), ("beta", C.c_float), ("splitk", C.c_int32),
-        ("seg", C.c_int32), ("taps", C.c_int32), ("Kin", C.c_int32), ("a_shift0", C.c_int32), ("a_shift_step", C.c_int32),
-        ("sBtap", C.c_int64), ("b_shift0", C.c_int32), ("b_shift_step", C.c_int32), ("c_dtype", C.c_int32),
-    ]
+# The binding is generated: every constant of the header under its own name (FS2_K_<X> also as K_<X>), every struct as
+# <CamelCase of its C name>C, every function typed in load().  A new entry point needs nothing here.
+_HEADER = parse_header()
+globals().update(_HEADER.constants)
+globals().update({n[4:]: v for n, v in _HEADER.constants.items() if n.startswith("FS2_K_")})
+globals().update({n.title().replace("_", "") + "C": t for n, t in _HEADER.structs.items()})
+BGemmDescC = _HEADER.structs["fs2_bgemm_desc"]  # the name this struct had before the binding was generated
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
     """Every function include/fs2.h declares (used to verify the library exports the full ABI)."""
-    with open(header_path) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(fs2_[a-z0-9_]+)\s*\(", text)))
-
-
-class Fs2LibraryError(RuntimeError):
-    pass
+    return sorted((_HEADER if header_path == HEADER_PATH else parse_header(header_path)).functions)
 
 
 _lib = None
@@ -99,146 +132,12 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in declared_symbols() if not hasattr(lib, s)]
+    missing = [s for s in _HEADER.functions if not hasattr(lib, s)]
     if missing:
         raise Fs2LibraryError(f"{LIB_PATH} does not export: {missing}")
-    vp, i32, i64p = C.c_void_p, C.c_int32, C.POINTER(C.c_int64)
-    lib.fs2_abi_version.restype = C.c_int
-    lib.fs2_status_string.restype = C.c_char_p
-    lib.fs2_status_string.argtypes = [C.c_int]
-    lib.fs2_last_error.restype = C.c_char_p
-    lib.fs2_last_error.argtypes = [vp]
-    lib.fs2_create.argtypes = [C.POINTER(Fs2ConfigC), C.POINTER(vp)]
-    lib.fs2_destroy.argtypes = [vp]
-    lib.fs2_clone.argtypes = [vp, C.POINTER(vp)]
-    lib.fs2_load_weight.argtypes = [vp, C.c_char_p, vp, i64p, i32]
-    lib.fs2_finalize.argtypes = [vp]
-    lib.fs2_encode.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.POINTER(i32)]
-    lib.fs2_last_totals.argtypes = [vp, vp, vp, i32]
-    lib.fs2_set_priors.argtypes = [vp, vp, i32]
-    lib.fs2_decode.argtypes = [vp, C.POINTER(Fs2OutputsC), vp]
-    lib.fs2_set_debug.argtypes = [vp, i32]
-    lib.fs2_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    lib.fs2_set_workspace.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
-    lib.fs2_set_frames.argtypes = [vp, i32]
-    lib.fs2_set_zero_pad_mel.argtypes = [vp, i32]
-    lib.fs2_set_fused_predictor.argtypes = [vp, i32]
-    lib.fs2_set_graphs.argtypes = [vp, i32]
-    lib.fs2_graph_replays.restype = C.c_int64
-    lib.fs2_graph_replays.argtypes = [vp]
-    lib.fs2_set_deferred_layernorm.argtypes = [vp, i32]
-    lib.fs2_set_folded_layernorm.argtypes = [vp, i32]
-    lib.fs2_set_tuning.argtypes = [vp, i32]
-    lib.fs2_debug_copy.argtypes = [vp, C.c_char_p, vp, vp]
-    lib.fs2_force_buckets.argtypes = [vp, i32, vp]
-    lib.fs2_force_variance_targets.argtypes = [vp, i32, vp]
-    lib.fs2_profile_enable.argtypes = [vp, i32, i32]
-    lib.fs2_profile_reserve.argtypes = [vp, i32, i32]
-    lib.fs2_profile_read.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.fs2_op_convert.argtypes = [i32, i32, vp, vp, C.c_size_t, vp]
-    lib.fs2_host_f32_to_f16.argtypes = [vp, vp, C.c_size_t]
-    lib.fs2_op_predictor.argtypes = [i32, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.fs2_op_attn_out_ln.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_predictor_dw.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_masked_loss_ws_bytes.restype = C.c_size_t
-    lib.fs2_op_masked_loss_ws_bytes.argtypes = []
-    lib.fs2_op_masked_loss.argtypes = [vp, vp, i32, vp, C.c_int64, i32, i32, vp, vp, vp]
-    lib.fs2_op_soft_dtw.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, vp]
-    lib.fs2_op_soft_dtw_grad_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.fs2_op_soft_dtw_grad_scratch_bytes.restype = C.c_size_t
-    lib.fs2_op_soft_dtw_grad.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp, C.c_size_t, vp]
-    lib.fs2_op_set_gemm_variant.argtypes = [i32]
-    lib.fs2_op_set_vocoder_lds_limit.argtypes = [i32]
-    lib.fs2_op_set_vocoder_fused_resblock.argtypes = [i32]
-    lib.fs2_op_gemm.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.fs2_op_gemm_relu_dropout.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_gemm_add.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.fs2_op_gemm_rowscale.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_gemm_rowscale_dt.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_gemm_stats.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_rowstats_finish.argtypes = [vp, i32, i32, C.c_float, vp, i32, vp]
-    lib.fs2_op_gemm_head.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_head_finish.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, i32, vp]
-    lib.fs2_op_gemm_splitk_choice.argtypes = [i32, i32, i32, i32, i32, i32]
-    lib.fs2_op_gemm_route.restype = i32
-    lib.fs2_op_gemm_route.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.c_uint32, i32]
-    lib.fs2_op_gemm_splitk.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.fs2_op_gemm_gated.argtypes = [i32, vp, vp, vp, vp, C.c_float, vp, i32, i32, i32, i32, i32, vp]
-    lib.fs2_op_gemm_ln_tape.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.fs2_op_gemm_ln_tape_dropout.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_gemm_ln.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.fs2_op_attention_scratch_bytes.restype = C.c_size_t
-    lib.fs2_op_attention_scratch_bytes.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_size_t)]
-    lib.fs2_op_attention.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_attention_x3.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_gemm_split_out.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_layernorm.argtypes = [i32, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, i32, i32, vp]
-    lib.fs2_op_dwconv.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_durations.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    lib.fs2_op_regulate.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_bucket_embed.argtypes = [i32, vp, vp, vp, vp, i32, C.c_float, C.c_float, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_embed.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_spk_proj.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
-    f32, sz = C.c_float, C.c_size_t
-    lib.fs2_op_bgemm_ws_bytes.restype = sz
-    lib.fs2_op_bgemm_ws_bytes.argtypes = [C.POINTER(BGemmDescC)]
-    lib.fs2_op_bgemm_tn256.restype = i32
-    lib.fs2_op_bgemm_tn256.argtypes = [C.POINTER(BGemmDescC)]
-    lib.fs2_op_bgemm.argtypes = [i32, C.POINTER(BGemmDescC), vp, vp, vp, vp, vp, vp]
-    lib.fs2_op_attention_train.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_attention_bwd_supported.restype = i32
-    lib.fs2_op_attention_bwd_supported.argtypes = [i32, i32, i32]
-    lib.fs2_op_attention_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_bgemm_softmax_bwd.argtypes = [i32, C.POINTER(BGemmDescC), vp, vp, vp, vp, vp, f32, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_attn_delta.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_layernorm_bwd_parts.restype = i32
-    lib.fs2_op_layernorm_bwd_parts.argtypes = [i32]
-    lib.fs2_op_layernorm_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_layernorm_bwd_dropout.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_layernorm_bwd_masked.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_layernorm_head.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    lib.fs2_op_layernorm_dropout.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_col_sum_ws_bytes.restype = sz
-    lib.fs2_op_col_sum_ws_bytes.argtypes = [i32, i32, i32]
-    lib.fs2_op_col_sum.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
-    lib.fs2_op_col_sum2.argtypes = [i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
-    lib.fs2_op_col_sum_weighted.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
-    lib.fs2_op_softmax_fwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, f32, vp]
-    lib.fs2_op_softmax_bwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, f32, vp]
-    lib.fs2_op_ew.argtypes = [i32, i32, vp, vp, vp, sz, f32, f32, vp]
-    lib.fs2_op_scatter_rows_ws_bytes.restype = sz
-    lib.fs2_op_scatter_rows_ws_bytes.argtypes = [i32, i32, i32]
-    lib.fs2_op_scatter_rows.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_regulate_bwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_masked_loss_bwd.argtypes = [vp, vp, i32, vp, vp, vp, C.c_int64, i32, i32, f32, vp]
-    lib.fs2_op_bucket_embed_utt.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_dropout.argtypes = [i32, vp, vp, sz, f32, C.c_uint64, C.c_uint64, vp]
-    lib.fs2_op_row_dot.argtypes = [i32, vp, vp, vp, vp, vp, C.c_int64, i32, vp]
-    lib.fs2_op_cwt_head_train_ws_bytes.restype = sz
-    lib.fs2_op_cwt_head_train_ws_bytes.argtypes = [i32, i32, i32]
-    lib.fs2_op_cwt_head_train.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_cwt_head_bwd_ws_bytes.restype = sz
-    lib.fs2_op_cwt_head_bwd_ws_bytes.argtypes = [i32, i32, i32]
-    lib.fs2_op_cwt_head_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_dwconv_dgrad.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_dwconv_wgrad_parts.restype = i32
-    lib.fs2_op_dwconv_wgrad_parts.argtypes = [i32, i32]
-    lib.fs2_op_dwconv_wgrad.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.fs2_op_fold_conv2.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    lib.fs2_op_unfold_conv2.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    lib.fs2_op_transpose_weight.argtypes = [i32, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_sum_sq_ws_bytes.restype = sz
-    lib.fs2_op_sum_sq_ws_bytes.argtypes = [sz]
-    lib.fs2_op_sum_sq.argtypes = [vp, sz, vp, vp, vp]
-    lib.fs2_op_adamw.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, i32, vp, f32, f32, vp]
-    lib.fs2_op_adamw_shadow.argtypes = [vp, vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, i32, vp, f32, f32, vp]
-    lib.fs2_op_transpose_weight_tiles.restype = C.c_int64
-    lib.fs2_op_transpose_weight_tiles.argtypes = [i32, i32, i32]
-    lib.fs2_op_transpose_weight_batch.argtypes = [vp, i32, C.c_int64, vp]
-    lib.fs2_op_bucket_embed_target.argtypes = [i32, vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_cwt_head.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.fs2_op_wav_pack.argtypes = [vp, vp, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
+    for name, (restype, argtypes) in _HEADER.functions.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.fs2_abi_version() != FS2_ABI_VERSION:
         raise Fs2LibraryError("libfs2_hip.so ABI version mismatch")
     _lib = lib

@@ -115,11 +115,7 @@ def fold_weight_norm(sd: Dict[str, "torch.Tensor | np.ndarray"]) -> Dict[str, np
     return out
 
 
-class Fs2VocConfigC(C.Structure):
-    _fields_ = [("abi_version", C.c_int32), ("dtype", C.c_int32), ("n_mels", C.c_int32),
-                ("initial_channel", C.c_int32), ("n_stages", C.c_int32),
-                ("up_rates", C.c_int32 * 8), ("up_kernels", C.c_int32 * 8),
-                ("n_kernels", C.c_int32), ("rb_kernels", C.c_int32 * 4), ("rb_dilations", (C.c_int32 * 3) * 4)]
+Fs2VocConfigC = _lib.Fs2VocConfigC
 
 
 def _config_to_c(cfg: HifiGanConfig, dtype: int) -> Fs2VocConfigC:
@@ -136,21 +132,6 @@ def _config_to_c(cfg: HifiGanConfig, dtype: int) -> Fs2VocConfigC:
         for m, d in enumerate(ds):
             c.rb_dilations[j][m] = d
     return c
-
-
-def _bind(lib):
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.fs2_voc_create.argtypes = [C.POINTER(Fs2VocConfigC), C.POINTER(vp)]
-    lib.fs2_voc_destroy.argtypes = [vp]
-    lib.fs2_voc_last_error.restype = C.c_char_p
-    lib.fs2_voc_last_error.argtypes = [vp]
-    lib.fs2_voc_load_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), i32]
-    lib.fs2_voc_finalize.argtypes = [vp]
-    lib.fs2_voc_hop.argtypes = [vp]
-    lib.fs2_voc_hop.restype = i32
-    lib.fs2_voc_synthesize.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-    lib.fs2_voc_debug_copy.argtypes = [vp, i32, vp, vp]
-    return lib
 
 
 _PRECISIONS = {"bf16": _lib.FS2_BF16, "fp32": _lib.FS2_F32, "fp16": _lib.FS2_F16}
@@ -199,7 +180,7 @@ class HifiGan:
         self.cfg, self.device = cfg, torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the HiFi-GAN generator runs on an MI355X only (no CPU fallback)")
-        self.lib = _bind(_lib.load())
+        self.lib = _lib.load()
         if precision not in _PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
         self.precision = precision

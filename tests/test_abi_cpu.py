@@ -1,6 +1,9 @@
 """CPU-side checks of the C-ABI boundary (no compute calls: there is no GPU here)."""
 import ctypes as C
 import os
+import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -32,6 +35,120 @@ def test_struct_layout_matches_header():
     assert _lib.FS2_ABI_VERSION == 4 and _lib.FS2_MAX_PRIORS == 8  # v4: var_level (phone-level variances)
     assert C.sizeof(_lib.Fs2ConfigC) == 4 * (8 + 36 + 36 + 1) + 4 * 32 + 4 * (4 + 4) + 4 * (4 + 4) + 4 * 7 + 4 + 8 * 32 + 4 * 4 + 4 * 4  # ... var_cwt, var_level
     assert C.sizeof(_lib.Fs2OutputsC) == 8 * (5 + 3 * _lib.FS2_MAX_VARIANCES)
+
+
+def test_every_declaration_is_bound_with_explicit_types(lib):
+    """The binding is generated from include/fs2.h: the parsed set is the set a loose scan of the header finds, and every member
+    carries an explicit restype and one argtype per parameter."""
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    loose = {m.group(1): m.group(2) for m in re.finditer(r"\b(fs2_[a-z0-9_]+)\s*\(([^()]*)\)", text)}
+    parsed = _lib.parse_header(_lib.HEADER_PATH).functions
+    assert len(loose) >= 124 and sorted(loose) == _lib.declared_symbols() == sorted(parsed)
+    for name, params in loose.items():
+        fn = getattr(lib, name)
+        returns_void = re.search(r"\bvoid\s+%s\s*\(" % name, text) is not None
+        assert fn.restype is parsed[name][0] and (fn.restype is None) == returns_void, name
+        assert fn.argtypes is not None and len(fn.argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), name
+    assert lib.fs2_abi_version.restype is C.c_int and lib.fs2_abi_version.argtypes == []
+    assert lib.fs2_voc_destroy.restype is None
+
+
+def test_binding_types_where_a_slip_would_hurt(lib):
+    assert lib.fs2_op_masked_loss.argtypes[4] is C.c_int64 and lib.fs2_op_masked_loss_bwd.argtypes[6] is C.c_int64
+    assert lib.fs2_op_dropout.argtypes[3:7] == [C.c_size_t, C.c_float, C.c_uint64, C.c_uint64]
+    assert C.sizeof(C.c_int64) == C.sizeof(C.c_uint64) == C.sizeof(C.c_size_t) == 8
+    assert lib.fs2_op_wav_pack.argtypes[7] is C.c_int64
+    assert lib.fs2_graph_replays.restype is C.c_int64 and lib.fs2_op_transpose_weight_tiles.restype is C.c_int64
+    sizes = [n for n in _lib.declared_symbols() if n.endswith(("_ws_bytes", "_scratch_bytes"))]
+    assert len(sizes) >= 8 and "fs2_op_attention_scratch_bytes" in sizes
+    for n in sizes:
+        assert getattr(lib, n).restype is C.c_size_t, n
+    for n in ("fs2_status_string", "fs2_last_error", "fs2_voc_last_error"):
+        assert getattr(lib, n).restype is C.c_char_p, n
+    assert lib.fs2_create.argtypes[0] is C.POINTER(_lib.Fs2ConfigC) and lib.fs2_create.argtypes[1] is C.POINTER(C.c_void_p)
+    assert lib.fs2_op_bgemm.argtypes[1] is C.POINTER(_lib.BGemmDescC)
+    assert lib.fs2_voc_create.argtypes[0] is C.POINTER(_lib.Fs2VocConfigC)
+
+
+def test_generated_structs_match_the_compiler(tmp_path):
+    """sizeof / offsetof of every struct and field of include/fs2.h as the host C compiler lays them out (a stand-alone program)
+    against the generated ctypes.Structure classes."""
+    structs = _lib.parse_header(_lib.HEADER_PATH).structs
+    assert sorted(structs) == ["fs2_bgemm_desc", "fs2_config", "fs2_outputs", "fs2_voc_config"]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "fs2.h"', 'int main(void) {']
+    for name, st in structs.items():
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name}.{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, _ in st._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    cc = [shutil.which("cc")] if shutil.which("cc") else [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-x", "c"]
+    assert os.path.exists(cc[0]), "no host C compiler (cc or hipcc) to check the struct layout with"
+    exe = str(tmp_path / "layout")
+    subprocess.run(cc + [str(src), "-I", os.path.dirname(_lib.HEADER_PATH), "-o", exe], check=True, capture_output=True, text=True)
+    got = {}
+    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+        key, *nums = line.split()
+        got[key] = tuple(int(n) for n in nums)
+    want = {}
+    for name, st in structs.items():
+        want[name] = (C.sizeof(st),)
+        want.update({f"{name}.{f}": (getattr(st, f).offset, getattr(st, f).size) for f, _ in st._fields_})
+    assert len(want) == 4 + 81 and got == want
+    for py, c in (("Fs2ConfigC", "fs2_config"), ("Fs2OutputsC", "fs2_outputs"), ("BGemmDescC", "fs2_bgemm_desc"), ("Fs2VocConfigC", "fs2_voc_config")):
+        assert [(f, C.sizeof(t)) for f, t in getattr(_lib, py)._fields_] == [(f, C.sizeof(t)) for f, t in structs[c]._fields_]
+
+
+_MINI = """
+#define FS2_N 3
+enum fs2_e { FS2_A, FS2_B = 5, FS2_C, FS2_D = FS2_N };
+typedef struct fs2_s { int32_t a, b[FS2_N][2]; const float* p; char name[FS2_C]; } fs2_s;
+typedef struct fs2_h fs2_h;
+int fs2_ok(const fs2_s* s, fs2_h** out, const char* name, uint16_t* dst,
+           size_t n);
+void fs2_none(void);
+"""
+
+
+def test_parser_reads_header_text():
+    h = _lib.parse_header(_MINI)
+    assert h.constants == {"FS2_N": 3, "FS2_A": 0, "FS2_B": 5, "FS2_C": 6, "FS2_D": 3}
+    s = h.structs["fs2_s"]
+    assert [f for f, _ in s._fields_] == ["a", "b", "p", "name"] and C.sizeof(s) == 4 + 24 + 4 + 8 + 6 + 2
+    assert s.b.size == 24 and len(s().b) == 3 and len(s().b[0]) == 2 and s.p.size == 8 and s.name.size == 6
+    assert h.functions == {"fs2_ok": (C.c_int, [C.POINTER(s), C.POINTER(C.c_void_p), C.c_char_p, C.c_void_p, C.c_size_t]),
+                           "fs2_none": (None, [])}
+
+
+@pytest.mark.parametrize("decl,named", [
+    ("int fs2_bad(long n);", "fs2_bad"),                                   # a scalar outside the table
+    ("int fs2_bad(unsigned n);", "fs2_bad"),
+    ("long fs2_bad(void);", "fs2_bad"),
+    ("int fs2_bad(const fs2_undeclared* d);", "fs2_bad"),                  # a pointer to a type the header does not declare
+    ("int fs2_bad(const struct fs2_s* d);", "fs2_bad"),
+    ("int fs2_bad(const char* fmt, ...);", "fs2_bad"),                     # variadic
+    ("int fs2_bad(int32_t v[4]);", "fs2_bad"),                             # array parameter
+    ("int fs2_bad(void (*cb)(int32_t));", "fs2_bad"),                      # function pointer
+    ("int fs2_first(void)\nint fs2_bad(void);", "fs2_bad"),                # two prototypes run together (a lost semicolon)
+    ("FS2_API int fs2_bad(void);", "fs2_bad"),                             # an attribute macro in front
+    ("#define FS2_DECL(n) int n(void)\nFS2_DECL(fs2_hidden);\nint fs2_bad(void)\n;", "fs2_hidden"),  # declared through a macro
+    ("#define fs2_old(v) fs2_none()", "fs2_old"),                          # a name only the loose scan sees
+    ("typedef struct fs2_t { long x; } fs2_t;", "fs2_t"),                  # a field outside the table
+    ("typedef struct fs2_t { int32_t x[FS2_NOPE]; } fs2_t;", "FS2_NOPE"),  # an array bound that is no constant
+])
+def test_parser_refuses_what_it_cannot_type(decl, named):
+    with pytest.raises(_lib.Fs2LibraryError, match=named):
+        _lib.parse_header(_MINI + decl + "\n")
+
+
+def test_constants_are_the_abi_promises():
+    assert _lib.FS2_ABI_VERSION == 4
+    assert (_lib.FS2_OK, _lib.FS2_ERR_HIP, _lib.FS2_ERR_SHAPE, _lib.FS2_ERR_ARG, _lib.FS2_ERR_WEIGHT, _lib.FS2_ERR_STATE,
+            _lib.FS2_ERR_NOMEM) == (0, 1, 2, 3, 4, 5, 6)
+    assert (_lib.FS2_F32, _lib.FS2_BF16, _lib.FS2_MIXED, _lib.FS2_MIXED_X3, _lib.FS2_F32_X3, _lib.FS2_F16,
+            _lib.FS2_MIXED_F16_X3) == (0, 1, 2, 3, 4, 5, 6)
+    assert _lib.FS2_K_COUNT == 8 and _lib.K_PREDICTOR == _lib.FS2_K_PREDICTOR == 7 and _lib.K_CONV_GEMM == 0
+    assert (_lib.FS2_MAX_LAYERS, _lib.FS2_MAX_VARIANCES, _lib.FS2_NAME_LEN, _lib.FS2_WAV_I16, _lib.FS2_WAV_F32) == (32, 4, 32, 0, 1)
+    assert (_lib.FS2_VOC_MAX_STAGES, _lib.FS2_VOC_MAX_KERNELS) == (8, 4)
 
 
 def _create(lib, cfg, dtype=_lib.FS2_F32):

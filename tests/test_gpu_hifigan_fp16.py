@@ -226,8 +226,7 @@ def test_synthesiser_int16():
 
 @pytest.mark.parametrize("dtype", [_lib.FS2_MIXED, _lib.FS2_MIXED_X3, _lib.FS2_F32_X3, _lib.FS2_MIXED_F16_X3])
 def test_create_refuses_engine_modes(dtype):
-    from lightningfastspeech2_amd.hifigan import _bind
-    lib = _bind(_lib.load())
+    lib = _lib.load()
     h = C.c_void_p()
     assert lib.fs2_voc_create(C.byref(_config_to_c(HifiGanConfig(), dtype)), C.byref(h)) == _lib.FS2_ERR_ARG
     assert not h.value
