@@ -642,6 +642,57 @@ int fs2_op_wav_pack(const float* wav, const int32_t* lengths, int32_t B, int32_t
                     int64_t out_capacity, int64_t* offsets, void* hip_stream);
 
 /* ================================================================================================
+ * Analysis front end: waveform -> log-mel spectrogram and frame energy (csrc/analysis.hip, DESIGN.md "Analysis front end").
+ * What the reference computes per item on the CPU with torchaudio and librosa (TTSDataset.__getitem__ / _create_variances,
+ * litfass/dataset/datasets.py:183-199,369-380,600-618,630-648), for a padded batch, on the device.  For one utterance x of
+ * n >= 1 samples, s = 1 / max|x| when peak_normalize is set and the maximum is > 0 (else 1; the reference divides unconditionally
+ * and gives NaN on silence), x~ = s x:
+ *   mel     T = 1 + n / hop frames; frame t = x~[t hop - n_fft / 2 + k], k < n_fft, zero outside [0, n) (the padding sits at the
+ *           utterance's own ends); periodic Hann window of win_length, zero-padded symmetrically to n_fft as torch.stft does;
+ *           mel_t[m] = sum_f basis[m][f] |X_t[f]|; the output is log10 or ln of max(mel, clip), or (FS2_MEL_LINEAR) mel_t itself,
+ *           unclamped - the quantity an accuracy figure is taken on: a float32 logarithm rounds away what separates two DFTs
+ *   energy  Te = ceil(n / hop) frames; e[t] = sqrt(sum_{j = t hop}^{min(t hop + win_length, n) - 1} x~[j]^2 / win_length)
+ * Samples at or past lengths[b] are never read (they may hold NaN).  fp32 throughout: the DFT and the mel product are exact-fp32
+ * MFMA GEMMs against tables built in float64 at create; sums never depend on the batch, so results are bitwise batch-invariant.
+ * The configuration is passed as scalars (no struct): n_fft a power of two in [256, 2048], 1 <= win_length <= n_fft, hop dividing
+ * n_fft, 1 <= n_mels <= 128, clip > 0, log_kind FS2_MEL_LOG10 / FS2_MEL_LN / FS2_MEL_LINEAR; anything else is FS2_ERR_SHAPE (geometry) or
+ * FS2_ERR_ARG (abi_version, null / non-finite basis, clip, log_kind), decided before any device call.  mel_basis is HOST memory,
+ * (n_mels, n_fft / 2 + 1) row-major; only the bins between its first and last non-zero column become DFT columns.  As with
+ * fs2_create the handle is returned on failure too, for fs2_mel_last_error; destroy it.
+ * ================================================================================================ */
+#define FS2_MEL_LOG10 0
+#define FS2_MEL_LN 1
+#define FS2_MEL_LINEAR 2
+typedef struct fs2_mel fs2_mel;
+int fs2_mel_create(int32_t abi_version, int32_t n_fft, int32_t win_length, int32_t hop, int32_t n_mels, float clip, int32_t log_kind,
+                   const float* mel_basis_host, fs2_mel** out);
+int fs2_mel_destroy(fs2_mel* m);
+const char* fs2_mel_last_error(const fs2_mel* m);
+/* The next two are DIAGNOSTIC: they describe how this build runs a configuration (for tests that place lengths at the kernel's tile
+ * seams and for tools/bench_analysis.py's byte counts), nothing a caller of fs2_mel_run needs.
+ * frames one workgroup owns (64, or 32 / 16 where a 64-frame sample span does not fit LDS): where the kernel's tile seams lie */
+int32_t fs2_mel_tile_frames(const fs2_mel* m);
+/* the DFT columns kept: bins first_bin .. first_bin + n_columns - 1 (n_columns a multiple of 32, zero-weight beyond the basis' last bin) */
+int fs2_mel_used_bins(const fs2_mel* m, int32_t* first_bin, int32_t* n_columns);
+/* bytes of device workspace fs2_mel_run needs for a (B, S) batch (the per-utterance peaks) */
+size_t fs2_mel_ws_bytes(const fs2_mel* m, int32_t B, int32_t S);
+/* wav (B, S) fp32, lengths (B) int32 (clamped to [0, S]; 0 = no frames): device.  mel (B, T_max, n_mels) with T_max >= 1 + S / hop,
+ * energy (B, Te_max) with Te_max >= ceil(S / hop) or NULL (Te_max is ignored then), mel_frames (B) int32, energy_frames (B) int32 or
+ * NULL: device, all written in full - rows at or past an utterance's own count are zeros.  ws: fs2_mel_ws_bytes(m, B, S) device bytes
+ * (required in every mode).  Enqueues a memset and up to three launches on the caller's stream; allocates nothing, never synchronises.
+ * Every argument error (FS2_ERR_ARG; FS2_ERR_NOMEM for a short workspace; FS2_ERR_STATE for a handle whose create failed) is
+ * answered before the first launch. */
+int fs2_mel_run(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B, int32_t S, int32_t peak_normalize, float* mel,
+                int32_t T_max, float* energy, int32_t Te_max, int32_t* mel_frames, int32_t* energy_frames, void* ws, size_t ws_bytes,
+                void* hip_stream);
+/* Phone-level reduction of a frame-level variance (datasets.py:631-648): values (B, T) fp32, frames (B) int32 valid frames per row or
+ * NULL (= T), durations (B, L) int32 -> out (B, L): with pos_j = sum of the durations before j and the segment [pos_j, pos_j + d_j)
+ * clipped to the row's frames, out[j] = (mean of the segment - mean) / std, and (empty_value - mean) / std for an empty segment (the
+ * reference's 1e-7).  The segment is summed in order in fp32.  std must be finite and non-zero (1 and mean 0: no normalisation). */
+int fs2_op_segment_mean(const float* values, const int32_t* frames, const int32_t* durations, int32_t B, int32_t T, int32_t L,
+                        float empty_value, float mean, float std, float* out, void* hip_stream);
+
+/* ================================================================================================
  * HiFi-GAN generator: the step right after the mel forward.  Replaces
  * litfass.third_party.hifigan.Synthesiser.__call__ -> Generator.forward
  * (litfass/third_party/hifigan/__init__.py:19-43, models.py:112-165), resblock type "1".

@@ -2,7 +2,8 @@
 from .config import Fs2Config, preset  # noqa: F401
 from .weights import state_dict_spec, synth_state_dict, synth_inputs  # noqa: F401
 
-__all__ = ["Fs2Config", "preset", "state_dict_spec", "synth_state_dict", "synth_inputs", "FastSpeech2", "Trainer"]
+__all__ = ["Fs2Config", "preset", "state_dict_spec", "synth_state_dict", "synth_inputs", "FastSpeech2", "Trainer", "MelAnalyzer",
+           "slaney_mel_basis"]
 
 
 def __getattr__(name):
@@ -13,4 +14,7 @@ def __getattr__(name):
     if name == "Trainer":  # the training step: forward tape + backward + clip + AdamW / Noam
         from .training import Trainer
         return Trainer
+    if name in ("MelAnalyzer", "slaney_mel_basis"):  # the analysis front end: waveform -> log-mel + energy on the device
+        from . import analysis
+        return getattr(analysis, name)
     raise AttributeError(name)

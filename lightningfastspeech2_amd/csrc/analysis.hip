@@ -1,0 +1,505 @@
+// Analysis front end: waveform -> log-mel spectrogram and frame energy on the device (DESIGN.md "Analysis front end").
+// What TTSDataset.__getitem__ / _create_variances compute on the CPU with torchaudio and librosa (litfass/dataset/datasets.py:
+// 183-199, 369-380, 600-618, 630-648), restated from the semantics: a centred Hann STFT magnitude times a mel basis, clamp, log;
+// the RMS of un-centred windows; the phone-level mean of a frame-level variance.
+//
+// The heavy launch (mel_stft_kernel): one workgroup = one utterance x TM consecutive frames.
+//   1. The one contiguous sample span those frames cover, (TM - 1) * hop + n_fft samples, goes into LDS once, scaled by the peak
+//      factor, zero outside [0, n) - samples at or past the utterance's length are never read.  Layout: rows of `hop` samples with one
+//      pad word per row (address s + s / hop), so that the A operand "frame i, sample k" = span[i * hop + k], whose lane stride is hop
+//      words, lands on bank i + const instead of one bank (hop is a power of two: hop + 1 is odd, every stride is conflict-free).
+//   2. The real DFT is an fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate) of the frames against a table
+//      of window[k] * cos / window[k] * sin built in float64 at create and rounded once.  Only the bins the basis weighs are columns.
+//      A wave owns 32 bins at a time and holds their real and imaginary accumulators for all TM frames: the C layout gives a lane
+//      column j = lane & 31 in both, so |X| is formed in registers.
+//   3. |X| of the wave's 32 bins goes through a per-wave LDS stage (C layout -> A layout) into a second small MFMA GEMM against the
+//      basis columns of those bins; the mel accumulators stay in registers across the wave's bin tiles.
+//   4. The four waves' partial mels are added in wave order in LDS (the span is dead by then), clamped, logged and stored for rows
+//      t < T_b; rows past the utterance's count are written as zeros.
+// The order of every sum depends on (t mod TM, bin, mel) only, never on the batch: results are bitwise batch-invariant.
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+
+#include <new>
+#include <vector>
+
+#include "fs2_common.h"
+#include "fs2_kernels.h"
+
+namespace fs2 {
+
+static constexpr int MEL_THREADS = 256;
+static constexpr int MEL_WAVES = MEL_THREADS / 64;
+static constexpr int MEL_STAGE_LD = 33;                // |X| stage row: 32 bins + 1 pad word
+static constexpr size_t MEL_LDS_LIMIT = 160u * 1024u;  // gfx950: 160 KiB per CU
+
+struct MelKernelArgs {
+    const float* wav;         // (B, S)
+    const int32_t* lengths;   // (B)
+    const uint32_t* peak;     // (B) bits of max |x| (mel_peak_kernel) or null: scale 1
+    const float4* table;      // [bin tile][k chunk][re, im][64 lanes] x 4 k-values
+    const float4* btab;       // [bin tile][4 chunks of 8 bins][mel tile][64 lanes] x 4 bins
+    float* mel;               // (B, T_max, n_mels)
+    int32_t* mel_frames;      // (B)
+    int32_t* energy_frames;   // (B) or null
+    int S, T_max, n_fft, hop, lh /* log2 hop */, n_mels, nbt /* bin tiles */, tm /* frames per workgroup */, log_kind;
+    float clip;
+};
+
+__device__ __forceinline__ float mel_scale(const uint32_t* __restrict__ peak, int b) {
+    if (!peak) return 1.0f;
+    const float m = __uint_as_float(peak[b]);
+    return m > 0.0f ? 1.0f / m : 1.0f;  // an all-zero utterance keeps scale 1 (the reference divides and gives NaN)
+}
+
+__device__ __forceinline__ int mel_len(const int32_t* __restrict__ lengths, int b, int S) {
+    const int n = lengths[b];
+    return n < 0 ? 0 : (n > S ? S : n);
+}
+
+// max |x| over each utterance's own samples -> peak[b] (bits of a non-negative float order as unsigned; zero-filled by the caller)
+__global__ __launch_bounds__(256) void mel_peak_kernel(const float* __restrict__ wav, const int32_t* __restrict__ lengths,
+                                                      uint32_t* __restrict__ peak, int S) {
+    const int b = blockIdx.y, n = mel_len(lengths, b, S);
+    const float* __restrict__ x = wav + (size_t)b * S;
+    float m = 0.0f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+    for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
+    if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(peak + b, __float_as_uint(m));
+}
+
+// e[t] = sqrt(sum_{j = t hop}^{min(t hop + win, n) - 1} (s x[j])^2 / win), one wave per frame; rows t >= ceil(n / hop) are zeros
+__global__ __launch_bounds__(256) void mel_energy_kernel(const float* __restrict__ wav, const int32_t* __restrict__ lengths,
+                                                        const uint32_t* __restrict__ peak, float* __restrict__ energy, int S,
+                                                        int Te_max, int hop, int win) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= Te_max) return;
+    const int n = mel_len(lengths, b, S);
+    const int te = (int)(((long long)n + hop - 1) / hop);
+    float* __restrict__ dst = energy + (size_t)b * Te_max + t;
+    if (t >= te) {
+        if (lane == 0) *dst = 0.0f;
+        return;
+    }
+    const float s = mel_scale(peak, b);
+    const float* __restrict__ x = wav + (size_t)b * S;
+    const long long lo = (long long)t * hop;
+    const int cnt = (int)((lo + win < n ? lo + win : (long long)n) - lo);
+    float acc = 0.0f;
+    for (int j = lane; j < cnt; j += 64) {
+        const float v = x[lo + j] * s;
+        acc = fmaf(v, v, acc);
+    }
+    for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o);
+    if (lane == 0) *dst = sqrtf(acc / (float)win);
+}
+
+// Orders a wave's LDS stores before its own later LDS loads (other lanes' words included): a fence at wavefront scope and a
+// scheduling barrier for the compiler; the LDS serves one wave's instructions in order.
+__device__ __forceinline__ void mel_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// MT = 32-row MFMA tiles per workgroup (frames per workgroup tm <= 32 * MT), NT = 32-column mel tiles
+template <int MT, int NT>
+__global__ __launch_bounds__(MEL_THREADS) void mel_stft_kernel(const MelKernelArgs a) {
+    extern __shared__ float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, hi = lane >> 5;
+    const int b = blockIdx.y, t0 = blockIdx.x * a.tm;
+    const int n = mel_len(a.lengths, b, a.S);
+    const int Tb = n > 0 ? 1 + n / a.hop : 0;
+    if (blockIdx.x == 0 && tid == 0) {
+        a.mel_frames[b] = Tb;
+        if (a.energy_frames) a.energy_frames[b] = (int)(((long long)n + a.hop - 1) / a.hop);
+    }
+    const int rows = a.T_max - t0 < a.tm ? a.T_max - t0 : a.tm;  // rows of this tile that exist in the output
+    float* __restrict__ dst = a.mel + ((size_t)b * a.T_max + t0) * a.n_mels;
+    if (t0 >= Tb) {  // uniform: a tile past the utterance's last frame is zeros
+        for (int i = tid; i < rows * a.n_mels; i += MEL_THREADS) dst[i] = 0.0f;
+        return;
+    }
+    // ---- 1. the sample span -> LDS (row of hop samples + 1 pad word)
+    const int span = (a.tm - 1) * a.hop + a.n_fft;
+    const int span_words = span + (span >> a.lh) + 1;
+    const int out_ld = NT * 32 + 1;
+    const int out_words = MT * 32 * out_ld;  // the cross-wave sum reuses the span's words
+    float* __restrict__ stage = smem + (span_words > out_words ? span_words : out_words) + wave * (MT * 32 * MEL_STAGE_LD);
+    {
+        const float s = mel_scale(a.peak, b);
+        const float* __restrict__ x = a.wav + (size_t)b * a.S;
+        const long long g0 = (long long)t0 * a.hop - a.n_fft / 2;
+        for (int i = tid; i < span; i += MEL_THREADS) {
+            const long long g = g0 + i;
+            smem[i + (i >> a.lh)] = (g >= 0 && g < n) ? x[g] * s : 0.0f;
+        }
+    }
+    __syncthreads();
+    // ---- 2 + 3. bin tile by bin tile: DFT GEMM, |X|, mel GEMM
+    f32x16_t macc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) macc[mt][nt][r] = 0.0f;
+    const int KC = a.n_fft / 8;
+    int fbase[MT];  // first sample of this lane's frame in each row tile (clamped: rows past tm are computed and dropped)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int f = mt * 32 + li;
+        fbase[mt] = (f < a.tm ? f : a.tm - 1) * a.hop + hi * 4;
+    }
+    const int rounds = (a.nbt + MEL_WAVES - 1) / MEL_WAVES;
+    for (int rd = 0; rd < rounds; ++rd) {
+        const int bt = rd * MEL_WAVES + wave;
+        const bool live = bt < a.nbt;  // uniform per wave
+        if (live) {
+            f32x16_t re[MT], im[MT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) re[mt][r] = im[mt][r] = 0.0f;
+            const float4* __restrict__ tb = a.table + (size_t)bt * KC * 128 + lane;
+            // this lane's four samples of chunk kc in every row tile (four consecutive samples share a row when hop >= 4)
+            auto load_a = [&](int kc, float (&av)[MT][4]) {
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const int s0 = fbase[mt] + kc * 8;
+                    if (a.lh >= 2) {
+                        const float* p = smem + s0 + (s0 >> a.lh);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) av[mt][e] = p[e];
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) av[mt][e] = smem[s0 + e + ((s0 + e) >> a.lh)];
+                    }
+                }
+            };
+            float4 bre = tb[0], bim = tb[64];
+            float av[MT][4];
+            load_a(0, av);
+            for (int kc = 0; kc < KC; ++kc) {
+                // the next chunk's table columns and samples are in flight under this chunk's MFMAs
+                const int nx = kc + 1 < KC ? kc + 1 : kc;
+                const float4 nre = tb[(size_t)nx * 128], nim = tb[(size_t)nx * 128 + 64];
+                float nav[MT][4];
+                load_a(nx, nav);
+                const float br[4] = {bre.x, bre.y, bre.z, bre.w}, bi[4] = {bim.x, bim.y, bim.z, bim.w};
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        re[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt][e], br[e], re[mt], 0, 0, 0);
+                        im[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt][e], bi[e], im[mt], 0, 0, 0);
+                    }
+                bre = nre;
+                bim = nim;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) av[mt][e] = nav[mt][e];
+            }
+            // |X| in registers (one lane holds both parts of bin li), C layout -> this wave's stage
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    stage[row * MEL_STAGE_LD + li] = sqrtf(fmaf(re[mt][r], re[mt][r], im[mt][r] * im[mt][r]));
+                }
+        }
+        mel_wave_sync();  // the stage is private to the wave: its own writes before its own reads, no workgroup barrier
+        if (live) {
+            const float4* __restrict__ bb = a.btab + (size_t)bt * 4 * NT * 64 + lane;
+#pragma unroll
+            for (int kc = 0; kc < 4; ++kc) {
+                float av[MT][4];
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) av[mt][e] = stage[(mt * 32 + li) * MEL_STAGE_LD + kc * 8 + hi * 4 + e];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float4 w = bb[(kc * NT + nt) * 64];
+                    const float wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            macc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt][e], wv[e], macc[mt][nt], 0, 0, 0);
+                }
+            }
+        }
+        mel_wave_sync();  // the stage is rewritten in the next round
+    }
+    __syncthreads();  // every wave is done with the span: it is dead from here
+    // ---- 4. partial mels of the four waves, added in wave order
+    for (int w = 0; w < MEL_WAVES; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int idx = (mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi) * out_ld + nt * 32 + li;
+                        smem[idx] = w == 0 ? macc[mt][nt][r] : smem[idx] + macc[mt][nt][r];
+                    }
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < rows * a.n_mels; i += MEL_THREADS) {
+        const int t = i / a.n_mels, m = i - t * a.n_mels;
+        float v = 0.0f;
+        if (t0 + t < Tb) {
+            // the logarithm in fp64 and rounded once: a few million values per call, and an fp32 log's own error would be the
+            // largest term of the log-domain figure
+            v = smem[t * out_ld + m];
+            if (a.log_kind != FS2_MEL_LINEAR) {
+                const double x = (double)fmaxf(v, a.clip);
+                v = (float)(a.log_kind == FS2_MEL_LN ? log(x) : log10(x));
+            }
+        }
+        dst[i] = v;
+    }
+}
+
+// out[b][j] = (mean(values[b][pos_j : pos_j + d_j]) - mean) / std, segments clipped to the utterance's frames; empty -> empty_value
+// Thread j adds the j durations in front of its phone itself: O(L^2) loads per row, fine for phone counts (hundreds), no scan launch.
+__global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restrict__ values, const int32_t* __restrict__ frames,
+                                                          const int32_t* __restrict__ dur, float* __restrict__ out, int T, int L,
+                                                          float empty_value, float mean, float stdev) {
+    const int b = blockIdx.x;
+    int F = frames ? frames[b] : T;
+    F = F < 0 ? 0 : (F > T ? T : F);
+    const int32_t* __restrict__ d = dur + (size_t)b * L;
+    const float* __restrict__ v = values + (size_t)b * T;
+    for (int j = threadIdx.x; j < L; j += 256) {
+        long long pos = 0;
+        for (int i = 0; i < j; ++i) pos += d[i] > 0 ? d[i] : 0;
+        const long long end = pos + (d[j] > 0 ? d[j] : 0);
+        const int lo = (int)(pos < F ? pos : F), hi = (int)(end < F ? end : F);
+        float m = empty_value;
+        if (hi > lo) {
+            float s = 0.0f;
+            for (int t = lo; t < hi; ++t) s += v[t];
+            m = s / (float)(hi - lo);
+        }
+        out[(size_t)b * L + j] = (m - mean) / stdev;
+    }
+}
+
+typedef void (*MelKernelFn)(const MelKernelArgs);
+
+static MelKernelFn mel_kernel_for(int mt, int nt) {
+    switch (mt * 10 + nt) {
+        case 11: return mel_stft_kernel<1, 1>;
+        case 12: return mel_stft_kernel<1, 2>;
+        case 13: return mel_stft_kernel<1, 3>;
+        case 14: return mel_stft_kernel<1, 4>;
+        case 21: return mel_stft_kernel<2, 1>;
+        case 22: return mel_stft_kernel<2, 2>;
+        case 23: return mel_stft_kernel<2, 3>;
+        case 24: return mel_stft_kernel<2, 4>;
+    }
+    return nullptr;
+}
+
+// LDS bytes of a workgroup of tm frames: max(padded span, cross-wave sum) + the four |X| stages
+static size_t mel_lds_bytes(int n_fft, int hop, int tm, int nt) {
+    const int mt = tm > 32 ? 2 : 1;
+    const size_t span = (size_t)(tm - 1) * hop + n_fft;
+    const size_t span_words = span + span / hop + 1;
+    const size_t out_words = (size_t)mt * 32 * (nt * 32 + 1);
+    return ((span_words > out_words ? span_words : out_words) + (size_t)MEL_WAVES * mt * 32 * MEL_STAGE_LD) * sizeof(float);
+}
+
+}  // namespace fs2
+
+using namespace fs2;
+
+struct fs2_mel {
+    int n_fft = 0, win = 0, hop = 0, lh = 0, n_mels = 0, log_kind = 0;
+    float clip = 0.0f;
+    int f_lo = 0, nbt = 0, tm = 0, mt = 0, nt = 0;
+    size_t lds = 0;
+    MelKernelFn kernel = nullptr;
+    float4* table = nullptr;
+    float4* btab = nullptr;
+    bool ready = false;
+    char err[256] = {0};
+};
+
+namespace {
+
+int mfail(fs2_mel* m, int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(m->err, sizeof(m->err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+size_t mel_ws_need(int B) { return (((size_t)B * sizeof(uint32_t)) + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int fs2_mel_create(int32_t abi_version, int32_t n_fft, int32_t win_length, int32_t hop, int32_t n_mels, float clip, int32_t log_kind,
+                   const float* mel_basis_host, fs2_mel** out) {
+    if (!out) return FS2_ERR_ARG;
+    *out = nullptr;
+    fs2_mel* m = new (std::nothrow) fs2_mel();
+    if (!m) return FS2_ERR_NOMEM;
+    *out = m;  // returned even on failure so the caller can read fs2_mel_last_error, then destroy
+    if (abi_version != FS2_ABI_VERSION) return mfail(m, FS2_ERR_ARG, "abi_version %d, this library is %d", abi_version, FS2_ABI_VERSION);
+    if (!mel_basis_host) return mfail(m, FS2_ERR_ARG, "mel_basis is null");
+    if (log_kind != FS2_MEL_LOG10 && log_kind != FS2_MEL_LN && log_kind != FS2_MEL_LINEAR)
+        return mfail(m, FS2_ERR_ARG, "log_kind %d is none of FS2_MEL_LOG10, FS2_MEL_LN, FS2_MEL_LINEAR", log_kind);
+    if (!(clip > 0.0f) || !isfinite(clip)) return mfail(m, FS2_ERR_ARG, "clip must be a positive finite number");
+    if (n_fft < 256 || n_fft > 2048 || (n_fft & (n_fft - 1))) return mfail(m, FS2_ERR_SHAPE, "n_fft %d is not a power of two in [256, 2048]", n_fft);
+    if (win_length < 1 || win_length > n_fft) return mfail(m, FS2_ERR_SHAPE, "win_length %d is outside [1, n_fft = %d]", win_length, n_fft);
+    if (hop < 1 || n_fft % hop) return mfail(m, FS2_ERR_SHAPE, "hop %d does not divide n_fft %d", hop, n_fft);
+    if (n_mels < 1 || n_mels > 128) return mfail(m, FS2_ERR_SHAPE, "n_mels %d is outside [1, 128]", n_mels);
+    const int nbins = n_fft / 2 + 1;
+    int f_lo = nbins, f_hi = -1;
+    for (int i = 0; i < n_mels; ++i)
+        for (int f = 0; f < nbins; ++f) {
+            const float w = mel_basis_host[(size_t)i * nbins + f];
+            if (!isfinite(w)) return mfail(m, FS2_ERR_ARG, "mel_basis[%d][%d] is not finite", i, f);
+            if (w != 0.0f) {
+                f_lo = f < f_lo ? f : f_lo;
+                f_hi = f > f_hi ? f : f_hi;
+            }
+        }
+    if (f_hi < 0) f_lo = f_hi = 0;  // an all-zero basis: one (zero-weight) bin tile, every mel is log(clip)
+    m->n_fft = n_fft, m->win = win_length, m->hop = hop, m->n_mels = n_mels, m->log_kind = log_kind, m->clip = clip;
+    while ((1 << m->lh) < hop) ++m->lh;
+    m->f_lo = f_lo;
+    m->nbt = (f_hi - f_lo + 1 + 31) / 32;
+    m->nt = (n_mels + 31) / 32;
+    for (int tm = 64; tm >= 16 && !m->tm; tm >>= 1)  // the tallest tile whose span fits the CU's LDS
+        if (mel_lds_bytes(n_fft, hop, tm, m->nt) <= MEL_LDS_LIMIT) m->tm = tm;
+    if (!m->tm) return mfail(m, FS2_ERR_SHAPE, "n_fft %d with hop %d does not fit a 16-frame tile into LDS", n_fft, hop);
+    m->mt = m->tm > 32 ? 2 : 1;
+    m->lds = mel_lds_bytes(n_fft, hop, m->tm, m->nt);
+    m->kernel = mel_kernel_for(m->mt, m->nt);
+    // ---- the tables, in float64, rounded once
+    const int KC = n_fft / 8;
+    std::vector<double> win, cs, sn;
+    std::vector<float> table, btab;
+    try {
+        win.assign(n_fft, 0.0), cs.resize(n_fft), sn.resize(n_fft);
+        table.resize((size_t)m->nbt * KC * 2 * 64 * 4);
+        btab.resize((size_t)m->nbt * 4 * m->nt * 64 * 4);
+    } catch (const std::bad_alloc&) {  // no exception crosses the C ABI
+        return mfail(m, FS2_ERR_NOMEM, "out of host memory for the DFT table");
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    const int left = (n_fft - win_length) / 2;  // torch.stft centres a short window
+    for (int i = 0; i < win_length; ++i) win[left + i] = 0.5 - 0.5 * cos(two_pi * i / win_length);
+    for (int r = 0; r < n_fft; ++r) cs[r] = cos(two_pi * r / n_fft), sn[r] = sin(two_pi * r / n_fft);
+    for (int bt = 0; bt < m->nbt; ++bt)
+        for (int kc = 0; kc < KC; ++kc)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 4; ++e) {
+                    const int k = kc * 8 + (lane >> 5) * 4 + e, f = f_lo + bt * 32 + (lane & 31);
+                    const size_t at = ((((size_t)bt * KC + kc) * 2) * 64 + lane) * 4 + e;
+                    const int r = (int)(((long long)f * k) % n_fft);  // the phase reduced exactly
+                    table[at] = f <= f_hi ? (float)(win[k] * cs[r]) : 0.0f;
+                    table[at + 64 * 4] = f <= f_hi ? (float)(win[k] * sn[r]) : 0.0f;
+                }
+    for (int bt = 0; bt < m->nbt; ++bt)
+        for (int kc = 0; kc < 4; ++kc)
+            for (int nt = 0; nt < m->nt; ++nt)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 4; ++e) {
+                        const int f = f_lo + bt * 32 + kc * 8 + (lane >> 5) * 4 + e, mel = nt * 32 + (lane & 31);
+                        btab[(((((size_t)bt * 4 + kc) * m->nt + nt) * 64) + lane) * 4 + e] =
+                            (f <= f_hi && mel < n_mels) ? mel_basis_host[(size_t)mel * nbins + f] : 0.0f;
+                    }
+    if (hipMalloc((void**)&m->table, table.size() * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&m->btab, btab.size() * sizeof(float)) != hipSuccess)
+        return mfail(m, FS2_ERR_HIP, "hipMalloc of the DFT table failed: %s", hipGetErrorString(hipGetLastError()));
+    if (hipMemcpy(m->table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(m->btab, btab.data(), btab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return mfail(m, FS2_ERR_HIP, "upload of the DFT table failed: %s", hipGetErrorString(hipGetLastError()));
+    if (hipFuncSetAttribute((const void*)m->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds) != hipSuccess)
+        return mfail(m, FS2_ERR_HIP, "cannot reserve %zu bytes of LDS: %s", m->lds, hipGetErrorString(hipGetLastError()));
+    m->ready = true;
+    return FS2_OK;
+}
+
+int fs2_mel_destroy(fs2_mel* m) {
+    if (!m) return FS2_ERR_ARG;
+    if (m->table) (void)hipFree(m->table);
+    if (m->btab) (void)hipFree(m->btab);
+    delete m;
+    return FS2_OK;
+}
+
+const char* fs2_mel_last_error(const fs2_mel* m) { return m ? m->err : "null mel handle"; }
+
+int32_t fs2_mel_tile_frames(const fs2_mel* m) { return m ? m->tm : 0; }
+
+int fs2_mel_used_bins(const fs2_mel* m, int32_t* first_bin, int32_t* n_columns) {
+    if (!m || !first_bin || !n_columns) return FS2_ERR_ARG;
+    *first_bin = m->f_lo;
+    *n_columns = m->nbt * 32;
+    return FS2_OK;
+}
+
+size_t fs2_mel_ws_bytes(const fs2_mel* m, int32_t B, int32_t S) {
+    (void)S;
+    return m && B > 0 ? mel_ws_need(B) : 0;
+}
+
+int fs2_mel_run(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B, int32_t S, int32_t peak_normalize, float* mel,
+                int32_t T_max, float* energy, int32_t Te_max, int32_t* mel_frames, int32_t* energy_frames, void* ws, size_t ws_bytes,
+                void* hip_stream) {
+    if (!m) return FS2_ERR_ARG;
+    if (!m->ready) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");
+    if (!wav || !lengths || !mel || !mel_frames) return mfail(m, FS2_ERR_ARG, "wav, lengths, mel and mel_frames must not be null");
+    if (B < 1 || S < 1) return mfail(m, FS2_ERR_ARG, "B = %d, S = %d: both must be at least 1", B, S);
+    if (B > 65535) return mfail(m, FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
+    if (T_max < 1 + S / m->hop) return mfail(m, FS2_ERR_ARG, "T_max = %d < 1 + S / hop = %d", T_max, 1 + S / m->hop);
+    const int te_need = (int)(((long long)S + m->hop - 1) / m->hop);
+    if (energy && Te_max < te_need) return mfail(m, FS2_ERR_ARG, "Te_max = %d < ceil(S / hop) = %d", Te_max, te_need);
+    if ((long long)T_max * m->n_mels > 0x7fffffffLL) return mfail(m, FS2_ERR_SHAPE, "T_max * n_mels exceeds 2^31");
+    if (!ws || ws_bytes < mel_ws_need(B))  // asked for in every mode: a caller sizes one buffer, whatever it switches later
+        return mfail(m, FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, mel_ws_need(B));
+    hipStream_t st = (hipStream_t)hip_stream;
+    uint32_t* peak = nullptr;
+    if (peak_normalize) {
+        peak = (uint32_t*)ws;
+        if (hipMemsetAsync(peak, 0, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return mfail(m, FS2_ERR_HIP, "hipMemsetAsync failed");
+        int chunks = (S + 4095) / 4096;
+        chunks = chunks > 64 ? 64 : chunks;
+        hipLaunchKernelGGL(mel_peak_kernel, dim3(chunks, B), dim3(256), 0, st, wav, lengths, peak, S);
+    }
+    MelKernelArgs a{wav, lengths, peak, m->table, m->btab, mel, mel_frames, energy_frames, S, T_max, m->n_fft, m->hop, m->lh,
+                    m->n_mels, m->nbt, m->tm, m->log_kind, m->clip};
+    void* kargs[] = {&a};
+    if (hipLaunchKernel((const void*)m->kernel, dim3((T_max + m->tm - 1) / m->tm, B), dim3(MEL_THREADS), kargs, m->lds, st) != hipSuccess)
+        return mfail(m, FS2_ERR_HIP, "launch of the STFT kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    if (energy) hipLaunchKernelGGL(mel_energy_kernel, dim3((Te_max + 3) / 4, B), dim3(256), 0, st, wav, lengths, peak, energy, S, Te_max, m->hop, m->win);
+    if (hipGetLastError() != hipSuccess) return mfail(m, FS2_ERR_HIP, "a launch of fs2_mel_run failed");
+    return FS2_OK;
+}
+
+int fs2_op_segment_mean(const float* values, const int32_t* frames, const int32_t* durations, int32_t B, int32_t T, int32_t L,
+                        float empty_value, float mean, float stdev, float* out, void* hip_stream) {
+    if (!values || !durations || !out || B < 1 || T < 1 || L < 1) return FS2_ERR_ARG;
+    if (!(stdev != 0.0f) || !isfinite(stdev) || !isfinite(mean)) return FS2_ERR_ARG;
+    hipLaunchKernelGGL(segment_mean_kernel, dim3(B), dim3(256), 0, (hipStream_t)hip_stream, values, frames, durations, out, T, L,
+                       empty_value, mean, stdev);
+    return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
+}
+
+}  // extern "C"

@@ -1,0 +1,129 @@
+#!/usr/bin/env python
+"""Benchmark of the analysis front end (waveform -> log-mel + energy, fs2_mel_run) at the mel forward's own output size:
+B utterances x S samples of noise resident in HBM -> (B, 1 + S / hop, n_mels) log-mel and (B, S / hop) energy.
+
+    python tools/bench_analysis.py [--batch 32 --samples 393216 --steps 20 --loops 5 --warmup 3 --no-cpu]
+
+One process, the fastest of --loops timed loops (device events around --steps calls) each:
+  * the whole operator (peak + STFT / mel + energy launches) and the STFT / mel launch alone;
+  * its share of the fp32 MFMA rate MI355X_MICROARCH gives as measured (155 TFLOP/s), from the algorithmic FLOPs of the trimmed
+    DFT and the mel product, and which limit it is on: the larger of FLOPs / 155 TF, HBM bytes / 6.29 TB/s and the DFT table
+    every workgroup streams from L2 / 17 TB/s;
+  * next to it the CPU recipe it replaces on this box: torch.stft + matmul + clamp + log10 in float32 on 16 threads.
+Prints ONE JSON line.  No GPU, no figure: the tool fails without a device.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+from lightningfastspeech2_amd import _lib
+from lightningfastspeech2_amd.analysis import MelAnalyzer
+
+MFMA_F32, HBM, L2 = 155e12, 6.29e12, 17e12  # measured rates (fp32 MFMA, float4 copy, rows shared by every workgroup from L2)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def cpu_recipe(x, basis, n_fft, hop, win, clip):
+    mag = torch.stft(x, n_fft, hop_length=hop, win_length=win, window=torch.hann_window(win), center=True, pad_mode="constant",
+                     return_complex=True).abs()
+    return torch.log10(torch.clamp(torch.matmul(basis, mag), min=clip))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--samples", type=int, default=393216)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--loops", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--no-cpu", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_analysis needs an MI355X: no figure without a device")
+    dev = torch.device("cuda:0")
+    an = MelAnalyzer(device=dev)
+    lib, B, S, hop, nm = an.lib, a.batch, a.samples, an.hop_length, an.n_mels
+    T, Te = 1 + S // hop, -(-S // hop)
+    wav = (0.3 * torch.randn(B, S, generator=torch.Generator().manual_seed(0))).to(dev)
+    lengths = torch.full((B,), S, dtype=torch.int32, device=dev)
+    mel = torch.empty(B, T, nm, device=dev)
+    energy = torch.empty(B, Te, device=dev)
+    mf, ef = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    need = lib.fs2_mel_ws_bytes(an.handle, B, S)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run(full):
+        st = lib.fs2_mel_run(an.handle, _p(wav), _p(lengths), B, S, int(full), _p(mel), T, _p(energy) if full else None, Te, _p(mf),
+                             _p(ef), _p(ws), need, stream)
+        assert st == 0, lib.fs2_mel_last_error(an.handle)
+
+    def fastest(full):
+        for _ in range(a.warmup):
+            run(full)
+        ms = []
+        for _ in range(a.loops):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                run(full)
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1) / a.steps)
+        return min(ms), ms
+
+    stft_ms, stft_loops = fastest(False)
+    full_ms, full_loops = fastest(True)
+    assert bool(torch.isfinite(mel).all()) and mf.tolist() == [T] * B
+    used = int(np.count_nonzero(an.mel_basis.any(axis=0)))
+    first, cols = C.c_int32(), C.c_int32()
+    assert lib.fs2_mel_used_bins(an.handle, C.byref(first), C.byref(cols)) == 0
+    frames = B * T
+    flops = frames * (2.0 * an.n_fft * 2 * used + 2.0 * used * nm)
+    hbm_bytes = 4.0 * (B * S + frames * nm)
+    tiles = B * -(-T // an.tile_frames)
+    l2_bytes = tiles * 4.0 * an.n_fft * 2 * cols.value
+    bounds = {"fp32_mfma": flops / MFMA_F32 * 1e3, "hbm": hbm_bytes / HBM * 1e3, "l2_table": l2_bytes / L2 * 1e3}
+    limit = max(bounds, key=bounds.get)
+    out = {"tool": "bench_analysis", "batch": B, "samples": S, "frames": frames, "n_fft": an.n_fft, "hop": hop, "n_mels": nm,
+           "tile_frames": an.tile_frames, "dft_bins": used, "dft_columns": 2 * cols.value,
+           "operator_ms": round(full_ms, 4), "operator_loops_ms": [round(x, 4) for x in full_loops],
+           "stft_mel_ms": round(stft_ms, 4), "stft_mel_loops_ms": [round(x, 4) for x in stft_loops],
+           "gflop": round(flops / 1e9, 2), "stft_mel_tflops": round(flops / stft_ms / 1e9, 2),
+           "share_of_fp32_mfma_155tf": round(bounds["fp32_mfma"] / stft_ms, 4),
+           "bounds_ms": {k: round(v, 4) for k, v in bounds.items()}, "limit": limit,
+           "share_of_limit": round(bounds[limit] / stft_ms, 4),
+           "audio_seconds_per_second": round(B * S / an.sampling_rate / (full_ms / 1e3), 1),
+           "steps": a.steps, "loops": a.loops, "warmup": a.warmup, "device": torch.cuda.get_device_name(0)}
+    if not a.no_cpu:
+        torch.set_num_threads(a.cpu_threads)
+        x, basis = wav.cpu(), torch.from_numpy(an.mel_basis)
+        cpu_recipe(x[:2], basis, an.n_fft, hop, an.win_length, an.clip)
+        cpu = []
+        for _ in range(a.loops):
+            t0 = time.perf_counter()
+            ref = cpu_recipe(x, basis, an.n_fft, hop, an.win_length, an.clip)
+            cpu.append((time.perf_counter() - t0) * 1e3)
+        run(False)
+        torch.cuda.synchronize()
+        out.update({"cpu_recipe_ms": round(min(cpu), 2), "cpu_threads": a.cpu_threads, "cpu_loops_ms": [round(v, 2) for v in cpu],
+                    "speedup_vs_cpu_recipe": round(min(cpu) / full_ms, 1),
+                    "max_abs_log10_vs_cpu_recipe": float((mel.cpu() - ref.permute(0, 2, 1)).abs().max())})
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
