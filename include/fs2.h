@@ -693,6 +693,67 @@ int fs2_op_segment_mean(const float* values, const int32_t* frames, const int32_
                         float empty_value, float mean, float std, float* out, void* hip_stream);
 
 /* ================================================================================================
+ * Training targets from audio: frame SNR, contour finishing, priors (csrc/analysis.hip, DESIGN.md "Analysis front end").  What
+ * TTSDataset._create_variances (litfass/dataset/datasets.py:562-650) and __getitem__ (:398-463) do to the "snr" and "pitch"
+ * variances and for the priors, on the device.  F0 tracking is NOT here (the reference uses pyworld): a caller supplies the raw F0
+ * contour in frames, 0 where unvoiced.  CWT decomposition, the "log" transform and "srmr" are not here either.
+ *
+ * 1. Windowed WADA (SNR.windowed_wada(window = win_length, stride = hop / win_length, use_samples = True), litfass/dataset/snr.py:
+ *    194-271, 328-371).  Per utterance x of n >= 1 samples, s and x~ = s x (an fp32 product) as in fs2_mel_run; Te = ceil(n / hop)
+ *    windows, window t = [t hop, min(t hop + win_length, n)) - the framing of the energy output.  win_length % hop == 0 is required
+ *    (FS2_ERR_SHAPE from fs2_mel_snr otherwise).  The statistic of a window:
+ *        a_j = max(|x~_j|, 1e-20),  v1 = max(1e-20, mean a),  v2 = mean ln a,  v3 = ln v1 - v2
+ *    (the terms |x~_j| and ln a_j in fp32 - the accurate logarithm -, every sum, the two means and v3 in fp64; the means divide by the
+ *    samples the window has).  The table g[0 .. K - 1] (double) belongs to the dB values db_lo + i; the reference has K = 121,
+ *    db_lo = -20.  i* = max{ i : g[i] < v3 } - NOT a binary search: the reference's table is not monotone (index 2 -> 3), so the
+ *    largest index that satisfies the predicate is the definition.  No i*, or i* = K - 1: the window is NaN.  Otherwise
+ *        out = i* + (v3 - g[i*]) / (g[i* + 1] - g[i*])
+ *    in double, rounded once to fp32, and NaN unless out < K - 1.  That is the reference's snr + 20 for -20 < snr < 100 (out = snr -
+ *    db_lo: db_lo names the table's first entry and does not enter the arithmetic).  DELIBERATE DIFFERENCE: the reference then
+ *    splits the window's energy with that estimate and returns 10 log10(dSigEng / dNoiseEng), which is the estimate again to
+ *    float64 rounding; that round trip is not reproduced.  A window is also NaN when every |x~_j| is zero, or when the sum of
+ *    x~_j^2 is zero in fp32.  Rows t >= Te are zeros; samples at or past lengths[b] are never read; no sum's order depends on the
+ *    batch, on S or on a row's alignment: results are bitwise batch-invariant, as the mel is.
+ *    THE TABLE IS AN ARGUMENT, the project ships none: it is Kim & Stern's WADA table for gamma shape 0.4, which a litfass
+ *    installation has as litfass/data/wada_values.npy.  fs2_mel_set_snr_table uploads it (HOST memory; it allocates, waits for the
+ *    device when it replaces an earlier table, and may be called again): table non-null, n in [2, 512], every entry and db_lo finite,
+ *    else FS2_ERR_ARG; FS2_ERR_STATE on a handle whose create failed.
+ *    fs2_mel_snr: wav, lengths, B, S, peak_normalize, ws as fs2_mel_run (ws: fs2_mel_ws_bytes; the peaks are computed again, nothing
+ *    is shared with an earlier fs2_mel_run); snr (B, Te_max) with Te_max >= ceil(S / hop), snr_frames (B) int32 or NULL: device, written
+ *    in full.  Enqueues a memset and two launches on the caller's stream; allocates nothing, never synchronises.  FS2_ERR_STATE
+ *    before a table is set; every argument error is answered before the first launch.
+ *
+ * 2. Contour finishing (datasets.py:576-598, _interpolate :831-837), for the SNR and the pitch alike.  values (B, T) fp32 the raw
+ *    frame contour, frames (B) int32 valid frames per row or NULL (= T), durations (B, L) int32 (negatives count as 0, as in
+ *    fs2_op_segment_mean), phone_silent (B, L) int32 (non-zero = a silent phone) or NULL -> out (B, T) fp32, frames_out (B) int32,
+ *    prior (B) fp32 or NULL.  Per row: F = min(sum of durations, frames[b]) = frames_out[b]; frame t < F belongs to the phone whose
+ *    duration segment contains it.  A frame is MISSING if its value is NaN, or zero_is_missing is set and it is 0, or its phone is
+ *    silent.  If every frame of [0, F) is missing, y[t] = all_missing_value (the reference: 1e-7 for pitch, 0 for SNR); otherwise
+ *    y[t] is the value where present and np.interp elsewhere: v[l] + (t - l) (v[r] - v[l]) / (r - l) between the nearest present
+ *    frames l < t < r, in double and rounded once; the first present value before it, the last present value after it.
+ *    prior[b] = the mean of y[t] over the frames of non-silent phones, before normalisation (fp64 sums of consecutive frames in frame
+ *    order, added in order), NaN if there are none.  out[t] = (y[t] - mean) / std for t < F (in double, rounded once), zeros for
+ *    t >= F.  std must be finite and non-zero (FS2_ERR_ARG).  LIMITS: T <= 4096 frames, L <= 2048 phones (one workgroup holds an
+ *    utterance in LDS; the reference caps an utterance at 2756 frames), FS2_ERR_SHAPE beyond.
+ *    Phone level: finish with mean 0, std 1, then fs2_op_segment_mean with the stats.  DELIBERATE DIFFERENCE: the reference writes
+ *    the phone means in place into the frame array it is still reading (datasets.py:633-640), so after leading zero-duration phones
+ *    a later phone can read an entry that already holds a phone mean; here every phone averages the original frames.  The two agree
+ *    whenever sum_{i < j} d_i >= j for every j.
+ *
+ * 3. fs2_op_masked_row_mean: values (B, N) fp32, counts (B) int32 or NULL (= N; clamped to [0, N]), skip (B, N) int32 or NULL ->
+ *    out (B): the mean over j < counts[b] with skip[b][j] == 0 (fp64 sums of consecutive entries in order, added in order), NaN for
+ *    an empty set.  The phone-level priors (over the phone means) and the duration prior (durations as fp32), datasets.py:412-435.
+ * ================================================================================================ */
+int fs2_mel_set_snr_table(fs2_mel* m, const double* table_host, int32_t n, float db_lo);
+int fs2_mel_snr(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B, int32_t S, int32_t peak_normalize, float* snr,
+                int32_t Te_max, int32_t* snr_frames, void* ws, size_t ws_bytes, void* hip_stream);
+int fs2_op_contour_finish(const float* values, const int32_t* frames, const int32_t* durations, const int32_t* phone_silent, int32_t B,
+                          int32_t T, int32_t L, int32_t zero_is_missing, float all_missing_value, float mean, float std, float* out,
+                          int32_t* frames_out, float* prior, void* hip_stream);
+int fs2_op_masked_row_mean(const float* values, const int32_t* counts, const int32_t* skip, int32_t B, int32_t N, float* out,
+                           void* hip_stream);
+
+/* ================================================================================================
  * HiFi-GAN generator: the step right after the mel forward.  Replaces
  * litfass.third_party.hifigan.Synthesiser.__call__ -> Generator.forward
  * (litfass/third_party/hifigan/__init__.py:19-43, models.py:112-165), resblock type "1".

@@ -8,6 +8,19 @@ stated in include/fs2.h and DESIGN.md; there is no CPU fallback.
 
 One deliberate difference: the reference divides by the peak unconditionally and gives NaN on an all-zero utterance; here such
 an utterance keeps scale 1 (its mel is ``log(clip)``, its energy 0).
+
+Training targets (include/fs2.h "Training targets from audio"): ``MelAnalyzer.snr`` is the reference's windowed WADA estimate
+(``SNR.windowed_wada``, litfass/dataset/snr.py), :func:`finish_contour` what ``_create_variances`` does to the SNR and pitch
+contours (silent phones and unvoiced frames become missing, gaps are filled by ``np.interp``, datasets.py:576-598), and
+``MelAnalyzer.items`` the items of ``TTSDataset.__getitem__`` with their priors (:412-435).  Three things to know:
+
+* the WADA table is an argument - the project ships none.  It is Kim & Stern's table for gamma shape 0.4; a litfass installation has
+  it as ``litfass/data/wada_values.npy``: ``MelAnalyzer(wada_table=np.load(...))``.
+* F0 tracking is not here (the reference uses pyworld's dio + stonemask): ``items(pitch=...)`` takes the raw F0 contour per
+  utterance, one value per frame, 0 where unvoiced, as pyworld returns it.
+* two deliberate differences: the reference's closing energy split ``10 log10(dSigEng / dNoiseEng)`` (the estimate again, to
+  float64 rounding) is not reproduced, and phone-level means average the original frames (the reference writes them in place
+  while reading, which differs only after leading zero-duration phones).
 """
 from __future__ import annotations
 
@@ -85,6 +98,72 @@ def segment_mean(values: torch.Tensor, durations: torch.Tensor, frames: Optional
     return out
 
 
+def _int_mat(rows, B, width, what):
+    """a list of per-utterance integer arrays, or a (B, width) array / tensor -> a padded (B, width) int32 host array"""
+    if isinstance(rows, torch.Tensor):
+        rows = rows.detach().cpu().numpy()
+    if isinstance(rows, np.ndarray) and rows.ndim == 2:
+        out = np.ascontiguousarray(rows, np.int32)
+    else:
+        rows = [np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r).astype(np.int32).reshape(-1) for r in rows]
+        out = np.zeros((len(rows), max([width] + [len(r) for r in rows])), np.int32)
+        for i, r in enumerate(rows):
+            out[i, :len(r)] = r
+    if out.shape[0] != B or (width and out.shape[1] != width):
+        raise ValueError(f"{what} must be ({B}, {width or 'L'}), got {out.shape}")
+    return out
+
+
+def finish_contour(values: torch.Tensor, durations, silent=None, frames=None, zero_is_missing: bool = False,
+                   all_missing_value: float = 0.0, mean: float = 0.0, std: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Contour finishing (datasets.py:576-598, ``_interpolate``) on the device: values (B, T) fp32 the raw frame contour, durations
+    (B, L) int (or a list of arrays), silent (B, L) non-zero = silent phone or None, frames (B) valid frames per row or None ->
+    {"values" (B, T): frames of silent phones, NaN and (zero_is_missing) zeros filled by np.interp from the present ones, or
+    all_missing_value where nothing is present, then (. - mean) / std, zeros from frames[b] on; "frames" (B) int32 =
+    min(sum of durations, frames); "prior" (B) the mean of the filled contour over the frames of non-silent phones, before
+    normalisation}.  Pitch: zero_is_missing=True, all_missing_value=1e-7; SNR: the defaults.  T <= 4096, L <= 2048."""
+    if values.device.type != "cuda":
+        raise RuntimeError("finish_contour runs on an MI355X only (no CPU fallback)")
+    values = values.to(torch.float32).contiguous()
+    B, T = values.shape
+    dur = torch.from_numpy(_int_mat(durations, B, 0, "durations")).to(values.device)
+    L = dur.shape[1]
+    sil = None if silent is None else torch.from_numpy(_int_mat(silent, B, L, "silent")).to(values.device)
+    fr = None if frames is None else torch.as_tensor(frames).to(values.device, torch.int32).contiguous()
+    if fr is not None and tuple(fr.shape) != (B,):
+        raise ValueError(f"frames must be ({B},), got {tuple(fr.shape)}")
+    out = torch.empty(B, T, dtype=torch.float32, device=values.device)
+    fout = torch.empty(B, dtype=torch.int32, device=values.device)
+    prior = torch.empty(B, dtype=torch.float32, device=values.device)
+    with torch.cuda.device(values.device):
+        st = _lib.load().fs2_op_contour_finish(_ptr(values), _ptr(fr), _ptr(dur), _ptr(sil), B, T, L, int(bool(zero_is_missing)),
+                                               C.c_float(all_missing_value), C.c_float(mean), C.c_float(std), _ptr(out), _ptr(fout),
+                                               _ptr(prior), C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream))
+    if st == _lib.FS2_ERR_SHAPE:
+        raise ValueError(f"finish_contour holds one utterance in LDS: T = {T} <= 4096 frames and L = {L} <= 2048 phones")
+    _lib.check(st, None, "op_contour_finish")
+    return {"values": out, "frames": fout, "prior": prior}
+
+
+def masked_row_mean(values: torch.Tensor, counts=None, skip=None) -> torch.Tensor:
+    """values (B, N) fp32, counts (B) or None, skip (B, N) non-zero = leave out, or None -> (B,): the mean of each row's first
+    counts[b] entries that are not skipped, NaN for none (the priors of datasets.py:412-435)."""
+    if values.device.type != "cuda":
+        raise RuntimeError("masked_row_mean runs on an MI355X only (no CPU fallback)")
+    values = values.to(torch.float32).contiguous()
+    B, N = values.shape
+    cn = None if counts is None else torch.as_tensor(counts).to(values.device, torch.int32).contiguous()
+    sk = None if skip is None else torch.as_tensor(skip).to(values.device, torch.int32).contiguous()
+    if (cn is not None and tuple(cn.shape) != (B,)) or (sk is not None and tuple(sk.shape) != (B, N)):
+        raise ValueError(f"counts must be ({B},) and skip ({B}, {N})")
+    out = torch.empty(B, dtype=torch.float32, device=values.device)
+    with torch.cuda.device(values.device):
+        st = _lib.load().fs2_op_masked_row_mean(_ptr(values), _ptr(cn), _ptr(sk), B, N, _ptr(out),
+                                                C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream))
+    _lib.check(st, None, "op_masked_row_mean")
+    return out
+
+
 class MelAnalyzer:
     """Waveforms -> {"mel", "mel_lengths", "energy", "energy_lengths"} on the device.  The defaults are ``TTSDataset``'s
     (datasets.py:183-199); ``log="ln", clip=1e-5`` is the HiFi-GAN convention, ``log="none"`` returns the mel itself, unclamped.  ``mel_basis`` (n_mels, n_fft // 2 + 1) replaces
@@ -92,7 +171,7 @@ class MelAnalyzer:
 
     def __init__(self, sampling_rate: int = 22050, n_fft: int = 1024, win_length: int = 1024, hop_length: int = 256, n_mels: int = 80,
                  fmin: float = 0.0, fmax: Optional[float] = 8000.0, log: str = "log10", clip: float = 1e-6, mel_basis=None,
-                 device="cuda:0"):
+                 device="cuda:0", wada_table=None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the analysis front end runs on an MI355X only (no CPU fallback)")
@@ -117,6 +196,20 @@ class MelAnalyzer:
             self.close()
             raise RuntimeError(f"fs2_mel_create failed ({st}): {self.lib.fs2_status_string(st).decode()}: {msg}")
         self.tile_frames = int(self.lib.fs2_mel_tile_frames(self.handle))
+        self.wada_table = None
+        if wada_table is not None:
+            self.set_wada_table(wada_table)
+
+    def set_wada_table(self, table, db_lo: float = -20.0):
+        """The WADA table ``snr`` looks its statistic up in: g[i] for db_lo + i dB, 2 to 512 finite values (the reference's:
+        ``np.load("litfass/data/wada_values.npy")``, 121 values from -20 dB).  May be called again."""
+        table = np.ascontiguousarray(table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table, np.float64).reshape(-1)
+        with torch.cuda.device(self.device):
+            st = self.lib.fs2_mel_set_snr_table(self.handle, table.ctypes.data_as(C.c_void_p), len(table), C.c_float(db_lo))
+        if st != _lib.FS2_OK:
+            raise RuntimeError(f"fs2_mel_set_snr_table failed ({st}): {self.lib.fs2_status_string(st).decode()}: "
+                               f"{self.lib.fs2_mel_last_error(self.handle).decode()}")
+        self.wada_table = table
 
     def close(self):
         if getattr(self, "handle", None):
@@ -203,4 +296,122 @@ class MelAnalyzer:
                 raise ValueError(f"utterance {i}: durations sum to {total} frames, the audio has {mel_len[i]} mel / {en_len[i]} energy frames")
             e = phone[i, :len(d)] if energy_level == "phone" else ((energy[i, :total] - np.float32(mean)) / np.float32(std)).astype(np.float32)
             items.append({"mel": mel[i, :total].copy(), "duration": d, "variances": {"energy": np.ascontiguousarray(e, np.float32)}})
+        return items
+
+    def snr(self, wav, lengths=None, peak_normalize: bool = True) -> Dict[str, torch.Tensor]:
+        """The windowed WADA estimate (``SNR.windowed_wada(window=win_length, stride=hop / win_length, use_samples=True)``): wav and
+        lengths as in ``__call__`` -> device tensors snr (B, ceil(S / hop)) fp32 - the reference's ``snr + 20`` per hop over
+        win_length-sample windows, NaN where it has NaN, rows past an utterance's own count zero - and snr_lengths (B) int32."""
+        if self.wada_table is None:
+            raise RuntimeError("MelAnalyzer.snr needs the WADA table, and the project ships none: pass wada_table= or call "
+                               "set_wada_table(np.load('<litfass>/litfass/data/wada_values.npy')) - Kim & Stern's table for gamma shape 0.4")
+        wav, lengths = self._batch(wav, lengths)
+        B, S = wav.shape
+        Te_max = -(-S // self.hop_length)
+        dev = self.device
+        out = torch.empty(B, Te_max, dtype=torch.float32, device=dev)
+        out_len = torch.empty(B, dtype=torch.int32, device=dev)
+        ws_bytes = int(self.lib.fs2_mel_ws_bytes(self.handle, B, S))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            st = self.lib.fs2_mel_snr(self.handle, _ptr(wav), _ptr(lengths), B, S, int(bool(peak_normalize)), _ptr(out), Te_max,
+                                      _ptr(out_len), _ptr(ws), ws_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if st != _lib.FS2_OK:
+            raise RuntimeError(f"fs2_mel_snr failed ({st}): {self.lib.fs2_status_string(st).decode()}: "
+                               f"{self.lib.fs2_mel_last_error(self.handle).decode()}")
+        return {"snr": out, "snr_lengths": out_len}
+
+    def items(self, wavs: Sequence, durations: Sequence, silent: Optional[Sequence] = None, pitch: Optional[Sequence] = None,
+              stats: Optional[dict] = None, variances: Sequence[str] = ("pitch", "energy", "snr"),
+              levels: Sequence[str] = ("frame",) * 3, priors: Sequence[str] = (), peak_normalize: bool = True) -> List[dict]:
+        """Per-utterance HOST items in the shape ``TTSDataset.__getitem__`` gives them (datasets.py:398-463): ``mel``, ``duration``,
+        ``variances`` {name: (sum(d),) at level "frame", (L,) at level "phone"}, ``priors`` {name: float}, ``silence_mask``
+        (sum(d),) and ``unexpanded_silence_mask`` (L,) bool.  A caller adds "phones" and "speaker" and hands the list to
+        ``frontend.collate``.  ``silent``: per utterance, True where a phone is silence (None: none is).  ``pitch``: per utterance
+        the raw F0 contour, one value per frame and 0 where unvoiced (pyworld's output; F0 tracking is not part of this project) -
+        required when "pitch" is asked for.  "snr" needs the WADA table.  ``energy`` gets no silence handling, as in the reference.
+        ``stats`` {name: {"mean", "std"}} normalises; priors are taken before normalisation (over non-silent frames, or phones at
+        level "phone"; "duration": over non-silent phones)."""
+        variances, levels, priors = list(variances), list(levels), list(priors)
+        if len(levels) != len(variances) or any(lv not in ("frame", "phone") for lv in levels):
+            raise ValueError(f"levels must name 'frame' or 'phone' for each of {variances}, got {levels}")
+        for v in variances:
+            if v not in ("pitch", "energy", "snr"):
+                raise ValueError(f"variance {v!r} is none of 'pitch', 'energy', 'snr'")
+        for p in priors:
+            if p != "duration" and p not in variances:
+                raise ValueError(f"prior {p!r} is neither 'duration' nor one of the variances {variances}")
+        if "pitch" in variances and pitch is None:
+            raise ValueError("variances includes 'pitch': pass pitch= (the raw F0 contour per utterance, 0 where unvoiced)")
+        if len(wavs) != len(durations) or (silent is not None and len(silent) != len(wavs)) or (pitch is not None and len(pitch) != len(wavs)):
+            raise ValueError("one duration array (and silent / pitch array) per waveform")
+        B = len(wavs)
+        durs = [np.asarray(d.cpu() if isinstance(d, torch.Tensor) else d, np.int64).reshape(-1) for d in durations]
+        sils = [np.zeros(len(d), bool) if silent is None else np.asarray(silent[i]).reshape(-1) != 0 for i, d in enumerate(durs)]
+        if any(len(s) != len(d) for s, d in zip(sils, durs)):
+            raise ValueError("silent must have one flag per phone")
+        totals = [int(np.maximum(d, 0).sum()) for d in durs]
+        dev = self.device
+        dpad = _int_mat(durs, B, 0, "durations")
+        L = dpad.shape[1]
+        spad = _int_mat(sils, B, L, "silent")
+        dur_t = torch.from_numpy(dpad)
+        n_phones = torch.tensor([len(d) for d in durs], dtype=torch.int32, device=dev)
+        frame_sil = [np.repeat(s, np.maximum(d, 0)) for s, d in zip(sils, durs)]
+        out = self(list(wavs), peak_normalize=peak_normalize)
+        mel_len, en_len = out["mel_lengths"].cpu().numpy(), out["energy_lengths"].cpu().numpy()
+        for i, total in enumerate(totals):
+            if total > mel_len[i] or total > en_len[i]:
+                raise ValueError(f"utterance {i}: durations sum to {total} frames, the audio has {mel_len[i]} mel / {en_len[i]} energy frames")
+            if pitch is not None and "pitch" in variances and len(pitch[i]) < total:
+                raise ValueError(f"utterance {i}: durations sum to {total} frames, the F0 contour has {len(pitch[i])}")
+        tot_dev = torch.tensor(totals, dtype=torch.int32, device=dev)
+        fs_pad = np.zeros((B, max(1, out["energy"].shape[1])), np.int32)  # frame-level silence, for the energy prior
+        for i, f in enumerate(frame_sil):
+            fs_pad[i, :len(f)] = f
+        var_host, prior_host = {}, {}
+        for name, level in zip(variances, levels):
+            mean, std = (float(stats[name]["mean"]), float(stats[name]["std"])) if stats is not None else (0.0, 1.0)
+            phone = level == "phone"
+            if name == "energy":
+                frame_vals, frames = out["energy"], tot_dev
+                if phone:
+                    vals = segment_mean(frame_vals, dur_t, frames, mean, std)
+                else:
+                    vals = (frame_vals - mean) / std
+                fprior = None
+            else:
+                if name == "snr":
+                    s = self.snr(list(wavs), peak_normalize=peak_normalize)
+                    raw, raw_len, kw = s["snr"], s["snr_lengths"], dict(zero_is_missing=False, all_missing_value=0.0)
+                else:
+                    f0 = [np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p, np.float32).reshape(-1) for p in pitch]
+                    host = np.zeros((B, max(1, max(len(p) for p in f0))), np.float32)
+                    for i, p in enumerate(f0):
+                        host[i, :len(p)] = p
+                    raw, raw_len = torch.from_numpy(host).to(dev), torch.tensor([len(p) for p in f0], dtype=torch.int32, device=dev)
+                    kw = dict(zero_is_missing=True, all_missing_value=1e-7)
+                fin = finish_contour(raw, dpad, spad, raw_len, mean=0.0 if phone else mean, std=1.0 if phone else std, **kw)
+                frame_vals, frames, fprior = fin["values"], fin["frames"], fin["prior"]
+                vals = segment_mean(frame_vals, dur_t, frames, mean, std) if phone else frame_vals
+            if name in priors:
+                if phone:  # over the phone means of the non-silent phones, un-normalised
+                    pm = segment_mean(out["energy"] if name == "energy" else frame_vals, dur_t, frames)
+                    pr = masked_row_mean(pm, n_phones, torch.from_numpy(spad))
+                elif fprior is None:
+                    pr = masked_row_mean(frame_vals, tot_dev, torch.from_numpy(fs_pad[:, :frame_vals.shape[1]]))
+                else:
+                    pr = fprior
+                prior_host[name] = pr.cpu().numpy()
+            var_host[name] = vals.cpu().numpy()
+        if "duration" in priors:
+            prior_host["duration"] = masked_row_mean(torch.from_numpy(dpad).to(dev, torch.float32), n_phones, torch.from_numpy(spad)).cpu().numpy()
+        mel = out["mel"].cpu().numpy()
+        items = []
+        for i, d in enumerate(durs):
+            n = {"frame": totals[i], "phone": len(d)}
+            items.append({"mel": mel[i, :totals[i]].copy(), "duration": d,
+                          "variances": {v: np.ascontiguousarray(var_host[v][i, :n[lv]], np.float32) for v, lv in zip(variances, levels)},
+                          "priors": {p: float(prior_host[p][i]) for p in priors},
+                          "silence_mask": frame_sil[i], "unexpanded_silence_mask": sils[i]})
         return items

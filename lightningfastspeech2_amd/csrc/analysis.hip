@@ -63,8 +63,21 @@ __global__ __launch_bounds__(256) void mel_peak_kernel(const float* __restrict__
                                                       uint32_t* __restrict__ peak, int S) {
     const int b = blockIdx.y, n = mel_len(lengths, b, S);
     const float* __restrict__ x = wav + (size_t)b * S;
+    // the samples in front of the row's first 16-byte boundary and behind its last one by 4-byte loads, the rest by 16-byte loads
+    // (a maximum does not depend on the order)
+    const int to_boundary = (int)((4 - ((reinterpret_cast<uintptr_t>(x) >> 2) & 3)) & 3);
+    const int head = to_boundary < n ? to_boundary : n;
+    const int nv = (n - head) >> 2, tail0 = head + 4 * nv;
+    const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + head);
     float m = 0.0f;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
+        const float4 q = xv[i];
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(q.x), fabsf(q.y))), fmaxf(fabsf(q.z), fabsf(q.w)));
+    }
+    if (blockIdx.x == 0) {
+        if ((int)threadIdx.x < head) m = fmaxf(m, fabsf(x[threadIdx.x]));
+        if (tail0 + (int)threadIdx.x < n) m = fmaxf(m, fabsf(x[tail0 + threadIdx.x]));  // at most three
+    }
     for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
     if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(peak + b, __float_as_uint(m));
 }
@@ -294,6 +307,240 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restri
     }
 }
 
+// ---- training targets: windowed WADA, contour finishing, masked row mean (include/fs2.h "Training targets from audio")
+static constexpr int SNR_TILE = 32;        // windows one workgroup owns: the kernel's seams lie at multiples of 32 windows
+static constexpr int SNR_MAX_TABLE = 512;  // table entries held in LDS
+static constexpr float SNR_EPS = 1e-20f;
+
+// the per-hop partials of one workgroup: sums in fp64, the two "anything there" flags as bits 0 (|x~| > 0) and 1 (fp32 x~^2 > 0)
+__host__ __device__ inline size_t snr_lds_bytes(int partials, int K) {
+    return (size_t)K * sizeof(double) + (size_t)partials * (2 * sizeof(double) + sizeof(int));
+}
+
+// Windowed WADA (Kim & Stern): out[t] = i* + (v3 - g[i*]) / (g[i* + 1] - g[i*]) with v3 = ln(mean a) - mean(ln a), a = max(|x~|, 1e-20)
+// over window t = [t hop, min(t hop + win, n)), i* = max{i : g[i] < v3}.  One workgroup = one utterance x SNR_TILE consecutive
+// windows.  Phase 1: the tile's hops and the win / hop - 1 after them are reduced once each, a wave per hop: lane l owns samples
+// 4 l + 256 k + e (e < 4; one 16-byte load where the address allows it, four 4-byte loads of the same samples where not), adds its
+// own in that order in fp64 (the terms |x~| and logf(a) are fp32), then a shuffle tree; the partials go to LDS.  Phase 2: a thread per
+// window adds its win / hop consecutive partials in order, forms v3 in fp64 and looks it up in the table held in LDS.  A hop past
+// the utterance's end has no samples; the last hops are short: a window's mean divides by the samples that exist.  No sum depends on
+// the batch, on S or on the alignment of a row: results are bitwise batch-invariant.
+__global__ __launch_bounds__(256) void mel_snr_kernel(const float* __restrict__ wav, const int32_t* __restrict__ lengths,
+                                                     const uint32_t* __restrict__ peak, const double* __restrict__ table, int K,
+                                                     float* __restrict__ snr, int32_t* __restrict__ snr_frames, int S, int Te_max,
+                                                     int hop, int win) {
+    extern __shared__ double snr_smem[];
+    const int r = win / hop, P = SNR_TILE + r - 1;
+    double* __restrict__ g = snr_smem;      // [K]
+    double* __restrict__ pa = g + K;        // [P] sum of a
+    double* __restrict__ pl = pa + P;       // [P] sum of ln a
+    int* __restrict__ pf = (int*)(pl + P);  // [P] flags
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, t0 = blockIdx.x * SNR_TILE;
+    const int n = mel_len(lengths, b, S);
+    const int te = (int)(((long long)n + hop - 1) / hop);
+    if (blockIdx.x == 0 && tid == 0 && snr_frames) snr_frames[b] = te;
+    const int rows = Te_max - t0 < SNR_TILE ? Te_max - t0 : SNR_TILE;
+    float* __restrict__ dst = snr + (size_t)b * Te_max + t0;
+    if (t0 >= te) {  // uniform: a tile past the utterance's last window is zeros
+        for (int i = tid; i < rows; i += 256) dst[i] = 0.0f;
+        return;
+    }
+    for (int i = tid; i < K; i += 256) g[i] = table[i];
+    const float s = mel_scale(peak, b);
+    const float* __restrict__ x = wav + (size_t)b * S;
+    for (int h = wave; h < P; h += 4) {
+        const long long lo = (long long)(t0 + h) * hop;
+        const int cnt = lo >= n ? 0 : (int)((lo + hop < n ? lo + hop : (long long)n) - lo);
+        const float* __restrict__ p = x + (lo < n ? lo : 0);
+        const bool vec = (((uintptr_t)p) & 15) == 0;  // uniform per wave
+        double sa = 0.0, sl = 0.0;
+        int fl = 0;
+        for (int j = lane * 4; j < cnt; j += 256) {
+            float v[4];
+            if (vec && j + 4 <= cnt) {
+                const float4 q = *reinterpret_cast<const float4*>(p + j);
+                v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = j + e < cnt ? p[j + e] : 0.0f;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j + e < cnt) {
+                    const float xs = v[e] * s, m = fabsf(xs), a = m < SNR_EPS ? SNR_EPS : m;  // a NaN sample stays NaN
+                    sa += (double)a;
+                    sl += (double)logf(a);
+                    fl |= (m > 0.0f ? 1 : 0) | (xs * xs > 0.0f ? 2 : 0);
+                }
+        }
+        for (int o = 32; o; o >>= 1) {
+            sa += __shfl_down(sa, o);
+            sl += __shfl_down(sl, o);
+            fl |= __shfl_down(fl, o);
+        }
+        if (lane == 0) pa[h] = sa, pl[h] = sl, pf[h] = fl;
+    }
+    __syncthreads();
+    if (tid < rows) {
+        const int t = t0 + tid;
+        float out = 0.0f;
+        if (t < te) {
+            double sa = 0.0, sl = 0.0;
+            int fl = 0;
+            for (int i = 0; i < r; ++i) sa += pa[tid + i], sl += pl[tid + i], fl |= pf[tid + i];
+            const long long lo = (long long)t * hop;
+            const double cnt = (double)((lo + win < n ? lo + win : (long long)n) - lo);
+            out = __builtin_nanf("");
+            if (fl == 3) {
+                const double mean_a = sa / cnt;
+                const double v3 = log(mean_a > (double)SNR_EPS ? mean_a : (double)SNR_EPS) - sl / cnt;
+                int i = K - 1;
+                while (i >= 0 && !(g[i] < v3)) --i;  // the largest index below v3: the table need not be monotone
+                if (i >= 0 && i < K - 1) {
+                    const double o = (double)i + (v3 - g[i]) / (g[i + 1] - g[i]);
+                    if (o < (double)(K - 1)) out = (float)o;
+                }
+            }
+        }
+        dst[tid] = out;
+    }
+}
+
+static constexpr int FIN_MAX_T = 4096;  // frames of one utterance (the reference caps one at 2756)
+static constexpr int FIN_MAX_L = 2048;  // phones of one utterance
+
+// inclusive scan of one int per thread over the workgroup's 256 threads in the order of `pos` (a permutation of 0..255)
+template <class Op>
+__device__ __forceinline__ int fin_scan(int v, int pos, int* __restrict__ sc, Op op) {
+    __syncthreads();
+    sc[pos] = v;
+    for (int o = 1; o < 256; o <<= 1) {
+        __syncthreads();
+        const int u = pos >= o ? sc[pos - o] : v;
+        __syncthreads();
+        if (pos >= o) sc[pos] = v = op(u, v);
+    }
+    __syncthreads();
+    return v;
+}
+
+// Contour finishing (datasets.py:576-598, 831-837): one workgroup = one utterance.  The contour, the durations' prefix sums
+// (saturated at T: only comparisons with t < F <= T are made), the frame flags and the nearest present frame to either side are in
+// LDS.  A thread owns T / 256 (rounded up) consecutive frames; the nearest present frame on the left is an inclusive max-scan
+// over the workgroup, the one on the right a min-scan from the other end.  The fill reads present frames only.
+__global__ __launch_bounds__(256) void contour_finish_kernel(const float* __restrict__ values, const int32_t* __restrict__ frames,
+                                                            const int32_t* __restrict__ dur, const int32_t* __restrict__ silent,
+                                                            float* __restrict__ out, int32_t* __restrict__ frames_out,
+                                                            float* __restrict__ prior, int T, int L, int zero_is_missing,
+                                                            float all_missing_value, float mean, float stdev) {
+    __shared__ float y[FIN_MAX_T];
+    __shared__ int cum[FIN_MAX_L];
+    __shared__ short left[FIN_MAX_T], right[FIN_MAX_T];
+    __shared__ unsigned char flag[FIN_MAX_T];  // bit 0: missing, bit 1: frame of a silent phone
+    __shared__ int sc[256];
+    __shared__ double psum[256];
+    __shared__ int pcnt[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int32_t* __restrict__ d = dur + (size_t)b * L;
+    const int32_t* __restrict__ sil = silent ? silent + (size_t)b * L : nullptr;
+    const float* __restrict__ v = values + (size_t)b * T;
+    auto sat_add = [T](int p, int q) { return p + q < T ? p + q : T; };  // both in [0, T]: no overflow
+    // ---- prefix sums of the durations, each clamped to [0, T]
+    const int cl = (L + 255) / 256, j0 = tid * cl, j1 = j0 + cl < L ? j0 + cl : L;
+    int own = 0;
+    for (int j = j0; j < j1; ++j) own = sat_add(own, d[j] < 0 ? 0 : (d[j] > T ? T : d[j]));
+    fin_scan(own, tid, sc, sat_add);  // inclusive over the threads
+    int run = tid ? sc[tid - 1] : 0;
+    const int total = sc[255];
+    for (int j = j0; j < j1; ++j) cum[j] = run = sat_add(run, d[j] < 0 ? 0 : (d[j] > T ? T : d[j]));
+    int F = frames ? frames[b] : T;
+    F = F < 0 ? 0 : (F > T ? T : F);
+    F = total < F ? total : F;
+    __syncthreads();
+    // ---- this thread's frames: value, phone (first j with cum[j] > t), flags, nearest present frame on either side within the chunk
+    const int ct = (T + 255) / 256, f0 = tid * ct, f1 = f0 + ct < F ? f0 + ct : F;
+    int last = -1;
+    for (int t = f0; t < f1; ++t) {
+        int lo = 0, hi = L - 1;  // cum[L - 1] = total > t: the search ends on a phone of positive duration
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cum[mid] > t) hi = mid; else lo = mid + 1;
+        }
+        const float x = v[t];
+        const bool s = sil && sil[lo] != 0;
+        const bool miss = s || isnan(x) || (zero_is_missing && x == 0.0f);
+        y[t] = x;
+        flag[t] = (unsigned char)((miss ? 1 : 0) | (s ? 2 : 0));
+        if (!miss) last = t;
+        left[t] = (short)last;  // -1: none in this chunk so far
+    }
+    int first = FIN_MAX_T;
+    for (int t = f1 - 1; t >= f0; --t) {
+        if (!(flag[t] & 1)) first = t;
+        right[t] = (short)first;  // FIN_MAX_T: none in this chunk from here on
+    }
+    fin_scan(last, tid, sc, [](int p, int q) { return p > q ? p : q; });
+    const int before = tid ? sc[tid - 1] : -1;  // nearest present frame in the chunks before this one
+    const bool any = sc[255] >= 0;
+    fin_scan(first, 255 - tid, sc, [](int p, int q) { return p < q ? p : q; });
+    const int after = tid < 255 ? sc[254 - tid] : FIN_MAX_T;  // ... in the chunks after it
+    // ---- the fill
+    double ps = 0.0;
+    int pc = 0;
+    for (int t = f0; t < f1; ++t) {
+        float o = y[t];
+        if (!any) {
+            o = all_missing_value;
+        } else if (flag[t] & 1) {
+            const int l = left[t] >= 0 ? left[t] : before, r = right[t] < FIN_MAX_T ? right[t] : after;
+            if (l < 0) o = y[r];
+            else if (r >= FIN_MAX_T) o = y[l];
+            else o = (float)((double)y[l] + (double)(t - l) * ((double)y[r] - (double)y[l]) / (double)(r - l));
+        }
+        if (!(flag[t] & 2)) ps += (double)o, ++pc;
+        out[(size_t)b * T + t] = (float)(((double)o - (double)mean) / (double)stdev);
+    }
+    for (int t = f0 > F ? f0 : F; t < (f0 + ct < T ? f0 + ct : T); ++t) out[(size_t)b * T + t] = 0.0f;  // the tail, from F on
+    psum[tid] = ps, pcnt[tid] = pc;
+    __syncthreads();
+    if (tid == 0) {
+        frames_out[b] = F;
+        if (prior) {
+            double sum = 0.0;
+            long long c = 0;
+            for (int i = 0; i < 256; ++i) sum += psum[i], c += pcnt[i];  // chunk sums in frame order
+            prior[b] = c ? (float)(sum / (double)c) : __builtin_nanf("");
+        }
+    }
+}
+
+// out[b] = mean of values[b][j] over j < counts[b] with skip[b][j] == 0, NaN for none: chunks of consecutive entries summed in order
+// in fp64, the chunk sums added in order
+__global__ __launch_bounds__(256) void masked_row_mean_kernel(const float* __restrict__ values, const int32_t* __restrict__ counts,
+                                                             const int32_t* __restrict__ skip, float* __restrict__ out, int N) {
+    __shared__ double psum[256];
+    __shared__ int pcnt[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int c = counts ? counts[b] : N;
+    c = c < 0 ? 0 : (c > N ? N : c);
+    const int ch = (N + 255) / 256;
+    const long long j0 = (long long)tid * ch;
+    const long long j1 = j0 + ch < c ? j0 + ch : c;
+    double s = 0.0;
+    int k = 0;
+    for (long long j = j0; j < j1; ++j)
+        if (!skip || skip[(size_t)b * N + j] == 0) s += (double)values[(size_t)b * N + j], ++k;
+    psum[tid] = s, pcnt[tid] = k;
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        long long cnt = 0;
+        for (int i = 0; i < 256; ++i) sum += psum[i], cnt += pcnt[i];
+        out[b] = cnt ? (float)(sum / (double)cnt) : __builtin_nanf("");
+    }
+}
+
 typedef void (*MelKernelFn)(const MelKernelArgs);
 
 static MelKernelFn mel_kernel_for(int mt, int nt) {
@@ -331,6 +578,9 @@ struct fs2_mel {
     MelKernelFn kernel = nullptr;
     float4* table = nullptr;
     float4* btab = nullptr;
+    double* snr_table = nullptr;  // the WADA table (fs2_mel_set_snr_table), snr_k entries for db_lo, db_lo + 1, ...
+    int snr_k = 0;
+    float snr_db_lo = 0.0f;
     bool ready = false;
     char err[256] = {0};
 };
@@ -440,6 +690,7 @@ int fs2_mel_destroy(fs2_mel* m) {
     if (!m) return FS2_ERR_ARG;
     if (m->table) (void)hipFree(m->table);
     if (m->btab) (void)hipFree(m->btab);
+    if (m->snr_table) (void)hipFree(m->snr_table);
     delete m;
     return FS2_OK;
 }
@@ -499,6 +750,74 @@ int fs2_op_segment_mean(const float* values, const int32_t* frames, const int32_
     if (!(stdev != 0.0f) || !isfinite(stdev) || !isfinite(mean)) return FS2_ERR_ARG;
     hipLaunchKernelGGL(segment_mean_kernel, dim3(B), dim3(256), 0, (hipStream_t)hip_stream, values, frames, durations, out, T, L,
                        empty_value, mean, stdev);
+    return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
+}
+
+int fs2_mel_set_snr_table(fs2_mel* m, const double* table_host, int32_t n, float db_lo) {
+    if (!m) return FS2_ERR_ARG;
+    if (!table_host) return mfail(m, FS2_ERR_ARG, "the SNR table is null");
+    if (n < 2 || n > SNR_MAX_TABLE) return mfail(m, FS2_ERR_ARG, "the SNR table has %d entries, outside [2, %d]", n, SNR_MAX_TABLE);
+    if (!isfinite(db_lo)) return mfail(m, FS2_ERR_ARG, "db_lo is not finite");
+    for (int i = 0; i < n; ++i)
+        if (!isfinite(table_host[i])) return mfail(m, FS2_ERR_ARG, "SNR table entry %d is not finite", i);
+    if (!m->ready) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");
+    double* dev = nullptr;
+    if (hipMalloc((void**)&dev, (size_t)n * sizeof(double)) != hipSuccess)
+        return mfail(m, FS2_ERR_HIP, "hipMalloc of the SNR table failed: %s", hipGetErrorString(hipGetLastError()));
+    if (hipMemcpy(dev, table_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        return mfail(m, FS2_ERR_HIP, "upload of the SNR table failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (m->snr_table) (void)hipFree(m->snr_table);  // waits for launches that still read the old one
+    m->snr_table = dev, m->snr_k = n, m->snr_db_lo = db_lo;
+    return FS2_OK;
+}
+
+int fs2_mel_snr(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B, int32_t S, int32_t peak_normalize, float* snr,
+                int32_t Te_max, int32_t* snr_frames, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!m) return FS2_ERR_ARG;
+    if (m->hop < 1) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");  // no geometry to judge
+    if (m->win % m->hop) return mfail(m, FS2_ERR_SHAPE, "win_length %d is not a multiple of hop %d: the windowed SNR needs one", m->win, m->hop);
+    if (!m->ready) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");
+    if (!m->snr_table) return mfail(m, FS2_ERR_STATE, "no SNR table: call fs2_mel_set_snr_table first (the library ships none)");
+    if (!wav || !lengths || !snr) return mfail(m, FS2_ERR_ARG, "wav, lengths and snr must not be null");
+    if (B < 1 || S < 1) return mfail(m, FS2_ERR_ARG, "B = %d, S = %d: both must be at least 1", B, S);
+    if (B > 65535) return mfail(m, FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
+    const int te_need = (int)(((long long)S + m->hop - 1) / m->hop);
+    if (Te_max < te_need) return mfail(m, FS2_ERR_ARG, "Te_max = %d < ceil(S / hop) = %d", Te_max, te_need);
+    if (!ws || ws_bytes < mel_ws_need(B))
+        return mfail(m, FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, mel_ws_need(B));
+    hipStream_t st = (hipStream_t)hip_stream;
+    uint32_t* peak = nullptr;
+    if (peak_normalize) {
+        peak = (uint32_t*)ws;
+        if (hipMemsetAsync(peak, 0, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return mfail(m, FS2_ERR_HIP, "hipMemsetAsync failed");
+        int chunks = (S + 4095) / 4096;
+        chunks = chunks > 64 ? 64 : chunks;
+        hipLaunchKernelGGL(mel_peak_kernel, dim3(chunks, B), dim3(256), 0, st, wav, lengths, peak, S);
+    }
+    const size_t lds = snr_lds_bytes(SNR_TILE + m->win / m->hop - 1, m->snr_k);
+    hipLaunchKernelGGL(mel_snr_kernel, dim3((Te_max + SNR_TILE - 1) / SNR_TILE, B), dim3(256), lds, st, wav, lengths, peak, m->snr_table,
+                       m->snr_k, snr, snr_frames, S, Te_max, m->hop, m->win);
+    if (hipGetLastError() != hipSuccess) return mfail(m, FS2_ERR_HIP, "a launch of fs2_mel_snr failed");
+    return FS2_OK;
+}
+
+int fs2_op_contour_finish(const float* values, const int32_t* frames, const int32_t* durations, const int32_t* phone_silent, int32_t B,
+                          int32_t T, int32_t L, int32_t zero_is_missing, float all_missing_value, float mean, float stdev, float* out,
+                          int32_t* frames_out, float* prior, void* hip_stream) {
+    if (!values || !durations || !out || !frames_out || B < 1 || T < 1 || L < 1) return FS2_ERR_ARG;
+    if (!(stdev != 0.0f) || !isfinite(stdev) || !isfinite(mean)) return FS2_ERR_ARG;
+    if (T > FIN_MAX_T || L > FIN_MAX_L) return FS2_ERR_SHAPE;
+    hipLaunchKernelGGL(contour_finish_kernel, dim3(B), dim3(256), 0, (hipStream_t)hip_stream, values, frames, durations, phone_silent, out,
+                       frames_out, prior, T, L, zero_is_missing, all_missing_value, mean, stdev);
+    return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
+}
+
+int fs2_op_masked_row_mean(const float* values, const int32_t* counts, const int32_t* skip, int32_t B, int32_t N, float* out,
+                           void* hip_stream) {
+    if (!values || !out || B < 1 || N < 1) return FS2_ERR_ARG;
+    hipLaunchKernelGGL(masked_row_mean_kernel, dim3(B), dim3(256), 0, (hipStream_t)hip_stream, values, counts, skip, out, N);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 

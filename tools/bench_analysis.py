@@ -10,6 +10,11 @@ One process, the fastest of --loops timed loops (device events around --steps ca
     DFT and the mel product, and which limit it is on: the larger of FLOPs / 155 TF, HBM bytes / 6.29 TB/s and the DFT table
     every workgroup streams from L2 / 17 TB/s;
   * next to it the CPU recipe it replaces on this box: torch.stft + matmul + clamp + log10 in float32 on 16 threads.
+With --snr, in the same process after the mel figures: the windowed WADA estimate (fs2_mel_snr: peak + statistic launches) on the
+same batch, its HBM floor - the waveform read twice, once for the peak and once for the statistic - and this project's own numpy
+loop of the same definition on --snr-cpu-rows utterances of the batch (one window at a time, as the reference's loop goes), scaled to
+the batch.  The WADA table is an argument of the operator (the project ships none): --wada-table names an .npy, or an .npz with a
+"wada_table" array (default: the test fixture).
 Prints ONE JSON line.  No GPU, no figure: the tool fails without a device.
 """
 import argparse
@@ -41,6 +46,25 @@ def cpu_recipe(x, basis, n_fft, hop, win, clip):
     return torch.log10(torch.clamp(torch.matmul(basis, mag), min=clip))
 
 
+def wada_numpy(x, win, hop, g):
+    """the definition of include/fs2.h, window by window, on one peak-normalised float32 utterance"""
+    n = len(x)
+    out = np.full(-(-n // hop), np.nan, np.float32)
+    for t in range(len(out)):
+        seg = np.abs(x[t * hop:min(t * hop + win, n)])
+        if not seg.any() or not (seg * seg).any():
+            continue
+        a = np.maximum(seg, np.float32(1e-20))
+        v3 = np.log(max(1e-20, float(a.mean(dtype=np.float64)))) - float(np.log(a).mean(dtype=np.float64))
+        below = np.nonzero(g < v3)[0]
+        if len(below) and below[-1] < len(g) - 1:
+            i = below[-1]
+            o = i + (v3 - g[i]) / (g[i + 1] - g[i])
+            if o < len(g) - 1:
+                out[t] = o
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -50,6 +74,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--snr", action="store_true")
+    ap.add_argument("--snr-cpu-rows", type=int, default=2)
+    ap.add_argument("--wada-table", default=os.path.join(ROOT, "tests", "golden", "frontend_targets.npz"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_analysis needs an MI355X: no figure without a device")
@@ -71,7 +98,7 @@ def main():
                              _p(ef), _p(ws), need, stream)
         assert st == 0, lib.fs2_mel_last_error(an.handle)
 
-    def fastest(full):
+    def fastest(full, run=run):
         for _ in range(a.warmup):
             run(full)
         ms = []
@@ -122,6 +149,36 @@ def main():
         out.update({"cpu_recipe_ms": round(min(cpu), 2), "cpu_threads": a.cpu_threads, "cpu_loops_ms": [round(v, 2) for v in cpu],
                     "speedup_vs_cpu_recipe": round(min(cpu) / full_ms, 1),
                     "max_abs_log10_vs_cpu_recipe": float((mel.cpu() - ref.permute(0, 2, 1)).abs().max())})
+    if a.snr:
+        table = np.load(a.wada_table)
+        table = np.asarray(table["wada_table"] if hasattr(table, "files") else table, np.float64)
+        an.set_wada_table(table)
+        snr = torch.empty(B, Te, device=dev)
+        sf = torch.empty(B, dtype=torch.int32, device=dev)
+
+        def run_snr(_full=True):
+            st = lib.fs2_mel_snr(an.handle, _p(wav), _p(lengths), B, S, 1, _p(snr), Te, _p(sf), _p(ws), need, stream)
+            assert st == 0, lib.fs2_mel_last_error(an.handle)
+
+        snr_ms, snr_loops = fastest(True, run_snr)
+        assert sf.tolist() == [Te] * B
+        floor_ms = 2 * 4.0 * B * S / HBM * 1e3
+        out.update({"snr_ms": round(snr_ms, 4), "snr_loops_ms": [round(x, 4) for x in snr_loops], "snr_windows": B * Te,
+                    "snr_hbm_floor_ms": round(floor_ms, 4), "snr_ratio_to_floor": round(snr_ms / floor_ms, 2),
+                    "snr_nan_share": round(float(torch.isnan(snr).float().mean()), 4)})
+        if not a.no_cpu:
+            rows = max(1, min(a.snr_cpu_rows, B))
+            x = wav[:rows].cpu().numpy()
+            x = x / np.abs(x).max(axis=1, keepdims=True)
+            t0 = time.perf_counter()
+            ref = np.stack([wada_numpy(r, an.win_length, hop, table) for r in x])
+            loop_ms = (time.perf_counter() - t0) * 1e3
+            got = snr[:rows].cpu().numpy()
+            both = ~np.isnan(ref) & ~np.isnan(got)
+            out.update({"snr_numpy_loop_rows": rows, "snr_numpy_loop_ms": round(loop_ms, 1),
+                        "snr_numpy_loop_ms_scaled_to_batch": round(loop_ms * B / rows, 1),
+                        "snr_speedup_vs_numpy_loop": round(loop_ms * B / rows / snr_ms, 0),
+                        "snr_max_abs_db_vs_numpy_loop": float(np.abs(ref[both] - got[both]).max()) if both.any() else None})
     print(json.dumps(out), flush=True)
 
 
