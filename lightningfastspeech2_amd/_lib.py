@@ -119,11 +119,26 @@ def declared_symbols(header_path: str = HEADER_PATH):
     return sorted((_HEADER if header_path == HEADER_PATH else parse_header(header_path)).functions)
 
 
+class DevPtr:
+    """The argtype load() gives every parameter the header types as a plain `void*`: a tensor (anything with data_ptr()), a
+    torch.cuda.Stream (anything with .cuda_stream), None, or whatever c_void_p takes (opaque handles, byref, ctypes arrays and
+    pointers, ints) goes into the call as a 64-bit pointer.  It converts and does not validate: strided views and host pointers
+    are legitimate arguments.  The argument stays referenced by the caller's frame for the call, so a temporary is safe here."""
+
+    @classmethod
+    def from_param(cls, obj):
+        try:
+            return _VOIDP(obj.data_ptr())  # a c_void_p, never the bare int: ctypes would pass that as a C int
+        except AttributeError:
+            return _VOIDP.from_param(getattr(obj, "cuda_stream", obj))
+
+
+_VOIDP = C.c_void_p
 _lib = None
 
 
 def load():
-    """dlopen libfs2_hip.so and type its entry points.  Raises Fs2LibraryError if it is absent."""
+    """dlopen libfs2_hip.so and type its entry points (plain void* parameters as DevPtr).  Raises Fs2LibraryError if it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -137,20 +152,22 @@ def load():
         raise Fs2LibraryError(f"{LIB_PATH} does not export: {missing}")
     for name, (restype, argtypes) in _HEADER.functions.items():
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+        fn.restype, fn.argtypes = restype, [DevPtr if t is C.c_void_p else t for t in argtypes]
     if lib.fs2_abi_version() != FS2_ABI_VERSION:
         raise Fs2LibraryError("libfs2_hip.so ABI version mismatch")
     _lib = lib
     return lib
 
 
-def check(status: int, engine=None, what: str = ""):
+def check(status: int, engine=None, what: str = "", last_error=None):
+    """Raise on a status other than FS2_OK.  engine = the handle whose message to append; last_error = the name of the
+    entry point that returns it, for handles other than the engine's ("fs2_voc_last_error", "fs2_mel_last_error")."""
     if status == FS2_OK:
         return
     lib = load()
     msg = lib.fs2_status_string(status).decode()
     if engine:
-        detail = lib.fs2_last_error(engine).decode()
+        detail = getattr(lib, last_error or "fs2_last_error")(engine).decode()
         if detail:
             msg = f"{msg}: {detail}"
     raise RuntimeError(f"fs2 {what} failed ({status}): {msg}")

@@ -74,10 +74,6 @@ def slaney_mel_basis(sr: int = 22050, n_fft: int = 1024, n_mels: int = 80, fmin:
 _LOG_KINDS = {"log10": _lib.FS2_MEL_LOG10, "ln": _lib.FS2_MEL_LN, "none": _lib.FS2_MEL_LINEAR}
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def segment_mean(values: torch.Tensor, durations: torch.Tensor, frames: Optional[torch.Tensor] = None, mean: float = 0.0,
                  std: float = 1.0, empty_value: float = 1e-7) -> torch.Tensor:
     """Phone-level reduction (datasets.py:631-648) on the device: values (B, T) fp32, durations (B, L) int, frames (B) valid
@@ -92,8 +88,7 @@ def segment_mean(values: torch.Tensor, durations: torch.Tensor, frames: Optional
         raise ValueError(f"durations must be ({B}, L) and frames ({B},)")
     out = torch.empty(B, L, dtype=torch.float32, device=values.device)
     with torch.cuda.device(values.device):
-        st = _lib.load().fs2_op_segment_mean(_ptr(values), _ptr(fr), _ptr(dur), B, T, L, C.c_float(empty_value), C.c_float(mean),
-                                             C.c_float(std), _ptr(out), C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream))
+        st = _lib.load().fs2_op_segment_mean(values, fr, dur, B, T, L, empty_value, mean, std, out, torch.cuda.current_stream(values.device))
     _lib.check(st, None, "op_segment_mean")
     return out
 
@@ -136,9 +131,8 @@ def finish_contour(values: torch.Tensor, durations, silent=None, frames=None, ze
     fout = torch.empty(B, dtype=torch.int32, device=values.device)
     prior = torch.empty(B, dtype=torch.float32, device=values.device)
     with torch.cuda.device(values.device):
-        st = _lib.load().fs2_op_contour_finish(_ptr(values), _ptr(fr), _ptr(dur), _ptr(sil), B, T, L, int(bool(zero_is_missing)),
-                                               C.c_float(all_missing_value), C.c_float(mean), C.c_float(std), _ptr(out), _ptr(fout),
-                                               _ptr(prior), C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream))
+        st = _lib.load().fs2_op_contour_finish(values, fr, dur, sil, B, T, L, int(bool(zero_is_missing)), all_missing_value, mean, std, out,
+                                               fout, prior, torch.cuda.current_stream(values.device))
     if st == _lib.FS2_ERR_SHAPE:
         raise ValueError(f"finish_contour holds one utterance in LDS: T = {T} <= 4096 frames and L = {L} <= 2048 phones")
     _lib.check(st, None, "op_contour_finish")
@@ -158,8 +152,7 @@ def masked_row_mean(values: torch.Tensor, counts=None, skip=None) -> torch.Tenso
         raise ValueError(f"counts must be ({B},) and skip ({B}, {N})")
     out = torch.empty(B, dtype=torch.float32, device=values.device)
     with torch.cuda.device(values.device):
-        st = _lib.load().fs2_op_masked_row_mean(_ptr(values), _ptr(cn), _ptr(sk), B, N, _ptr(out),
-                                                C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream))
+        st = _lib.load().fs2_op_masked_row_mean(values, cn, sk, B, N, out, torch.cuda.current_stream(values.device))
     _lib.check(st, None, "op_masked_row_mean")
     return out
 
@@ -188,13 +181,13 @@ class MelAnalyzer:
         self.mel_basis = basis
         self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            st = self.lib.fs2_mel_create(_lib.FS2_ABI_VERSION, n_fft, win_length, hop_length, n_mels, C.c_float(self.clip),
-                                         _LOG_KINDS[log], basis.ctypes.data_as(C.c_void_p),
-                                         C.byref(self.handle))
-        if st != _lib.FS2_OK:
-            msg = self.lib.fs2_mel_last_error(self.handle).decode() if self.handle else ""
-            self.close()
-            raise RuntimeError(f"fs2_mel_create failed ({st}): {self.lib.fs2_status_string(st).decode()}: {msg}")
+            st = self.lib.fs2_mel_create(_lib.FS2_ABI_VERSION, n_fft, win_length, hop_length, n_mels, self.clip, _LOG_KINDS[log],
+                                         basis.ctypes.data_as(C.c_void_p), C.byref(self.handle))
+        if st != _lib.FS2_OK:  # the handle comes back on failure too, for its message
+            try:
+                _lib.check(st, self.handle, "fs2_mel_create", "fs2_mel_last_error")
+            finally:
+                self.close()
         self.tile_frames = int(self.lib.fs2_mel_tile_frames(self.handle))
         self.wada_table = None
         if wada_table is not None:
@@ -205,10 +198,8 @@ class MelAnalyzer:
         ``np.load("litfass/data/wada_values.npy")``, 121 values from -20 dB).  May be called again."""
         table = np.ascontiguousarray(table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table, np.float64).reshape(-1)
         with torch.cuda.device(self.device):
-            st = self.lib.fs2_mel_set_snr_table(self.handle, table.ctypes.data_as(C.c_void_p), len(table), C.c_float(db_lo))
-        if st != _lib.FS2_OK:
-            raise RuntimeError(f"fs2_mel_set_snr_table failed ({st}): {self.lib.fs2_status_string(st).decode()}: "
-                               f"{self.lib.fs2_mel_last_error(self.handle).decode()}")
+            st = self.lib.fs2_mel_set_snr_table(self.handle, table.ctypes.data_as(C.c_void_p), len(table), db_lo)
+        _lib.check(st, self.handle, "fs2_mel_set_snr_table", "fs2_mel_last_error")
         self.wada_table = table
 
     def close(self):
@@ -259,12 +250,9 @@ class MelAnalyzer:
         ws_bytes = int(self.lib.fs2_mel_ws_bytes(self.handle, B, S))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            st = self.lib.fs2_mel_run(self.handle, _ptr(wav), _ptr(lengths), B, S, int(bool(peak_normalize)), _ptr(mel), T_max, _ptr(en),
-                                      Te_max, _ptr(mel_len), _ptr(en_len), _ptr(ws), ws_bytes,
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if st != _lib.FS2_OK:
-            raise RuntimeError(f"fs2_mel_run failed ({st}): {self.lib.fs2_status_string(st).decode()}: "
-                               f"{self.lib.fs2_mel_last_error(self.handle).decode()}")
+            st = self.lib.fs2_mel_run(self.handle, wav, lengths, B, S, int(bool(peak_normalize)), mel, T_max, en, Te_max, mel_len, en_len,
+                                      ws, ws_bytes, torch.cuda.current_stream(dev))
+        _lib.check(st, self.handle, "fs2_mel_run", "fs2_mel_last_error")
         return {"mel": mel, "mel_lengths": mel_len, "energy": en, "energy_lengths": en_len}
 
     def targets(self, wavs: Sequence, durations: Sequence, stats: Optional[dict] = None, energy_level: str = "frame",
@@ -314,11 +302,9 @@ class MelAnalyzer:
         ws_bytes = int(self.lib.fs2_mel_ws_bytes(self.handle, B, S))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            st = self.lib.fs2_mel_snr(self.handle, _ptr(wav), _ptr(lengths), B, S, int(bool(peak_normalize)), _ptr(out), Te_max,
-                                      _ptr(out_len), _ptr(ws), ws_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if st != _lib.FS2_OK:
-            raise RuntimeError(f"fs2_mel_snr failed ({st}): {self.lib.fs2_status_string(st).decode()}: "
-                               f"{self.lib.fs2_mel_last_error(self.handle).decode()}")
+            st = self.lib.fs2_mel_snr(self.handle, wav, lengths, B, S, int(bool(peak_normalize)), out, Te_max, out_len, ws, ws_bytes,
+                                      torch.cuda.current_stream(dev))
+        _lib.check(st, self.handle, "fs2_mel_snr", "fs2_mel_last_error")
         return {"snr": out, "snr_lengths": out_len}
 
     def items(self, wavs: Sequence, durations: Sequence, silent: Optional[Sequence] = None, pitch: Optional[Sequence] = None,

@@ -161,9 +161,7 @@ def wav_pack(wav: torch.Tensor, lengths: Optional[torch.Tensor], hop: int, dtype
     offsets = torch.empty(B + 1, dtype=torch.int64, device=wav.device)
     lib = _lib.load()
     with torch.cuda.device(wav.device):
-        st = lib.fs2_op_wav_pack(C.c_void_p(wav.data_ptr()), None if lengths is None else C.c_void_p(lengths.data_ptr()), B, S // hop,
-                                 hop, kind, C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(offsets.data_ptr()),
-                                 C.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream))
+        st = lib.fs2_op_wav_pack(wav, lengths, B, S // hop, hop, kind, out, out.numel(), offsets, torch.cuda.current_stream(wav.device))
     _lib.check(st, None, f"op_wav_pack (capacity {out.numel()} for {B} x {S} samples)")
     return out, offsets
 
@@ -193,8 +191,7 @@ class HifiGan:
 
     def _init(self, cfg, cc, state_dict):
         st = self.lib.fs2_voc_create(C.byref(cc), C.byref(self.handle))
-        if st != 0:
-            raise RuntimeError(f"fs2_voc_create: {_lib.load().fs2_status_string(st).decode()}")
+        _lib.check(st, None, "fs2_voc_create")
         sd = fold_weight_norm(state_dict)
         spec = state_dict_spec(cfg)
         missing = [k for k in spec if k not in sd]
@@ -209,9 +206,7 @@ class HifiGan:
         self.hop = int(self.lib.fs2_voc_hop(self.handle))
 
     def _check(self, status, what):
-        if status != 0:
-            raise RuntimeError(f"{what}: {_lib.load().fs2_status_string(status).decode()}: "
-                               f"{self.lib.fs2_voc_last_error(self.handle).decode()}")
+        _lib.check(status, self.handle, what, "fs2_voc_last_error")
 
     def __del__(self):
         try:
@@ -228,11 +223,9 @@ class HifiGan:
             raise ValueError(f"mel has {M} bins, generator wants {self.cfg.num_mels}")
         wav = (torch.zeros if zero_pads else torch.empty)(B, T * self.hop, dtype=torch.float32, device=self.device)
         ld = None if lengths is None else lengths.to(self.device, torch.int32).contiguous()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):  # arena hipMalloc + launches must hit the engine's device
-            self._check(self.lib.fs2_voc_synthesize(self.handle, C.c_void_p(mel.data_ptr()),
-                                                    None if ld is None else C.c_void_p(ld.data_ptr()), B, T,
-                                                    C.c_void_p(wav.data_ptr()), stream), "synthesize")
+            self._check(self.lib.fs2_voc_synthesize(self.handle, mel, ld, B, T, wav, stream), "synthesize")
         self._last = (B, T)
         return wav, ld
 
@@ -256,9 +249,9 @@ class HifiGan:
         B, T = self._last
         up = int(np.prod(self.cfg.upsample_rates[:stage])) if stage else 1
         t = torch.empty(B, T * up, self.cfg.channels()[stage], dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            self._check(self.lib.fs2_voc_debug_copy(self.handle, stage, C.c_void_p(t.data_ptr()), stream), "debug_copy")
+            self._check(self.lib.fs2_voc_debug_copy(self.handle, stage, t, stream), "debug_copy")
         return t
 
 

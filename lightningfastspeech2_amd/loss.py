@@ -12,18 +12,13 @@ stochastic durations, and backward (SURVEY §8 f4's second half).
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List
 
 import torch
 
 from . import _lib
 
 _KIND = {"l1": 0, "mse": 1}
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class FastSpeech2Loss:
@@ -73,8 +68,7 @@ class FastSpeech2Loss:
             raise ValueError(f"shape mismatch: pred {tuple(pred.shape)}, truth {tuple(truth.shape)}, mask {tuple(mask.shape)}")
         out = torch.empty(2, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            st = self.lib.fs2_op_masked_loss(_ptr(pred), _ptr(truth), truth_kind, _ptr(mask), rows, inner, _KIND[kind],
-                                             _ptr(self._ws[key]), _ptr(out), C.c_void_p(stream.cuda_stream))
+            st = self.lib.fs2_op_masked_loss(pred, truth, truth_kind, mask, rows, inner, _KIND[kind], self._ws[key], out, stream)
         _lib.check(st, None, "fs2_op_masked_loss")
         return out[0]
 

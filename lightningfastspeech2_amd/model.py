@@ -34,10 +34,6 @@ _PRECISIONS = {"fp32": _lib.FS2_F32, "f32": _lib.FS2_F32, "bf16": _lib.FS2_BF16,
 # (FS2_F32_X3): ~1e-5 on the mel against "fp32" at about half its time
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class Engine:
     """Thin owner of one ``fs2_engine`` handle (one per device)."""
 
@@ -117,7 +113,7 @@ class Engine:
             pass
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return torch.cuda.current_stream(self.device)
 
     def set_debug(self, on: bool):
         _lib.check(self.lib.fs2_set_debug(self.handle, int(on)), self.handle, "set_debug")
@@ -127,12 +123,11 @@ class Engine:
         B, L = phones.shape
         T = C.c_int32(0)
         if priors is not None:  # (n_priors, B) fp32 on the device
-            _lib.check(self.lib.fs2_set_priors(self.handle, _ptr(priors), B), self.handle, "set_priors")
+            _lib.check(self.lib.fs2_set_priors(self.handle, priors, B), self.handle, "set_priors")
         with torch.cuda.device(self.device):
             if self.torch_workspace:  # sized for the frame count this (B, L) produced last time, if any
                 self._ensure_workspace(B, L, self._t_hint.get((B, L), 0))
-            st = self.lib.fs2_encode(self.handle, _ptr(phones), _ptr(speaker), B, L, _ptr(forced_durations),
-                                     self._stream(), C.byref(T))
+            st = self.lib.fs2_encode(self.handle, phones, speaker, B, L, forced_durations, self._stream(), C.byref(T))
         _lib.check(st, self.handle, "encode")
         self._last = (B, L, T.value)
         self._t_hint[(B, L)] = T.value
@@ -157,8 +152,8 @@ class Engine:
             self._ws_persist = torch.empty(pb + pb // 8, dtype=torch.uint8, device=self.device)
         if grow_s:
             self._ws_scratch = torch.empty(sb + sb // 8, dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.fs2_set_workspace(self.handle, _ptr(self._ws_persist), self._ws_persist.numel(),
-                                              _ptr(self._ws_scratch), self._ws_scratch.numel()), self.handle,
+        _lib.check(self.lib.fs2_set_workspace(self.handle, self._ws_persist, self._ws_persist.numel(), self._ws_scratch,
+                                              self._ws_scratch.numel()), self.handle,
                    "set_workspace")
 
     def set_frames(self, T: int):
@@ -181,7 +176,7 @@ class Engine:
     def force_buckets(self, var_index: int, idx: torch.Tensor):
         """Next decode embeds these (B, T) int32 bucket indices for that variance (parity aid)."""
         self._keep = getattr(self, "_keep", []) + [idx]
-        _lib.check(self.lib.fs2_force_buckets(self.handle, var_index, _ptr(idx)), self.handle, "force_buckets")
+        _lib.check(self.lib.fs2_force_buckets(self.handle, var_index, idx), self.handle, "force_buckets")
 
     def alloc_outputs(self, B: int, L: int, T: int, want_aux: bool = True) -> Dict[str, torch.Tensor]:
         """Fresh output tensors for a (B, L, T) forward (the reference returns fresh tensors too)."""
@@ -203,7 +198,7 @@ class Engine:
     def force_variance_targets(self, var_index: int, tgt: torch.Tensor):
         """Next decode embeds bucketize(tgt*std+mean) for that variance (teacher forcing)."""
         self._keep = getattr(self, "_keep", []) + [tgt]
-        _lib.check(self.lib.fs2_force_variance_targets(self.handle, var_index, _ptr(tgt)), self.handle,
+        _lib.check(self.lib.fs2_force_variance_targets(self.handle, var_index, tgt), self.handle,
                    "force_variance_targets")
 
     def decode(self, want_aux: bool = True, outputs: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
@@ -243,7 +238,7 @@ class Engine:
             t = torch.empty(B, L if phone else T, dtype=torch.int32, device=self.device)
         else:
             t = torch.empty(B, T, H, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.fs2_debug_copy(self.handle, what.encode(), _ptr(t), self._stream()), self.handle,
+        _lib.check(self.lib.fs2_debug_copy(self.handle, what.encode(), t, self._stream()), self.handle,
                    f"debug_copy({what})")
         return t
 

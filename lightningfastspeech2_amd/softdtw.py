@@ -3,8 +3,6 @@
 All arithmetic in libfs2_hip.so (csrc/softdtw.hip) through ``fs2_op_soft_dtw``; no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -19,9 +17,8 @@ def soft_dtw_values(x: torch.Tensor, y: torch.Tensor, gamma: float) -> torch.Ten
         raise ValueError(f"expected (B, N, D) and (B, M, D), got {tuple(x.shape)} and {tuple(y.shape)}")
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        st = _lib.load().fs2_op_soft_dtw(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), x.shape[0], x.shape[1], y.shape[1],
-                                         x.shape[2], float(gamma), C.c_void_p(out.data_ptr()),
-                                         C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        st = _lib.load().fs2_op_soft_dtw(x, y, x.shape[0], x.shape[1], y.shape[1], x.shape[2], gamma, out,
+                                         torch.cuda.current_stream(x.device))
     _lib.check(st, None, "fs2_op_soft_dtw")
     return out
 
@@ -42,9 +39,7 @@ def soft_dtw_value_and_grad(x: torch.Tensor, y: torch.Tensor, gamma: float):
     nbytes = lib.fs2_op_soft_dtw_grad_scratch_bytes(B, N, M)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        st = lib.fs2_op_soft_dtw_grad(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), B, N, M, D, float(gamma),
-                                      C.c_void_p(out.data_ptr()), C.c_void_p(gx.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes,
-                                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        st = lib.fs2_op_soft_dtw_grad(x, y, B, N, M, D, gamma, out, gx, scratch, nbytes, torch.cuda.current_stream(x.device))
     _lib.check(st, None, "fs2_op_soft_dtw_grad")
     return out, gx
 

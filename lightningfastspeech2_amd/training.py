@@ -43,10 +43,6 @@ _KIND = {"l1": 0, "mse": 1}
 _PRECISIONS = {"fp32": (F32, torch.float32), "bf16": (BF16, torch.bfloat16)}
 
 
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class _Ops:
     """Thin typed wrappers: torch tensors in, C ABI launches on torch's current stream."""
 
@@ -79,7 +75,7 @@ class _Ops:
         return self._site
 
     def st(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        return torch.cuda.current_stream(self.dev)
 
     def empty(self, *shape, dtype=torch.float32):
         return torch.empty(*shape, dtype=dtype, device=self.dev)
@@ -92,7 +88,7 @@ class _Ops:
         if self.dt == F32:
             return x
         y = self.act(*x.shape)
-        self.ck(self.lib.fs2_op_convert(F32, self.dt, _p(x), _p(y), x.numel(), self.st()), "convert")
+        _lib.check(self.lib.fs2_op_convert(F32, self.dt, x, y, x.numel(), self.st()), None, "convert")
         return y
 
     @staticmethod
@@ -125,35 +121,30 @@ class _Ops:
             self._ws[key] = t
         return t
 
-    def ck(self, status, what):
-        _lib.check(status, None, what)
-
     # ---- forward operators (the inference path's own launches, fp32) ----
     def gemm(self, x, w, bias, M, N, Cin, taps=1, S=None, relu=False, out_f32=False, gate=None, gate_scale=1.0):
         y = self.empty(M, N) if out_f32 else self.act(M, N)
         if gate is not None:  # y = gate > 0 ? gate_scale * x w^T : 0 in the store, where the kernel has that epilogue
-            st_ = self.lib.fs2_op_gemm_gated(self.dt, _p(x), _p(w), _p(bias), _p(gate), C.c_float(gate_scale), _p(y), M, N, Cin, taps,
-                                             S or M, self.st())
+            st_ = self.lib.fs2_op_gemm_gated(self.dt, x, w, bias, gate, gate_scale, y, M, N, Cin, taps, S or M, self.st())
             if st_ == 0:
                 return y
             if st_ != _lib.FS2_ERR_SHAPE:  # only "no such epilogue for this shape" falls back; a launch failure is raised
-                self.ck(st_, "gemm_gated")
-            self.ck(self.lib.fs2_op_gemm(self.dt, self.dt, _p(x), _p(w), _p(bias), _p(y), M, N, Cin, taps, S or M, 0, self.st()), "gemm")
+                _lib.check(st_, None, "gemm_gated")
+            _lib.check(self.lib.fs2_op_gemm(self.dt, self.dt, x, w, bias, y, M, N, Cin, taps, S or M, 0, self.st()), None, "gemm")
             return self.gate_(y, gate, gate_scale)
-        self.ck(self.lib.fs2_op_gemm(self.dt, F32 if out_f32 else self.dt, _p(x), _p(w), _p(bias), _p(y), M, N, Cin, taps, S or M,
-                                     int(relu), self.st()), "gemm")
+        _lib.check(self.lib.fs2_op_gemm(self.dt, F32 if out_f32 else self.dt, x, w, bias, y, M, N, Cin, taps, S or M, int(relu), self.st()), None, "gemm")
         return y
 
     def gemm_relu_dropout(self, x, w, bias, M, N, Cin, taps, S, p, key):
         """dropout(relu(x W^T + bias)) - the mask of ``dropout(., p, key)`` - in one launch where the slab kernel runs the shape."""
         if p > 0 and self.fuse_ln_drop:
             y = self.act(M, N)
-            st_ = self.lib.fs2_op_gemm_relu_dropout(self.dt, _p(x), _p(w), _p(bias), _p(y), M, N, Cin, taps, S or M, C.c_float(p),
-                                                    C.c_uint64(self.seed), C.c_uint64(key), self.st())
+            st_ = self.lib.fs2_op_gemm_relu_dropout(self.dt, x, w, bias, y, M, N, Cin, taps, S or M, p, C.c_uint64(self.seed),
+                                                    C.c_uint64(key), self.st())
             if st_ == 0:
                 return y
             if st_ != _lib.FS2_ERR_SHAPE:
-                self.ck(st_, "gemm_relu_dropout")
+                _lib.check(st_, None, "gemm_relu_dropout")
         return self.dropout(self.gemm(x, w, bias, M, N, Cin, taps=taps, S=S, relu=True), p, key)
 
     def gemm_ln_tape(self, x, w, bias, res, g, b, M, N, Cin, taps=1, S=None, relu=False, drop=None):
@@ -166,22 +157,19 @@ class _Ops:
         if drop is not None and drop[0] > 0:
             if not self.fuse_ln_drop:
                 return None
-            st_ = self.lib.fs2_op_gemm_ln_tape_dropout(self.dt, _p(x), _p(w), _p(bias), _p(res), _p(g), _p(b), _p(y), _p(z), M, N, Cin, taps,
-                                                       S or M, int(relu), C.c_float(drop[0]), C.c_uint64(self.seed), C.c_uint64(drop[1]),
-                                                       self.st())
+            st_ = self.lib.fs2_op_gemm_ln_tape_dropout(self.dt, x, w, bias, res, g, b, y, z, M, N, Cin, taps, S or M, int(relu), drop[0],
+                                                       C.c_uint64(self.seed), C.c_uint64(drop[1]), self.st())
         else:
-            st_ = self.lib.fs2_op_gemm_ln_tape(self.dt, _p(x), _p(w), _p(bias), _p(res), _p(g), _p(b), _p(y), _p(z), M, N, Cin, taps,
-                                               S or M, int(relu), self.st())
+            st_ = self.lib.fs2_op_gemm_ln_tape(self.dt, x, w, bias, res, g, b, y, z, M, N, Cin, taps, S or M, int(relu), self.st())
         if st_ == _lib.FS2_ERR_SHAPE:
             return None
-        self.ck(st_, "gemm_ln_tape")
+        _lib.check(st_, None, "gemm_ln_tape")
         return y, z
 
     def layernorm(self, x, res, g, b, M, H, dot_w=None, dot_b=0.0, mask=None, want_y=True):
         y = self.act(M, H) if want_y else None
         pred = self.empty(M) if dot_w is not None else None
-        self.ck(self.lib.fs2_op_layernorm(self.dt, _p(x), _p(res), _p(g), _p(b), _p(y), _p(dot_w), C.c_float(dot_b), _p(mask),
-                                          _p(pred), M, H, self.st()), "layernorm")
+        _lib.check(self.lib.fs2_op_layernorm(self.dt, x, res, g, b, y, dot_w, dot_b, mask, pred, M, H, self.st()), None, "layernorm")
         return y, pred
 
     # ---- backward operators ----
@@ -195,8 +183,7 @@ class _Ops:
         if A.dtype != B.dtype:
             raise TypeError(f"bgemm operands differ: {A.dtype} vs {B.dtype}")
         ws = self.ws("bgemm", int(self.lib.fs2_op_bgemm_ws_bytes(C.byref(d))))
-        self.ck(self.lib.fs2_op_bgemm(F32 if A.dtype == torch.float32 else BF16, C.byref(d), _p(A), _p(B), _p(Cout), _p(bias), _p(ws),
-                                      self.st()), "bgemm")
+        _lib.check(self.lib.fs2_op_bgemm(F32 if A.dtype == torch.float32 else BF16, C.byref(d), A, B, Cout, bias, ws, self.st()), None, "bgemm")
         return Cout
 
     def tn256(self, **kw):
@@ -214,37 +201,36 @@ class _Ops:
 
     def col_sum(self, x, out, M, N, seg=0, accumulate=True, scale=1.0, ldx=None):
         ws = self.ws("colsum", int(self.lib.fs2_op_col_sum_ws_bytes(M, N, seg)))
-        self.ck(self.lib.fs2_op_col_sum(self._dt(x), _p(x), _p(out), _p(ws), M, N, ldx or N, seg, int(accumulate), C.c_float(scale),
-                                        self.st()), "col_sum")
+        _lib.check(self.lib.fs2_op_col_sum(self._dt(x), x, out, ws, M, N, ldx or N, seg, int(accumulate), scale, self.st()), None, "col_sum")
 
     def col_sum2(self, x, out, out2, n1, M, N, ldx=None, accumulate=True, accumulate2=True):
         """columns [0, n1) of the sums to out, [n1, N) to out2"""
         ws = self.ws("colsum", int(self.lib.fs2_op_col_sum_ws_bytes(M, N, 0)))
-        self.ck(self.lib.fs2_op_col_sum2(self._dt(x), _p(x), _p(out), _p(out2), n1, _p(ws), M, N, ldx or N, int(accumulate),
-                                         int(accumulate2), C.c_float(1.0), self.st()), "col_sum2")
+        _lib.check(self.lib.fs2_op_col_sum2(self._dt(x), x, out, out2, n1, ws, M, N, ldx or N, int(accumulate), int(accumulate2), 1.0,
+                                            self.st()), None, "col_sum2")
 
     def scatter_rows(self, x, idx32, idx64, table, R, H, V, skip_row):
         """embedding backward: table[idx[r]] += x[r]"""
         ws = self.ws("scatter", int(self.lib.fs2_op_scatter_rows_ws_bytes(R, H, V)))
-        self.ck(self.lib.fs2_op_scatter_rows(self._dt(x), _p(x), _p(idx32), _p(idx64), _p(table), _p(ws), R, H, V, skip_row, self.st()),
+        _lib.check(self.lib.fs2_op_scatter_rows(self._dt(x), x, idx32, idx64, table, ws, R, H, V, skip_row, self.st()), None,
                 "scatter_rows")
 
     def relu_bwd(self, dy, y):
         """in place: dy *= (y > 0)"""
         self._guard(dy)
-        self.ck(self.lib.fs2_op_ew(self._dt(dy), 1, _p(dy), _p(y), _p(dy), dy.numel(), C.c_float(0), C.c_float(0), self.st()), "relu_bwd")
+        _lib.check(self.lib.fs2_op_ew(self._dt(dy), 1, dy, y, dy, dy.numel(), 0, 0, self.st()), None, "relu_bwd")
         return dy
 
     def gate_(self, dy, y, scale=1.0):
         """in place: dy = y > 0 ? scale * dy : 0"""
         self.relu_bwd(dy, y)
         if scale != 1.0:
-            self.ck(self.lib.fs2_op_ew(self._dt(dy), 2, _p(dy), None, _p(dy), dy.numel(), C.c_float(scale), C.c_float(0), self.st()), "scale")
+            _lib.check(self.lib.fs2_op_ew(self._dt(dy), 2, dy, None, dy, dy.numel(), scale, 0, self.st()), None, "scale")
         return dy
 
     def dwconv(self, x, w, bias, B, S, Cc, k):
         y = self.act(B * S, Cc)
-        self.ck(self.lib.fs2_op_dwconv(self.dt, _p(x), _p(w), _p(bias), _p(y), B, S, Cc, k, self.st()), "dwconv")
+        _lib.check(self.lib.fs2_op_dwconv(self.dt, x, w, bias, y, B, S, Cc, k, self.st()), None, "dwconv")
         return y
 
     def dwconv_bwd(self, du, x, w, gw, gb, B, S, Cc, k):
@@ -253,7 +239,7 @@ class _Ops:
 
         def wg():  # parameter gradients: a leaf (side stream where there is one)
             part = self.empty(nparts, Cc * (k + 1))
-            self.ck(self.lib.fs2_op_dwconv_wgrad(self.dt, _p(du), _p(x), _p(part), B, S, Cc, k, self.st()), "dwconv_wgrad")
+            _lib.check(self.lib.fs2_op_dwconv_wgrad(self.dt, du, x, part, B, S, Cc, k, self.st()), None, "dwconv_wgrad")
             if gb.data_ptr() == gw.data_ptr() + 4 * Cc * k:
                 self.col_sum(part, gw, nparts, Cc * (k + 1))
             else:
@@ -261,7 +247,7 @@ class _Ops:
                 self.col_sum(part[:, Cc * k:], gb, nparts, Cc, ldx=Cc * (k + 1))
         self.on_side((du, x), wg)
         dx = self.act(B * S, Cc)
-        self.ck(self.lib.fs2_op_dwconv_dgrad(self.dt, _p(du), _p(w), _p(dx), B, S, Cc, k, self.st()), "dwconv_dgrad")
+        _lib.check(self.lib.fs2_op_dwconv_dgrad(self.dt, du, w, dx, B, S, Cc, k, self.st()), None, "dwconv_dgrad")
         return dx
 
     def dropout(self, x, p, key, out=None):
@@ -271,13 +257,12 @@ class _Ops:
             return x
         y = x if out is None else out
         self._guard(y)
-        self.ck(self.lib.fs2_op_dropout(self._dt(x), _p(x), _p(y), x.numel(), C.c_float(p), C.c_uint64(self.seed), C.c_uint64(key),
-                                        self.st()), "dropout")
+        _lib.check(self.lib.fs2_op_dropout(self._dt(x), x, y, x.numel(), p, C.c_uint64(self.seed), C.c_uint64(key), self.st()), None, "dropout")
         return y
 
     def add_(self, a, b):
         self._guard(a)
-        self.ck(self.lib.fs2_op_ew(self._dt(a), 0, _p(a), _p(b), _p(a), a.numel(), C.c_float(1), C.c_float(1), self.st()), "add")
+        _lib.check(self.lib.fs2_op_ew(self._dt(a), 0, a, b, a, a.numel(), 1, 1, self.st()), None, "add")
         return a
 
     # y = x W^T + b backward pieces.  w is (N, taps*Cin) tap-major; x (M, Cin); dy (M, N); rows in utterances of S.
@@ -293,24 +278,24 @@ class _Ops:
             if ks > 1:
                 dx = out if out is not None else self.act(M, Cin)
                 part = self.empty(ks, M, Cin)
-                st_ = self.lib.fs2_op_gemm_splitk(self.dt, self._dt(dx), _p(dy), _p(wt), _p(dx), _p(part), M, Cin, N, taps, S or M, ks,
+                st_ = self.lib.fs2_op_gemm_splitk(self.dt, self._dt(dx), dy, wt, dx, part, M, Cin, N, taps, S or M, ks,
                                                   int(bool(accumulate and out is not None)), self.st())
                 if st_ == 0:
                     return dx
                 if st_ != _lib.FS2_ERR_SHAPE:
-                    self.ck(st_, "gemm_splitk")
+                    _lib.check(st_, None, "gemm_splitk")
             if out is not None and accumulate and gate is None and self.fuse_add:
                 # out += dy . wt in the GEMM's own store (the accumulators start at out's tile)
-                st_ = self.lib.fs2_op_gemm_add(self.dt, _p(dy), _p(wt), None, _p(out), _p(out), M, Cin, N, taps, S or M, self.st())
+                st_ = self.lib.fs2_op_gemm_add(self.dt, dy, wt, None, out, out, M, Cin, N, taps, S or M, self.st())
                 if st_ == 0:
                     return out
                 if st_ != _lib.FS2_ERR_SHAPE:
-                    self.ck(st_, "gemm_add")
+                    _lib.check(st_, None, "gemm_add")
             dx = self.gemm(dy, wt, None, M, Cin, N, taps=taps, S=S, gate=gate, gate_scale=gate_scale)
             if out is None:
                 return dx
             if accumulate:
-                self.ck(self.lib.fs2_op_ew(self._dt(out), 0, _p(out), _p(dx), _p(out), out.numel(), C.c_float(1), C.c_float(1), self.st()), "add")
+                _lib.check(self.lib.fs2_op_ew(self._dt(out), 0, out, dx, out, out.numel(), 1, 1, self.st()), None, "add")
             else:
                 out.copy_(dx)
             return out
@@ -505,12 +490,12 @@ class Trainer:
         o = self.ops
         with torch.cuda.device(self.dev):
             if o.dt != F32 and not converted:
-                o.ck(o.lib.fs2_op_convert(F32, o.dt, _p(self.flat_p), _p(self.flat_w), self.n_flat, o.st()), "convert")
+                _lib.check(o.lib.fs2_op_convert(F32, o.dt, self.flat_p, self.flat_w, self.n_flat, o.st()), None, "convert")
             for pfx, f in self.fold.items():
                 Hh, Ff = f["Wf"].shape
-                o.ck(o.lib.fs2_op_fold_conv2(o.dt, _p(self.P[f"{pfx}.conv2.0.weight"]), _p(self.P[f"{pfx}.conv2.0.bias"]),
-                                             _p(self.P[f"{pfx}.conv2.1.weight"]), _p(self.P[f"{pfx}.conv2.1.bias"]), _p(f["Wf"]), _p(f["bf"]),
-                                             Hh, Ff, o.st()), "fold_conv2")
+                _lib.check(o.lib.fs2_op_fold_conv2(o.dt, self.P[f"{pfx}.conv2.0.weight"], self.P[f"{pfx}.conv2.0.bias"],
+                                                   self.P[f"{pfx}.conv2.1.weight"], self.P[f"{pfx}.conv2.1.bias"], f["Wf"], f["bf"], Hh, Ff,
+                                                   o.st()), None, "fold_conv2")
             jobs = [(f["Wf"], f["WfT"], f["Wf"].shape[0], f["Wf"].shape[1], 1) for f in self.fold.values()]
             if self.use_forward_dgrad:
                 for n, wt in self.WT.items():
@@ -520,7 +505,7 @@ class Trainer:
                 return
             if o.dt == F32 or os.environ.get("FS2_TRAIN_TW_BATCH", "1") == "0":  # (A/B switch)
                 for src, dst, N, Cin, taps in jobs:
-                    o.ck(o.lib.fs2_op_transpose_weight(o.dt, _p(src), _p(dst), N, Cin, taps, o.st()), "transpose_weight")
+                    _lib.check(o.lib.fs2_op_transpose_weight(o.dt, src, dst, N, Cin, taps, o.st()), None, "transpose_weight")
                 return
             if self._tw_table is None:  # the buffers never move: build the device table once
                 rows, tiles = [], 0
@@ -529,7 +514,7 @@ class Trainer:
                     tiles += int(o.lib.fs2_op_transpose_weight_tiles(N, Cin, taps))
                 self._tw_table = (torch.tensor(rows, dtype=torch.int64, device=self.dev), len(rows), tiles)
             tab, n, tiles = self._tw_table
-            o.ck(o.lib.fs2_op_transpose_weight_batch(_p(tab), n, tiles, o.st()), "transpose_weight_batch")
+            _lib.check(o.lib.fs2_op_transpose_weight_batch(tab, n, tiles, o.st()), None, "transpose_weight_batch")
 
     def _wt(self, name):
         return self.WT.get(name) if self.use_forward_dgrad else None
@@ -612,14 +597,14 @@ class Trainer:
             vb = int(o.lib.fs2_op_attention_scratch_bytes(o.dt, B, S, H, heads, C.byref(bb)))
             vt, bits = o.ws("attn_vt", vb), o.ws("attn_bits", int(bb.value))
             lse = o.empty(B, heads, S)
-            o.ck(o.lib.fs2_op_attention_train(o.dt, _p(qkv), _p(key_pad), _p(attn), _p(vt), _p(bits), _p(lse), B, S, H, heads,
-                                              C.c_float(pd), C.c_uint64(o.seed), C.c_uint64(t["k_attn"]), o.st()), "attention_train")
+            _lib.check(o.lib.fs2_op_attention_train(o.dt, qkv, key_pad, attn, vt, bits, lse, B, S, H, heads, pd, C.c_uint64(o.seed),
+                                                    C.c_uint64(t["k_attn"]), o.st()), None, "attention_train")
         else:
             scores = o.empty(B, heads, S, S)  # fp32 in either mode; the probabilities are kept in the activation dtype
             o.bgemm(qkv, qkv[:, H:], scores, M=S, N=S, K=d, sAm=3 * H, sAk=1, sBk=1, sBn=3 * H, ldc=S, nb1=B, nb2=heads,
                     sA1=S * 3 * H, sA2=d, sB1=S * 3 * H, sB2=d, sC1=heads * S * S, sC2=S * S)
             prob = scores if o.dt == F32 else o.act(B, heads, S, S)
-            o.ck(o.lib.fs2_op_softmax_fwd(o.dt, _p(scores), _p(key_pad), _p(prob), B, heads, S, C.c_float(scale), o.st()), "softmax")
+            _lib.check(o.lib.fs2_op_softmax_fwd(o.dt, scores, key_pad, prob, B, heads, S, scale, o.st()), None, "softmax")
             del scores
             prob_d = o.dropout(prob, pd, t["k_attn"], out=o.act(B, heads, S, S)) if pd > 0 else prob  # MHA drops attention weights
             o.bgemm(prob_d, qkv[:, 2 * H:], attn, M=S, N=d, K=S, sAm=S, sAk=1, sBk=3 * H, sBn=1, ldc=H, nb1=B, nb2=heads,
@@ -664,15 +649,13 @@ class Trainer:
         dzm = None
         if out_drop is not None and out_drop[0] > 0:
             dzm = o.act(M, H)
-            o.ck(o.lib.fs2_op_layernorm_bwd_masked(o.dt, _p(z), _p(res), _p(dy), _p(self.P[gname]), _p(dz), _p(dzm), _p(part), M, H,
-                                                   int(relu_mask), C.c_float(out_drop[0]), C.c_uint64(o.seed), C.c_uint64(out_drop[1]),
-                                                   o.st()), "layernorm_bwd")
+            _lib.check(o.lib.fs2_op_layernorm_bwd_masked(o.dt, z, res, dy, self.P[gname], dz, dzm, part, M, H, int(relu_mask), out_drop[0],
+                                                         C.c_uint64(o.seed), C.c_uint64(out_drop[1]), o.st()), None, "layernorm_bwd")
         elif drop is not None and drop[0] > 0:  # dy is the gradient of dropout(y): the mask is applied on load, no separate pass
-            o.ck(o.lib.fs2_op_layernorm_bwd_dropout(o.dt, _p(z), _p(res), _p(dy), _p(self.P[gname]), _p(dz), _p(part), M, H, int(relu_mask),
-                                                    C.c_float(drop[0]), C.c_uint64(o.seed), C.c_uint64(drop[1]), o.st()), "layernorm_bwd")
+            _lib.check(o.lib.fs2_op_layernorm_bwd_dropout(o.dt, z, res, dy, self.P[gname], dz, part, M, H, int(relu_mask), drop[0],
+                                                          C.c_uint64(o.seed), C.c_uint64(drop[1]), o.st()), None, "layernorm_bwd")
         else:
-            o.ck(o.lib.fs2_op_layernorm_bwd(o.dt, _p(z), _p(res), _p(dy), _p(self.P[gname]), _p(dz), _p(part), M, H, int(relu_mask),
-                                            o.st()), "layernorm_bwd")
+            _lib.check(o.lib.fs2_op_layernorm_bwd(o.dt, z, res, dy, self.P[gname], dz, part, M, H, int(relu_mask), o.st()), None, "layernorm_bwd")
         gw, gb = self.G[gname], self.G[bname]
 
         def sums():
@@ -715,9 +698,9 @@ class Trainer:
             f = self.fold[prefix]
             dWf = torch.zeros(H, F_, device=self.dev)
             o.wgrad(dc2, t["h"], dWf, None, M, H, F_, sync=True)
-            o.ck(o.lib.fs2_op_unfold_conv2(_p(dWf), _p(dbf), _p(P[f"{prefix}.conv2.0.weight"]), _p(P[f"{prefix}.conv2.0.bias"]),
-                                           _p(P[f"{prefix}.conv2.1.weight"]), _p(G[f"{prefix}.conv2.0.weight"]), _p(G[f"{prefix}.conv2.0.bias"]),
-                                           _p(G[f"{prefix}.conv2.1.weight"]), _p(G[f"{prefix}.conv2.1.bias"]), H, F_, o.st()), "unfold_conv2")
+            _lib.check(o.lib.fs2_op_unfold_conv2(dWf, dbf, P[f"{prefix}.conv2.0.weight"], P[f"{prefix}.conv2.0.bias"],
+                                                 P[f"{prefix}.conv2.1.weight"], G[f"{prefix}.conv2.0.weight"], G[f"{prefix}.conv2.0.bias"],
+                                                 G[f"{prefix}.conv2.1.weight"], G[f"{prefix}.conv2.1.bias"], H, F_, o.st()), None, "unfold_conv2")
         # dh = (dc2 . W2) o [h > 0] / (1 - p): h = dropout(relu(.)) of the forward is > 0 exactly where the element was kept AND the
         # pre-activation was positive, so the ReLU backward and the dropout backward ride in the product's store together
         gate = t["h"] if os.environ.get("FS2_TRAIN_GATE", "1") != "0" else None  # (A/B switch)
@@ -752,11 +735,11 @@ class Trainer:
         qkv, prob = t["qkv"], t["prob"]
         dqkv = o.act(M, 3 * H)
         delta = o.empty(B, heads, S)
-        o.ck(o.lib.fs2_op_attn_delta(o.dt, _p(dattn), _p(t["attn"]), _p(delta), B, S, H, heads, o.st()), "attn_delta")
+        _lib.check(o.lib.fs2_op_attn_delta(o.dt, dattn, t["attn"], delta, B, S, H, heads, o.st()), None, "attn_delta")
         if t["lse"] is not None:  # recomputing backward: P, dP, dS live in registers only
         # (its two launches - (dK, dV) and dQ - side by side on two streams measured nothing: 10.4-10.5 ms either way, r04)
-            o.ck(o.lib.fs2_op_attention_bwd(o.dt, _p(qkv), _p(dattn), _p(t["lse"]), _p(delta), _p(t["key_pad"]), _p(dqkv), B, S, H, heads,
-                                            C.c_float(pd), C.c_uint64(o.seed), C.c_uint64(t["k_attn"]), o.st()), "attention_bwd")
+            _lib.check(o.lib.fs2_op_attention_bwd(o.dt, qkv, dattn, t["lse"], delta, t["key_pad"], dqkv, B, S, H, heads, pd,
+                                                  C.c_uint64(o.seed), C.c_uint64(t["k_attn"]), o.st()), None, "attention_bwd")
         else:
             bat = dict(nb1=B, nb2=heads)
             sP = dict(sA1=heads * S * S, sA2=S * S)
@@ -770,8 +753,8 @@ class Trainer:
                                sC1=heads * S * S, sC2=S * S, alpha=t["scale"], beta=0.0, splitk=1, taps=1, nb1=B, nb2=heads,
                                c_dtype=o.dt).items():
                 setattr(dsc, k_, v_)
-            o.ck(o.lib.fs2_op_bgemm_softmax_bwd(o.dt, C.byref(dsc), _p(dattn), _p(qkv[:, 2 * H:]), _p(dp), _p(prob), _p(delta),
-                                                C.c_float(pd), C.c_uint64(o.seed), C.c_uint64(t["k_attn"]), o.st()), "bgemm_softmax_bwd")
+            _lib.check(o.lib.fs2_op_bgemm_softmax_bwd(o.dt, C.byref(dsc), dattn, qkv[:, 2 * H:], dp, prob, delta, pd, C.c_uint64(o.seed),
+                                                      C.c_uint64(t["k_attn"]), o.st()), None, "bgemm_softmax_bwd")
             # dQ = dS K ; dK = dS^T Q
             o.bgemm(dp, qkv[:, H:], dqkv, M=S, N=d, K=S, sAm=S, sAk=1, sBk=3 * H, sBn=1, ldc=3 * H, sB1=S * 3 * H, sB2=d,
                     sC1=S * 3 * H, sC2=d, **bat, **sP)
@@ -811,30 +794,29 @@ class Trainer:
             if pd > 0:  # VarianceConvolutionLayer ends in nn.Dropout (model.py:539,557): inside the LayerNorm launch
                 kd = o.site()
                 yn, pred = o.act(M, filt), None
-                o.ck(o.lib.fs2_op_layernorm_dropout(o.dt, _p(c), None, _p(P[f"{p}.2.weight"]), _p(P[f"{p}.2.bias"]), _p(yn), M, filt,
-                                                    C.c_float(pd), C.c_uint64(o.seed), C.c_uint64(kd), o.st()), "layernorm_dropout")
+                _lib.check(o.lib.fs2_op_layernorm_dropout(o.dt, c, None, P[f"{p}.2.weight"], P[f"{p}.2.bias"], yn, M, filt, pd,
+                                                          C.c_uint64(o.seed), C.c_uint64(kd), o.st()), None, "layernorm_dropout")
             else:
                 if fused_head:  # LayerNorm + the Linear(filter, 1) head + mask in one launch, the head's bias read on the device
                     yn, pred = o.act(M, filt), o.empty(M)
-                    o.ck(o.lib.fs2_op_layernorm_head(o.dt, _p(c), None, _p(P[f"{p}.2.weight"]), _p(P[f"{p}.2.bias"]), _p(yn),
-                                                     _p(P[f"{prefix}.linear.weight"]), _p(P[f"{prefix}.linear.bias"]), _p(mask), _p(pred),
-                                                     M, filt, o.st()), "layernorm_head")
+                    _lib.check(o.lib.fs2_op_layernorm_head(o.dt, c, None, P[f"{p}.2.weight"], P[f"{p}.2.bias"], yn,
+                                                           P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, pred, M, filt,
+                                                           o.st()), None, "layernorm_head")
                 else:
                     yn, pred = o.layernorm(c, None, P[f"{p}.2.weight"], P[f"{p}.2.bias"], M, filt)
                 kd = o.site()
             if last and pd > 0 and cwt is None:
                 pred = o.empty(M)
-                o.ck(o.lib.fs2_op_row_dot(o.dt, _p(yn), _p(P[f"{prefix}.linear.weight"]), _p(P[f"{prefix}.linear.bias"]), _p(mask), _p(pred),
-                                          M, filt, o.st()), "row_dot")
+                _lib.check(o.lib.fs2_op_row_dot(o.dt, yn, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, pred, M, filt, o.st()), None, "row_dot")
             tape.append({"xin": y, "c": c, "cin": cin, "u": u, "kd": kd})
             y, cin = yn, filt
         ybar = None
         if cwt is not None:  # out_conv = y (behind the last layer's Dropout): ten dots per row + the utterance mean, one pass
             spec, ybar, ms = o.empty(M, 10), o.empty(B, filt), o.empty(B, 2)
             ws = o.ws("cwt_head", int(o.lib.fs2_op_cwt_head_train_ws_bytes(B, S, filt)))
-            o.ck(o.lib.fs2_op_cwt_head_train(o.dt, _p(y), _p(P[f"{prefix}.linear.weight"]), _p(P[f"{prefix}.linear.bias"]),
-                                             _p(P[f"{cwt}.mean_std_linear.weight"]), _p(P[f"{cwt}.mean_std_linear.bias"]), _p(mask),
-                                             _p(spec), _p(ybar), _p(ms), _p(ws), B, S, filt, o.st()), "cwt_head_train")
+            _lib.check(o.lib.fs2_op_cwt_head_train(o.dt, y, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"],
+                                                   P[f"{cwt}.mean_std_linear.weight"], P[f"{cwt}.mean_std_linear.bias"], mask, spec, ybar,
+                                                   ms, ws, B, S, filt, o.st()), None, "cwt_head_train")
             pred = (spec, ms)
         return pred, {"layers": tape, "y": y, "pd": pd, "ybar": ybar}
 
@@ -847,10 +829,10 @@ class Trainer:
             dspec, dms = dpred
             dy = o.act(M, filt)
             ws = o.ws("cwt_head_bwd", int(o.lib.fs2_op_cwt_head_bwd_ws_bytes(B, S, filt)))
-            o.ck(o.lib.fs2_op_cwt_head_bwd(o.dt, _p(t["y"]), _p(dspec), _p(dms), _p(t["ybar"]), _p(P[f"{prefix}.linear.weight"]),
-                                           _p(P[f"{cwt}.mean_std_linear.weight"]), _p(dy), _p(G[f"{prefix}.linear.weight"]),
-                                           _p(G[f"{prefix}.linear.bias"]), _p(G[f"{cwt}.mean_std_linear.weight"]),
-                                           _p(G[f"{cwt}.mean_std_linear.bias"]), _p(ws), B, S, filt, o.st()), "cwt_head_bwd")
+            _lib.check(o.lib.fs2_op_cwt_head_bwd(o.dt, t["y"], dspec, dms, t["ybar"], P[f"{prefix}.linear.weight"],
+                                                 P[f"{cwt}.mean_std_linear.weight"], dy, G[f"{prefix}.linear.weight"],
+                                                 G[f"{prefix}.linear.bias"], G[f"{cwt}.mean_std_linear.weight"],
+                                                 G[f"{cwt}.mean_std_linear.bias"], ws, B, S, filt, o.st()), None, "cwt_head_bwd")
             return self._predictor_layers_bwd(dy, t, prefix, nlayers, filt, k, B, S, dx_out, dw)
         # pred = y . w + b  (masked rows carry dpred = 0 already): dw = sum_m dpred[m] y[m] as a row-weighted column sum (fp32
         # weights; as a 1 x filt x M product on the 128 x 128 GEMM tile it took 51 us per head)
@@ -858,8 +840,8 @@ class Trainer:
 
         def head_w():
             ws = o.ws("colsum", int(o.lib.fs2_op_col_sum_ws_bytes(M, filt, 0)))
-            o.ck(o.lib.fs2_op_col_sum_weighted(o._dt(t["y"]), _p(t["y"]), _p(dpred32), _p(G[f"{prefix}.linear.weight"]), _p(ws), M, filt, filt, 1,
-                                               C.c_float(1.0), o.st()), "col_sum_weighted")
+            _lib.check(o.lib.fs2_op_col_sum_weighted(o._dt(t["y"]), t["y"], dpred32, G[f"{prefix}.linear.weight"], ws, M, filt, filt, 1,
+                                                     1.0, o.st()), None, "col_sum_weighted")
         head_w()
         dpred = o.to_act(dpred)
         o.col_sum(dpred, G[f"{prefix}.linear.bias"], M, 1)
@@ -921,13 +903,12 @@ class Trainer:
         if kind == "soft_dtw":
             return self._loss_soft_dtw(name, pred, truth, truth_kind, mask, rows, inner)
         stat = o.empty(2)
-        o.ck(o.lib.fs2_op_masked_loss(_p(pred), _p(truth), truth_kind, _p(mask), rows, inner, _KIND[kind], _p(self._loss_ws),
-                                      _p(stat), o.st()), "masked_loss")
+        _lib.check(o.lib.fs2_op_masked_loss(pred, truth, truth_kind, mask, rows, inner, _KIND[kind], self._loss_ws, stat, o.st()), None, "masked_loss")
         dpred = None
         if want_grad:
             dpred = o.empty(rows, inner) if inner > 1 else o.empty(rows)
-            o.ck(o.lib.fs2_op_masked_loss_bwd(_p(pred), _p(truth), truth_kind, _p(mask), _p(stat), _p(dpred), rows, inner,
-                                              _KIND[kind], C.c_float(self.loss_alphas[name]), o.st()), "masked_loss_bwd")
+            _lib.check(o.lib.fs2_op_masked_loss_bwd(pred, truth, truth_kind, mask, stat, dpred, rows, inner, _KIND[kind],
+                                                    self.loss_alphas[name], o.st()), None, "masked_loss_bwd")
         return stat, dpred
 
     # ---- the step ----
@@ -974,17 +955,16 @@ class Trainer:
             pe_drop = self.p_enc > 0  # PositionalEncoding(dropout=encoder_dropout) serves both stacks (fastspeech2.py:296-298)
             k_pe_enc, k_pe_dec = o.site(), o.site()
             spk = o.empty(B, H)
-            o.ck(o.lib.fs2_op_spk_proj(_p(dvec), _p(P["speaker_embedding.projection.weight"]), _p(P["speaker_embedding.projection.bias"]),
-                                       _p(spk), B, H, dvec.shape[1], o.st()), "spk_proj")
+            _lib.check(o.lib.fs2_op_spk_proj(dvec, P["speaker_embedding.projection.weight"], P["speaker_embedding.projection.bias"], spk, B,
+                                             H, dvec.shape[1], o.st()), None, "spk_proj")
             x = o.act(B * L, H)
             src_mask = o.empty(B, L, dtype=torch.uint8)
             zero_spk = torch.zeros(B, H, device=dev) if pe_drop else None
-            o.ck(o.lib.fs2_op_embed(o.dt, _p(phones), _p(P["phone_embedding.weight"]), _p(pe), _p(zero_spk if pe_drop else spk), _p(x),
-                                    _p(src_mask), B, L, H, cfg.n_phones, o.st()), "embed")
+            _lib.check(o.lib.fs2_op_embed(o.dt, phones, P["phone_embedding.weight"], pe, zero_spk if pe_drop else spk, x, src_mask, B, L, H,
+                                          cfg.n_phones, o.st()), None, "embed")
             if pe_drop:  # x = dropout(E[phones] + pe) + spk   (model.py:53-55, fastspeech2.py:655-660)
                 o.dropout(x, self.p_enc, k_pe_enc)
-                o.ck(o.lib.fs2_op_bucket_embed(o.dt, _p(x), None, None, None, 0, C.c_float(1), C.c_float(0), None, _p(spk), _p(x), None,
-                                               B, L, H, o.st()), "add_spk")
+                _lib.check(o.lib.fs2_op_bucket_embed(o.dt, x, None, None, None, 0, 1, 0, None, spk, x, None, B, L, H, o.st()), None, "add_spk")
             enc_t = []
             for i in range(cfg.encoder_layers):
                 x, t = self._layer_fwd(x, f"encoder.layers.{i}", B, L, cfg.encoder_head, cfg.encoder_conv_filter_size,
@@ -998,12 +978,11 @@ class Trainer:
                 if vals.numel() != B:
                     raise ValueError(f"priors_{pr} must hold one value per utterance")
                 remb = o.empty(cfg.variance_nbins, H)
-                o.ck(o.lib.fs2_op_ew(F32, 1, _p(P[f"{pfx}.embedding.weight"]), _p(P[f"{pfx}.embedding.weight"]), _p(remb), remb.numel(),
-                                     C.c_float(0), C.c_float(0), o.st()), "relu")
+                _lib.check(o.lib.fs2_op_ew(F32, 1, P[f"{pfx}.embedding.weight"], P[f"{pfx}.embedding.weight"], remb, remb.numel(), 0, 0, o.st()), None, "relu")
                 idx = o.empty(B * L, dtype=torch.int32)
                 xn = o.act(B * L, H)
-                o.ck(o.lib.fs2_op_bucket_embed_utt(o.dt, _p(x), _p(vals), _p(self.buffers[f"{pfx}.bins"]), _p(remb), cfg.variance_nbins,
-                                                   _p(xn), _p(idx), B, L, H, o.st()), "prior_embed")
+                _lib.check(o.lib.fs2_op_bucket_embed_utt(o.dt, x, vals, self.buffers[f"{pfx}.bins"], remb, cfg.variance_nbins, xn, idx, B,
+                                                         L, H, o.st()), None, "prior_embed")
                 prior_idx[pr] = idx.view(B, L)[:, 0].contiguous()
                 x = xn
             dur_pred, dur_tape = self._predictor_fwd(x, "variance_adaptor.duration_predictor", cfg.duration_nlayers,
@@ -1021,9 +1000,9 @@ class Trainer:
                 idx = o.empty(B * S_, dtype=torch.int32)
                 xn = o.act(B * S_, H)
                 st_ = {"std": 1.0, "mean": 0.0} if cfg.is_cwt(vi) else cfg.stats[v]  # log(signal) is bucketised as it is
-                o.ck(o.lib.fs2_op_bucket_embed_target(o.dt, _p(xa), _p(var_t[v]), _p(self.buffers[f"{pfx}.bins"]), _p(P[f"{pfx}.embedding.weight"]),
-                                                      cfg.variance_nbins, C.c_float(st_["std"]), C.c_float(st_["mean"]), pe_, spk_, _p(xn), _p(idx),
-                                                      B, S_, H, o.st()), "bucket_embed_target")
+                _lib.check(o.lib.fs2_op_bucket_embed_target(o.dt, xa, var_t[v], self.buffers[f"{pfx}.bins"], P[f"{pfx}.embedding.weight"],
+                                                            cfg.variance_nbins, st_["std"], st_["mean"], pe_, spk_, xn, idx, B, S_, H,
+                                                            o.st()), None, "bucket_embed_target")
                 var_idx[v] = idx
                 return xn
             # the duration predictor saw x as it is here; the phone-level variances follow in order, each on x + the earlier embeddings
@@ -1032,24 +1011,22 @@ class Trainer:
             forced = dur_t.to(torch.int32)
             dur, cum, totals, guard = (o.empty(B, L, dtype=torch.int32), o.empty(B, L, dtype=torch.int32),
                                        o.empty(B, dtype=torch.int32), o.empty(B, dtype=torch.int32))
-            o.ck(o.lib.fs2_op_durations(_p(dur_pred), _p(src_mask), _p(forced), _p(dur), _p(cum), _p(totals), _p(guard), B, L, o.st()), "durations")
+            _lib.check(o.lib.fs2_op_durations(dur_pred, src_mask, forced, dur, cum, totals, guard, B, L, o.st()), None, "durations")
             xr = o.act(B * T, H)
             tgt_mask = o.empty(B, T, dtype=torch.uint8)
-            o.ck(o.lib.fs2_op_regulate(o.dt, _p(x), _p(cum), _p(totals), _p(xr), _p(tgt_mask), B, L, T, H, o.st()), "regulate")
+            _lib.check(o.lib.fs2_op_regulate(o.dt, x, cum, totals, xr, tgt_mask, B, L, T, H, o.st()), None, "regulate")
             xa = xr
             for vi in frame_vis:  # the last frame-level embedding launch also adds pe (and spk)
                 last = vi == frame_vis[-1]
-                xa = variance_fwd(vi, xa, T, tgt_mask, _p(pe) if last else None, _p(spk) if (last and not pe_drop) else None)
+                xa = variance_fwd(vi, xa, T, tgt_mask, pe if last else None, spk if (last and not pe_drop) else None)
             if not frame_vis:
                 xn = o.act(B * T, H)
-                o.ck(o.lib.fs2_op_bucket_embed(o.dt, _p(xa), None, None, None, 0, C.c_float(1), C.c_float(0), _p(pe),
-                                               None if pe_drop else _p(spk), _p(xn), None, B, T, H, o.st()), "pe_spk")
+                _lib.check(o.lib.fs2_op_bucket_embed(o.dt, xa, None, None, None, 0, 1, 0, pe, None if pe_drop else spk, xn, None, B, T, H, o.st()), None, "pe_spk")
                 xa = xn
             y = xa
             if pe_drop:  # y = dropout(x + pe) + spk   (fastspeech2.py:705-718)
                 o.dropout(y, self.p_enc, k_pe_dec)
-                o.ck(o.lib.fs2_op_bucket_embed(o.dt, _p(y), None, None, None, 0, C.c_float(1), C.c_float(0), None, _p(spk), _p(y), None,
-                                               B, T, H, o.st()), "add_spk")
+                _lib.check(o.lib.fs2_op_bucket_embed(o.dt, y, None, None, None, 0, 1, 0, None, spk, y, None, B, T, H, o.st()), None, "add_spk")
             dec_t = []
             for i in range(cfg.decoder_layers):
                 y, t = self._layer_fwd(y, f"decoder.layers.{i}", B, T, cfg.decoder_head, cfg.decoder_conv_filter_size,
@@ -1108,7 +1085,7 @@ class Trainer:
             for vi in reversed(frame_vis):
                 variance_bwd(vi, dx, T)
             dxe = o.act(B * L, H)
-            o.ck(o.lib.fs2_op_regulate_bwd(o.dt, _p(dx), _p(cum), _p(dxe), B, L, T, H, o.st()), "regulate_bwd")
+            _lib.check(o.lib.fs2_op_regulate_bwd(o.dt, dx, cum, dxe, B, L, T, H, o.st()), None, "regulate_bwd")
             # the phone-level tape, all residual adds onto dxe in ONE order (bit-equal reruns): the regulator's segment sums, then the
             # phone-level variances last to first, then the duration predictor (which saw the encoder output before any of them)
             for vi in reversed(phone_vis):
@@ -1159,13 +1136,12 @@ class Trainer:
         with torch.cuda.device(self.dev):
             nsq = None
             if self.gradient_clip_val is not None:
-                o.ck(o.lib.fs2_op_sum_sq(_p(self.flat_g), self.n_flat, _p(self._nsq_ws), _p(self._nsq), o.st()), "sum_sq")
+                _lib.check(o.lib.fs2_op_sum_sq(self.flat_g, self.n_flat, self._nsq_ws, self._nsq, o.st()), None, "sum_sq")
                 nsq = self._nsq
             shadow = self.flat_w if o.dt != F32 and os.environ.get("FS2_TRAIN_ADAMW_SHADOW", "1") != "0" else None  # (A/B switch)
-            o.ck(o.lib.fs2_op_adamw_shadow(_p(self.flat_p), _p(self.flat_g), _p(self.flat_m), _p(self.flat_v), _p(shadow), self.n_flat,
-                                           C.c_float(lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                                           C.c_float(self.weight_decay), self.steps + 1, _p(nsq), C.c_float(self.gradient_clip_val or 0.0),
-                                           C.c_float(1.0 / (self._accum * world)), o.st()), "adamw")
+            _lib.check(o.lib.fs2_op_adamw_shadow(self.flat_p, self.flat_g, self.flat_m, self.flat_v, shadow, self.n_flat, lr, self.betas[0],
+                                                 self.betas[1], self.eps, self.weight_decay, self.steps + 1, nsq,
+                                                 self.gradient_clip_val or 0.0, 1.0 / (self._accum * world), o.st()), None, "adamw")
         self.steps += 1
         self.zero_grad()
         self._refresh_shadow(converted=shadow is not None)

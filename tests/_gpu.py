@@ -4,9 +4,11 @@ import ctypes as C
 import numpy as np
 import torch
 
+import _f16
 from lightningfastspeech2_amd import _lib
 
-F32, BF16 = _lib.FS2_F32, _lib.FS2_BF16
+F32, BF16, F16 = _lib.FS2_F32, _lib.FS2_BF16, _lib.FS2_F16
+_TDT = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 DEV = "cuda:0"
 
 
@@ -14,55 +16,59 @@ def lib():
     return _lib.load()
 
 
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def ok(status, what=""):
     assert status == 0, f"{what}: status {status} ({lib().fs2_status_string(status).decode()})"
 
 
 def to_dev(x, dtype):
-    """fp32 host/torch tensor -> device tensor in the engine dtype (bf16 kept as torch.bfloat16)."""
-    t = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).float().to(DEV)
-    return t.to(torch.bfloat16).contiguous() if dtype == BF16 else t.contiguous()
+    """fp32 host/torch tensor -> device tensor in the storage dtype, by the storage rule of _f16.store."""
+    t = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x)
+    return _f16.store(t, _TDT[dtype]).to(DEV).contiguous()
 
 
 def tdt(dtype):
-    return torch.bfloat16 if dtype == BF16 else torch.float32
+    return _TDT[dtype]
 
 
 def rounded(x, dtype):
-    """What the kernel actually sees: fp32 value of the (possibly bf16-rounded) input."""
-    x = torch.as_tensor(x).float()
-    return x.to(torch.bfloat16).float() if dtype == BF16 else x
+    """What the kernel actually sees: fp32 value of the (possibly 16-bit-rounded) input."""
+    return _f16.rnd16(torch.as_tensor(x).float(), _TDT[dtype])
 
 
-def gemm(dtype, x, w_packed, bias, taps=1, S=None, relu=False, out_dtype=None):
+def host(t, raw=False):
+    """a device result on the host: widened to fp32, or (raw) in its storage dtype, for tests that compare bit patterns"""
+    return None if t is None else t.cpu() if raw else t.float().cpu()
+
+
+def convert(src_dtype, dst_dtype, src):
+    """fs2_op_convert on a device tensor -> a device tensor"""
+    out = torch.empty(src.shape, dtype=tdt(dst_dtype), device=DEV)
+    ok(lib().fs2_op_convert(src_dtype, dst_dtype, src, out, src.numel(), torch.cuda.current_stream()), "convert")
+    torch.cuda.synchronize()
+    return out
+
+
+def gemm(dtype, x, w_packed, bias, taps=1, S=None, relu=False, out_dtype=None, raw=False):
     M, Cin = x.shape
     N = w_packed.shape[0]
     out_dtype = dtype if out_dtype is None else out_dtype
     xd, wd = to_dev(x, dtype), to_dev(w_packed, dtype)
     bd = None if bias is None else torch.as_tensor(bias).float().to(DEV)
     c = torch.empty(M, N, dtype=tdt(out_dtype), device=DEV)
-    ok(lib().fs2_op_gemm(dtype, out_dtype, p(xd), p(wd), p(bd), p(c), M, N, Cin, taps, S or M, int(relu), stream()), "gemm")
+    ok(lib().fs2_op_gemm(dtype, out_dtype, xd, wd, bd, c, M, N, Cin, taps, S or M, int(relu), torch.cuda.current_stream()), "gemm")
     torch.cuda.synchronize()
-    return c.float().cpu()
+    return host(c, raw)
 
 
-def gemm_add(dtype, x, w_packed, bias, addend, taps=1, S=None, in_place=True):
+def gemm_add(dtype, x, w_packed, bias, addend, taps=1, S=None, in_place=True, raw=False):
     M, Cin = x.shape
     N = w_packed.shape[0]
     xd, wd, ad = to_dev(x, dtype), to_dev(w_packed, dtype), to_dev(addend, dtype)
     bd = None if bias is None else torch.as_tensor(bias).float().to(DEV)
     c = ad if in_place else torch.empty(M, N, dtype=tdt(dtype), device=DEV)
-    ok(lib().fs2_op_gemm_add(dtype, p(xd), p(wd), p(bd), p(ad), p(c), M, N, Cin, taps, S or M, stream()), "gemm_add")
+    ok(lib().fs2_op_gemm_add(dtype, xd, wd, bd, ad, c, M, N, Cin, taps, S or M, torch.cuda.current_stream()), "gemm_add")
     torch.cuda.synchronize()
-    return c.float().cpu()
+    return host(c, raw)
 
 
 def gemm_rowscale(x, w_folded, bias_folded, parts, wg, eps=1e-5):
@@ -75,11 +81,38 @@ def gemm_rowscale(x, w_folded, bias_folded, parts, wg, eps=1e-5):
     sd = torch.as_tensor(parts).float().to(DEV).contiguous()
     gd = torch.as_tensor(wg).float().to(DEV).contiguous()
     rs = torch.empty(M, 2, dtype=torch.float32, device=DEV)
-    ok(lib().fs2_op_rowstats_finish(p(sd), int(parts.shape[1]), Cin, float(eps), p(rs), M, stream()), "rowstats_finish")
+    ok(lib().fs2_op_rowstats_finish(sd, int(parts.shape[1]), Cin, eps, rs, M, torch.cuda.current_stream()), "rowstats_finish")
     c = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
-    ok(lib().fs2_op_gemm_rowscale(p(xd), p(wd), p(bd), p(rs), p(gd), p(c), M, N, Cin, stream()), "gemm_rowscale")
+    ok(lib().fs2_op_gemm_rowscale(xd, wd, bd, rs, gd, c, M, N, Cin, torch.cuda.current_stream()), "gemm_rowscale")
     torch.cuda.synchronize()
     return c.float().cpu()
+
+
+def gemm_stats(dtype, x, w, bias, res, relu=False):
+    """fs2_op_gemm_stats: the deferred-LayerNorm epilogue -> (v (M, N) in dtype, stats (M, ceil(N / 256), 2) fp32), both left on the device."""
+    M, Cin = x.shape
+    N = w.shape[0]
+    xd, wd, bd = to_dev(x, dtype), to_dev(w, dtype), to_dev(bias, F32)
+    rd = None if res is None else to_dev(res, dtype)
+    v = torch.empty(M, N, dtype=tdt(dtype), device=DEV)
+    st = torch.full((M, (N + 255) // 256, 2), float("nan"), dtype=torch.float32, device=DEV)
+    ok(lib().fs2_op_gemm_stats(dtype, xd, wd, bd, rd, v, st, M, N, Cin, int(relu), torch.cuda.current_stream()), "gemm_stats")
+    torch.cuda.synchronize()
+    return v, st
+
+
+def gemm_rowscale_dt(dtype, v_dev, stats_dev, w_folded, bias_folded, wg, out_dtype=None, eps=1e-5):
+    """fs2_op_rowstats_finish + fs2_op_gemm_rowscale_dt on device tensors as gemm_stats left them; the result in out_dtype."""
+    M, Cin = v_dev.shape
+    N = w_folded.shape[0]
+    out_dtype = dtype if out_dtype is None else out_dtype
+    wd, bd, gd = to_dev(w_folded, dtype), to_dev(bias_folded, F32), to_dev(wg, F32)
+    rs = torch.empty(M, 2, dtype=torch.float32, device=DEV)
+    ok(lib().fs2_op_rowstats_finish(stats_dev, int(stats_dev.shape[1]), Cin, eps, rs, M, torch.cuda.current_stream()), "rowstats_finish")
+    c = torch.empty(M, N, dtype=tdt(out_dtype), device=DEV)
+    ok(lib().fs2_op_gemm_rowscale_dt(dtype, out_dtype, v_dev, wd, bd, rs, gd, c, M, N, Cin, torch.cuda.current_stream()), "gemm_rowscale_dt")
+    torch.cuda.synchronize()
+    return c.cpu()
 
 
 def gemm_head(x, w, bias, gamma, beta, w_head, b_head, mask=None, relu=True, eps=1e-5):
@@ -94,11 +127,11 @@ def gemm_head(x, w, bias, gamma, beta, w_head, b_head, mask=None, relu=True, eps
     gd = gw.to(DEV).contiguous()
     st = torch.full((M, nparts, 2), float("nan"), dtype=torch.float32, device=DEV)
     hd = torch.full((M, nparts), float("nan"), dtype=torch.float32, device=DEV)
-    ok(lib().fs2_op_gemm_head(p(xd), p(wd), p(bd), p(gd), p(st), p(hd), M, N, Cin, int(relu), stream()), "gemm_head")
+    ok(lib().fs2_op_gemm_head(xd, wd, bd, gd, st, hd, M, N, Cin, int(relu), torch.cuda.current_stream()), "gemm_head")
     md = None if mask is None else torch.as_tensor(mask).to(torch.uint8).to(DEV).contiguous()
     pred = torch.empty(M, dtype=torch.float32, device=DEV)
     cst = float((torch.as_tensor(beta).double() * torch.as_tensor(w_head).double()).sum() + b_head)
-    ok(lib().fs2_op_head_finish(p(st), p(hd), nparts, N, float(eps), float(gw.double().sum()), cst, p(md), p(pred), M, stream()), "head_finish")
+    ok(lib().fs2_op_head_finish(st, hd, nparts, N, eps, gw.double().sum(), cst, md, pred, M, torch.cuda.current_stream()), "head_finish")
     torch.cuda.synchronize()
     return pred.cpu(), st.cpu(), hd.cpu()
 
@@ -112,13 +145,13 @@ def gemm_splitk(dtype, x, w_packed, ksplit, taps=1, S=None, out_dtype=None, into
     xd, wd = to_dev(x, dtype), to_dev(w_packed, dtype)
     c = torch.empty(M, N, dtype=tdt(out_dtype), device=DEV) if into is None else to_dev(into, out_dtype).clone()
     part = torch.empty(ksplit, M, N, dtype=torch.float32, device=DEV)
-    ok(lib().fs2_op_gemm_splitk(dtype, out_dtype, p(xd), p(wd), p(c), p(part), M, N, Cin, taps, S or M, ksplit, int(into is not None),
-                                stream()), "gemm_splitk")
+    ok(lib().fs2_op_gemm_splitk(dtype, out_dtype, xd, wd, c, part, M, N, Cin, taps, S or M, ksplit, int(into is not None),
+                                torch.cuda.current_stream()), "gemm_splitk")
     torch.cuda.synchronize()
     return c.float().cpu()
 
 
-def gemm_ln(dtype, x, w_packed, bias, res, g, b, taps=1, S=None, relu=False, dot_w=None, dot_b=0.0, mask=None, want_y=True):
+def gemm_ln(dtype, x, w_packed, bias, res, g, b, taps=1, S=None, relu=False, dot_w=None, dot_b=0.0, mask=None, want_y=True, raw=False):
     M, Cin = x.shape
     N = w_packed.shape[0]
     f = lambda a: None if a is None else torch.as_tensor(a).float().to(DEV).contiguous()
@@ -129,10 +162,10 @@ def gemm_ln(dtype, x, w_packed, bias, res, g, b, taps=1, S=None, relu=False, dot
     pred = torch.empty(M, dtype=torch.float32, device=DEV) if dot_w is not None else None
     mk = None if mask is None else torch.as_tensor(mask).to(torch.uint8).to(DEV)
     bd, gd, bed, dwd = f(bias), f(g), f(b), f(dot_w)
-    ok(lib().fs2_op_gemm_ln(dtype, p(xd), p(wd), p(bd), p(rd), p(gd), p(bed), p(dwd), float(dot_b), p(mk), p(pred),
-                            p(y), p(tmp), M, N, Cin, taps, S or M, int(relu), stream()), "gemm_ln")
+    ok(lib().fs2_op_gemm_ln(dtype, xd, wd, bd, rd, gd, bed, dwd, dot_b, mk, pred, y, tmp, M, N, Cin, taps, S or M, int(relu),
+                            torch.cuda.current_stream()), "gemm_ln")
     torch.cuda.synchronize()
-    return (None if y is None else y.float().cpu()), (None if pred is None else pred.cpu())
+    return host(y, raw), host(pred)
 
 
 def predictor(x, ws, biases, gammas, betas, head_w, head_b, mask, B, S):
@@ -146,8 +179,7 @@ def predictor(x, ws, biases, gammas, betas, head_w, head_b, mask, B, S):
     mk = None if mask is None else torch.as_tensor(mask).to(torch.uint8).to(DEV).contiguous()
     pred = torch.full((B * S,), float("nan"), dtype=torch.float32, device=DEV)
     scratch = torch.empty(nl * H * k * H * 2, dtype=torch.uint8, device=DEV)
-    ok(lib().fs2_op_predictor(BF16, p(xd), p(wd), p(bd), p(gd), p(bed), p(hw), float(head_b), p(mk), p(pred), p(scratch),
-                              B, S, H, nl, k, stream()), "predictor")
+    ok(lib().fs2_op_predictor(BF16, xd, wd, bd, gd, bed, hw, head_b, mk, pred, scratch, B, S, H, nl, k, torch.cuda.current_stream()), "predictor")
     torch.cuda.synchronize()
     return pred.cpu().reshape(B, S)
 
@@ -164,8 +196,8 @@ def predictor_dw(x, dws, dwbs, ws, biases, gammas, betas, head_w, head_b, mask, 
     mk = None if mask is None else torch.as_tensor(mask).to(torch.uint8).to(DEV).contiguous()
     pred = torch.full((B * S,), float("nan"), dtype=torch.float32, device=DEV)
     scratch = torch.empty(nl * H * H * 2, dtype=torch.uint8, device=DEV)
-    ok(lib().fs2_op_predictor_dw(BF16, p(xd), p(dwd), p(dbd), p(wd), p(bd), p(gd), p(bed), p(hw), float(head_b), p(mk), p(pred), p(scratch),
-                                 B, S, H, nl, stream()), "predictor_dw")
+    ok(lib().fs2_op_predictor_dw(BF16, xd, dwd, dbd, wd, bd, gd, bed, hw, head_b, mk, pred, scratch, B, S, H, nl,
+                                 torch.cuda.current_stream()), "predictor_dw")
     torch.cuda.synchronize()
     return pred.cpu().reshape(B, S)
 
@@ -176,7 +208,7 @@ def pack_conv_weight(w):
     return w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous()
 
 
-def attention(dtype, qkv, key_pad_mask, B, S, H, heads):
+def attention(dtype, qkv, key_pad_mask, B, S, H, heads, raw=False):
     qd = to_dev(qkv, dtype)
     md = torch.as_tensor(key_pad_mask).to(torch.uint8).to(DEV).contiguous()
     out = torch.empty(B * S, H, dtype=tdt(dtype), device=DEV)
@@ -184,22 +216,22 @@ def attention(dtype, qkv, key_pad_mask, B, S, H, heads):
     vt_bytes = lib().fs2_op_attention_scratch_bytes(dtype, B, S, H, heads, C.byref(bits_bytes))
     vt = torch.empty(vt_bytes, dtype=torch.uint8, device=DEV)
     bits = torch.empty(bits_bytes.value, dtype=torch.uint8, device=DEV)
-    ok(lib().fs2_op_attention(dtype, p(qd), p(md), p(out), p(vt), p(bits), B, S, H, heads, stream()), "attention")
+    ok(lib().fs2_op_attention(dtype, qd, md, out, vt, bits, B, S, H, heads, torch.cuda.current_stream()), "attention")
     torch.cuda.synchronize()
-    return out.float().cpu()
+    return host(out, raw)
 
 
-def attn_out_ln(qkv, key_pad_mask, w_out, bias, res, gamma, beta, B, S, H, heads):
-    """fs2_op_attn_out_ln (bf16): LayerNorm(res + MHA-core(qkv) w_out^T + bias)."""
-    qd, rd, wd = to_dev(qkv, BF16), to_dev(res, BF16), to_dev(w_out, BF16)
+def attn_out_ln(qkv, key_pad_mask, w_out, bias, res, gamma, beta, B, S, H, heads, dtype=BF16, raw=False):
+    """fs2_op_attn_out_ln (16-bit storage): LayerNorm(res + MHA-core(qkv) w_out^T + bias)."""
+    qd, rd, wd = to_dev(qkv, dtype), to_dev(res, dtype), to_dev(w_out, dtype)
     md = torch.as_tensor(key_pad_mask).to(torch.uint8).to(DEV).contiguous()
     f = lambda v: torch.as_tensor(v).float().to(DEV).contiguous()
     bd, gd, bed = f(bias), f(gamma), f(beta)
-    out = torch.empty(B * S, H, dtype=torch.bfloat16, device=DEV)
+    out = torch.empty(B * S, H, dtype=tdt(dtype), device=DEV)
     scratch = torch.empty(H * H * 2 + B * ((S + 63) // 64) * 8, dtype=torch.uint8, device=DEV)
-    ok(lib().fs2_op_attn_out_ln(BF16, p(qd), p(md), p(wd), p(bd), p(rd), p(gd), p(bed), p(out), p(scratch), B, S, H, heads, stream()), "attn_out_ln")
+    ok(lib().fs2_op_attn_out_ln(dtype, qd, md, wd, bd, rd, gd, bed, out, scratch, B, S, H, heads, torch.cuda.current_stream()), "attn_out_ln")
     torch.cuda.synchronize()
-    return out.float().cpu()
+    return host(out, raw)
 
 
 def attention_x3(qkv, key_pad_mask, B, S, H, heads):
@@ -209,7 +241,7 @@ def attention_x3(qkv, key_pad_mask, B, S, H, heads):
     out = torch.empty(B * S, H, dtype=torch.float32, device=DEV)
     split = torch.empty(2 * B * S * 3 * H, dtype=torch.bfloat16, device=DEV)
     bits = torch.empty(B * ((S + 63) // 64) * 8, dtype=torch.uint8, device=DEV)
-    ok(lib().fs2_op_attention_x3(p(qd), p(md), p(out), p(split), p(bits), B, S, H, heads, stream()), "attention_x3")
+    ok(lib().fs2_op_attention_x3(qd, md, out, split, bits, B, S, H, heads, torch.cuda.current_stream()), "attention_x3")
     torch.cuda.synchronize()
     return out.cpu()
 
@@ -221,12 +253,12 @@ def gemm_split_out(x, w, bias, split=True):
     bd = None if bias is None else torch.as_tensor(bias).float().to(DEV)
     hi = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     lo = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
-    ok(lib().fs2_op_gemm_split_out(p(xd), p(wd), p(bd), p(hi), p(lo), M, N, K, int(split), stream()), "gemm_split_out")
+    ok(lib().fs2_op_gemm_split_out(xd, wd, bd, hi, lo, M, N, K, int(split), torch.cuda.current_stream()), "gemm_split_out")
     torch.cuda.synchronize()
     return hi.float().cpu(), lo.float().cpu()
 
 
-def layernorm(dtype, x, res, gamma, beta, dot_w=None, dot_b=0.0, mask=None, want_y=True):
+def layernorm(dtype, x, res, gamma, beta, dot_w=None, dot_b=0.0, mask=None, want_y=True, raw=False):
     M, H = x.shape
     xd = to_dev(x, dtype)
     rd = None if res is None else to_dev(res, dtype)
@@ -235,88 +267,27 @@ def layernorm(dtype, x, res, gamma, beta, dot_w=None, dot_b=0.0, mask=None, want
     dw = None if dot_w is None else torch.as_tensor(dot_w).float().to(DEV)
     mk = None if mask is None else torch.as_tensor(mask).to(torch.uint8).to(DEV)
     pred = torch.empty(M, dtype=torch.float32, device=DEV) if dot_w is not None else None
-    ok(lib().fs2_op_layernorm(dtype, p(xd), p(rd), p(g), p(b), p(y), p(dw), float(dot_b), p(mk), p(pred), M, H, stream()), "layernorm")
+    ok(lib().fs2_op_layernorm(dtype, xd, rd, g, b, y, dw, dot_b, mk, pred, M, H, torch.cuda.current_stream()), "layernorm")
     torch.cuda.synchronize()
-    return (None if y is None else y.float().cpu()), (None if pred is None else pred.cpu())
+    return host(y, raw), host(pred)
 
 
-def dwconv(dtype, x, w, bias, B, S):
+def dwconv(dtype, x, w, bias, B, S, raw=False):
     C_ = x.shape[1]
     k = w.shape[-1]
     xd = to_dev(x, dtype)
     wd = torch.as_tensor(w).float().reshape(C_, k).to(DEV).contiguous()
     bd = torch.as_tensor(bias).float().to(DEV)
     y = torch.empty(B * S, C_, dtype=tdt(dtype), device=DEV)
-    ok(lib().fs2_op_dwconv(dtype, p(xd), p(wd), p(bd), p(y), B, S, C_, k, stream()), "dwconv")
+    ok(lib().fs2_op_dwconv(dtype, xd, wd, bd, y, B, S, C_, k, torch.cuda.current_stream()), "dwconv")
     torch.cuda.synchronize()
-    return y.float().cpu()
-
-
-def durations(dur_pred, src_mask, forced=None):
-    B, L = dur_pred.shape
-    dp = torch.as_tensor(dur_pred).float().to(DEV).contiguous()
-    mk = torch.as_tensor(src_mask).to(torch.uint8).to(DEV).contiguous()
-    fd = None if forced is None else torch.as_tensor(forced).to(torch.int32).to(DEV).contiguous()
-    dur = torch.empty(B, L, dtype=torch.int32, device=DEV)
-    cum = torch.empty(B, L, dtype=torch.int32, device=DEV)
-    tot = torch.empty(B, dtype=torch.int32, device=DEV)
-    grd = torch.empty(B, dtype=torch.int32, device=DEV)
-    ok(lib().fs2_op_durations(p(dp), p(mk), p(fd), p(dur), p(cum), p(tot), p(grd), B, L, stream()), "durations")
-    torch.cuda.synchronize()
-    return dur.cpu(), cum.cpu(), tot.cpu(), grd.cpu()
-
-
-def regulate(dtype, x, cum, totals, B, L, T, H):
-    xd = to_dev(x, dtype)
-    cd = torch.as_tensor(cum).to(torch.int32).to(DEV).contiguous()
-    td = torch.as_tensor(totals).to(torch.int32).to(DEV).contiguous()
-    y = torch.empty(B * T, H, dtype=tdt(dtype), device=DEV)
-    mk = torch.empty(B, T, dtype=torch.uint8, device=DEV)
-    ok(lib().fs2_op_regulate(dtype, p(xd), p(cd), p(td), p(y), p(mk), B, L, T, H, stream()), "regulate")
-    torch.cuda.synchronize()
-    return y.float().cpu(), mk.bool().cpu()
-
-
-def bucket_embed(dtype, x, pred, bins, emb, std, mean, pe, spk, B, T, H):
-    xd = to_dev(x, dtype)
-    f = lambda a: None if a is None else torch.as_tensor(a).float().to(DEV).contiguous()
-    pd, bd, ed, ped, sd = f(pred), f(bins), f(emb), f(pe), f(spk)
-    nb = 0 if emb is None else emb.shape[0]
-    y = torch.empty(B * T, H, dtype=tdt(dtype), device=DEV)
-    idx = torch.empty(B * T, dtype=torch.int32, device=DEV)
-    ok(lib().fs2_op_bucket_embed(dtype, p(xd), p(pd), p(bd), p(ed), nb, float(std), float(mean), p(ped), p(sd), p(y),
-                                 p(idx), B, T, H, stream()), "bucket_embed")
-    torch.cuda.synchronize()
-    return y.float().cpu(), idx.cpu()
-
-
-def embed(dtype, phones, table, pe, spk, n_phones):
-    B, L = phones.shape
-    H = table.shape[1]
-    ph = torch.as_tensor(phones).long().to(DEV).contiguous()
-    f = lambda a: torch.as_tensor(a).float().to(DEV).contiguous()
-    x = torch.empty(B * L, H, dtype=tdt(dtype), device=DEV)
-    mk = torch.empty(B, L, dtype=torch.uint8, device=DEV)
-    td, ped, sd = f(table), f(pe), f(spk)
-    ok(lib().fs2_op_embed(dtype, p(ph), p(td), p(ped), p(sd), p(x), p(mk), B, L, H, n_phones, stream()), "embed")
-    torch.cuda.synchronize()
-    return x.float().cpu(), mk.bool().cpu()
-
-
-def spk_proj(dvec, w, b):
-    B, Din = dvec.shape
-    H = w.shape[0]
-    f = lambda a: torch.as_tensor(a).float().to(DEV).contiguous()
-    dd, wd, bd = f(dvec), f(w), f(b)
-    out = torch.empty(B, H, dtype=torch.float32, device=DEV)
-    ok(lib().fs2_op_spk_proj(p(dd), p(wd), p(bd), p(out), B, H, Din, stream()), "spk_proj")
-    torch.cuda.synchronize()
-    return out.cpu()
+    return host(y, raw)
 
 
 # ------------------------------------------------------------------------------------------------
-# Sentinel-filled outputs (tests/test_gpu_decisions.py): a row the kernel never writes, or a write past the end, shows up
-# instead of passing by the luck of what torch.empty handed out.  These return (status, outputs...) and never raise on a status.
+# Sentinel-filled outputs: a row the kernel never writes, or a write past the end, shows up instead of passing by the luck of what
+# torch.empty handed out.  x_s returns (status, buffers...) and never raises on a status (tests/test_gpu_decisions.py); the plain x
+# is x_s + ok(status), with the guard rows cut off and the results on the host.
 def sentinel(rows, width, dtype):
     """(rows + 1, width) device buffer: floats NaN, integers / masks bytes of 0x5a; the last row is the guard row."""
     if dtype in (torch.float32, torch.bfloat16):
@@ -327,9 +298,9 @@ def sentinel(rows, width, dtype):
 
 
 def bits(t):
-    """Raw bits of a float tensor (bf16 -> int16, fp32 -> int32) on the host: equality of these is bit equality."""
+    """Raw bits of a float tensor (bf16, f16 -> int16, fp32 -> int32) on the host: equality of these is bit equality."""
     t = t.detach().cpu().contiguous()
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
 
 
 def to_bits(x, dtype):
@@ -357,10 +328,16 @@ def durations_s(dur_pred, src_mask, forced=None):
     fd = None if forced is None else torch.as_tensor(forced).to(torch.int32).to(DEV).contiguous()
     dur, cum = sentinel(B, L, torch.int32), sentinel(B, L, torch.int32)
     tot, grd = sentinel(B, 1, torch.int32), sentinel(B, 1, torch.int32)
-    st = lib().fs2_op_durations(p(dp), p(mk), p(fd), p(dur), p(cum), p(tot), p(grd), B, L, stream())
+    st = lib().fs2_op_durations(dp, mk, fd, dur, cum, tot, grd, B, L, torch.cuda.current_stream())
     torch.cuda.synchronize()
     intact = all(guard_intact(b) for b in (dur, cum, tot, grd))
     return st, dur[:B].cpu(), cum[:B].cpu(), tot[:B, 0].cpu(), grd[:B, 0].cpu(), intact
+
+
+def durations(dur_pred, src_mask, forced=None):
+    st, *out, _ = durations_s(dur_pred, src_mask, forced)
+    ok(st, "durations")
+    return tuple(out)
 
 
 def regulate_s(dtype, x, cum, totals, B, L, T, H):
@@ -369,9 +346,15 @@ def regulate_s(dtype, x, cum, totals, B, L, T, H):
     cd = torch.as_tensor(cum).to(torch.int32).to(DEV).contiguous()
     td = torch.as_tensor(totals).to(torch.int32).to(DEV).contiguous()
     y, mk = sentinel(B * T, H, tdt(dtype)), sentinel(B, T, torch.uint8)
-    st = lib().fs2_op_regulate(dtype, p(xd), p(cd), p(td), p(y), p(mk), B, L, T, H, stream())
+    st = lib().fs2_op_regulate(dtype, xd, cd, td, y, mk, B, L, T, H, torch.cuda.current_stream())
     torch.cuda.synchronize()
     return st, y, mk
+
+
+def regulate(dtype, x, cum, totals, B, L, T, H):
+    st, y, mk = regulate_s(dtype, x, cum, totals, B, L, T, H)
+    ok(st, "regulate")
+    return y[:-1].float().cpu(), mk[:-1].bool().cpu()
 
 
 def bucket_embed_s(entry, dtype, x, src, bins, emb, std, mean, pe, spk, B, T, H):
@@ -384,12 +367,18 @@ def bucket_embed_s(entry, dtype, x, src, bins, emb, std, mean, pe, spk, B, T, H)
     y, idx = sentinel(B * T, H, tdt(dtype)), sentinel(B * T, 1, torch.int32)
     if entry == "utt":
         assert std == 1.0 and mean == 0.0 and pe is None and spk is None
-        st = lib().fs2_op_bucket_embed_utt(dtype, p(xd), p(sd), p(bd), p(ed), nb, p(y), p(idx), B, T, H, stream())
+        st = lib().fs2_op_bucket_embed_utt(dtype, xd, sd, bd, ed, nb, y, idx, B, T, H, torch.cuda.current_stream())
     else:
         fn = lib().fs2_op_bucket_embed if entry == "row" else lib().fs2_op_bucket_embed_target
-        st = fn(dtype, p(xd), p(sd), p(bd), p(ed), nb, float(std), float(mean), p(ped), p(spd), p(y), p(idx), B, T, H, stream())
+        st = fn(dtype, xd, sd, bd, ed, nb, std, mean, ped, spd, y, idx, B, T, H, torch.cuda.current_stream())
     torch.cuda.synchronize()
     return st, y, idx
+
+
+def bucket_embed(dtype, x, pred, bins, emb, std, mean, pe, spk, B, T, H):
+    st, y, idx = bucket_embed_s("row", dtype, x, pred, bins, emb, std, mean, pe, spk, B, T, H)
+    ok(st, "bucket_embed")
+    return y[:-1].float().cpu(), idx[:-1, 0].cpu()
 
 
 def embed_s(dtype, phones, table, pe, spk, n_phones):
@@ -400,9 +389,15 @@ def embed_s(dtype, phones, table, pe, spk, n_phones):
     f = lambda a: torch.as_tensor(a).float().to(DEV).contiguous()
     td, ped, sd = f(table), f(pe), f(spk)
     x, mk = sentinel(B * L, H, tdt(dtype)), sentinel(B, L, torch.uint8)
-    st = lib().fs2_op_embed(dtype, p(ph), p(td), p(ped), p(sd), p(x), p(mk), B, L, H, n_phones, stream())
+    st = lib().fs2_op_embed(dtype, ph, td, ped, sd, x, mk, B, L, H, n_phones, torch.cuda.current_stream())
     torch.cuda.synchronize()
     return st, x, mk
+
+
+def embed(dtype, phones, table, pe, spk, n_phones):
+    st, x, mk = embed_s(dtype, phones, table, pe, spk, n_phones)
+    ok(st, "embed")
+    return x[:-1].float().cpu(), mk[:-1].bool().cpu()
 
 
 def spk_proj_s(dvec, w, b):
@@ -412,9 +407,15 @@ def spk_proj_s(dvec, w, b):
     f = lambda a: torch.as_tensor(a).float().to(DEV).contiguous()
     dd, wd, bd = f(dvec), f(w), f(b)
     out = sentinel(B, H, torch.float32)
-    st = lib().fs2_op_spk_proj(p(dd), p(wd), p(bd), p(out), B, H, Din, stream())
+    st = lib().fs2_op_spk_proj(dd, wd, bd, out, B, H, Din, torch.cuda.current_stream())
     torch.cuda.synchronize()
     return st, out
+
+
+def spk_proj(dvec, w, b):
+    st, out = spk_proj_s(dvec, w, b)
+    ok(st, "spk_proj")
+    return out[:-1].cpu()
 
 
 def cwt_head_s(dtype, out_conv, spec, mask, ms_w, ms_b, B, T, F):
@@ -424,6 +425,6 @@ def cwt_head_s(dtype, out_conv, spec, mask, ms_w, ms_b, B, T, F):
     sd, wd, bd = f(spec), f(ms_w), f(ms_b)
     md = None if mask is None else torch.as_tensor(mask).to(torch.uint8).to(DEV).contiguous()
     ms, pred, so = sentinel(B, 2, torch.float32), sentinel(B, T, torch.float32), sentinel(B * T, 10, torch.float32)
-    st = lib().fs2_op_cwt_head(dtype, p(od), p(sd), int(spec.shape[1]), p(md), p(wd), p(bd), p(ms), p(pred), p(so), B, T, F, stream())
+    st = lib().fs2_op_cwt_head(dtype, od, sd, int(spec.shape[1]), md, wd, bd, ms, pred, so, B, T, F, torch.cuda.current_stream())
     torch.cuda.synchronize()
     return st, ms, pred, so

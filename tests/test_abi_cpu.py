@@ -312,3 +312,78 @@ def test_library_has_no_mutable_tuning_globals():
         if len(parts) == 3 and parts[1] in "bBdD" and "fs2::g_" in parts[2] and "(" not in parts[2] and "g_zero_page" not in parts[2]:
             bad.append(parts[2])
     assert not bad, bad
+
+
+# ---- the pointer converter: a tensor or a stream goes into a call as it is ----------------------------------------------------
+def test_converter_sits_on_every_plain_pointer_parameter_and_on_no_other(lib):
+    """By the header's own text: a parameter that is a single-star pointer to a scalar, to void or to an opaque handle carries
+    _lib.DevPtr; values, `const char*` names, struct pointers and `**` out-handles keep the type the parser gave them."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    parsed = _lib.parse_header(_lib.HEADER_PATH)
+    n = 0
+    for m in re.finditer(r"\b(fs2_[a-z0-9_]+)\s*\(([^()]*)\)", text):
+        name, params = m.groups()
+        for i, prm in enumerate([] if params.strip() == "void" else params.split(",")):
+            base, stars = re.fullmatch(r"\s*(\w+)\s*(\**)\s*\w*\s*", re.sub(r"\bconst\b", " ", prm)).groups()
+            plain = stars == "*" and base not in parsed.structs and not (base == "char" and "const" in prm)
+            got = getattr(lib, name).argtypes[i]
+            assert (got is _lib.DevPtr) == plain and (plain or got.__name__ == parsed.functions[name][1][i].__name__), (name, i, prm)
+            n += plain
+    assert n >= 500  # the operator entry points alone take several hundred tensors
+
+
+def _identity():
+    """memcpy(dst, src, 0) returns dst: a host function that hands a pointer argument back, typed with the converter"""
+    f = C.CDLL(None).memcpy
+    f.restype, f.argtypes = C.c_void_p, [_lib.DevPtr, _lib.DevPtr, C.c_size_t]
+    src = C.c_int(0)
+    return lambda x: f(x, C.byref(src), 0)
+
+
+def test_converter_passes_each_kind_of_argument_as_a_64_bit_pointer():
+    ident = _identity()
+    high = 0x7F12_3456_789A  # above 4 GiB: a converter that hands ctypes a bare int would pass a C int
+    word, arr = C.c_int(5), (C.c_int32 * 4)()
+
+    class Stream:
+        cuda_stream = high + 16
+
+    class Tensor:
+        def data_ptr(self):
+            return high + 32
+
+    assert ident(None) is None
+    assert ident(C.c_void_p(high)) == high and ident(high) == high
+    assert ident(C.byref(word)) == C.addressof(word) and ident(C.pointer(word)) == C.addressof(word)
+    assert ident(arr) == C.addressof(arr)
+    assert ident(Stream()) == high + 16 and ident(Tensor()) == high + 32
+    a = np.zeros(3, np.float32)
+    assert ident(a.ctypes.data_as(C.c_void_p)) == a.ctypes.data
+    with pytest.raises(C.ArgumentError):
+        ident(1.5)  # what c_void_p refuses stays refused
+
+
+def test_host_conversion_takes_tensors_directly(lib):
+    """One real call through 64-bit heap pointers (fs2_host_f32_to_f16 is host code): tensors passed as they are, the same call
+    through explicit pointers, and the storage rule in torch give the same bits; so does a temporary passed inline."""
+    import torch
+    import _f16
+    x = _f16.edge_values()
+    n = x.numel()
+    direct, explicit, inline = (torch.full((n,), 0x5A5A, dtype=torch.int16) for _ in range(3))
+    assert lib.fs2_host_f32_to_f16(x, direct, n) == 0
+    src, dst = x.data_ptr(), explicit.data_ptr()
+    assert lib.fs2_host_f32_to_f16(C.c_void_p(src), C.c_void_p(dst), n) == 0
+    assert lib.fs2_host_f32_to_f16(x.clone(), inline, n) == 0  # the temporary lives until the call returns
+    want = _f16.f16_bits(x)
+    assert torch.equal(direct, want) and torch.equal(explicit, want) and torch.equal(inline, want)
+
+
+def test_check_names_the_handle_kind(lib):
+    """_lib.check formats every handle's failure alike; last_error picks the entry point that holds the handle's message."""
+    with pytest.raises(RuntimeError, match=r"^fs2 set_debug failed \(1\): ") as e:
+        _lib.check(1, None, "set_debug")
+    assert str(e.value) == f"fs2 set_debug failed (1): {lib.fs2_status_string(1).decode()}"
+    with pytest.raises(AttributeError):
+        _lib.check(1, C.c_void_p(1), "x", last_error="fs2_no_such_last_error")
+    _lib.check(0, C.c_void_p(1), "x", last_error="fs2_no_such_last_error")  # FS2_OK: nothing is looked up

@@ -150,7 +150,7 @@ def _create(lib, n_fft=1024, win=1024, hop=256, n_mels=80, clip=1e-6, kind=0, ba
     if isinstance(basis, str):
         basis = np.ascontiguousarray(np.abs(np.random.RandomState(0).standard_normal((max(n_mels, 1), n_fft // 2 + 1))), np.float32)
     h = C.c_void_p()
-    st = lib.fs2_mel_create(_lib.FS2_ABI_VERSION if abi is None else abi, n_fft, win, hop, n_mels, C.c_float(clip), kind,
+    st = lib.fs2_mel_create(_lib.FS2_ABI_VERSION if abi is None else abi, n_fft, win, hop, n_mels, clip, kind,
                             None if basis is None else basis.ctypes.data_as(C.c_void_p), C.byref(h))
     msg = lib.fs2_mel_last_error(h).decode()
     assert h.value, "the handle comes back on failure too"
@@ -187,7 +187,7 @@ def test_mel_create_refuses_bad_configs_before_any_device_call(lib):
         st, msg, ws, run = _create(lib, **kw)
         assert st == want and text in msg, (kw, st, msg)
         assert run == STATE, kw  # a handle whose create failed runs nothing
-    assert lib.fs2_mel_create(_lib.FS2_ABI_VERSION, 1024, 1024, 256, 80, C.c_float(1e-6), 0, nan_basis.ctypes.data_as(C.c_void_p), None) == ARG
+    assert lib.fs2_mel_create(_lib.FS2_ABI_VERSION, 1024, 1024, 256, 80, 1e-6, 0, nan_basis.ctypes.data_as(C.c_void_p), None) == ARG
     assert lib.fs2_mel_destroy(None) == ARG and lib.fs2_mel_last_error(None) == b"null mel handle"
     assert lib.fs2_mel_ws_bytes(None, 4, 1000) == 0 and lib.fs2_mel_tile_frames(None) == 0
     if not torch.cuda.is_available():  # a good config gets as far as the device, and says so
@@ -199,12 +199,12 @@ def test_segment_mean_refuses_bad_arguments(lib):
     one = (C.c_float * 4)()
     d = (C.c_int32 * 4)()
     f = lib.fs2_op_segment_mean
-    assert f(None, None, d, 1, 4, 4, C.c_float(1e-7), C.c_float(0), C.c_float(1), one, None) == _lib.FS2_ERR_ARG
-    assert f(one, None, None, 1, 4, 4, C.c_float(1e-7), C.c_float(0), C.c_float(1), one, None) == _lib.FS2_ERR_ARG
-    assert f(one, None, d, 1, 4, 4, C.c_float(1e-7), C.c_float(0), C.c_float(1), None, None) == _lib.FS2_ERR_ARG
-    assert f(one, None, d, 0, 4, 4, C.c_float(1e-7), C.c_float(0), C.c_float(1), one, None) == _lib.FS2_ERR_ARG
-    assert f(one, None, d, 1, 4, 4, C.c_float(1e-7), C.c_float(0), C.c_float(0), one, None) == _lib.FS2_ERR_ARG  # std 0
-    assert f(one, None, d, 1, 4, 4, C.c_float(1e-7), C.c_float(0), C.c_float(np.nan), one, None) == _lib.FS2_ERR_ARG
+    assert f(None, None, d, 1, 4, 4, 1e-7, 0, 1, one, None) == _lib.FS2_ERR_ARG
+    assert f(one, None, None, 1, 4, 4, 1e-7, 0, 1, one, None) == _lib.FS2_ERR_ARG
+    assert f(one, None, d, 1, 4, 4, 1e-7, 0, 1, None, None) == _lib.FS2_ERR_ARG
+    assert f(one, None, d, 0, 4, 4, 1e-7, 0, 1, one, None) == _lib.FS2_ERR_ARG
+    assert f(one, None, d, 1, 4, 4, 1e-7, 0, 0, one, None) == _lib.FS2_ERR_ARG  # std 0
+    assert f(one, None, d, 1, 4, 4, 1e-7, 0, np.nan, one, None) == _lib.FS2_ERR_ARG
 
 
 def test_declared_symbols_and_types(lib):
@@ -214,7 +214,7 @@ def test_declared_symbols_and_types(lib):
     for n in new:
         assert n in names and hasattr(lib, n), n
     assert (_lib.FS2_MEL_LOG10, _lib.FS2_MEL_LN, _lib.FS2_MEL_LINEAR) == (0, 1, 2)
-    assert lib.fs2_mel_create.argtypes == [C.c_int32] * 5 + [C.c_float, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    assert lib.fs2_mel_create.argtypes == [C.c_int32] * 5 + [C.c_float, C.c_int32, _lib.DevPtr, C.POINTER(C.c_void_p)]
     assert lib.fs2_mel_ws_bytes.restype is C.c_size_t and lib.fs2_mel_last_error.restype is C.c_char_p
     assert lib.fs2_mel_run.argtypes[13] is C.c_size_t and len(lib.fs2_mel_run.argtypes) == 15
     assert lib.fs2_op_segment_mean.argtypes[6:9] == [C.c_float] * 3

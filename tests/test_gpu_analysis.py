@@ -31,10 +31,6 @@ GEOMETRIES = {"default": DEFAULT, "small": SMALL, "mid": R.Geometry(n_fft=2048, 
               "wide": R.Geometry(n_fft=2048, win_length=1024, hop=2048, n_mels=128)}
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 @functools.lru_cache(maxsize=None)
 def basis_of(name):
     if name == "default":
@@ -57,7 +53,7 @@ class Mel:
         self.g, self.basis, self.lib = geom(name), basis_of(name), _lib.load()
         self.h = C.c_void_p()
         g = self.g
-        st = self.lib.fs2_mel_create(_lib.FS2_ABI_VERSION, g.n_fft, g.win_length, g.hop, g.n_mels, C.c_float(g.clip), kind,
+        st = self.lib.fs2_mel_create(_lib.FS2_ABI_VERSION, g.n_fft, g.win_length, g.hop, g.n_mels, g.clip, kind,
                                      self.basis.ctypes.data_as(C.c_void_p), C.byref(self.h))
         assert st == 0, self.lib.fs2_mel_last_error(self.h)
         self.tile = self.lib.fs2_mel_tile_frames(self.h)
@@ -82,11 +78,11 @@ class Mel:
         ef = torch.full((Bw + SLACK,), ICANARY, dtype=torch.int32, device=DEV)
         need = self.lib.fs2_mel_ws_bytes(self.h, Bw, S)
         ws = torch.zeros(need + SLACK, dtype=torch.uint8, device=DEV)
-        args = {"wav": _p(w), "mel": _p(mel), "mel_frames": _p(mf), "energy": _p(en) if energy else None}
+        args = {"wav": w, "mel": mel, "mel_frames": mf, "energy": en if energy else None}
         for k in null:
             args[k] = None
-        st = self.lib.fs2_mel_run(self.h, args["wav"], _p(ld), B, S, int(pn), args["mel"], T_max, args["energy"], Te_max, args["mel_frames"],
-                                  _p(ef), _p(ws), need - ws_short, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        st = self.lib.fs2_mel_run(self.h, args["wav"], ld, B, S, int(pn), args["mel"], T_max, args["energy"], Te_max, args["mel_frames"],
+                                  ef, ws, need - ws_short, torch.cuda.current_stream())
         torch.cuda.synchronize()
         mel, en, mf, ef = mel.cpu().numpy(), en.cpu().numpy(), mf.cpu().numpy(), ef.cpu().numpy()
         out = {"status": st, "mel": mel[:-SLACK].reshape(Bw, T_max, nm), "energy": en[:-SLACK].reshape(Bw, Te_max),
@@ -307,8 +303,8 @@ def test_segment_mean():
         print(f"segment mean (mean {mean}, std {std}): device {dev:.2e}, sequential float32 model {model:.2e}")
         assert model > 0 and dev <= 2 * model
         assert got[2, 5] == got[2, 6] == np.float32((np.float32(1e-7) - np.float32(mean)) / np.float32(std))
-    st = _lib.load().fs2_op_segment_mean(_p(vd), None, _p(torch.from_numpy(durations).to(DEV)), B, T, L, C.c_float(1e-7), C.c_float(0),
-                                         C.c_float(1), _p(canary), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    st = _lib.load().fs2_op_segment_mean(vd, None, torch.from_numpy(durations).to(DEV), B, T, L, 1e-7, 0, 1, canary,
+                                         torch.cuda.current_stream())
     torch.cuda.synchronize()
     out = canary.cpu().numpy()
     assert st == 0 and (out[B * L:] == CANARY).all()  # frames = NULL: every row has T frames

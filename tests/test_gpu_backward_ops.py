@@ -15,14 +15,6 @@ DEV = "cuda:0"
 F32 = _lib.FS2_F32
 
 
-def p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def bgemm(desc_kw, A, B, Cout, bias=None, dtype=F32):
     lib = _lib.load()
     d = _lib.BGemmDescC()
@@ -35,7 +27,7 @@ def bgemm(desc_kw, A, B, Cout, bias=None, dtype=F32):
     nbytes = lib.fs2_op_bgemm_ws_bytes(C.byref(d))
     if nbytes:
         ws = torch.empty(nbytes // 4, device=DEV)
-    _lib.check(lib.fs2_op_bgemm(dtype, C.byref(d), p(A), p(B), p(Cout), p(bias), p(ws), st()), what="bgemm")
+    _lib.check(lib.fs2_op_bgemm(dtype, C.byref(d), A, B, Cout, bias, ws, torch.cuda.current_stream()), what="bgemm")
     return Cout
 
 
@@ -133,16 +125,16 @@ def test_layernorm_bwd(M, H, res):
     dz = torch.empty(M, H, device=DEV)
     part = torch.empty(nparts, 3, H, device=DEV)
     zd, rd, dyd, gd = z.detach().float().to(DEV), r.float().to(DEV) if res else None, dy.float().to(DEV), gam.detach().float().to(DEV)
-    _lib.check(lib.fs2_op_layernorm_bwd(F32, p(zd), p(rd), p(dyd), p(gd), p(dz), p(part), M, H, 0, st()))
+    _lib.check(lib.fs2_op_layernorm_bwd(F32, zd, rd, dyd, gd, dz, part, M, H, 0, torch.cuda.current_stream()))
     close(dz, z.grad, 2e-5)
     out = torch.full((1, 3 * H), 1.0, device=DEV)
     ws = torch.zeros(max(1, lib.fs2_op_col_sum_ws_bytes(nparts, 3 * H, 0) // 4), device=DEV)
-    _lib.check(lib.fs2_op_col_sum(F32, p(part), p(out), p(ws), nparts, 3 * H, 3 * H, 0, 1, 1.0, st()))
+    _lib.check(lib.fs2_op_col_sum(F32, part, out, ws, nparts, 3 * H, 3 * H, 0, 1, 1.0, torch.cuda.current_stream()))
     close(out[0, :H] - 1.0, gam.grad, 2e-5)
     close(out[0, H:2 * H] - 1.0, bet.grad, 2e-5)
     close(out[0, 2 * H:] - 1.0, z.grad.sum(0), 5e-5)
     if not res:  # relu_mask: z doubles as a ReLU output - dz is zeroed where z <= 0, and so is its column sum
-        _lib.check(lib.fs2_op_layernorm_bwd(F32, p(zd), None, p(dyd), p(gd), p(dz), p(part), M, H, 1, st()))
+        _lib.check(lib.fs2_op_layernorm_bwd(F32, zd, None, dyd, gd, dz, part, M, H, 1, torch.cuda.current_stream()))
         want = torch.where(z.detach() > 0, z.grad, torch.zeros((), dtype=torch.float64))
         close(dz, want, 2e-5)
         close(part.sum(0)[2], want.sum(0), 5e-5)
@@ -154,7 +146,7 @@ def test_col_sum_segments():
     out = torch.empty(6, 100, device=DEV)
     ws = torch.zeros(lib.fs2_op_col_sum_ws_bytes(6 * 700, 100, 700) // 4, device=DEV)
     xd = x.to(DEV)
-    _lib.check(lib.fs2_op_col_sum(F32, p(xd), p(out), p(ws), 6 * 700, 100, 100, 700, 0, 0.5, st()))
+    _lib.check(lib.fs2_op_col_sum(F32, xd, out, ws, 6 * 700, 100, 100, 700, 0, 0.5, torch.cuda.current_stream()))
     close(out, 0.5 * x.double().view(6, 700, 100).sum(1), 1e-5)
 
 
@@ -170,10 +162,10 @@ def test_softmax_fwd_bwd(B, heads, S):
     pr.backward(dp)
     sd = s.detach().float().to(DEV)
     padd = pad.to(torch.uint8).to(DEV)
-    _lib.check(lib.fs2_op_softmax_fwd(F32, p(sd), p(padd), p(sd), B, heads, S, 0.3, st()))
+    _lib.check(lib.fs2_op_softmax_fwd(F32, sd, padd, sd, B, heads, S, 0.3, torch.cuda.current_stream()))
     close(sd, pr.detach(), 1e-5)
     dd = dp.float().to(DEV)
-    _lib.check(lib.fs2_op_softmax_bwd(F32, p(dd), p(sd), p(dd), B, heads, S, 0.3, st()))
+    _lib.check(lib.fs2_op_softmax_bwd(F32, dd, sd, dd, B, heads, S, 0.3, torch.cuda.current_stream()))
     close(dd, s.grad, 2e-5)
 
 
@@ -188,7 +180,7 @@ def test_scatter_rows_and_regulate_bwd():
         i32 = idx.int().to(DEV) if kind == "i32" else None
         i64 = idx.to(DEV) if kind == "i64" else None
         xd = x.to(DEV)
-        _lib.check(lib.fs2_op_scatter_rows(F32, p(xd), p(i32), p(i64), p(table), None, R, H, V, 0, st()))
+        _lib.check(lib.fs2_op_scatter_rows(F32, xd, i32, i64, table, None, R, H, V, 0, torch.cuda.current_stream()))
         want = torch.ones(V, H, dtype=torch.float64).index_add_(0, idx, x.double())
         want[0] = 1.0
         close(table, want, 1e-5)
@@ -199,7 +191,7 @@ def test_scatter_rows_and_regulate_bwd():
     dy = torch.randn(B * T, H, generator=g)
     dx = torch.empty(B * L, H, device=DEV)
     dyd, cumd = dy.to(DEV), cum.to(DEV)
-    _lib.check(lib.fs2_op_regulate_bwd(F32, p(dyd), p(cumd), p(dx), B, L, T, H, st()))
+    _lib.check(lib.fs2_op_regulate_bwd(F32, dyd, cumd, dx, B, L, T, H, torch.cuda.current_stream()))
     want = torch.zeros(B, L, H, dtype=torch.float64)
     for b in range(B):
         t = 0
@@ -225,9 +217,9 @@ def test_masked_loss_bwd(kind, inner):
     ws = torch.zeros(lib.fs2_op_masked_loss_ws_bytes(), dtype=torch.uint8, device=DEV)
     stat = torch.empty(2, device=DEV)
     pd, td, md = pred.detach().float().to(DEV), truth.float().to(DEV), mask.to(torch.uint8).to(DEV)
-    _lib.check(lib.fs2_op_masked_loss(p(pd), p(td), 0, p(md), rows, inner, kind, p(ws), p(stat), st()))
+    _lib.check(lib.fs2_op_masked_loss(pd, td, 0, md, rows, inner, kind, ws, stat, torch.cuda.current_stream()))
     dpred = torch.empty(rows, inner, device=DEV)
-    _lib.check(lib.fs2_op_masked_loss_bwd(p(pd), p(td), 0, p(md), p(stat), p(dpred), rows, inner, kind, 1.7, st()))
+    _lib.check(lib.fs2_op_masked_loss_bwd(pd, td, 0, md, stat, dpred, rows, inner, kind, 1.7, torch.cuda.current_stream()))
     close(dpred, pred.grad, 1e-5)
 
 
@@ -247,13 +239,13 @@ def test_adamw_matches_torch_with_clipping():
         torch.nn.utils.clip_grad_norm_([ref], 1.0)
         opt.step()
         gd = grad.to(DEV)
-        _lib.check(lib.fs2_op_sum_sq(p(gd), n, p(ws), p(nsq), st()))
+        _lib.check(lib.fs2_op_sum_sq(gd, n, ws, nsq, torch.cuda.current_stream()))
         assert abs(float(nsq) - float((grad.double() ** 2).sum())) <= 1e-5 * float((grad.double() ** 2).sum())
         if step == 2:
-            _lib.check(lib.fs2_op_adamw(p(wd), p(gd), p(m), p(v), n, 2e-4, 0.9, 0.98, 1e-8, 0.01, step, p(nsq), 1.0, 1.0, st()))
+            _lib.check(lib.fs2_op_adamw(wd, gd, m, v, n, 2e-4, 0.9, 0.98, 1e-8, 0.01, step, nsq, 1.0, 1.0, torch.cuda.current_stream()))
         else:  # the variant that also leaves the bf16 shadow of the new weights
             sh = torch.empty(n, device=DEV, dtype=torch.bfloat16)
-            _lib.check(lib.fs2_op_adamw_shadow(p(wd), p(gd), p(m), p(v), p(sh), n, 2e-4, 0.9, 0.98, 1e-8, 0.01, step, p(nsq), 1.0, 1.0, st()))
+            _lib.check(lib.fs2_op_adamw_shadow(wd, gd, m, v, sh, n, 2e-4, 0.9, 0.98, 1e-8, 0.01, step, nsq, 1.0, 1.0, torch.cuda.current_stream()))
             assert torch.equal(sh, wd.to(torch.bfloat16))
         close(wd, ref.detach(), 1e-6)
 
@@ -264,15 +256,15 @@ def test_ew_ops():
     a, b = a[:5000], b[:5000]
     out = torch.empty(5000, device=DEV)
     ad, bd = a.to(DEV), b.to(DEV)
-    _lib.check(lib.fs2_op_ew(F32, 0, p(ad), p(bd), p(out), 5000, 2.0, -1.0, st()))
+    _lib.check(lib.fs2_op_ew(F32, 0, ad, bd, out, 5000, 2.0, -1.0, torch.cuda.current_stream()))
     assert torch.equal(out.cpu(), 2.0 * a - b)
-    _lib.check(lib.fs2_op_ew(F32, 1, p(ad), p(bd), p(out), 5000, 0.0, 0.0, st()))
+    _lib.check(lib.fs2_op_ew(F32, 1, ad, bd, out, 5000, 0.0, 0.0, torch.cuda.current_stream()))
     assert torch.equal(out.cpu(), torch.where(b > 0, a, torch.zeros(())))
     n = 4099  # odd length: body of 4096 + tail of 3; and an unaligned view (scalar path only)
     ad, bd, out = torch.randn(n + 1, device=DEV), torch.randn(n + 1, device=DEV), torch.empty(n + 1, device=DEV)
-    _lib.check(lib.fs2_op_ew(F32, 0, p(ad), p(bd), p(out), n, 1.5, 0.5, st()))
+    _lib.check(lib.fs2_op_ew(F32, 0, ad, bd, out, n, 1.5, 0.5, torch.cuda.current_stream()))
     assert torch.allclose(out[:n].cpu(), (1.5 * ad[:n] + 0.5 * bd[:n]).cpu(), rtol=1e-6, atol=1e-6)  # fma vs two roundings
-    _lib.check(lib.fs2_op_ew(F32, 1, p(ad[1:]), p(bd[1:]), p(out[1:]), n, 0.0, 0.0, st()))
+    _lib.check(lib.fs2_op_ew(F32, 1, ad[1:], bd[1:], out[1:], n, 0.0, 0.0, torch.cuda.current_stream()))
     assert torch.equal(out[1:].cpu(), torch.where(bd[1:] > 0, ad[1:], torch.zeros((), device=DEV)).cpu())
 
 
@@ -338,7 +330,7 @@ def test_row_ops_bf16():
     dz = torch.empty(M, H, device=DEV, dtype=torch.bfloat16)
     part = torch.empty(nparts, 3, H, device=DEV)
     zd, rd, dyd, gd = z.to(DEV), r.to(DEV), dy.to(DEV), gam.to(DEV)
-    _lib.check(lib.fs2_op_layernorm_bwd(BF, p(zd), p(rd), p(dyd), p(gd), p(dz), p(part), M, H, 0, st()))
+    _lib.check(lib.fs2_op_layernorm_bwd(BF, zd, rd, dyd, gd, dz, part, M, H, 0, torch.cuda.current_stream()))
     close(dz, zz.grad, 5e-3)
     close(part.sum(0)[0], gg.grad, 1e-4)
     # softmax: fp32 scores -> bf16 probabilities; fp32 dP + bf16 P -> bf16 dS
@@ -347,30 +339,30 @@ def test_row_ops_bf16():
     pr = torch.softmax(0.5 * s.double(), dim=-1)
     sd = s.to(DEV)
     pd = torch.empty(B, heads, S, S, device=DEV, dtype=torch.bfloat16)
-    _lib.check(lib.fs2_op_softmax_fwd(BF, p(sd), None, p(pd), B, heads, S, 0.5, st()))
+    _lib.check(lib.fs2_op_softmax_fwd(BF, sd, None, pd, B, heads, S, 0.5, torch.cuda.current_stream()))
     close(pd, pr, 5e-3)
     dp = torch.randn(B, heads, S, S, generator=g)
     prb = pd.cpu().double()
     want = 0.5 * prb * (dp.double() - (dp.double() * prb).sum(-1, keepdim=True))
     dpd = dp.to(DEV)
     ds = torch.empty_like(pd)
-    _lib.check(lib.fs2_op_softmax_bwd(BF, p(dpd), p(pd), p(ds), B, heads, S, 0.5, st()))
+    _lib.check(lib.fs2_op_softmax_bwd(BF, dpd, pd, ds, B, heads, S, 0.5, torch.cuda.current_stream()))
     close(ds, want, 5e-3)
     # column sums / scatter / regulate / relu on bf16 inputs
     x = _bf(torch.randn(1000, 72, generator=g))
     xd = x.to(DEV)
     out = torch.empty(1, 72, device=DEV)
     ws = torch.zeros(lib.fs2_op_col_sum_ws_bytes(1000, 72, 0) // 4, device=DEV)
-    _lib.check(lib.fs2_op_col_sum(BF, p(xd), p(out), p(ws), 1000, 72, 72, 0, 0, 1.0, st()))
+    _lib.check(lib.fs2_op_col_sum(BF, xd, out, ws, 1000, 72, 72, 0, 0, 1.0, torch.cuda.current_stream()))
     close(out[0], x.double().sum(0), 1e-5)
     idx = torch.randint(0, 20, (1000,), generator=g).int()
     table = torch.zeros(20, 72, device=DEV)
     idxd = idx.to(DEV)
-    _lib.check(lib.fs2_op_scatter_rows(BF, p(xd), p(idxd), None, p(table), None, 1000, 72, 20, -1, st()))
+    _lib.check(lib.fs2_op_scatter_rows(BF, xd, idxd, None, table, None, 1000, 72, 20, -1, torch.cuda.current_stream()))
     close(table, torch.zeros(20, 72, dtype=torch.float64).index_add_(0, idx.long(), x.double()), 1e-5)
     y = _bf(torch.randn(1000, 72, generator=g)).to(DEV)
     o2 = torch.empty_like(xd)
-    _lib.check(lib.fs2_op_ew(BF, 1, p(xd), p(y), p(o2), 1000 * 72, 0.0, 0.0, st()))
+    _lib.check(lib.fs2_op_ew(BF, 1, xd, y, o2, 1000 * 72, 0.0, 0.0, torch.cuda.current_stream()))
     assert torch.equal(o2.cpu(), torch.where(y.cpu() > 0, x, torch.zeros((), dtype=torch.bfloat16)))
 
 
@@ -391,11 +383,11 @@ def test_dwconv_backward(B, S, Cc, k, dtype):
     dt = BF if bf else F32
     dyd, xd, wd = dy.to(tdt).to(DEV).contiguous(), x.detach().to(tdt).to(DEV).contiguous(), w.detach().float().view(Cc, k).to(DEV).contiguous()
     dx = torch.empty(B * S, Cc, device=DEV, dtype=tdt)
-    _lib.check(lib.fs2_op_dwconv_dgrad(dt, p(dyd), p(wd), p(dx), B, S, Cc, k, st()))
+    _lib.check(lib.fs2_op_dwconv_dgrad(dt, dyd, wd, dx, B, S, Cc, k, torch.cuda.current_stream()))
     close(dx, x.grad.reshape(B * S, Cc), 5e-3 if bf else 2e-5)
     nparts = lib.fs2_op_dwconv_wgrad_parts(B, S)
     part = torch.empty(nparts, Cc * (k + 1), device=DEV)
-    _lib.check(lib.fs2_op_dwconv_wgrad(dt, p(dyd), p(xd), p(part), B, S, Cc, k, st()))
+    _lib.check(lib.fs2_op_dwconv_wgrad(dt, dyd, xd, part, B, S, Cc, k, torch.cuda.current_stream()))
     tot = part.sum(0).cpu().double()
     close(tot[:Cc * k].view(Cc, k), w.grad.view(Cc, k), 2e-5)
     close(tot[Cc * k:], bias.grad, 2e-5)
@@ -418,13 +410,13 @@ def test_fold_unfold_conv2():
     Gd, bgd, Wd, bd = (t.detach().float().reshape(t.shape[0], -1).squeeze(-1).contiguous().to(DEV) if t.dim() > 1 else t.detach().float().to(DEV)
                        for t in (G, bg, W21, b21))
     Wf, bf_ = torch.empty(H, Fc, device=DEV), torch.empty(H, device=DEV)
-    _lib.check(lib.fs2_op_fold_conv2(F32, p(Gd), p(bgd), p(Wd), p(bd), p(Wf), p(bf_), H, Fc, st()))
+    _lib.check(lib.fs2_op_fold_conv2(F32, Gd, bgd, Wd, bd, Wf, bf_, H, Fc, torch.cuda.current_stream()))
     yf = Wf.cpu().double() @ x[0] + bf_.cpu().double()[:, None]
     close(yf, y[0].detach(), 1e-5)
     dWf = (dy[0] @ x[0].t()).float().to(DEV).contiguous()  # gradient of the folded map
     dbf = dy[0].sum(1).float().to(DEV)
     dG, dbg, dW, db = (torch.ones_like(t) for t in (Gd, bgd, Wd, bd))
-    _lib.check(lib.fs2_op_unfold_conv2(p(dWf), p(dbf), p(Gd), p(bgd), p(Wd), p(dG), p(dbg), p(dW), p(db), H, Fc, st()))
+    _lib.check(lib.fs2_op_unfold_conv2(dWf, dbf, Gd, bgd, Wd, dG, dbg, dW, db, H, Fc, torch.cuda.current_stream()))
     close(dG - 1, G.grad.view(Fc, gs), 1e-5)
     close(dbg - 1, bg.grad, 1e-5)
     close(dW - 1, W21.grad.view(H, Fc), 1e-5)
@@ -450,7 +442,7 @@ def test_fused_softmax_backward_epilogue(dtype, drop):
     if drop > 0:  # the mask the op regenerates: run it on ones
         ones = torch.ones(B, heads, S, S, device=DEV)
         m = torch.empty_like(ones)
-        _lib.check(lib.fs2_op_dropout(F32, p(ones), p(m), ones.numel(), C.c_float(drop), C.c_uint64(seed), C.c_uint64(key), st()))
+        _lib.check(lib.fs2_op_dropout(F32, ones, m, ones.numel(), drop, C.c_uint64(seed), C.c_uint64(key), torch.cuda.current_stream()))
         mask = m.cpu().double()
     else:
         mask = torch.ones(B, heads, S, S, dtype=torch.float64)
@@ -459,14 +451,14 @@ def test_fused_softmax_backward_epilogue(dtype, drop):
     out.backward(dout.double())
     od, dod, qkvd = out.detach().to(tdt).to(DEV).contiguous(), dout.to(DEV), qkv.to(DEV)
     delta = torch.empty(B, heads, S, device=DEV)
-    _lib.check(lib.fs2_op_attn_delta(dt, p(dod), p(od), p(delta), B, S, H, heads, st()))
+    _lib.check(lib.fs2_op_attn_delta(dt, dod, od, delta, B, S, H, heads, torch.cuda.current_stream()))
     ds = torch.empty(B, heads, S, S, device=DEV, dtype=tdt)
     dsc = _lib.BGemmDescC()
     for kk, vv in dict(M=S, N=S, K=d, sAm=H, sAk=1, sBk=1, sBn=3 * H, ldc=S, sA1=S * H, sA2=d, sB1=S * 3 * H, sB2=d, sC1=heads * S * S,
                        sC2=S * S, alpha=1.0 / d ** 0.5, beta=0.0, splitk=1, taps=1, nb1=B, nb2=heads, c_dtype=dt).items():
         setattr(dsc, kk, vv)
-    _lib.check(lib.fs2_op_bgemm_softmax_bwd(dt, C.byref(dsc), p(dod), p(qkvd[:, 2 * H:]), p(ds), p(Pd), p(delta), C.c_float(drop),
-                                            C.c_uint64(seed), C.c_uint64(key), st()))
+    _lib.check(lib.fs2_op_bgemm_softmax_bwd(dt, C.byref(dsc), dod, qkvd[:, 2 * H:], ds, Pd, delta, drop, C.c_uint64(seed), C.c_uint64(key),
+                                            torch.cuda.current_stream()))
     close(ds, scores.grad / d ** 0.5, 2e-2 if bf else 3e-5)  # gradient of the RAW product Q K^T (what dQ = dS K and dK = dS^T Q consume)
 
 
@@ -502,7 +494,7 @@ def test_flash_attention_training_forward_and_backward(B, S, heads, drop, attn_b
     if drop > 0:
         ones = torch.ones(B, heads, S, S, device=DEV)
         m = torch.empty_like(ones)
-        _lib.check(lib.fs2_op_dropout(F32, p(ones), p(m), ones.numel(), C.c_float(drop), C.c_uint64(seed), C.c_uint64(key), st()))
+        _lib.check(lib.fs2_op_dropout(F32, ones, m, ones.numel(), drop, C.c_uint64(seed), C.c_uint64(key), torch.cuda.current_stream()))
         mask = m.cpu().double()
     else:
         mask = torch.ones(B, heads, S, S, dtype=torch.float64)
@@ -516,8 +508,8 @@ def test_flash_attention_training_forward_and_backward(B, S, heads, drop, attn_b
     vb = lib.fs2_op_attention_scratch_bytes(BF, B, S, H, heads, C.byref(bb))
     vt, bits = torch.empty(vb, dtype=torch.uint8, device=DEV), torch.empty(bb.value, dtype=torch.uint8, device=DEV)
     lse = torch.empty(B, heads, S, device=DEV)
-    _lib.check(lib.fs2_op_attention_train(BF, p(qd), p(padd), p(od), p(vt), p(bits), p(lse), B, S, H, heads, C.c_float(drop),
-                                          C.c_uint64(seed), C.c_uint64(key), st()))
+    _lib.check(lib.fs2_op_attention_train(BF, qd, padd, od, vt, bits, lse, B, S, H, heads, drop, C.c_uint64(seed), C.c_uint64(key),
+                                          torch.cuda.current_stream()))
     close(od, out.detach(), 2e-2)
     want_lse = torch.logsumexp(scores.detach(), dim=-1) / np.log(2.0)
     assert float((lse.cpu().double() - want_lse).abs().max()) <= 2e-2
@@ -525,10 +517,10 @@ def test_flash_attention_training_forward_and_backward(B, S, heads, drop, attn_b
     assert lib.fs2_op_attention_bwd_supported(BF, H, heads) == 1
     dod = dout.to(DEV)
     delta = torch.empty(B, heads, S, device=DEV)
-    _lib.check(lib.fs2_op_attn_delta(BF, p(dod), p(od), p(delta), B, S, H, heads, st()))
+    _lib.check(lib.fs2_op_attn_delta(BF, dod, od, delta, B, S, H, heads, torch.cuda.current_stream()))
     dqkv = torch.full((B * S, 3 * H), float("nan"), device=DEV, dtype=torch.bfloat16)
-    _lib.check(lib.fs2_op_attention_bwd(BF, p(qd), p(dod), p(lse), p(delta), p(padd), p(dqkv), B, S, H, heads, C.c_float(drop),
-                                        C.c_uint64(seed), C.c_uint64(key), st()))
+    _lib.check(lib.fs2_op_attention_bwd(BF, qd, dod, lse, delta, padd, dqkv, B, S, H, heads, drop, C.c_uint64(seed), C.c_uint64(key),
+                                        torch.cuda.current_stream()))
     want = torch.cat([t.grad.transpose(1, 2).reshape(B * S, H) for t in (q, k, v)], dim=1)
     assert bool(torch.isfinite(dqkv.float()).all())
     for name, sl in (("dq", slice(0, H)), ("dk", slice(H, 2 * H)), ("dv", slice(2 * H, 3 * H))):
@@ -657,7 +649,7 @@ def _col_sum_cases(lib):
     for it in range(4):
         out = torch.ones(n1, device=DEV)
         out2 = torch.full((N - n1,), 5.0, device=DEV)
-        _lib.check(lib.fs2_op_col_sum2(F32, p(xd), p(out), p(out2), n1, p(ws), M, N, N, 1, 0, 1.0, st()))
+        _lib.check(lib.fs2_op_col_sum2(F32, xd, out, out2, n1, ws, M, N, N, 1, 0, 1.0, torch.cuda.current_stream()))
         close(out, want[:n1] + 1.0, 1e-5)
         close(out2, want[n1:], 1e-5)
         both = torch.cat([out, out2]).cpu()
@@ -667,14 +659,14 @@ def _col_sum_cases(lib):
         assert not ws[:8192].any()
         # a different shape on the same workspace in between
         o3 = torch.empty(72, device=DEV)
-        _lib.check(lib.fs2_op_col_sum(F32, p(xd), p(o3), p(ws), M, 72, N, 0, 0, 2.0, st()))
+        _lib.check(lib.fs2_op_col_sum(F32, xd, o3, ws, M, 72, N, 0, 0, 2.0, torch.cuda.current_stream()))
         close(o3, 2.0 * want[:72], 1e-5)
     # more (column block, segment) pairs than counters: 70 column blocks x 120 segments
     nseg, seg, N2 = 120, 130, 64 * 70
     x2 = torch.randn(nseg * seg, N2, generator=g)
     ws2 = torch.zeros(lib.fs2_op_col_sum_ws_bytes(nseg * seg, N2, seg) // 4, device=DEV)
     out = torch.empty(nseg, N2, device=DEV)
-    _lib.check(lib.fs2_op_col_sum(F32, p(x2.to(DEV)), p(out), p(ws2), nseg * seg, N2, N2, seg, 0, 1.0, st()))
+    _lib.check(lib.fs2_op_col_sum(F32, x2.to(DEV), out, ws2, nseg * seg, N2, N2, seg, 0, 1.0, torch.cuda.current_stream()))
     close(out, x2.double().view(nseg, seg, N2).sum(1), 1e-5)
 
 
@@ -703,7 +695,7 @@ def test_scatter_rows_chunked_form(R, H, V, skip, dtype):
         table = torch.ones(V, H, device=DEV)
         i32 = idx.int().to(DEV) if kind == "i32" else None
         i64 = idx.to(DEV) if kind == "i64" else None
-        _lib.check(lib.fs2_op_scatter_rows(_lib.FS2_BF16 if dtype == "bf16" else F32, p(xd), p(i32), p(i64), p(table), p(ws), R, H, V, skip, st()))
+        _lib.check(lib.fs2_op_scatter_rows(_lib.FS2_BF16 if dtype == "bf16" else F32, xd, i32, i64, table, ws, R, H, V, skip, torch.cuda.current_stream()))
         close(table, want, 1e-5)
         if first is None:
             first = table.clone()
@@ -721,13 +713,13 @@ def test_transpose_weight_batch_matches_single_launches():
     for N, Cin, taps in shapes:
         src = torch.randn(N, taps * Cin, generator=g).to(torch.bfloat16).to(DEV)
         want = torch.empty(Cin, taps * N, device=DEV, dtype=torch.bfloat16)
-        _lib.check(lib.fs2_op_transpose_weight(_lib.FS2_BF16, p(src), p(want), N, Cin, taps, st()))
+        _lib.check(lib.fs2_op_transpose_weight(_lib.FS2_BF16, src, want, N, Cin, taps, torch.cuda.current_stream()))
         got = torch.zeros_like(want)
         rows.append([src.data_ptr(), got.data_ptr(), N, Cin, taps, tiles])
         tiles += int(lib.fs2_op_transpose_weight_tiles(N, Cin, taps))
         keep.append((src, want, got))
     tab = torch.tensor(rows, dtype=torch.int64, device=DEV)
-    _lib.check(lib.fs2_op_transpose_weight_batch(p(tab), len(rows), tiles, st()))
+    _lib.check(lib.fs2_op_transpose_weight_batch(tab, len(rows), tiles, torch.cuda.current_stream()))
     for (src, want, got), (N, Cin, taps) in zip(keep, shapes):
         assert torch.equal(got, want), (N, Cin, taps)
         ref = src.view(N, taps, Cin).flip(1).permute(2, 1, 0).reshape(Cin, taps * N)
@@ -765,16 +757,16 @@ def test_gemm_gated_store(M, N, Cin, taps, S, dtype):
     gate = torch.relu(torch.randn(M, N, generator=g)).to(td)   # a ReLU output: zeros and positives
     xd, wd, gd = x.to(DEV), w.to(DEV), gate.to(DEV)
     c = torch.empty(M, N, device=DEV, dtype=td)
-    _lib.check(lib.fs2_op_gemm_gated(dt, p(xd), p(wd), None, p(gd), 1.0, p(c), M, N, Cin, taps, S, st()))
+    _lib.check(lib.fs2_op_gemm_gated(dt, xd, wd, None, gd, 1.0, c, M, N, Cin, taps, S, torch.cuda.current_stream()))
     c0 = torch.empty(M, N, device=DEV, dtype=td)
-    _lib.check(lib.fs2_op_gemm(dt, dt, p(xd), p(wd), None, p(c0), M, N, Cin, taps, S, 0, st()))
+    _lib.check(lib.fs2_op_gemm(dt, dt, xd, wd, None, c0, M, N, Cin, taps, S, 0, torch.cuda.current_stream()))
     want = torch.where(gd > 0, c0, torch.zeros_like(c0))
     assert torch.equal(c, want)
     assert float((want != 0).float().mean()) > 0.3 and float((want == 0).float().mean()) > 0.3
     if taps == 1:
         ref = torch.where(gate.double() > 0, x.double() @ w.double().t(), torch.zeros(M, N, dtype=torch.float64))
         close(c, ref, rel=2e-2 if bf else 2e-5)
-        _lib.check(lib.fs2_op_gemm_gated(dt, p(xd), p(wd), None, p(gd), 1.25, p(c), M, N, Cin, taps, S, st()))   # dropout's 1 / (1 - p)
+        _lib.check(lib.fs2_op_gemm_gated(dt, xd, wd, None, gd, 1.25, c, M, N, Cin, taps, S, torch.cuda.current_stream()))   # dropout's 1 / (1 - p)
         close(c, 1.25 * ref, rel=2e-2 if bf else 2e-5)
 
 
@@ -783,8 +775,8 @@ def test_gemm_gated_rejects_shapes_without_the_epilogue():
     x = torch.zeros(256, 64, device=DEV)
     w = torch.zeros(128, 64, device=DEV)
     c = torch.zeros(256, 128, device=DEV)
-    assert lib.fs2_op_gemm_gated(F32, p(x), p(w), None, p(c), 1.0, p(c), 256, 128, 64, 1, 256, st()) != 0   # N < 192: not the slab kernel
-    assert lib.fs2_op_gemm_gated(F32, p(x), p(w), None, None, 1.0, p(c), 256, 128, 64, 1, 256, st()) != 0
+    assert lib.fs2_op_gemm_gated(F32, x, w, None, c, 1.0, c, 256, 128, 64, 1, 256, torch.cuda.current_stream()) != 0   # N < 192: not the slab kernel
+    assert lib.fs2_op_gemm_gated(F32, x, w, None, None, 1.0, c, 256, 128, 64, 1, 256, torch.cuda.current_stream()) != 0
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
@@ -799,8 +791,8 @@ def test_col_sum_weighted(dtype):
     w = torch.randn(M, generator=g)
     ws = torch.zeros(lib.fs2_op_col_sum_ws_bytes(M, N, 0) // 4, device=DEV)
     out = torch.ones(N, device=DEV)
-    _lib.check(lib.fs2_op_col_sum_weighted(_lib.FS2_BF16 if dtype == "bf16" else F32, p(x.to(DEV)), p(w.to(DEV)), p(out), p(ws), M, N, N, 1,
-                                           0.5, st()))
+    _lib.check(lib.fs2_op_col_sum_weighted(_lib.FS2_BF16 if dtype == "bf16" else F32, x.to(DEV), w.to(DEV), out, ws, M, N, N, 1, 0.5,
+                                           torch.cuda.current_stream()))
     close(out, 1.0 + 0.5 * (w.double()[:, None] * x.double()).sum(0), 1e-5)
 
 
@@ -816,20 +808,20 @@ def test_layernorm_with_dropout_matches_the_two_pass_form(dtype):
     x = torch.randn(M, H, generator=g).to(td).to(DEV)
     gam, bet = (1 + 0.1 * torch.randn(H, generator=g)).to(DEV), (0.1 * torch.randn(H, generator=g)).to(DEV)
     y1 = torch.empty(M, H, device=DEV, dtype=td)
-    _lib.check(lib.fs2_op_layernorm_dropout(dt, p(x), None, p(gam), p(bet), p(y1), M, H, pdrop, seed, key, st()))
+    _lib.check(lib.fs2_op_layernorm_dropout(dt, x, None, gam, bet, y1, M, H, pdrop, seed, key, torch.cuda.current_stream()))
     y0 = torch.empty(M, H, device=DEV, dtype=td)
-    _lib.check(lib.fs2_op_layernorm(dt, p(x), None, p(gam), p(bet), p(y0), None, 0.0, None, None, M, H, st()))
-    _lib.check(lib.fs2_op_dropout(dt, p(y0), p(y0), M * H, pdrop, seed, key, st()))
+    _lib.check(lib.fs2_op_layernorm(dt, x, None, gam, bet, y0, None, 0.0, None, None, M, H, torch.cuda.current_stream()))
+    _lib.check(lib.fs2_op_dropout(dt, y0, y0, M * H, pdrop, seed, key, torch.cuda.current_stream()))
     assert torch.equal(y1 == 0, y0 == 0) and 0.25 < float((y1 == 0).float().mean()) < 0.35
     close(y1, y0.cpu(), rel=1e-2 if bf else 1e-6)
     dy = torch.randn(M, H, generator=g).to(td).to(DEV)
     nparts = lib.fs2_op_layernorm_bwd_parts(M)
     dz1, part1 = torch.empty(M, H, device=DEV, dtype=td), torch.empty(nparts, 3 * H, device=DEV)
-    _lib.check(lib.fs2_op_layernorm_bwd_dropout(dt, p(x), None, p(dy), p(gam), p(dz1), p(part1), M, H, 0, pdrop, seed, key, st()))
+    _lib.check(lib.fs2_op_layernorm_bwd_dropout(dt, x, None, dy, gam, dz1, part1, M, H, 0, pdrop, seed, key, torch.cuda.current_stream()))
     dyd = dy.clone()
-    _lib.check(lib.fs2_op_dropout(dt, p(dyd), p(dyd), M * H, pdrop, seed, key, st()))
+    _lib.check(lib.fs2_op_dropout(dt, dyd, dyd, M * H, pdrop, seed, key, torch.cuda.current_stream()))
     dz0, part0 = torch.empty(M, H, device=DEV, dtype=td), torch.empty(nparts, 3 * H, device=DEV)
-    _lib.check(lib.fs2_op_layernorm_bwd(dt, p(x), None, p(dyd), p(gam), p(dz0), p(part0), M, H, 0, st()))
+    _lib.check(lib.fs2_op_layernorm_bwd(dt, x, None, dyd, gam, dz0, part0, M, H, 0, torch.cuda.current_stream()))
     if bf:
         close(dz1, dz0.cpu(), rel=2e-2)
         close(part1, part0.cpu(), rel=1e-2)

@@ -1,6 +1,5 @@
 """Boundary behaviour on the GPU (`-m gpu`): caller-owned workspace (fs2_workspace_bytes / fs2_set_workspace),
 the data-parallel aids (zeroed pad rows in the mel store, global-pad frame count) and the host mirror's argument checks."""
-import ctypes as C
 import json
 import os
 import socket
@@ -60,7 +59,7 @@ def test_caller_workspace_matches_engine_arenas_bitwise():
     assert pb == pb0 and sb >= sb0 > 0
     small = torch.empty(4096, dtype=torch.uint8, device="cuda:0")
     lib = _lib.load()
-    st = lib.fs2_set_workspace(a.engine.handle, C.c_void_p(small.data_ptr()), small.numel(), C.c_void_p(small.data_ptr()), small.numel())
+    st = lib.fs2_set_workspace(a.engine.handle, small, small.numel(), small, small.numel())
     assert st == 0
     a.engine.torch_workspace = False  # stop the mirror from replacing it
     with pytest.raises(RuntimeError, match="workspace too small"):

@@ -7,7 +7,6 @@ Every other oracle test sets debug mode or forces durations / buckets, and both 
 the ways a served engine is driven: replays on the same input tensors, new data in the same tensors, a shape change with the
 zero-duration guard firing and back, a kernel switch under graphs, pipelines, a clone made after capture, and a caller workspace of
 exactly the reported size."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -330,8 +329,7 @@ def _check_exact_workspace(c):
     bufs = {}
 
     def ws(what, persist, scratch):
-        _lib.check(lib.fs2_set_workspace(h, C.c_void_p(persist.data_ptr()), persist.numel(), C.c_void_p(scratch.data_ptr()),
-                                         scratch.numel()), h, what)
+        _lib.check(lib.fs2_set_workspace(h, persist, persist.numel(), scratch, scratch.numel()), h, what)
     for k in ("A", "G", "A", "A", "G", "A"):
         bt = c.dev(k) if k not in bufs else bufs[k][0]
         Bq, Lq = bt["phones"].shape

@@ -453,11 +453,11 @@ def test_gemm_relu_dropout_store_uses_the_dropout_op_mask(dtype, B, S, Cin, N, k
     xd, wd = G.to_dev(x.reshape(M, Cin), dtype), G.to_dev(G.pack_conv_weight(w), dtype)
     bd = b.float().to(G.DEV)
     c = torch.empty(M, N, dtype=G.tdt(dtype), device=G.DEV)
-    G.ok(G.lib().fs2_op_gemm_relu_dropout(dtype, G.p(xd), G.p(wd), G.p(bd), G.p(c), M, N, Cin, k, S, C.c_float(pdrop), C.c_uint64(seed),
-                                          C.c_uint64(key), G.stream()), "gemm_relu_dropout")
+    G.ok(G.lib().fs2_op_gemm_relu_dropout(dtype, xd, wd, bd, c, M, N, Cin, k, S, pdrop, C.c_uint64(seed), C.c_uint64(key),
+                                          torch.cuda.current_stream()), "gemm_relu_dropout")
     ones = torch.ones(M, N, dtype=torch.float32, device=G.DEV)
     mask = torch.empty_like(ones)
-    G.ok(G.lib().fs2_op_dropout(G.F32, G.p(ones), G.p(mask), M * N, C.c_float(pdrop), C.c_uint64(seed), C.c_uint64(key), G.stream()), "dropout")
+    G.ok(G.lib().fs2_op_dropout(G.F32, ones, mask, M * N, pdrop, C.c_uint64(seed), C.c_uint64(key), torch.cuda.current_stream()), "dropout")
     torch.cuda.synchronize()
     plain = G.gemm(dtype, x.reshape(M, Cin), G.pack_conv_weight(w), b, taps=k, S=S, relu=True)
     got, mask = c.float().cpu(), mask.cpu()
@@ -473,8 +473,8 @@ def test_gemm_split_k_rejects_what_it_cannot_run():
     c = torch.empty(256, 256, dtype=torch.bfloat16, device=G.DEV)
     part = torch.empty(3, 256, 256, dtype=torch.float32, device=G.DEV)
     # 256 channels = 4 blocks of 64: 3 does not divide them
-    assert G.lib().fs2_op_gemm_splitk(G.BF16, G.BF16, G.p(xd), G.p(wd), G.p(c), G.p(part), 256, 256, 256, 1, 256, 3, 0, G.stream()) != 0
-    assert G.lib().fs2_op_gemm_splitk(G.BF16, G.BF16, G.p(xd), G.p(wd), G.p(c), None, 256, 256, 256, 1, 256, 2, 0, G.stream()) != 0
+    assert G.lib().fs2_op_gemm_splitk(G.BF16, G.BF16, xd, wd, c, part, 256, 256, 256, 1, 256, 3, 0, torch.cuda.current_stream()) != 0
+    assert G.lib().fs2_op_gemm_splitk(G.BF16, G.BF16, xd, wd, c, None, 256, 256, 256, 1, 256, 2, 0, torch.cuda.current_stream()) != 0
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

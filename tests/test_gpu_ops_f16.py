@@ -11,11 +11,12 @@ import torch
 import torch.nn.functional as F
 
 import _f16 as H16
+import _gpu as G
 from lightningfastspeech2_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-F32, F16 = H16.F32, H16.F16
+F32, F16 = G.F32, G.F16
 T16 = torch.float16
 UNIT, UNIT_LN = 1.5e-3, 3.2e-3
 
@@ -34,7 +35,7 @@ def r16(x):
 
 
 def knob(v):
-    assert H16.lib().fs2_op_set_gemm_variant(v) == 0
+    assert G.lib().fs2_op_set_gemm_variant(v) == 0
 
 
 def pack_conv_weight(w):
@@ -53,18 +54,44 @@ def test_convert_f32_f16_f32_is_the_host_rule_bit_for_bit():
     """fp32 -> FS2_F16 on the device gives the bits of clamp(+-65504) + round-to-nearest-even on every class of input (normals,
     ties, subnormals, the largest finite value and beyond, infinities -> +-65504, signed zeros, NaN -> NaN); back to fp32 exactly."""
     x = H16.edge_values()
-    h = H16.convert(F32, F16, x.to(H16.DEV))
+    h = G.convert(F32, F16, x.to(G.DEV))
     assert h.dtype == T16
     got, want = h.cpu().view(torch.int16), H16.f16_bits(x)
     bad = (got != want).nonzero().flatten()
     assert bad.numel() == 0, [(float(x[i]), hex(int(got[i]) & 0xFFFF), hex(int(want[i]) & 0xFFFF)) for i in bad[:8]]
-    back = H16.convert(F16, F32, h).cpu()
+    back = G.convert(F16, F32, h).cpu()
     ref = want.view(T16).float()
     nan = torch.isnan(x)
     assert torch.equal(back[~nan], ref[~nan]) and bool(torch.isnan(back[nan]).all())
     assert float(back[~nan].abs().max()) == 65504.0
-    same = H16.convert(F16, F16, h).cpu().view(torch.int16)
+    same = G.convert(F16, F16, h).cpu().view(torch.int16)
     assert torch.equal(same[~nan], want[~nan])
+
+
+def test_convert_takes_tensors_and_streams_as_they_are():
+    """The binding's converter against explicit pointers on a side stream: (tensor | c_void_p of its data_ptr) x (torch.cuda.Stream |
+    c_void_p of its handle) give the same bits, the host rule's.  1027 values: neither whole 256-thread blocks nor whole 16-byte vectors."""
+    e = H16.edge_values()
+    x = torch.cat([e[::e.numel() // 1000][:1006], e[-21:]]).contiguous()
+    assert x.numel() == 1027
+    xd = x.to(G.DEV)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    assert side.cuda_stream != torch.cuda.current_stream().cuda_stream
+    outs = []
+    handle = side.cuda_stream
+    for explicit in (False, True):
+        for st in (side, C.c_void_p(handle)):
+            out = torch.full((1027 + 5,), 7.0, dtype=T16, device=G.DEV)
+            torch.cuda.synchronize()
+            src, dst = xd.data_ptr(), out.data_ptr()
+            args = (C.c_void_p(src), C.c_void_p(dst)) if explicit else (xd, out)
+            G.ok(G.lib().fs2_op_convert(F32, F16, *args, 1027, st), "convert")
+            side.synchronize()
+            outs.append(out.cpu())
+    want = H16.f16_bits(x)
+    for out in outs:
+        assert torch.equal(out[:1027].view(torch.int16), want) and bool((out[1027:] == 7.0).all())
 
 
 # ---- GEMM / conv ---------------------------------------------------------------------------------------------------------------
@@ -73,7 +100,7 @@ def test_convert_f32_f16_f32_is_the_host_rule_bit_for_bit():
 def test_gemm_plain(M, N, K, out_dt, gemm_variant):
     x, w, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5), rnd(N, seed=3)
     ref = r16(x) @ r16(w).T + b   # asymmetric, transpose-detecting
-    got = H16.gemm(x, w, b, out_dt=out_dt)
+    got = G.gemm(F16, x, w, b, out_dtype=out_dt, raw=True)
     assert got.dtype == (T16 if out_dt == F16 else torch.float32)
     err = float((got.float() - ref).abs().max())
     assert err <= tol(ref), (err, tol(ref))
@@ -85,11 +112,11 @@ def test_gemm_store_saturates_instead_of_overflowing():
     x, w = torch.full((M, K), 60.0), torch.full((N, K), 30.0)
     w[1::2] = -30.0
     b = torch.zeros(N)
-    got = H16.gemm(x, w, b).float()
+    got = G.gemm(F16, x, w, b).float()
     assert bool(torch.isfinite(got).all())
     assert torch.equal(got[:, 0::2], torch.full((M, N // 2), 65504.0)) and torch.equal(got[:, 1::2], torch.full((M, N // 2), -65504.0))
-    assert torch.equal(H16.gemm(x, w, b, relu=True).float()[:, 1::2], torch.zeros(M, N // 2))
-    assert float(H16.gemm(x, w, b, out_dt=F32)[0, 0]) == 60.0 * 30.0 * K
+    assert torch.equal(G.gemm(F16, x, w, b, relu=True).float()[:, 1::2], torch.zeros(M, N // 2))
+    assert float(G.gemm(F16, x, w, b, out_dtype=F32)[0, 0]) == 60.0 * 30.0 * K
 
 
 @pytest.mark.parametrize("variant", [0, 1, 3], ids=["auto", "gemm128x128", "slab128"])
@@ -101,7 +128,7 @@ def test_gemm_conv_same_padding_per_utterance(B, S, Cin, N, k, variant):
     ref = F.conv1d(r16(x).transpose(1, 2), r16(w), b, padding="same").transpose(1, 2)
     knob(variant)
     try:
-        got = H16.gemm(x.reshape(B * S, Cin), pack_conv_weight(w), b, taps=k, S=S).float().reshape(B, S, N)
+        got = G.gemm(F16, x.reshape(B * S, Cin), pack_conv_weight(w), b, taps=k, S=S).float().reshape(B, S, N)
     finally:
         knob(0)
     err = float((got - ref).abs().max())
@@ -120,7 +147,7 @@ def test_gemm_residual_layernorm_epilogue(B, S, Cin, N, k, relu):
     z = F.conv1d(r16(x).transpose(1, 2), r16(w), b, padding="same").transpose(1, 2).reshape(B * S, N)
     z = (torch.relu(z) if relu else z) + r16(res)
     ref = F.layer_norm(z, (N,), g, be, 1e-5)
-    run = lambda: H16.gemm_ln(x.reshape(B * S, Cin), pack_conv_weight(w), b, res, g, be, taps=k, S=S, relu=relu)
+    run = lambda: G.gemm_ln(F16, x.reshape(B * S, Cin), pack_conv_weight(w), b, res, g, be, taps=k, S=S, relu=relu, raw=True)[0]
     y, again = run(), run()
     assert torch.equal(y.view(torch.int16), again.view(torch.int16))
     assert float((y.float() - ref).abs().max()) <= tol(ref, UNIT_LN)
@@ -131,7 +158,7 @@ def test_gemm_with_addend(M, N, K):
     """c = x w^T + bias + addend: the residual-in-the-accumulators path of the deferred epilogue."""
     x, w, b, add = rnd(M, K, seed=31), rnd(N, K, seed=32, scale=K ** -0.5), rnd(N, seed=33), rnd(M, N, seed=34)
     ref = r16(x) @ r16(w).T + b + r16(add)
-    got = H16.gemm_add(x, w, b, add).float()
+    got = G.gemm_add(F16, x, w, b, add, in_place=False)
     assert float((got - ref).abs().max()) <= tol(ref)
 
 
@@ -161,8 +188,8 @@ def test_deferred_statistics_then_rowscaled_gemm_is_layernorm_then_gemm(M, Kin, 
     try:
         for kn in (220, 221, 221):
             knob(kn)
-            v, st = H16.gemm_stats(x, w1, b1, res)
-            runs.setdefault(kn, []).append((v.cpu(), st.cpu(), H16.gemm_rowscale(v, st, wf, bf, wg, out_dt=out_dt)))
+            v, st = G.gemm_stats(F16, x, w1, b1, res)
+            runs.setdefault(kn, []).append((v.cpu(), st.cpu(), G.gemm_rowscale_dt(F16, v, st, wf, bf, wg, out_dtype=out_dt)))
     finally:
         knob(221)
     (v0, st0, c0), (v1, st1, c1), (v2, st2, c2) = runs[220][0], runs[221][0], runs[221][1]
@@ -189,10 +216,10 @@ def test_wres_gemm_is_bit_identical_to_the_slab_kernel(M, N):
     x, w, b = rnd(M, 256, seed=3), rnd(N, 256, seed=4) / 16, rnd(N, seed=5)
     try:
         knob(1400)
-        old = H16.gemm(x, w, b, relu=(N == 256))
+        old = G.gemm(F16, x, w, b, relu=(N == 256), raw=True)
         knob(1402)   # the weight-resident kernel at every size
-        got = H16.gemm(x, w, b, relu=(N == 256))
-        again = H16.gemm(x, w, b, relu=(N == 256))
+        got = G.gemm(F16, x, w, b, relu=(N == 256), raw=True)
+        again = G.gemm(F16, x, w, b, relu=(N == 256), raw=True)
     finally:
         knob(1401)
     assert torch.equal(got.view(torch.int16), old.view(torch.int16)) and torch.equal(got.view(torch.int16), again.view(torch.int16))
@@ -206,7 +233,7 @@ def test_wres_gemm_is_bit_identical_to_the_slab_kernel(M, N):
 def test_persistent_gemm_is_bit_identical_to_the_slab_kernel(M, N, K, add):
     x, w, b = rnd(M, K, seed=31), rnd(N, K, seed=32) / math.sqrt(K), rnd(N, seed=33)
     addend = rnd(M, N, seed=34) if add else None
-    run = (lambda: H16.gemm_add(x, w, b, addend)) if add else (lambda: H16.gemm(x, w, b, relu=True))
+    run = (lambda: G.gemm_add(F16, x, w, b, addend, in_place=False, raw=True)) if add else (lambda: G.gemm(F16, x, w, b, relu=True, raw=True))
     try:
         knob(220)
         old = run()
@@ -253,7 +280,7 @@ def test_attention(B, S, H, heads, mask_kind):
         mask = _mask(mask_kind, B, S)
     qkv = rnd(B * S, 3 * H, seed=10)
     ref = _attn_ref(r16(qkv), mask, B, S, H, heads)
-    got = H16.attention(qkv, mask, B, S, H, heads).float()
+    got = G.attention(F16, qkv, mask, B, S, H, heads).float()
     err = float((got - ref).abs().max())
     assert err <= tol(ref, 2.5e-3), (err, tol(ref, 2.5e-3))   # bf16's bound here is 2e-2 (q, p AND the output are rounded)
 
@@ -266,7 +293,7 @@ def test_attention_spike_forces_rescale():
     qkv[200, H:H + 128] = 6.0 * qkv[5, :128]  # key 200 aligned with query 5 (head 0)
     mask = torch.zeros(B, S, dtype=torch.bool)
     ref = _attn_ref(r16(qkv), mask, B, S, H, heads)
-    got = H16.attention(qkv, mask, B, S, H, heads).float()
+    got = G.attention(F16, qkv, mask, B, S, H, heads).float()
     assert bool(torch.isfinite(got).all())
     assert float((got - ref).abs().max()) <= tol(ref, 2.5e-3)
     assert float((got[5, :128] - r16(qkv)[200, 2 * H:2 * H + 128]).abs().max()) <= tol(ref, 2.5e-3)   # query 5 attends to key 200 alone
@@ -284,13 +311,13 @@ def test_attention_out_projection_layernorm_one_launch(B, S, mask_kind):
     mask = _mask(mask_kind, B, S)
     att = r16(_attn_ref(r16(qkv), mask, B, S, H, heads))
     ref = F.layer_norm(r16(res) + att @ r16(w).T + bias, (H,), g, be, 1e-5)
-    got = H16.attn_out_ln(qkv, mask, w, bias, res, g, be, B, S, H, heads)
+    got = G.attn_out_ln(qkv, mask, w, bias, res, g, be, B, S, H, heads, dtype=F16, raw=True)
     assert not torch.isnan(got).any()
     assert float((got.float() - ref).abs().max()) <= 5e-3 * (float(ref.abs().max()) + 1)
-    two = H16.gemm_ln(H16.attention(qkv, mask, B, S, H, heads).float(), w, bias, res, g, be).float()
+    two = G.gemm_ln(F16, G.attention(F16, qkv, mask, B, S, H, heads), w, bias, res, g, be)[0]
     assert float((got.float() - two).abs().max()) <= 2.5e-3 * (float(two.abs().max()) + 1)    # one f16 ulp of an O(1) value at most
     assert float((got.float() - two).abs().mean()) <= 1.25e-4
-    assert torch.equal(H16.attn_out_ln(qkv, mask, w, bias, res, g, be, B, S, H, heads).view(torch.int16), got.view(torch.int16))
+    assert torch.equal(G.attn_out_ln(qkv, mask, w, bias, res, g, be, B, S, H, heads, dtype=F16, raw=True).view(torch.int16), got.view(torch.int16))
 
 
 # ---- row kernels ---------------------------------------------------------------------------------------------------------------
@@ -299,7 +326,7 @@ def test_attention_out_projection_layernorm_one_launch(B, S, mask_kind):
 def test_dwconv(B, S, C_, k):
     x, w, b = rnd(B, S, C_, seed=18), rnd(C_, 1, k, seed=19, scale=k ** -0.5), rnd(C_, seed=20)
     ref = F.conv1d(r16(x).transpose(1, 2), w, b, padding="same", groups=C_).transpose(1, 2)
-    got = H16.dwconv(x.reshape(B * S, C_), w, b, B, S).float().reshape(B, S, C_)
+    got = G.dwconv(F16, x.reshape(B * S, C_), w, b, B, S).float().reshape(B, S, C_)
     assert float((got - ref).abs().max()) <= tol(ref)
 
 
@@ -308,8 +335,8 @@ def test_dwconv_tile_heights_are_bit_identical(k):
     """An utterance gives the same bits alone (128-row tiles) and inside a batch of 64 (256-row tiles)."""
     B, S, C_ = 64, 300, 256
     x, w, b = rnd(B, S, C_, seed=180), rnd(C_, 1, k, seed=190, scale=k ** -0.5), rnd(C_, seed=200)
-    whole = H16.dwconv(x.reshape(B * S, C_), w, b, B, S).reshape(B, S, C_)
-    alone = H16.dwconv(x[5:6].reshape(S, C_), w, b, 1, S).reshape(1, S, C_)
+    whole = G.dwconv(F16, x.reshape(B * S, C_), w, b, B, S, raw=True).reshape(B, S, C_)
+    alone = G.dwconv(F16, x[5:6].reshape(S, C_), w, b, 1, S, raw=True).reshape(1, S, C_)
     assert torch.equal(alone.view(torch.int16), whole[5:6].contiguous().view(torch.int16))
     ref = F.conv1d(r16(x[:2]).transpose(1, 2), w, b, padding="same", groups=C_).transpose(1, 2)
     assert float((whole[:2].float() - ref).abs().max()) <= tol(ref)
@@ -324,11 +351,11 @@ def test_layernorm_residual_and_head(M, Hd):
     mask = torch.zeros(M, dtype=torch.bool)
     mask[::3] = True
     ref = F.layer_norm(r16(x) + r16(r), (Hd,), g, b, 1e-5)
-    y, pred = H16.layernorm(x, r, g, b, dot_w=w, dot_b=0.25, mask=mask)
+    y, pred = G.layernorm(F16, x, r, g, b, dot_w=w, dot_b=0.25, mask=mask)
     assert float((y.float() - ref).abs().max()) <= tol(ref)
     pref = (ref @ w + 0.25).masked_fill(mask, 0)
     assert float((pred - pref).abs().max()) <= 5e-5 * (float(pref.abs().max()) + 1)
-    y2, _ = H16.layernorm(x, None, g, b)
+    y2, _ = G.layernorm(F16, x, None, g, b)
     ref2 = F.layer_norm(r16(x), (Hd,), g, b, 1e-5)
     assert float((y2.float() - ref2).abs().max()) <= tol(ref2)
 
@@ -336,8 +363,8 @@ def test_layernorm_residual_and_head(M, Hd):
 # ---- what does not take the type says so ---------------------------------------------------------------------------------------
 def test_operators_without_an_f16_form_reject_it():
     """Valid small buffers, FS2_F16 as the dtype: an error status before anything is launched (0 from the *_supported query)."""
-    lib, p, st = H16.lib(), H16.p, H16.stream
-    dv = H16.DEV
+    lib, st = G.lib(), torch.cuda.current_stream()
+    dv = G.DEV
     B, S, Hd = 2, 8, 256
     x = torch.zeros(B * S, Hd, dtype=T16, device=dv)
     y = torch.full((B * S, Hd), 7.0, dtype=T16, device=dv)
@@ -347,20 +374,19 @@ def test_operators_without_an_f16_form_reject_it():
     for k, v in dict(M=16, N=16, K=16, sAm=16, sAk=1, sBk=16, sBn=1, ldc=16, nb1=1, nb2=1, alpha=1.0, beta=0.0, splitk=1, taps=1, c_dtype=F16).items():
         setattr(d, k, v)
     a16 = torch.zeros(16, 16, dtype=T16, device=dv)
-    assert lib.fs2_op_bgemm(F16, C.byref(d), p(a16), p(a16), p(a16.clone()), None, None, st()) != 0
+    assert lib.fs2_op_bgemm(F16, C.byref(d), a16, a16, a16.clone(), None, None, st) != 0
     w = torch.zeros(2, Hd, 3 * Hd, dtype=T16, device=dv)
     scratch = torch.zeros(2 * Hd * 3 * Hd * 2, dtype=torch.uint8, device=dv)
-    assert lib.fs2_op_predictor(F16, p(x), p(w), p(f32(2, Hd)), p(f32(2, Hd)), p(f32(2, Hd)), p(f32(Hd)), 0.0, None, p(f32(B * S)),
-                                p(scratch), B, S, Hd, 2, 3, st()) != 0
+    assert lib.fs2_op_predictor(F16, x, w, f32(2, Hd), f32(2, Hd), f32(2, Hd), f32(Hd), 0.0, None, f32(B * S), scratch, B, S, Hd, 2, 3, st) != 0
     cum = torch.tensor([[1, 2, 3, 4]] * B, dtype=torch.int32, device=dv)
     tot = torch.tensor([4] * B, dtype=torch.int32, device=dv)
     xs = torch.zeros(B * 4, Hd, dtype=T16, device=dv)
     mk = torch.zeros(B, 4, dtype=torch.uint8, device=dv)
-    assert lib.fs2_op_regulate(F16, p(xs), p(cum), p(tot), p(y), p(mk), B, 4, 4, Hd, st()) != 0
+    assert lib.fs2_op_regulate(F16, xs, cum, tot, y, mk, B, 4, 4, Hd, st) != 0
     idx = torch.zeros(B * S, dtype=torch.int32, device=dv)
-    assert lib.fs2_op_bucket_embed(F16, p(x), p(f32(B * S)), p(f32(3)), p(f32(4, Hd)), 4, 1.0, 0.0, None, None, p(y), p(idx), B, S, Hd, st()) != 0
+    assert lib.fs2_op_bucket_embed(F16, x, f32(B * S), f32(3), f32(4, Hd), 4, 1.0, 0.0, None, None, y, idx, B, S, Hd, st) != 0
     ph = torch.ones(B, S, dtype=torch.int64, device=dv)
     smk = torch.zeros(B, S, dtype=torch.uint8, device=dv)
-    assert lib.fs2_op_embed(F16, p(ph), p(f32(10, Hd)), p(f32(S, Hd)), p(f32(B, Hd)), p(y), p(smk), B, S, Hd, 10, st()) != 0
+    assert lib.fs2_op_embed(F16, ph, f32(10, Hd), f32(S, Hd), f32(B, Hd), y, smk, B, S, Hd, 10, st) != 0
     torch.cuda.synchronize()
     assert bool((y == 7.0).all())   # nothing was written

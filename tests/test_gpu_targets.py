@@ -31,10 +31,6 @@ SNR_TILE = 32  # windows one workgroup of mel_snr_kernel owns (stated in its com
 GEOMETRIES = {"default": (1024, 1024, 256), "small": (256, 256, 64)}
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def table():
     return T.fixture()[0]["wada_table"]
 
@@ -46,12 +42,12 @@ class Snr:
         self.n_fft, self.win, self.hop = GEOMETRIES[name]
         self.lib, self.h = _lib.load(), C.c_void_p()
         basis = np.ones((8, self.n_fft // 2 + 1), np.float32)
-        st = self.lib.fs2_mel_create(_lib.FS2_ABI_VERSION, self.n_fft, self.win, self.hop, 8, C.c_float(1e-6), 0,
-                                     basis.ctypes.data_as(C.c_void_p), C.byref(self.h))
+        st = self.lib.fs2_mel_create(_lib.FS2_ABI_VERSION, self.n_fft, self.win, self.hop, 8, 1e-6, 0, basis.ctypes.data_as(C.c_void_p),
+                                     C.byref(self.h))
         assert st == 0, self.lib.fs2_mel_last_error(self.h)
         if with_table:
             g = np.ascontiguousarray(table(), np.float64)
-            assert self.lib.fs2_mel_set_snr_table(self.h, g.ctypes.data_as(C.c_void_p), len(g), C.c_float(-20)) == 0
+            assert self.lib.fs2_mel_set_snr_table(self.h, g.ctypes.data_as(C.c_void_p), len(g), -20) == 0
 
     def __del__(self):
         if self.h:
@@ -69,11 +65,11 @@ class Snr:
         fr = torch.full((Bw + SLACK,), ICANARY, dtype=torch.int32, device=DEV)
         need = self.lib.fs2_mel_ws_bytes(self.h, Bw, S)
         ws = torch.zeros(need + SLACK, dtype=torch.uint8, device=DEV)
-        args = {"wav": _p(w), "snr": _p(out)}
+        args = {"wav": w, "snr": out}
         for k in null:
             args[k] = None
-        st = self.lib.fs2_mel_snr(self.h, args["wav"], _p(ld), B, S, int(pn), args["snr"], Te_max, _p(fr) if frames else None, _p(ws),
-                                  need - ws_short, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        st = self.lib.fs2_mel_snr(self.h, args["wav"], ld, B, S, int(pn), args["snr"], Te_max, fr if frames else None, ws, need - ws_short,
+                                  torch.cuda.current_stream())
         torch.cuda.synchronize()
         out, fr = out.cpu().numpy(), fr.cpu().numpy()
         res = {"status": st, "snr": out[:-SLACK].reshape(Bw, Te_max), "frames": fr[:Bw],
@@ -221,7 +217,7 @@ def test_snr_argument_errors_write_nothing():
     assert o["status"] == STATE and o["untouched"] and b"fs2_mel_set_snr_table" in bare.lib.fs2_mel_last_error(bare.h)
     g = np.ascontiguousarray(table(), np.float64)
     for _ in range(2):  # the table may be set again
-        assert bare.lib.fs2_mel_set_snr_table(bare.h, g.ctypes.data_as(C.c_void_p), len(g), C.c_float(-20)) == 0
+        assert bare.lib.fs2_mel_set_snr_table(bare.h, g.ctypes.data_as(C.c_void_p), len(g), -20) == 0
     ok = bare.run(x, [3000], True)
     assert ok["status"] == 0 and np.array_equal(ok["snr"].view(np.uint32), h.run(x, [3000], True)["snr"].view(np.uint32))
 
@@ -238,8 +234,8 @@ def finish_raw(values, frames, dur, silent, zim, amv, mean, std, with_prior=True
     out = torch.full((B * Tn + SLACK,), CANARY, dtype=torch.float32, device=DEV)
     fo = torch.full((B + SLACK,), ICANARY, dtype=torch.int32, device=DEV)
     pr = torch.full((B + SLACK,), CANARY, dtype=torch.float32, device=DEV)
-    st = _lib.load().fs2_op_contour_finish(_p(v), _p(f), _p(d), _p(s), B, Tn, L, int(zim), C.c_float(amv), C.c_float(mean), C.c_float(std),
-                                           _p(out), _p(fo), _p(pr) if with_prior else None, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    st = _lib.load().fs2_op_contour_finish(v, f, d, s, B, Tn, L, int(zim), amv, mean, std, out, fo, pr if with_prior else None,
+                                           torch.cuda.current_stream())
     torch.cuda.synchronize()
     out, fo, pr = out.cpu().numpy(), fo.cpu().numpy(), pr.cpu().numpy()
     assert st == 0 and (out[B * Tn:] == CANARY).all() and (fo[B:] == ICANARY).all() and (pr[B if with_prior else 0:] == CANARY).all()

@@ -183,11 +183,11 @@ def test_dropout_op_statistics_and_determinism():
     lib = _lib.load()
     n, p = 1 << 20, 0.3
     x = torch.ones(n, device="cuda:0")
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = torch.cuda.current_stream()
     outs = []
     for seed, key in ((5, 1), (5, 1), (5, 2), (6, 1)):
         y = torch.empty_like(x)
-        _lib.check(lib.fs2_op_dropout(_lib.FS2_F32, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), n, C.c_float(p), C.c_uint64(seed), C.c_uint64(key), st))
+        _lib.check(lib.fs2_op_dropout(_lib.FS2_F32, x, y, n, p, C.c_uint64(seed), C.c_uint64(key), st))
         outs.append(y.cpu())
     a, b, c, d = outs
     assert torch.equal(a, b) and not torch.equal(a, c) and not torch.equal(a, d)
@@ -198,7 +198,7 @@ def test_dropout_op_statistics_and_determinism():
     assert abs(both - (1 - p) ** 2) <= 5e-3
     xb = torch.ones(n, device="cuda:0", dtype=torch.bfloat16)
     yb = torch.empty_like(xb)
-    _lib.check(lib.fs2_op_dropout(_lib.FS2_BF16, C.c_void_p(xb.data_ptr()), C.c_void_p(yb.data_ptr()), n, C.c_float(p), C.c_uint64(5), C.c_uint64(1), st))
+    _lib.check(lib.fs2_op_dropout(_lib.FS2_BF16, xb, yb, n, p, C.c_uint64(5), C.c_uint64(1), st))
     assert torch.equal(yb.cpu() != 0, a != 0)  # the mask depends on (seed, key, index) only: an fp32 gradient meets the bf16 mask
 
 

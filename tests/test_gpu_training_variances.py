@@ -3,7 +3,6 @@ fixtures the REAL reference produced (tools/gen_golden_train_variances.py), (b) 
 other shapes, and the two CWT-head operators (fs2_op_cwt_head_train / fs2_op_cwt_head_bwd) against float64 numpy.
 Tolerances are those of tests/test_gpu_training.py: losses 1e-5 relative, gradients 1e-4 of the tensor's largest entry,
 gradient norms 2e-4, learning rates 1e-12, weights after three steps 2e-5."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -172,10 +171,6 @@ def test_bf16_mixed_precision_step_tracks_the_fp32_gradients():
 
 
 # ---- 6. the two operators ----
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def _op_inputs(B, S, F, tdt, seed):
     rs = np.random.RandomState(seed)
     y = torch.from_numpy(rs.randn(B * S, F).astype(np.float32)).to(tdt)
@@ -205,7 +200,7 @@ def test_cwt_head_operators_match_float64(B, S, F, dtype):
     lib = _lib.load()
     dt, tdt = (_lib.FS2_F32, torch.float32) if dtype == "fp32" else (_lib.FS2_BF16, torch.bfloat16)
     d = _op_inputs(B, S, F, tdt, 100 + S)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = torch.cuda.current_stream()
     dev = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)).cuda() for k, v in d.items()}
     y64 = d["y"].double().numpy()
     valid = 1.0 - d["mask"].reshape(-1, 1).astype(np.float64)
@@ -216,8 +211,8 @@ def test_cwt_head_operators_match_float64(B, S, F, dtype):
     for _ in range(2):
         spec, ybar, ms = (torch.full((B * S, 10), 7.0, device="cuda"), torch.full((B, F), 7.0, device="cuda"), torch.full((B, 2), 7.0, device="cuda"))
         ws = torch.zeros(int(lib.fs2_op_cwt_head_train_ws_bytes(B, S, F)) // 4 + 1, device="cuda")
-        _lib.check(lib.fs2_op_cwt_head_train(dt, _p(dev["y"]), _p(dev["w10"]), _p(dev["b10"]), _p(dev["ms_w"]), _p(dev["ms_b"]), _p(dev["mask"]),
-                                             _p(spec), _p(ybar), _p(ms), _p(ws), B, S, F, st))
+        _lib.check(lib.fs2_op_cwt_head_train(dt, dev["y"], dev["w10"], dev["b10"], dev["ms_w"], dev["ms_b"], dev["mask"], spec, ybar, ms,
+                                             ws, B, S, F, st))
         runs.append((spec, ybar, ms))
     for a, b in zip(*runs):
         assert torch.equal(a, b)
@@ -235,8 +230,8 @@ def test_cwt_head_operators_match_float64(B, S, F, dtype):
         g = {k: dev[k].clone() for k in want}
         dy = torch.full((B * S, F), 7.0, device="cuda", dtype=tdt)
         ws = torch.zeros(int(lib.fs2_op_cwt_head_bwd_ws_bytes(B, S, F)) // 4 + 1, device="cuda")
-        _lib.check(lib.fs2_op_cwt_head_bwd(dt, _p(dev["y"]), _p(dev["dspec"]), _p(dev["dms"]), _p(ybar32), _p(dev["w10"]), _p(dev["ms_w"]), _p(dy),
-                                           _p(g["g_w10"]), _p(g["g_b10"]), _p(g["g_ms_w"]), _p(g["g_ms_b"]), _p(ws), B, S, F, st))
+        _lib.check(lib.fs2_op_cwt_head_bwd(dt, dev["y"], dev["dspec"], dev["dms"], ybar32, dev["w10"], dev["ms_w"], dy, g["g_w10"],
+                                           g["g_b10"], g["g_ms_w"], g["g_ms_b"], ws, B, S, F, st))
         runs.append((dy, g))
     assert torch.equal(runs[0][0], runs[1][0])
     for k in want:
@@ -256,15 +251,13 @@ def test_cwt_head_operators_reject_an_unsupported_width():
     from lightningfastspeech2_amd import _lib
     lib = _lib.load()
     B, S, F = 2, 5, 100
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = torch.cuda.current_stream()
     z = lambda *s, dtype=torch.float32: torch.zeros(*s, device="cuda", dtype=dtype)
     y, w10, b10, msw, msb, mask = z(B * S, 128), z(10, 128), z(10), z(2, 128), z(2), z(B * S, dtype=torch.uint8)
     spec, ybar, ms, ws, dy = z(B * S, 10), z(B, 128), z(B, 2), z(1 << 16), z(B * S, 128)
     for F_ in (F, 32, 1088):
-        assert lib.fs2_op_cwt_head_train(_lib.FS2_F32, _p(y), _p(w10), _p(b10), _p(msw), _p(msb), _p(mask), _p(spec), _p(ybar), _p(ms), _p(ws),
-                                         B, S, F_, st) == _lib.FS2_ERR_ARG
-        assert lib.fs2_op_cwt_head_bwd(_lib.FS2_F32, _p(y), _p(spec), _p(ms), _p(ybar), _p(w10), _p(msw), _p(dy), _p(w10.clone()), _p(b10),
-                                       _p(msw.clone()), _p(msb), _p(ws), B, S, F_, st) == _lib.FS2_ERR_ARG
+        assert lib.fs2_op_cwt_head_train(_lib.FS2_F32, y, w10, b10, msw, msb, mask, spec, ybar, ms, ws, B, S, F_, st) == _lib.FS2_ERR_ARG
+        assert lib.fs2_op_cwt_head_bwd(_lib.FS2_F32, y, spec, ms, ybar, w10, msw, dy, w10.clone(), b10, msw.clone(), msb, ws, B, S, F_, st) == _lib.FS2_ERR_ARG
     torch.cuda.synchronize()
 
 

@@ -1,7 +1,6 @@
 """fs2_op_wav_pack on its own (no generator): the float32 -> int16 cast and the int16 -> float32 rescale bit for bit against numpy (what
 Synthesiser.__call__ and int16_samples_to_float32 do on the host), the offsets and the packed layout of ragged batches on the wide
 (16 B) and the narrow path, writes behind the packed total, argument errors."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -17,10 +16,6 @@ CANARY = {"int16": 12345, "float32": 777.0}
 SLACK = 64  # canary elements behind the capacity the operator asks for
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def pack(wav, lengths, hop, dtype, capacity=None):
     """-> status, out (whole buffer, canaries included), offsets; straight through the C ABI."""
     kind, tdt, _ = KINDS[dtype]
@@ -30,8 +25,7 @@ def pack(wav, lengths, hop, dtype, capacity=None):
     cap = B * S if capacity is None else capacity
     out = torch.full((cap + SLACK,), CANARY[dtype], dtype=tdt, device=DEV)
     off = torch.full((B + 2,), -7, dtype=torch.int64, device=DEV)
-    st = _lib.load().fs2_op_wav_pack(_p(w), _p(ld), B, S // hop, hop, kind, _p(out), cap, _p(off),
-                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    st = _lib.load().fs2_op_wav_pack(w, ld, B, S // hop, hop, kind, out, cap, off, torch.cuda.current_stream())
     torch.cuda.synchronize()
     return st, out.cpu().numpy(), off.cpu().numpy()
 
@@ -165,8 +159,8 @@ def test_errors():
     w = torch.zeros(2, 24, device=DEV)
     out = torch.zeros(48, dtype=torch.int16, device=DEV)
     off = torch.zeros(3, dtype=torch.int64, device=DEV)
-    args = lambda **k: [k.get("wav", _p(w)), None, k.get("B", 2), k.get("T", 3), k.get("hop", 8), k.get("kind", 0), k.get("out", _p(out)),
-                        48, k.get("off", _p(off)), None]
+    args = lambda **k: [k.get("wav", w), None, k.get("B", 2), k.get("T", 3), k.get("hop", 8), k.get("kind", 0), k.get("out", out),
+                        48, k.get("off", off), None]
     assert lib.fs2_op_wav_pack(*args()) == 0
     for bad in (dict(wav=None), dict(out=None), dict(off=None), dict(kind=2), dict(B=0), dict(T=0), dict(hop=0)):
         assert lib.fs2_op_wav_pack(*args(**bad)) == _lib.FS2_ERR_ARG, bad

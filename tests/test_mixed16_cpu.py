@@ -69,7 +69,7 @@ def test_f16_alone_is_not_an_engine_mode(lib):
 def test_host_conversion_saturates_and_rounds_to_nearest_even(lib):
     x = _f16.edge_values()
     got = torch.empty(x.numel(), dtype=torch.int16)
-    assert lib.fs2_host_f32_to_f16(C.c_void_p(x.data_ptr()), C.c_void_p(got.data_ptr()), x.numel()) == 0
+    assert lib.fs2_host_f32_to_f16(x, got, x.numel()) == 0
     want = _f16.f16_bits(x)
     bad = (got != want).nonzero().flatten()
     assert bad.numel() == 0, [(float(x[i]), hex(int(got[i]) & 0xFFFF), hex(int(want[i]) & 0xFFFF)) for i in bad[:8]]

@@ -115,7 +115,7 @@ def test_finish_yardstick_cases():
 def _handle(lib, n_fft=1024, win=1024, hop=256):
     basis = np.ones((80, n_fft // 2 + 1), np.float32)
     h = C.c_void_p()
-    st = lib.fs2_mel_create(_lib.FS2_ABI_VERSION, n_fft, win, hop, 80, C.c_float(1e-6), 0, basis.ctypes.data_as(C.c_void_p), C.byref(h))
+    st = lib.fs2_mel_create(_lib.FS2_ABI_VERSION, n_fft, win, hop, 80, 1e-6, 0, basis.ctypes.data_as(C.c_void_p), C.byref(h))
     assert h.value
     return st, h
 
@@ -128,10 +128,10 @@ def test_snr_table_and_snr_refuse_bad_arguments(lib):
     bad[60] = np.nan
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     f = lib.fs2_mel_set_snr_table
-    assert f(None, p(good), 121, C.c_float(-20)) == ARG
+    assert f(None, p(good), 121, -20) == ARG
     for args, text in (((None, 121), "null"), ((p(good), 1), "entries"), ((p(good), 513), "entries"), ((p(bad), 121), "not finite")):
-        assert f(h, args[0], args[1], C.c_float(-20)) == ARG and text in lib.fs2_mel_last_error(h).decode(), args
-    assert f(h, p(good), 121, C.c_float(np.inf)) == ARG
+        assert f(h, args[0], args[1], -20) == ARG and text in lib.fs2_mel_last_error(h).decode(), args
+    assert f(h, p(good), 121, np.inf) == ARG
     # no table yet (and, without a device, no handle that could take one): FS2_ERR_STATE, nothing read
     assert lib.fs2_mel_snr(h, None, None, 1, 1, 1, None, 1, None, None, 0, None) == STATE
     assert lib.fs2_mel_snr(None, None, None, 1, 1, 1, None, 1, None, None, 0, None) == ARG
@@ -158,7 +158,7 @@ def test_contour_finish_and_row_mean_refuse_bad_arguments(lib):
     f = lib.fs2_op_contour_finish
 
     def call(values=v, dur=d, out=o, fout=fo, B=1, T=8, L=8, mean=0.0, std=1.0):
-        return f(values, None, dur, None, B, T, L, 0, C.c_float(0), C.c_float(mean), C.c_float(std), out, fout, None, None)
+        return f(values, None, dur, None, B, T, L, 0, 0, mean, std, out, fout, None, None)
     assert call(std=0.0) == ARG and call(std=np.nan) == ARG and call(std=np.inf) == ARG and call(mean=np.nan) == ARG
     assert call(values=None) == ARG and call(dur=None) == ARG and call(out=None) == ARG and call(fout=None) == ARG
     assert call(B=0) == ARG and call(T=0) == ARG and call(L=0) == ARG
@@ -172,7 +172,7 @@ def test_new_symbols_and_python_surface(lib):
     names = _lib.declared_symbols()
     for n in NEW:
         assert n in names and hasattr(lib, n), n
-    assert lib.fs2_mel_set_snr_table.argtypes == [C.c_void_p, C.c_void_p, C.c_int32, C.c_float]
+    assert lib.fs2_mel_set_snr_table.argtypes == [_lib.DevPtr, _lib.DevPtr, C.c_int32, C.c_float]
     assert len(lib.fs2_mel_snr.argtypes) == 12 and lib.fs2_mel_snr.argtypes[10] is C.c_size_t
     assert lib.fs2_op_contour_finish.argtypes[7:11] == [C.c_int32, C.c_float, C.c_float, C.c_float] and len(lib.fs2_op_contour_finish.argtypes) == 15
     assert len(lib.fs2_op_masked_row_mean.argtypes) == 7

@@ -36,10 +36,6 @@ from lightningfastspeech2_amd.analysis import MelAnalyzer
 MFMA_F32, HBM, L2 = 155e12, 6.29e12, 17e12  # measured rates (fp32 MFMA, float4 copy, rows shared by every workgroup from L2)
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def cpu_recipe(x, basis, n_fft, hop, win, clip):
     mag = torch.stft(x, n_fft, hop_length=hop, win_length=win, window=torch.hann_window(win), center=True, pad_mode="constant",
                      return_complex=True).abs()
@@ -91,11 +87,10 @@ def main():
     mf, ef = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
     need = lib.fs2_mel_ws_bytes(an.handle, B, S)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = torch.cuda.current_stream()
 
     def run(full):
-        st = lib.fs2_mel_run(an.handle, _p(wav), _p(lengths), B, S, int(full), _p(mel), T, _p(energy) if full else None, Te, _p(mf),
-                             _p(ef), _p(ws), need, stream)
+        st = lib.fs2_mel_run(an.handle, wav, lengths, B, S, int(full), mel, T, energy if full else None, Te, mf, ef, ws, need, stream)
         assert st == 0, lib.fs2_mel_last_error(an.handle)
 
     def fastest(full, run=run):
@@ -157,7 +152,7 @@ def main():
         sf = torch.empty(B, dtype=torch.int32, device=dev)
 
         def run_snr(_full=True):
-            st = lib.fs2_mel_snr(an.handle, _p(wav), _p(lengths), B, S, 1, _p(snr), Te, _p(sf), _p(ws), need, stream)
+            st = lib.fs2_mel_snr(an.handle, wav, lengths, B, S, 1, snr, Te, sf, ws, need, stream)
             assert st == 0, lib.fs2_mel_last_error(an.handle)
 
         snr_ms, snr_loops = fastest(True, run_snr)

@@ -19,16 +19,12 @@ DEV = "cuda:0"
 BF16 = _lib.FS2_BF16
 
 
-def p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 FLUSH = [None]  # --flush MB: a torch pass over that many MB between reps (evicts the L2s, and the Infinity Cache from 256 MB on):
                  # what a launch costs inside a forward, where its weights were last touched a whole layer ago
 
 
 def timeit(fn, reps):
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = torch.cuda.current_stream()
     for _ in range(3):
         fn(st)
     if FLUSH[0] is not None:
@@ -58,7 +54,7 @@ def gemm_case(name, M, N, Cin, taps, S, reps, variant):
     w = (torch.randn(N, taps * Cin, device=DEV) * (taps * Cin) ** -0.5).to(torch.bfloat16)
     b = torch.randn(N, device=DEV)
     c = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
-    t = timeit(lambda st: lib.fs2_op_gemm(BF16, BF16, p(x), p(w), p(b), p(c), M, N, Cin, taps, S, 1, st), reps)
+    t = timeit(lambda st: lib.fs2_op_gemm(BF16, BF16, x, w, b, c, M, N, Cin, taps, S, 1, st), reps)
     fl = 2.0 * M * N * Cin * taps
     print(f"{name:28s} M={M:6d} N={N:5d} K={taps*Cin:5d} variant={variant}  {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF  ({fl/t/2.5e15*100:4.1f}% of 2.5 PF)")
     lib.fs2_op_set_gemm_variant(0)
@@ -82,7 +78,7 @@ def splitk_case(name, M, N, Cin, taps, S, ks, reps):
     w = (torch.randn(N, taps * Cin, device=DEV) * (taps * Cin) ** -0.5).to(torch.bfloat16)
     c = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     part = torch.empty(ks, M, N, device=DEV)
-    t = timeit(lambda st: lib.fs2_op_gemm_splitk(BF16, BF16, p(x), p(w), p(c), p(part), M, N, Cin, taps, S, ks, 1, st), reps)
+    t = timeit(lambda st: lib.fs2_op_gemm_splitk(BF16, BF16, x, w, c, part, M, N, Cin, taps, S, ks, 1, st), reps)
     fl = 2.0 * M * N * Cin * taps
     print(f"{name:34s} M={M} N={N} K={taps}x{Cin}  {t * 1e6:8.1f} us  {fl / t / 1e12:7.1f} TF  (launch + plane sum, accumulating)")
 
@@ -98,8 +94,7 @@ def gemm_ln_case(name, M, N, Cin, taps, S, reps, variant, res=True, relu=False):
     be = torch.randn(N, device=DEV)
     y = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     tmp = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
-    t = timeit(lambda st: lib.fs2_op_gemm_ln(BF16, p(x), p(w), p(b), p(r), p(g), p(be), None, C.c_float(0.0), None, None,
-                                             p(y), p(tmp), M, N, Cin, taps, S, int(relu), st), reps)
+    t = timeit(lambda st: lib.fs2_op_gemm_ln(BF16, x, w, b, r, g, be, None, 0.0, None, None, y, tmp, M, N, Cin, taps, S, int(relu), st), reps)
     fl = 2.0 * M * N * Cin * taps
     by = 2.0 * (M * Cin + M * N * (2 if res else 1))
     print(f"{name:28s} M={M:6d} N={N:5d} K={taps*Cin:5d} variant={variant}  {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF  "
@@ -117,7 +112,7 @@ def bgemm_case(name, dims, A, Bm, Cout, reps, **kw):
     nb = lib.fs2_op_bgemm_ws_bytes(C.byref(d))
     ws = torch.empty(max(1, nb // 4), device=DEV)
     dt = _lib.FS2_F32 if A.dtype == torch.float32 else BF16
-    t = timeit(lambda st: lib.fs2_op_bgemm(dt, C.byref(d), p(A), p(Bm), p(Cout), None, p(ws), st), reps)
+    t = timeit(lambda st: lib.fs2_op_bgemm(dt, C.byref(d), A, Bm, Cout, None, ws, st), reps)
     fl = 2.0 * dims
     print(f"{name:34s} {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF  ({fl/t/2.5e15*100:4.1f}% of 2.5 PF)")
 
@@ -197,8 +192,8 @@ def flash_bwd_case(name, B, S, H, heads, reps):
     for knobs in ((900, 902), (900, 903), (901, 902), (905, 903), (900, 907), (900, 908), (905, 907), (905, 908)):  # blocks per wave of the (dK dV, dQ) launches (905 / 907: 3, 908: 4)
         for knob in knobs:
             lib.fs2_op_set_gemm_variant(knob)
-        t = timeit(lambda st: lib.fs2_op_attention_bwd(BF16, p(qkv), p(dout), p(lse), p(delta), None, p(dqkv), B, S, H, heads,
-                                                       C.c_float(0.0), C.c_uint64(0), C.c_uint64(0), st), reps)
+        t = timeit(lambda st: lib.fs2_op_attention_bwd(BF16, qkv, dout, lse, delta, None, dqkv, B, S, H, heads, 0.0, C.c_uint64(0),
+                                                       C.c_uint64(0), st), reps)
         fl = 5 * 2.0 * B * S * S * H  # dV, dP, dS-products: five S x S x d GEMMs are the useful work
         print(f"{name:30s} knobs={knobs[0]},{knobs[1]}  {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF useful ({fl/t/2.5e15*100:4.1f}% of 2.5 PF)")
     lib.fs2_op_set_gemm_variant(909)
@@ -214,8 +209,7 @@ def predictor_case(name, B, S, nl, reps):
     hw = torch.randn(H, device=DEV)
     pred = torch.empty(B * S, device=DEV)
     scratch = torch.empty(nl * H * k * H * 2, dtype=torch.uint8, device=DEV)
-    t = timeit(lambda st: lib.fs2_op_predictor(BF16, p(x), p(w), p(b), p(g), p(be), p(hw), C.c_float(0.1), None, p(pred),
-                                               p(scratch), B, S, H, nl, k, st), reps)
+    t = timeit(lambda st: lib.fs2_op_predictor(BF16, x, w, b, g, be, hw, 0.1, None, pred, scratch, B, S, H, nl, k, st), reps)
     fl = 2.0 * B * S * H * H * k * nl
     print(f"{name:28s} B={B} S={S} layers={nl}  {t*1e6:8.1f} us (incl. {nl} weight-pack launches)  {fl/t/1e12:7.1f} TF  "
           f"({fl/t/2.5e15*100:4.1f}% of 2.5 PF)")
@@ -231,8 +225,7 @@ def predictor_dw_case(name, B, S, nl, reps):
     hw = torch.randn(H, device=DEV)
     pred = torch.empty(B * S, device=DEV)
     scratch = torch.empty(nl * H * H * 2, dtype=torch.uint8, device=DEV)
-    t = timeit(lambda st: lib.fs2_op_predictor_dw(BF16, p(x), p(dw), p(dwb), p(w), p(b), p(g), p(be), p(hw), C.c_float(0.1), None, p(pred),
-                                                  p(scratch), B, S, H, nl, st), reps)
+    t = timeit(lambda st: lib.fs2_op_predictor_dw(BF16, x, dw, dwb, w, b, g, be, hw, 0.1, None, pred, scratch, B, S, H, nl, st), reps)
     fl = 2.0 * B * S * H * (H + 3) * nl
     print(f"{name:28s} B={B} S={S} layers={nl}  {t*1e6:8.1f} us (incl. {nl} weight-pack launches)  {fl/t/1e12:7.1f} TF  "
           f"({fl/t/2.5e15*100:4.1f}% of 2.5 PF)")
@@ -246,7 +239,7 @@ def attn_case(name, B, S, H, heads, reps):
     vb = lib.fs2_op_attention_scratch_bytes(BF16, B, S, H, heads, C.byref(bb))
     vt = torch.empty(vb, dtype=torch.uint8, device=DEV)
     bits = torch.empty(bb.value, dtype=torch.uint8, device=DEV)
-    t = timeit(lambda st: lib.fs2_op_attention(BF16, p(qkv), p(mask), p(out), p(vt), p(bits), B, S, H, heads, st), reps)
+    t = timeit(lambda st: lib.fs2_op_attention(BF16, qkv, mask, out, vt, bits, B, S, H, heads, st), reps)
     fl = 4.0 * B * S * S * H
     print(f"{name:28s} B={B} S={S} H={H} heads={heads}  {t*1e6:8.1f} us (incl. mask bits + V^T staging)  {fl/t/1e12:7.1f} TF")
 
@@ -267,10 +260,10 @@ def attn_out_case(name, B, S, reps):
     vb = lib.fs2_op_attention_scratch_bytes(BF16, B, S, H, heads, C.byref(bb))
     vt = torch.empty(max(vb, 16), dtype=torch.uint8, device=DEV)
     bits = torch.empty(bb.value, dtype=torch.uint8, device=DEV)
-    t1 = timeit(lambda st: lib.fs2_op_attn_out_ln(BF16, p(qkv), p(mask), p(w), p(bias), p(res), p(g), p(be), p(out), p(scratch), B, S, H, heads, st), reps)
+    t1 = timeit(lambda st: lib.fs2_op_attn_out_ln(BF16, qkv, mask, w, bias, res, g, be, out, scratch, B, S, H, heads, st), reps)
     def two(st):
-        lib.fs2_op_attention(BF16, p(qkv), p(mask), p(att), p(vt), p(bits), B, S, H, heads, st)
-        lib.fs2_op_gemm_ln(BF16, p(att), p(w), p(bias), p(res), p(g), p(be), None, C.c_float(0.0), None, None, p(out), p(tmp), B * S, H, H, 1, B * S, 0, st)
+        lib.fs2_op_attention(BF16, qkv, mask, att, vt, bits, B, S, H, heads, st)
+        lib.fs2_op_gemm_ln(BF16, att, w, bias, res, g, be, None, 0.0, None, None, out, tmp, B * S, H, H, 1, B * S, 0, st)
     t2 = timeit(two, reps)
     fl = 4.0 * B * S * S * H + 2.0 * B * S * H * H
     print(f"{name:28s} B={B} S={S}  one launch {t1 * 1e6:7.1f} us (incl. mask bits + weight pack)   two launches {t2 * 1e6:7.1f} us (incl. mask bits)   "
@@ -283,7 +276,7 @@ def dwconv_case(name, B, S, Cc, k, reps):
     w = torch.randn(Cc, k, device=DEV) * k ** -0.5
     b = torch.randn(Cc, device=DEV)
     y = torch.empty_like(x)
-    t = timeit(lambda st: lib.fs2_op_dwconv(BF16, p(x), p(w), p(b), p(y), B, S, Cc, k, st), reps)
+    t = timeit(lambda st: lib.fs2_op_dwconv(BF16, x, w, b, y, B, S, Cc, k, st), reps)
     by = 2.0 * x.numel() * 2
     print(f"{name:28s} B={B} S={S} C={Cc} k={k:2d}   {t * 1e6:8.1f} us   {by / t / 1e12:6.2f} TB/s  ({by / t / 8e12 * 100:4.1f}% of 8 TB/s)", flush=True)
 

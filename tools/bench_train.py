@@ -89,22 +89,19 @@ def loops(tr, batch, steps, warmup, repeats=5):
 
 def op_times(precision, B, S, F, n=20):
     """us per launch of the two CWT-head operators on (B S, F) rows (events around n launches, the fastest of five)"""
-    import ctypes as C
     from lightningfastspeech2_amd import _lib
     lib = _lib.load()
     dt, tdt = (_lib.FS2_F32, torch.float32) if precision == "fp32" else (_lib.FS2_BF16, torch.bfloat16)
     z = lambda *s, dtype=torch.float32: torch.randn(*s, device="cuda").to(dtype)
-    p = lambda t: C.c_void_p(t.data_ptr())
     y, w10, b10, msw, msb = z(B * S, F, dtype=tdt), z(10, F), z(10), z(2, F), z(2)
     mask = torch.zeros(B * S, dtype=torch.uint8, device="cuda")
     spec, ybar, ms, dy = z(B * S, 10), z(B, F), z(B, 2), z(B * S, F, dtype=tdt)
     g = [z(10, F), z(10), z(2, F), z(2)]
     ws1 = torch.zeros(int(lib.fs2_op_cwt_head_train_ws_bytes(B, S, F)) // 4 + 1, device="cuda")
     ws2 = torch.zeros(int(lib.fs2_op_cwt_head_bwd_ws_bytes(B, S, F)) // 4 + 1, device="cuda")
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    fwd = lambda: _lib.check(lib.fs2_op_cwt_head_train(dt, p(y), p(w10), p(b10), p(msw), p(msb), p(mask), p(spec), p(ybar), p(ms), p(ws1), B, S, F, st))
-    bwd = lambda: _lib.check(lib.fs2_op_cwt_head_bwd(dt, p(y), p(spec), p(ms), p(ybar), p(w10), p(msw), p(dy), p(g[0]), p(g[1]), p(g[2]), p(g[3]),
-                                                     p(ws2), B, S, F, st))
+    st = torch.cuda.current_stream()
+    fwd = lambda: _lib.check(lib.fs2_op_cwt_head_train(dt, y, w10, b10, msw, msb, mask, spec, ybar, ms, ws1, B, S, F, st))
+    bwd = lambda: _lib.check(lib.fs2_op_cwt_head_bwd(dt, y, spec, ms, ybar, w10, msw, dy, g[0], g[1], g[2], g[3], ws2, B, S, F, st))
     out = {}
     for name, fn in (("cwt_head_train_us", fwd), ("cwt_head_bwd_us", bwd)):
         fn()
