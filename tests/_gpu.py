@@ -428,3 +428,90 @@ def cwt_head_s(dtype, out_conv, spec, mask, ms_w, ms_b, B, T, F):
     st = lib().fs2_op_cwt_head(dtype, od, sd, int(spec.shape[1]), md, wd, bd, ms, pred, so, B, T, F, torch.cuda.current_stream())
     torch.cuda.synchronize()
     return st, ms, pred, so
+
+
+# ------------------------------------------------------------------------------------------------
+# The training tape's launches (tests/test_gpu_tape_ops.py), in the x_s convention: (status, sentinel buffers...), never raising.
+def _f32(a):
+    return None if a is None else torch.as_tensor(a).float().to(DEV).contiguous()
+
+
+def _u8(a):
+    return None if a is None else torch.as_tensor(a).to(torch.uint8).to(DEV).contiguous()
+
+
+def dropout_keep(shape, p, seed, key):
+    """fs2_op_dropout on fp32 ones of `shape`: the multiplier per element, 0 or the device's 1 / (1 - p), on the host."""
+    ones = torch.ones(shape, dtype=torch.float32, device=DEV)
+    out = torch.empty_like(ones)
+    ok(lib().fs2_op_dropout(F32, ones, out, ones.numel(), p, C.c_uint64(seed), C.c_uint64(key), torch.cuda.current_stream()), "dropout")
+    torch.cuda.synchronize()
+    return out.cpu()
+
+
+def gemm_ln_tape(dtype, x, w_packed, bias, res, g, b, taps, S, relu, drop=None, want_z=True):
+    """fs2_op_gemm_ln_tape, or with drop = (p, seed, key) fs2_op_gemm_ln_tape_dropout -> status, y buffer, z buffer ((M + 1, N)
+    sentinel buffers on the device; z None with want_z = False, which hands the entry a NULL z_out)."""
+    M, Cin = x.shape
+    N = w_packed.shape[0]
+    xd, wd = to_dev(x, dtype), to_dev(w_packed, dtype)
+    rd = None if res is None else to_dev(res, dtype)
+    bd, gd, bed = _f32(bias), _f32(g), _f32(b)
+    y = sentinel(M, N, tdt(dtype))
+    z = sentinel(M, N, tdt(dtype)) if want_z else None
+    if drop is None:
+        st = lib().fs2_op_gemm_ln_tape(dtype, xd, wd, bd, rd, gd, bed, y, z, M, N, Cin, taps, S or M, int(relu), torch.cuda.current_stream())
+    else:
+        p, seed, key = drop
+        st = lib().fs2_op_gemm_ln_tape_dropout(dtype, xd, wd, bd, rd, gd, bed, y, z, M, N, Cin, taps, S or M, int(relu), p,
+                                               C.c_uint64(seed), C.c_uint64(key), torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    return st, y, z
+
+
+def layernorm_bwd_s(dtype, z, res, dy, gamma, relu_mask, masked=None, want_dzm=True):
+    """fs2_op_layernorm_bwd, or with masked = (out_p, seed, out_key) fs2_op_layernorm_bwd_masked -> status, dz buffer, dzm buffer
+    (None for the plain entry or with want_dzm = False: a NULL dzm), part buffer (nparts * 3 + 1, H) fp32; z, res, dy are taken
+    in the storage dtype by to_dev."""
+    M, H = z.shape
+    zd, dyd = to_dev(z, dtype), to_dev(dy, dtype)
+    rd = None if res is None else to_dev(res, dtype)
+    gd = _f32(gamma)
+    nparts = lib().fs2_op_layernorm_bwd_parts(M)
+    dz, part = sentinel(M, H, tdt(dtype)), sentinel(nparts * 3, H, torch.float32)
+    dzm = None
+    if masked is None:
+        st = lib().fs2_op_layernorm_bwd(dtype, zd, rd, dyd, gd, dz, part, M, H, int(relu_mask), torch.cuda.current_stream())
+    else:
+        p, seed, key = masked
+        dzm = sentinel(M, H, tdt(dtype)) if want_dzm else None
+        st = lib().fs2_op_layernorm_bwd_masked(dtype, zd, rd, dyd, gd, dz, dzm, part, M, H, int(relu_mask), p, C.c_uint64(seed),
+                                               C.c_uint64(key), torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    return st, dz, dzm, part
+
+
+def layernorm_head_s(dtype, x, res, gamma, beta, dot_w, dot_b, mask, want_pred=True):
+    """fs2_op_layernorm_head (the head's bias read from device memory; dot_w / dot_b None hand it a NULL) -> status, y buffer
+    (M + 1, H), pred buffer (M + 1, 1) fp32 (None with want_pred = False)."""
+    M, H = x.shape
+    xd = to_dev(x, dtype)
+    rd = None if res is None else to_dev(res, dtype)
+    bdev = None if dot_b is None else torch.tensor([dot_b], dtype=torch.float32, device=DEV)
+    y = sentinel(M, H, tdt(dtype))
+    pred = sentinel(M, 1, torch.float32) if want_pred else None
+    st = lib().fs2_op_layernorm_head(dtype, xd, rd, _f32(gamma), _f32(beta), y, _f32(dot_w), bdev, _u8(mask), pred, M, H,
+                                     torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    return st, y, pred
+
+
+def row_dot_s(dtype, y, w, b, mask):
+    """fs2_op_row_dot -> status, pred buffer (M + 1, 1) fp32 on the device."""
+    M, H = y.shape
+    yd = to_dev(y, dtype)
+    bdev = torch.tensor([b], dtype=torch.float32, device=DEV)
+    pred = sentinel(M, 1, torch.float32)
+    st = lib().fs2_op_row_dot(dtype, yd, _f32(w), bdev, _u8(mask), pred, M, H, torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    return st, pred

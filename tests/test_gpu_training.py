@@ -3,6 +3,8 @@
 after three clipped AdamW + Noam steps) and (b) the CPU oracle (oracle/train_cpu.py) on other shapes: ragged lengths, odd
 kernel sizes, gradient accumulation.  fp32 arithmetic; tolerances: gradients 1e-4 of the tensor's largest entry
 (the chain is ~40 fp32 GEMMs deep), losses 1e-5 relative, weights 2e-5 where Adam is well conditioned."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -85,11 +87,17 @@ PRIORS = dict(priors=["pitch", "duration"],
                      "pitch_prior": {"min": -1.0, "max": 1.0}, "duration_prior": {"min": 0.0, "max": 5.0}})
 DW = dict(encoder_depthwise_conv=True, decoder_depthwise_conv=True, variance_depthwise_conv=True, duration_depthwise_conv=True,
           encoder_conv_filter_size=128, decoder_conv_filter_size=192, decoder_kernel_sizes=[17, 3])
+# The smallest width at which the step's fused launches run (fs2_op_gemm_ln_tape[_dropout], fs2_op_gemm_relu_dropout,
+# fs2_op_gemm_gated, fs2_op_gemm_add): the slab kernel takes N >= 192.  At the hidden size 64 of the cases above every one of them
+# answers FS2_ERR_SHAPE and the step runs its fallbacks - tests/test_tape_route_cpu.py pins both.
+WIDE = dict(encoder_hidden=192, decoder_hidden=192, encoder_head=2, decoder_head=2, encoder_layers=1, decoder_layers=1,
+            encoder_kernel_sizes=[5], decoder_kernel_sizes=[9], encoder_conv_filter_size=256, decoder_conv_filter_size=256,
+            variance_filter_size=192, duration_filter_size=192)
 
 
 @pytest.mark.parametrize("seed,B,L,lengths,kw", [(3, 4, 13, [13, 9, 5, 1], {}), (8, 2, 37, [37, 20], {}), (5, 3, 21, [21, 8, 2], DW),
                                                  (6, 2, 9, [9, 4], dict(DW, decoder_depthwise_conv=False, variance_depthwise_conv=False)),
-                                                 (7, 3, 10, [10, 6, 8], PRIORS)])
+                                                 (7, 3, 10, [10, 6, 8], PRIORS), (41, 3, 17, [17, 11, 4], WIDE)])
 def test_training_step_matches_oracle_on_ragged_batches(seed, B, L, lengths, kw):
     from lightningfastspeech2_amd.training import Trainer
     cfg, sd, batch = _case(seed, B, L, lengths, **kw)
@@ -202,13 +210,16 @@ def test_dropout_op_statistics_and_determinism():
     assert torch.equal(yb.cpu() != 0, a != 0)  # the mask depends on (seed, key, index) only: an fp32 gradient meets the bf16 mask
 
 
-@pytest.mark.parametrize("kw", [{}, DW])
+@pytest.mark.parametrize("kw", [{}, DW, WIDE])
 def test_backward_is_the_derivative_of_the_forward_under_dropout(kw):
     """With every dropout site switched on (fixed seed, so the step is a deterministic function of the weights) the gradient
     buffer must be the directional derivative of the total loss: (L(w + eps v) - L(w - eps v)) / (2 eps) = g . v.  The
     directions are the gradient itself re-weighted element by element (v = g * u, u ~ U(0.5, 1.5)), so g . v = sum g^2 u is far
     above the fp32 noise of a loss difference and a wrong mask, scale or position in the chain at any site shows up in it;
-    tools/probes/fd_check.py does the same with random directions, site by site."""
+    tools/probes/fd_check.py does the same with random directions, site by site.  The WIDE case runs the fused dropout forward
+    (fs2_op_gemm_ln_tape_dropout, fs2_op_gemm_relu_dropout) against the masked LayerNorm backward and the gated data gradient
+    (every such site of the decoder and the frame-level predictors, the encoder's two residual sites; tests/test_tape_route_cpu.py);
+    the other two run the stand-alone dropout launches."""
     from lightningfastspeech2_amd.training import Trainer
     cfg, sd, batch = _case(31, 3, 12, [12, 7, 3], **kw)
     drop = dict(encoder_dropout=0.2, decoder_dropout=0.15, variance_dropout=[0.3, 0.25], duration_dropout=0.3, seed=9)
@@ -221,8 +232,19 @@ def test_backward_is_the_derivative_of_the_forward_under_dropout(kw):
     assert abs(float(tr0.training_step(bd)["total"]) - l0) > 1e-3  # dropout really is on
     w0 = tr.flat_p.clone()
     gen = torch.Generator(device="cuda:0").manual_seed(3)
-    for trial in range(3):
+    # ... and once more along the parameters inside the layers' residual branches alone (attention, conv1, conv2: 15 - 27 % of
+    # |g|^2).  Only their gradients pass through the backward of the residual-site dropouts, and the whole-gradient direction
+    # dilutes an error there: with the fused epilogue's mask index off by one the WIDE case measured 2.5e-2 along the whole
+    # gradient and 1.5e-1 along these (as it stands: 5e-3 and 7e-3).
+    branch = torch.zeros(tr.n_flat, device="cuda:0")
+    for n, (off, ks, _) in tr._layout.items():
+        if ".self_attn." in n or ".conv1" in n or ".conv2" in n:
+            branch[off:off + int(np.prod(ks))] = 1
+    assert 0 < float(branch.sum()) < tr.n_flat
+    for trial in range(6):
         v = g.float() * (0.5 + torch.rand(tr.n_flat, device="cuda:0", generator=gen))
+        if trial >= 3:
+            v = v * branch
         eps = 1e-4 / float(v.norm()) * float(w0.norm())  # |eps v| = 1e-4 |w|: few ReLU / L1 kinks are crossed
         vals = []
         for sgn in (1.0, -1.0):
@@ -233,8 +255,51 @@ def test_backward_is_the_derivative_of_the_forward_under_dropout(kw):
             tr.zero_grad()
         fd = (vals[0] - vals[1]) / (2 * eps)
         an = float((g * v.double()).sum())
+        print(f"trial {trial}: finite difference {fd:.6e} analytic {an:.6e} relative {abs(fd - an) / an:.2e}")
         assert an > 0 and abs(fd - an) <= 3e-2 * an, (trial, fd, an)
     tr.flat_p.copy_(w0)
+
+
+SWITCHES = [("FS2_TRAIN_FUSE_LN", "0", lambda tr: not tr.ops.fuse_ln), ("FS2_TRAIN_FUSE_LN_DROPOUT", "0", lambda tr: not tr.ops.fuse_ln_drop),
+            ("FS2_TRAIN_GATE", "0", lambda tr: True), ("FS2_TRAIN_FUSE_ADD", "0", lambda tr: not tr.ops.fuse_add),
+            ("FS2_TRAIN_DGRAD", "bgemm", lambda tr: not tr.use_forward_dgrad)]
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_dropout_step():
+    """one fp32 step of the WIDE case with every dropout site on, on a fresh Trainer, under the environment as it stands"""
+    from lightningfastspeech2_amd.training import Trainer
+    cfg, sd, batch = _case(41, 3, 17, [17, 11, 4], **WIDE)
+    tr = Trainer(cfg, sd, gradient_clip_val=None, encoder_dropout=0.2, decoder_dropout=0.15, variance_dropout=[0.3, 0.25],
+                 duration_dropout=0.3, seed=9)
+    losses = {k: float(v) for k, v in tr.training_step(_dev(batch)).items()}
+    return tr, losses, tr.gradients(), tr.flat_g.clone()
+
+
+@pytest.mark.parametrize("switch", SWITCHES, ids=[s[0] for s in SWITCHES])
+def test_fused_tape_switches_agree_with_their_fallbacks(monkeypatch, switch):
+    """Each FS2_TRAIN_* A/B switch replaces fused launches by their stand-alone forms: GEMM + LayerNorm epilogue with the pre-norm
+    store (FUSE_LN), the dropout inside that epilogue / inside the FFN's ReLU store, and the masked LayerNorm backward
+    (FUSE_LN_DROPOUT), the ReLU + dropout backward in a data gradient's store (GATE), "dx +=" inside the GEMM (FUSE_ADD), the
+    data gradients on the forward's conv kernel instead of the strided-batched GEMM (DGRAD).  include/fs2.h defines every mask by
+    (p, seed, key) and the element index, so both sides compute the same function of the same weights: one fp32 step of the WIDE
+    case (where tests/test_tape_route_cpu.py shows the fused forms launch) with every dropout site on must give the same losses
+    (1e-5) and gradients (GRAD_TOL), and - other kernels, another summation order - not the same bits, which is also what shows
+    that a switch the step reads from the environment as it goes (FS2_TRAIN_GATE) took effect.  No switch is left out: at this
+    size each one changes the launches of at least one GEMM."""
+    name, value, took_effect = switch
+    tr0, l0, g0, flat0 = _wide_dropout_step()
+    assert tr0.ops.fuse_ln and tr0.ops.fuse_ln_drop and tr0.ops.fuse_add and tr0.use_forward_dgrad
+    monkeypatch.setenv(name, value)
+    tr, l1, g1, flat1 = _wide_dropout_step.__wrapped__()
+    assert took_effect(tr), name
+    for k, w in l0.items():
+        print(f"{name} loss {k}: {l1[k]!r} vs {w!r}")
+        assert abs(l1[k] - w) <= 1e-5 * max(1.0, abs(w)), (k, l1[k], w)
+    worst = max((float((g1[n] - w).abs().max()) / (float(w.abs().max()) + 1e-3), n) for n, w in g0.items())
+    print(f"{name} worst gradient difference {worst[0]:.3e} ({worst[1]}) bound {GRAD_TOL:.1e}; bit-equal: {torch.equal(flat0, flat1)}")
+    _check_grads(g1, g0)
+    assert not torch.equal(flat0, flat1), name
 
 
 @pytest.mark.parametrize("dw", [False, True])
