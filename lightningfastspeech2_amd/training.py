@@ -43,6 +43,11 @@ _KIND = {"l1": 0, "mse": 1}
 _PRECISIONS = {"fp32": (F32, torch.float32), "bf16": (BF16, torch.bfloat16)}
 
 
+def _desc(c_dtype, **kw):
+    """the descriptor of a strided-batched product: one plain product into c_dtype unless the fields say otherwise"""
+    return _lib.BGemmDescC(**{"nb1": 1, "nb2": 1, "alpha": 1.0, "beta": 0.0, "splitk": 1, "taps": 1, "c_dtype": c_dtype, **kw})
+
+
 class _Ops:
     """Thin typed wrappers: torch tensors in, C ABI launches on torch's current stream."""
 
@@ -59,6 +64,7 @@ class _Ops:
         self.fuse_ln_drop = os.environ.get("FS2_TRAIN_FUSE_LN_DROPOUT", "1") != "0"  # A/B switch: the residual-site dropout inside that launch
         self.fuse_add = os.environ.get("FS2_TRAIN_FUSE_ADD", "1") != "0"  # A/B switch: "dx +=" of a data-gradient product inside the GEMM launch
         self.splitk = os.environ.get("FS2_TRAIN_SPLITK", "1") != "0"    # A/B switch: split-K data-gradient convs where fs2_op_gemm_splitk_choice says so
+        self.gate = os.environ.get("FS2_TRAIN_GATE", "1") != "0"        # A/B switch: the FFN's ReLU + dropout backward inside the data-gradient GEMM's store
         # Weight gradients are leaves of the backward: nothing downstream reads them before the optimizer step.  With
         # FS2_TRAIN_WGRAD_STREAM=1 they run on a second HIP stream (dW GEMM + split-K reduce + bias column sums: ~110 of a step's
         # ~510 launches) beside the data-gradient chain, ordered by events: the side stream waits for dy, the main stream waits
@@ -110,6 +116,15 @@ class _Ops:
             torch.cuda.current_stream(self.dev).wait_stream(self.side)
             self._pending.clear()
 
+    @staticmethod
+    def took(status, what):
+        """the answer of a fused entry point: True = launched; False = FS2_ERR_SHAPE, "no such kernel for this shape" - the one status
+        the caller answers with its stand-alone launches; anything else is a failure and raises"""
+        if status == _lib.FS2_ERR_SHAPE:
+            return False
+        _lib.check(status, None, what)
+        return True
+
     def ws(self, key: str, nbytes: int) -> Optional[torch.Tensor]:
         if nbytes <= 0:
             return None
@@ -125,11 +140,8 @@ class _Ops:
     def gemm(self, x, w, bias, M, N, Cin, taps=1, S=None, relu=False, out_f32=False, gate=None, gate_scale=1.0):
         y = self.empty(M, N) if out_f32 else self.act(M, N)
         if gate is not None:  # y = gate > 0 ? gate_scale * x w^T : 0 in the store, where the kernel has that epilogue
-            st_ = self.lib.fs2_op_gemm_gated(self.dt, x, w, bias, gate, gate_scale, y, M, N, Cin, taps, S or M, self.st())
-            if st_ == 0:
+            if self.took(self.lib.fs2_op_gemm_gated(self.dt, x, w, bias, gate, gate_scale, y, M, N, Cin, taps, S or M, self.st()), "gemm_gated"):
                 return y
-            if st_ != _lib.FS2_ERR_SHAPE:  # only "no such epilogue for this shape" falls back; a launch failure is raised
-                _lib.check(st_, None, "gemm_gated")
             _lib.check(self.lib.fs2_op_gemm(self.dt, self.dt, x, w, bias, y, M, N, Cin, taps, S or M, 0, self.st()), None, "gemm")
             return self.gate_(y, gate, gate_scale)
         _lib.check(self.lib.fs2_op_gemm(self.dt, F32 if out_f32 else self.dt, x, w, bias, y, M, N, Cin, taps, S or M, int(relu), self.st()), None, "gemm")
@@ -139,12 +151,9 @@ class _Ops:
         """dropout(relu(x W^T + bias)) - the mask of ``dropout(., p, key)`` - in one launch where the slab kernel runs the shape."""
         if p > 0 and self.fuse_ln_drop:
             y = self.act(M, N)
-            st_ = self.lib.fs2_op_gemm_relu_dropout(self.dt, x, w, bias, y, M, N, Cin, taps, S or M, p, C.c_uint64(self.seed),
-                                                    C.c_uint64(key), self.st())
-            if st_ == 0:
+            if self.took(self.lib.fs2_op_gemm_relu_dropout(self.dt, x, w, bias, y, M, N, Cin, taps, S or M, p, C.c_uint64(self.seed),
+                                                           C.c_uint64(key), self.st()), "gemm_relu_dropout"):
                 return y
-            if st_ != _lib.FS2_ERR_SHAPE:
-                _lib.check(st_, None, "gemm_relu_dropout")
         return self.dropout(self.gemm(x, w, bias, M, N, Cin, taps=taps, S=S, relu=True), p, key)
 
     def gemm_ln_tape(self, x, w, bias, res, g, b, M, N, Cin, taps=1, S=None, relu=False, drop=None):
@@ -161,10 +170,7 @@ class _Ops:
                                                        C.c_uint64(self.seed), C.c_uint64(drop[1]), self.st())
         else:
             st_ = self.lib.fs2_op_gemm_ln_tape(self.dt, x, w, bias, res, g, b, y, z, M, N, Cin, taps, S or M, int(relu), self.st())
-        if st_ == _lib.FS2_ERR_SHAPE:
-            return None
-        _lib.check(st_, None, "gemm_ln_tape")
-        return y, z
+        return (y, z) if self.took(st_, "gemm_ln_tape") else None
 
     def layernorm(self, x, res, g, b, M, H, dot_w=None, dot_b=0.0, mask=None, want_y=True):
         y = self.act(M, H) if want_y else None
@@ -175,25 +181,16 @@ class _Ops:
     # ---- backward operators ----
     def bgemm(self, A, B, Cout, bias=None, **kw):
         """operands in A's dtype (both fp32 or both bf16); C fp32 or the activation dtype, by Cout's dtype"""
-        d = _lib.BGemmDescC()
-        base = dict(nb1=1, nb2=1, alpha=1.0, beta=0.0, splitk=1, taps=1, c_dtype=F32 if Cout.dtype == torch.float32 else BF16)
-        base.update(kw)
-        for k, v in base.items():
-            setattr(d, k, v)
+        d = _desc(self._dt(Cout), **kw)
         if A.dtype != B.dtype:
             raise TypeError(f"bgemm operands differ: {A.dtype} vs {B.dtype}")
         ws = self.ws("bgemm", int(self.lib.fs2_op_bgemm_ws_bytes(C.byref(d))))
-        _lib.check(self.lib.fs2_op_bgemm(F32 if A.dtype == torch.float32 else BF16, C.byref(d), A, B, Cout, bias, ws, self.st()), None, "bgemm")
+        _lib.check(self.lib.fs2_op_bgemm(self._dt(A), C.byref(d), A, B, Cout, bias, ws, self.st()), None, "bgemm")
         return Cout
 
     def tn256(self, **kw):
         """does this bf16 product run on the 256 x 256 tile kernel (include/fs2.h fs2_op_bgemm_tn256)"""
-        d = _lib.BGemmDescC()
-        base = dict(nb1=1, nb2=1, alpha=1.0, beta=0.0, splitk=1, taps=1, c_dtype=F32)
-        base.update(kw)
-        for k, v in base.items():
-            setattr(d, k, v)
-        return bool(self.lib.fs2_op_bgemm_tn256(C.byref(d)))
+        return bool(self.lib.fs2_op_bgemm_tn256(C.byref(_desc(F32, **kw))))
 
     @staticmethod
     def _dt(t):
@@ -202,6 +199,20 @@ class _Ops:
     def col_sum(self, x, out, M, N, seg=0, accumulate=True, scale=1.0, ldx=None):
         ws = self.ws("colsum", int(self.lib.fs2_op_col_sum_ws_bytes(M, N, seg)))
         _lib.check(self.lib.fs2_op_col_sum(self._dt(x), x, out, ws, M, N, ldx or N, seg, int(accumulate), scale, self.st()), None, "col_sum")
+
+    def col_sums(self, part, M, ld, ga, na, gb, nb, gc=None, accumulate_c=True):
+        """part is (M, ld): ga (na), gb (nb) += the sums of its first na, next nb columns - one launch where gb follows ga in the flat
+        buffer (a bias behind its weight, a LayerNorm's beta behind its gamma) - and, where asked, gc += (or =) those of the columns left"""
+        adjacent = gb.data_ptr() == ga.data_ptr() + 4 * na
+        if adjacent and gc is not None:
+            return self.col_sum2(part, ga, gc, na + nb, M, ld, accumulate2=accumulate_c)
+        if adjacent:
+            self.col_sum(part, ga, M, na + nb, ldx=ld)
+        else:
+            self.col_sum(part, ga, M, na, ldx=ld)
+            self.col_sum(part[:, na:], gb, M, nb, ldx=ld)
+        if gc is not None:
+            self.col_sum(part[:, na + nb:], gc, M, ld - na - nb, ldx=ld, accumulate=accumulate_c)
 
     def col_sum2(self, x, out, out2, n1, M, N, ldx=None, accumulate=True, accumulate2=True):
         """columns [0, n1) of the sums to out, [n1, N) to out2"""
@@ -240,11 +251,7 @@ class _Ops:
         def wg():  # parameter gradients: a leaf (side stream where there is one)
             part = self.empty(nparts, Cc * (k + 1))
             _lib.check(self.lib.fs2_op_dwconv_wgrad(self.dt, du, x, part, B, S, Cc, k, self.st()), None, "dwconv_wgrad")
-            if gb.data_ptr() == gw.data_ptr() + 4 * Cc * k:
-                self.col_sum(part, gw, nparts, Cc * (k + 1))
-            else:
-                self.col_sum(part, gw, nparts, Cc * k, ldx=Cc * (k + 1))
-                self.col_sum(part[:, Cc * k:], gb, nparts, Cc, ldx=Cc * (k + 1))
+            self.col_sums(part, nparts, Cc * (k + 1), gw, Cc * k, gb, Cc)
         self.on_side((du, x), wg)
         dx = self.act(B * S, Cc)
         _lib.check(self.lib.fs2_op_dwconv_dgrad(self.dt, du, w, dx, B, S, Cc, k, self.st()), None, "dwconv_dgrad")
@@ -278,27 +285,17 @@ class _Ops:
             if ks > 1:
                 dx = out if out is not None else self.act(M, Cin)
                 part = self.empty(ks, M, Cin)
-                st_ = self.lib.fs2_op_gemm_splitk(self.dt, self._dt(dx), dy, wt, dx, part, M, Cin, N, taps, S or M, ks,
-                                                  int(bool(accumulate and out is not None)), self.st())
-                if st_ == 0:
+                if self.took(self.lib.fs2_op_gemm_splitk(self.dt, self._dt(dx), dy, wt, dx, part, M, Cin, N, taps, S or M, ks,
+                                                         int(bool(accumulate and out is not None)), self.st()), "gemm_splitk"):
                     return dx
-                if st_ != _lib.FS2_ERR_SHAPE:
-                    _lib.check(st_, None, "gemm_splitk")
-            if out is not None and accumulate and gate is None and self.fuse_add:
-                # out += dy . wt in the GEMM's own store (the accumulators start at out's tile)
-                st_ = self.lib.fs2_op_gemm_add(self.dt, dy, wt, None, out, out, M, Cin, N, taps, S or M, self.st())
-                if st_ == 0:
-                    return out
-                if st_ != _lib.FS2_ERR_SHAPE:
-                    _lib.check(st_, None, "gemm_add")
+            # out += dy . wt in the GEMM's own store (the accumulators start at out's tile)
+            if out is not None and accumulate and gate is None and self.fuse_add and self.took(
+                    self.lib.fs2_op_gemm_add(self.dt, dy, wt, None, out, out, M, Cin, N, taps, S or M, self.st()), "gemm_add"):
+                return out
             dx = self.gemm(dy, wt, None, M, Cin, N, taps=taps, S=S, gate=gate, gate_scale=gate_scale)
             if out is None:
                 return dx
-            if accumulate:
-                _lib.check(self.lib.fs2_op_ew(self._dt(out), 0, out, dx, out, out.numel(), 1, 1, self.st()), None, "add")
-            else:
-                out.copy_(dx)
-            return out
+            return self.add_(out, dx) if accumulate else out.copy_(dx)
         if gate is not None and (out is not None or accumulate):
             raise ValueError("dgrad: a gate goes with a fresh output only")
         dx = out if out is not None else self.act(M, Cin)
@@ -432,25 +429,26 @@ class Trainer:
         self.flat_g = torch.zeros(off, device=self.dev)
         self.flat_m = torch.zeros(off, device=self.dev)
         self.flat_v = torch.zeros(off, device=self.dev)
-        self.P = {n: self.flat_p[o:o + int(np.prod(ks))].view(ks) for n, (o, ks, _) in self._layout.items()}
-        self.G = {n: self.flat_g[o:o + int(np.prod(ks))].view(ks) for n, (o, ks, _) in self._layout.items()}
+        self.P, self.G = self._views(self.flat_p), self._views(self.flat_g)
         # GEMM operands: the fp32 masters themselves, or their bf16 shadow (refreshed after every optimizer step)
         if self.ops.dt == F32:
             self.W = self.P
         else:
             self.flat_w = torch.zeros(off, device=self.dev, dtype=torch.bfloat16)
-            self.W = {n: self.flat_w[o:o + int(np.prod(ks))].view(ks) for n, (o, ks, _) in self._layout.items()}
+            self.W = self._views(self.flat_w)
+        self.use_forward_dgrad = os.environ.get("FS2_TRAIN_DGRAD", "forward") == "forward"  # A/B switch: data gradients on the forward's GEMM / conv kernels ("bgemm": on the strided-batched GEMM)
+        self.tw_batch = os.environ.get("FS2_TRAIN_TW_BATCH", "1") != "0"            # A/B switch: every weight transpose of a bf16 refresh in one launch
+        self.adamw_shadow = os.environ.get("FS2_TRAIN_ADAMW_SHADOW", "1") != "0"    # A/B switch: the optimizer launch writes the bf16 shadow too
         # transposed, tap-flipped copies of every GEMM weight (activation dtype): the data gradients run on the forward kernels
-        self.use_forward_dgrad = os.environ.get("FS2_TRAIN_DGRAD", "forward") == "forward"
         self.flat_wt = torch.zeros(off, device=self.dev, dtype=self.ops.tdt)
         self.WT = {}
         self._tw_table = None
-        for n, (o, ks, rs) in self._layout.items():
+        for n, wt in self._views(self.flat_wt).items():
+            rs = self._layout[n][2]
             gemm_w = n.endswith("weight") and "embedding" not in n and (
                 len(rs) == 2 or (len(rs) == 3 and rs[1] > 1 and ".conv2.0." not in n))  # not LayerNorm (1-D), depth-wise or grouped convs
             if gemm_w:
-                taps = rs[2] if len(rs) == 3 else 1
-                self.WT[n] = self.flat_wt[o:o + int(np.prod(ks))].view(rs[1], taps * rs[0])
+                self.WT[n] = wt.view(rs[1], -1)
         # depth-wise ConformerEncoderLayer: conv2 = grouped 1x1 + pointwise folded into one (H, F) map per optimizer step
         self.fold: Dict[str, dict] = {}
         H_ = cfg.hidden
@@ -468,15 +466,33 @@ class Trainer:
         self._nsq_ws = self.ops.empty(int(self.ops.lib.fs2_op_sum_sq_ws_bytes(off)) // 4 + 1)
 
     # ---- state ----
+    def _views(self, flat):
+        """name -> the parameter's part of a flat buffer, in kernel layout"""
+        return {n: flat[o:o + math.prod(ks)].view(ks) for n, (o, ks, _) in self._layout.items()}
+
+    def _to_kernel_layout(self, name, v, what):
+        """a tensor or array in the reference's layout -> fp32 in the kernel's: conv weights (out, in, taps) tap-major, (out, taps * in)"""
+        _, ks, rs = self._layout[name]
+        t = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32)
+        if tuple(t.shape) != rs:
+            raise ValueError(f"{what}: shape {tuple(t.shape)} != {rs}")
+        return (t.permute(0, 2, 1) if len(rs) == 3 else t).reshape(ks)
+
+    def _to_ref_layout(self, name, t):
+        """a view in the kernel's layout -> a host tensor in the reference's (the inverse of _to_kernel_layout)"""
+        _, ks, rs = self._layout[name]
+        t = t.detach().cpu()
+        if len(rs) == 3:
+            t = t.view(rs[0], rs[2], rs[1]).permute(0, 2, 1)
+        return t.reshape(rs).contiguous()
+
+    def _ref_views(self, flat):
+        """name -> the parameter's part of a flat buffer, on the host in the reference's layout"""
+        return OrderedDict((n, self._to_ref_layout(n, v)) for n, v in self._views(flat).items())
+
     def load_state_dict(self, sd):
-        for name, (o, ks, rs) in self._layout.items():
-            v = sd[name]
-            t = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32)
-            if tuple(t.shape) != rs:
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != {rs}")
-            if len(rs) == 3:
-                t = t.permute(0, 2, 1).reshape(ks)
-            self.P[name].copy_(t.contiguous())
+        for name, p in self.P.items():
+            p.copy_(self._to_kernel_layout(name, sd[name], name))
         for name in state_dict_spec(self.cfg):
             if name == "positional_encoding.pe" or name.endswith(".bins"):
                 v = sd[name]
@@ -503,7 +519,7 @@ class Trainer:
                     jobs.append((self.W[n], wt, rs[0], rs[1], rs[2] if len(rs) == 3 else 1))
             if not jobs:
                 return
-            if o.dt == F32 or os.environ.get("FS2_TRAIN_TW_BATCH", "1") == "0":  # (A/B switch)
+            if o.dt == F32 or not self.tw_batch:
                 for src, dst, N, Cin, taps in jobs:
                     _lib.check(o.lib.fs2_op_transpose_weight(o.dt, src, dst, N, Cin, taps, o.st()), None, "transpose_weight")
                 return
@@ -519,16 +535,9 @@ class Trainer:
     def _wt(self, name):
         return self.WT.get(name) if self.use_forward_dgrad else None
 
-    def _to_ref_layout(self, name, t):
-        _, ks, rs = self._layout[name]
-        t = t.detach().cpu()
-        if len(rs) == 3:
-            t = t.view(rs[0], rs[2], rs[1]).permute(0, 2, 1)
-        return t.reshape(rs).contiguous()
-
     def state_dict(self):
         """Reference key names and layouts (feeds FastSpeech2(...) of this package or the reference's load_state_dict)."""
-        out = OrderedDict((n, self._to_ref_layout(n, self.P[n])) for n in self._layout)
+        out = self._ref_views(self.flat_p)
         for n, b in self.buffers.items():
             out[n] = b.cpu().reshape(1, *b.shape) if n.endswith(".pe") else b.cpu()
         return out
@@ -537,19 +546,12 @@ class Trainer:
         """Adam moments under the reference's parameter names and layouts + the step counter (what a Lightning checkpoint keeps
         as ``optimizer_states`` / ``lr_schedulers``): ``{"step": n, "exp_avg": {name: tensor}, "exp_avg_sq": {name: tensor}}``.
         Together with ``state_dict()`` this resumes a run exactly."""
-        def views(flat):
-            return OrderedDict((n, self._to_ref_layout(n, flat[o:o + int(np.prod(ks))].view(ks))) for n, (o, ks, _) in self._layout.items())
-        return {"step": self.steps, "micro_step": self._micro, "exp_avg": views(self.flat_m), "exp_avg_sq": views(self.flat_v)}
+        return {"step": self.steps, "micro_step": self._micro, "exp_avg": self._ref_views(self.flat_m), "exp_avg_sq": self._ref_views(self.flat_v)}
 
     def load_optimizer_state(self, st):
         for key, flat in (("exp_avg", self.flat_m), ("exp_avg_sq", self.flat_v)):
-            for n, (o, ks, rs) in self._layout.items():
-                t = torch.as_tensor(st[key][n]).to(torch.float32)
-                if tuple(t.shape) != rs:
-                    raise ValueError(f"{key}[{n}]: shape {tuple(t.shape)} != {rs}")
-                if len(rs) == 3:
-                    t = t.permute(0, 2, 1).reshape(ks)
-                flat[o:o + int(np.prod(ks))].view(ks).copy_(t.contiguous())
+            for n, view in self._views(flat).items():
+                view.copy_(self._to_kernel_layout(n, st[key][n], f"{key}[{n}]"))
         self.steps = int(st["step"])
         self._micro = int(st.get("micro_step", 0))
 
@@ -571,7 +573,7 @@ class Trainer:
         self.load_optimizer_state(from_lightning_optimizer_state(self.cfg, checkpoint, int(accumulate_grad_batches)))
 
     def gradients(self):
-        return OrderedDict((n, self._to_ref_layout(n, self.G[n])) for n in self._layout)
+        return self._ref_views(self.flat_g)
 
     def zero_grad(self):
         self.flat_g.zero_()
@@ -609,41 +611,54 @@ class Trainer:
             prob_d = o.dropout(prob, pd, t["k_attn"], out=o.act(B, heads, S, S)) if pd > 0 else prob  # MHA drops attention weights
             o.bgemm(prob_d, qkv[:, 2 * H:], attn, M=S, N=d, K=S, sAm=S, sAk=1, sBk=3 * H, sBn=1, ldc=H, nb1=B, nb2=heads,
                     sA1=heads * S * S, sA2=S * S, sB1=S * 3 * H, sB2=d, sC1=S * H, sC2=d)
-        # without dropout the out-projection, the residual add and norm1 are ONE launch that also leaves the pre-norm sum for the
-        # tape (t["proj"] then holds x + proj and the backward's LayerNorm takes no separate residual)
-        f1 = o.gemm_ln_tape(attn, W[f"{prefix}.self_attn.out_proj.weight"], P[f"{prefix}.self_attn.out_proj.bias"], x,
-                            P[f"{prefix}.norm1.weight"], P[f"{prefix}.norm1.bias"], M, H, H, drop=(pd, t["k_sa"]))  # (dropout1 inside)
-        if f1 is not None:
-            x1, proj = f1
-        else:
-            proj = o.dropout(o.gemm(attn, W[f"{prefix}.self_attn.out_proj.weight"], P[f"{prefix}.self_attn.out_proj.bias"], M, H, H),
-                             pd, t["k_sa"])  # dropout1
-            x1, _ = o.layernorm(proj, x, P[f"{prefix}.norm1.weight"], P[f"{prefix}.norm1.bias"], M, H)
-        t["sum1"] = f1 is not None
+        x1, proj, t["sum1"] = self._sublayer_fwd(attn, f"{prefix}.self_attn.out_proj", x, f"{prefix}.norm1", M, H, H, pd, t["k_sa"])  # dropout1
         if prefix in self.fold:  # depth-wise FFN (model.py:73-93): dw(k) -> pw H->F -> ReLU -> [grouped 1x1 . pw F->H] folded
             t["u"] = o.dwconv(x1, P[f"{prefix}.conv1.0.weight"], P[f"{prefix}.conv1.0.bias"], B, S, H, k)
             h = o.gemm_relu_dropout(t["u"], W[f"{prefix}.conv1.1.weight"], P[f"{prefix}.conv1.1.bias"], M, F_, H, 1, None, pd, t["k_h"])
             c2 = o.dropout(o.gemm(h, self.fold[prefix]["Wf"], self.fold[prefix]["bf"], M, H, F_), pd, t["k_ff"])
+            t["sum2"] = False  # the folded map has no fused form: c2 is the summand, norm2 adds the residual
+            x2, _ = o.layernorm(c2, x1, P[f"{prefix}.norm2.weight"], P[f"{prefix}.norm2.bias"], M, H)
         else:
             h = o.gemm_relu_dropout(x1, W[f"{prefix}.conv1.weight"], P[f"{prefix}.conv1.bias"], M, F_, H, k, S, pd, t["k_h"])
-            f2 = o.gemm_ln_tape(h, W[f"{prefix}.conv2.weight"], P[f"{prefix}.conv2.bias"], x1, P[f"{prefix}.norm2.weight"],
-                                P[f"{prefix}.norm2.bias"], M, H, F_, drop=(pd, t["k_ff"]))  # (dropout2 inside)
-            if f2 is not None:
-                x2, c2 = f2
-            else:
-                c2 = o.dropout(o.gemm(h, W[f"{prefix}.conv2.weight"], P[f"{prefix}.conv2.bias"], M, H, F_), pd, t["k_ff"])  # dropout2
-        t["sum2"] = prefix not in self.fold and f2 is not None
-        if not t["sum2"]:
-            x2, _ = o.layernorm(c2, x1, P[f"{prefix}.norm2.weight"], P[f"{prefix}.norm2.bias"], M, H)
+            x2, c2, t["sum2"] = self._sublayer_fwd(h, f"{prefix}.conv2", x1, f"{prefix}.norm2", M, H, F_, pd, t["k_ff"])  # dropout2
         t.update(qkv=qkv, prob=prob, prob_d=prob_d, lse=lse, key_pad=key_pad, attn=attn, proj=proj, x1=x1, h=h, c2=c2, scale=scale)
         return x2, t
 
-    def _ln_bwd(self, z, res, dy, gname, bname, M, H, bias_name=None, relu_mask=False, bias_out=None, drop=None, out_drop=None):
-        """dz of y = LN(z [+ res]); dgamma / dbeta (adjacent in the flat buffer: one column-sum launch) and, when asked, the
-        bias gradient of the layer that produced z (= column sums of dz; with relu_mask dz is the pre-activation gradient).
+    def _sublayer_fwd(self, x, lin, res, norm, M, N, Cin, p, key):
+        """A residual sub-layer, z = res + dropout(x W^T + b) and y = LN(z), from the names of its linear map and its norm: ONE launch
+        where the fused GEMM + LayerNorm epilogue takes the shape - it leaves the pre-norm sum for the tape too - else GEMM, dropout
+        and the LayerNorm that adds the residual.  Returns (y, z, z_holds_residual): the stored z is the whole sum in the first case,
+        the summand dropout(x W^T + b) in the second, and the backward's LayerNorm takes its residual accordingly."""
+        o, P = self.ops, self.P
+        w, b, g, beta = self.W[f"{lin}.weight"], P[f"{lin}.bias"], P[f"{norm}.weight"], P[f"{norm}.bias"]
+        fused = o.gemm_ln_tape(x, w, b, res, g, beta, M, N, Cin, drop=(p, key))
+        if fused is not None:
+            return (*fused, True)
+        z = o.dropout(o.gemm(x, w, b, M, N, Cin), p, key)
+        return o.layernorm(z, res, g, beta, M, N)[0], z, False
+
+    def _sublayer_bwd(self, dy, z, res, norm, db, M, H, p, key, accumulate=True):
+        """Backward of _sublayer_fwd (res = None where z holds the residual): returns (the residual's gradient dz, the gradient of the
+        sub-layer's output u = x W^T + b) and adds - or stores, for a scratch bias - u's bias gradient to db.  u's gradient is dz itself
+        without dropout and the masked LayerNorm backward's second output with it; the bias gradient is then the third column block of
+        that launch's partial sums.  With the fused dropout switched off: an explicit dropout pass and a column sum of its own."""
+        o = self.ops
+        fm = p > 0 and o.fuse_ln_drop
+        if p <= 0 or fm:
+            d = self._ln_bwd(z, res, dy, norm, M, H, bias_grad=db, bias_accumulate=accumulate, out_drop=(p, key) if fm else None)
+            return d if fm else (d, d)
+        dz = self._ln_bwd(z, res, dy, norm, M, H)
+        du = o.dropout(dz, p, key, out=o.act(M, H))
+        o.col_sum(du, db, M, H, accumulate=accumulate)
+        return dz, du
+
+    def _ln_bwd(self, z, res, dy, norm, M, H, bias_grad=None, bias_accumulate=True, relu_mask=False, drop=None, out_drop=None):
+        """dz of y = LN(z [+ res]); dgamma / dbeta and, when asked, the bias gradient of the layer that produced z (= column sums of
+        dz; with relu_mask dz is the pre-activation gradient) added to - or stored in - bias_grad.
         out_drop = (p, key): z = res + dropout(u) - returns (dz, dzm) with dzm = u's gradient (the mask applied in the same launch)
         and the bias gradient asked for is u's."""
         o = self.ops
+        gname = f"{norm}.weight"
         nparts = int(o.lib.fs2_op_layernorm_bwd_parts(M))
         dz, part = o.act(M, H), o.empty(nparts, 3 * H)
         dzm = None
@@ -656,44 +671,19 @@ class Trainer:
                                                           C.c_uint64(o.seed), C.c_uint64(drop[1]), o.st()), None, "layernorm_bwd")
         else:
             _lib.check(o.lib.fs2_op_layernorm_bwd(o.dt, z, res, dy, self.P[gname], dz, part, M, H, int(relu_mask), o.st()), None, "layernorm_bwd")
-        gw, gb = self.G[gname], self.G[bname]
-
-        def sums():
-            if gb.data_ptr() == gw.data_ptr() + 4 * H and (bias_name is None) != (bias_out is None):
-                # dgamma | dbeta (adjacent in the flat buffer) and the bias gradient out of one launch
-                o.col_sum2(part, gw, self.G[bias_name] if bias_name is not None else bias_out, 2 * H, nparts, 3 * H,
-                           accumulate2=bias_name is not None)
-                return
-            if gb.data_ptr() == gw.data_ptr() + 4 * H:
-                o.col_sum(part, gw, nparts, 2 * H, ldx=3 * H)
-            else:
-                o.col_sum(part, gw, nparts, H, ldx=3 * H)
-                o.col_sum(part[:, H:], gb, nparts, H, ldx=3 * H)
-            if bias_name is not None:
-                o.col_sum(part[:, 2 * H:], self.G[bias_name], nparts, H, ldx=3 * H)
-            if bias_out is not None:
-                o.col_sum(part[:, 2 * H:], bias_out, nparts, H, ldx=3 * H, accumulate=False)
         # (these column sums are leaves too, but on the side stream they measured SLOWER - 10.6 -> 11.0 ms per step: ~125 launches of
         # ~6 us each cost more in event records / waits than they free on the main chain; only the weight-gradient GEMMs go there)
-        sums()
+        o.col_sums(part, nparts, 3 * H, self.G[gname], H, self.G[f"{norm}.bias"], H, bias_grad, bias_accumulate)
         return dz if dzm is None else (dz, dzm)
 
     def _layer_bwd(self, dx2, t, prefix, B, S, heads, F_, k):
         o, P, W, G, H = self.ops, self.P, self.W, self.G, self.cfg.hidden
         M, d = B * S, H // heads
         pd, folded = t["pd"], prefix in self.fold
-        dbf = o.empty(H) if folded else None
+        dbf = o.empty(H) if folded else None  # the folded map's bias gradient: stored, then unfolded into the conv2 pair's
         # x2 = LN2(x1 + dropout2(c2)): dz2 is the gradient of x1 (residual) and, through dropout2, of c2
-        fm = pd > 0 and o.fuse_ln_drop  # the dropout backward of the sub-layer's summand as a second output of the LayerNorm backward
-        dx1 = self._ln_bwd(t["c2"], None if t["sum2"] else t["x1"], dx2, f"{prefix}.norm2.weight", f"{prefix}.norm2.bias", M, H,
-                           bias_name=f"{prefix}.conv2.bias" if ((pd <= 0 or fm) and not folded) else None,
-                           bias_out=dbf if ((pd <= 0 or fm) and folded) else None, out_drop=(pd, t["k_ff"]) if fm else None)
-        dc2 = dx1
-        if fm:
-            dx1, dc2 = dx1
-        elif pd > 0:
-            dc2 = o.dropout(dx1, pd, t["k_ff"], out=o.act(M, H))
-            o.col_sum(dc2, dbf if folded else G[f"{prefix}.conv2.bias"], M, H, accumulate=not folded)
+        dx1, dc2 = self._sublayer_bwd(dx2, t["c2"], None if t["sum2"] else t["x1"], f"{prefix}.norm2",
+                                      dbf if folded else G[f"{prefix}.conv2.bias"], M, H, pd, t["k_ff"], accumulate=not folded)
         if folded:
             f = self.fold[prefix]
             dWf = torch.zeros(H, F_, device=self.dev)
@@ -703,7 +693,7 @@ class Trainer:
                                                  G[f"{prefix}.conv2.1.weight"], G[f"{prefix}.conv2.1.bias"], H, F_, o.st()), None, "unfold_conv2")
         # dh = (dc2 . W2) o [h > 0] / (1 - p): h = dropout(relu(.)) of the forward is > 0 exactly where the element was kept AND the
         # pre-activation was positive, so the ReLU backward and the dropout backward ride in the product's store together
-        gate = t["h"] if os.environ.get("FS2_TRAIN_GATE", "1") != "0" else None  # (A/B switch)
+        gate = t["h"] if o.gate else None
         gs = 1.0 / (1.0 - pd) if pd > 0 else 1.0
         if folded:
             dh = o.dgrad(dc2, f["Wf"], M, H, F_, wt=f["WfT"] if self.use_forward_dgrad else None, gate=gate, gate_scale=gs)
@@ -721,15 +711,8 @@ class Trainer:
             o.wgrad(dh, t["x1"], G[f"{prefix}.conv1.weight"], G[f"{prefix}.conv1.bias"], M, F_, H, taps=k, S=S)
             o.dgrad(dh, W[f"{prefix}.conv1.weight"], M, F_, H, taps=k, S=S, out=dx1, accumulate=True, wt=self._wt(f"{prefix}.conv1.weight"))
         # x1 = LN1(x + dropout1(proj))
-        dx = self._ln_bwd(t["proj"], None if t["sum1"] else t["x"], dx1, f"{prefix}.norm1.weight", f"{prefix}.norm1.bias", M, H,
-                          bias_name=f"{prefix}.self_attn.out_proj.bias" if (pd <= 0 or fm) else None,
-                          out_drop=(pd, t["k_sa"]) if fm else None)
-        dproj = dx
-        if fm:
-            dx, dproj = dx
-        elif pd > 0:
-            dproj = o.dropout(dx, pd, t["k_sa"], out=o.act(M, H))
-            o.col_sum(dproj, G[f"{prefix}.self_attn.out_proj.bias"], M, H)
+        dx, dproj = self._sublayer_bwd(dx1, t["proj"], None if t["sum1"] else t["x"], f"{prefix}.norm1",
+                                       G[f"{prefix}.self_attn.out_proj.bias"], M, H, pd, t["k_sa"])
         o.wgrad(dproj, t["attn"], G[f"{prefix}.self_attn.out_proj.weight"], None, M, H, H)
         dattn = o.dgrad(dproj, W[f"{prefix}.self_attn.out_proj.weight"], M, H, H, wt=self._wt(f"{prefix}.self_attn.out_proj.weight"))
         qkv, prob = t["qkv"], t["prob"]
@@ -748,11 +731,8 @@ class Trainer:
                     sC1=S * 3 * H, sC2=d, **bat, **sP)
             # dS = P o (dropout(dO V^T) - delta) / sqrt(d) in the product's epilogue: no dP tensor, no softmax-backward pass
             dp = o.act(B, heads, S, S)
-            dsc = _lib.BGemmDescC()
-            for k_, v_ in dict(M=S, N=S, K=d, sAm=H, sAk=1, sBk=1, sBn=3 * H, ldc=S, sA1=S * H, sA2=d, sB1=S * 3 * H, sB2=d,
-                               sC1=heads * S * S, sC2=S * S, alpha=t["scale"], beta=0.0, splitk=1, taps=1, nb1=B, nb2=heads,
-                               c_dtype=o.dt).items():
-                setattr(dsc, k_, v_)
+            dsc = _desc(o.dt, M=S, N=S, K=d, sAm=H, sAk=1, sBk=1, sBn=3 * H, ldc=S, sA1=S * H, sA2=d, sB1=S * 3 * H, sB2=d,
+                        sC1=heads * S * S, sC2=S * S, alpha=t["scale"], **bat)
             _lib.check(o.lib.fs2_op_bgemm_softmax_bwd(o.dt, C.byref(dsc), dattn, qkv[:, 2 * H:], dp, prob, delta, pd, C.c_uint64(o.seed),
                                                       C.c_uint64(t["k_attn"]), o.st()), None, "bgemm_softmax_bwd")
             # dQ = dS K ; dK = dS^T Q
@@ -836,13 +816,9 @@ class Trainer:
             return self._predictor_layers_bwd(dy, t, prefix, nlayers, filt, k, B, S, dx_out, dw)
         # pred = y . w + b  (masked rows carry dpred = 0 already): dw = sum_m dpred[m] y[m] as a row-weighted column sum (fp32
         # weights; as a 1 x filt x M product on the 128 x 128 GEMM tile it took 51 us per head)
-        dpred32 = dpred
-
-        def head_w():
-            ws = o.ws("colsum", int(o.lib.fs2_op_col_sum_ws_bytes(M, filt, 0)))
-            _lib.check(o.lib.fs2_op_col_sum_weighted(o._dt(t["y"]), t["y"], dpred32, G[f"{prefix}.linear.weight"], ws, M, filt, filt, 1,
-                                                     1.0, o.st()), None, "col_sum_weighted")
-        head_w()
+        ws = o.ws("colsum", int(o.lib.fs2_op_col_sum_ws_bytes(M, filt, 0)))
+        _lib.check(o.lib.fs2_op_col_sum_weighted(o._dt(t["y"]), t["y"], dpred, G[f"{prefix}.linear.weight"], ws, M, filt, filt, 1, 1.0,
+                                                 o.st()), None, "col_sum_weighted")
         dpred = o.to_act(dpred)
         o.col_sum(dpred, G[f"{prefix}.linear.bias"], M, 1)
         dy = o.act(M, filt)
@@ -856,26 +832,20 @@ class Trainer:
         for j in reversed(range(nlayers)):
             p = f"{prefix}.layers.{j}.layers"
             lt = t["layers"][j]
-            drop = (t["pd"], lt["kd"])  # the layer's Dropout behind its LayerNorm: undone inside the LayerNorm backward launch
+            lin = f"{p}.0.module.1" if dw else f"{p}.0.module"  # the layer's GEMM: the point-wise conv behind the depth-wise one, or the conv
+            # (the layer's Dropout behind its LayerNorm is undone inside the LayerNorm backward launch)
+            dc = self._ln_bwd(lt["c"], None, dy, f"{p}.2", M, filt, bias_grad=G[f"{lin}.bias"], relu_mask=True, drop=(t["pd"], lt["kd"]))
             if dw:
-                dc = self._ln_bwd(lt["c"], None, dy, f"{p}.2.weight", f"{p}.2.bias", M, filt, bias_name=f"{p}.0.module.1.bias", relu_mask=True,
-                                  drop=drop)
-                o.wgrad(dc, lt["u"], G[f"{p}.0.module.1.weight"], None, M, filt, lt["cin"])
-                du = o.dgrad(dc, W[f"{p}.0.module.1.weight"], M, filt, lt["cin"], wt=self._wt(f"{p}.0.module.1.weight"))
-                dxin = o.dwconv_bwd(du, lt["xin"], P[f"{p}.0.module.0.weight"], G[f"{p}.0.module.0.weight"], G[f"{p}.0.module.0.bias"],
-                                    B, S, lt["cin"], k)
+                o.wgrad(dc, lt["u"], G[f"{lin}.weight"], None, M, filt, lt["cin"])
+                du = o.dgrad(dc, W[f"{lin}.weight"], M, filt, lt["cin"], wt=self._wt(f"{lin}.weight"))
+                dy = o.dwconv_bwd(du, lt["xin"], P[f"{p}.0.module.0.weight"], G[f"{p}.0.module.0.weight"], G[f"{p}.0.module.0.bias"],
+                                  B, S, lt["cin"], k)
                 if j == 0:
-                    o.add_(dx_out, dxin)
-                else:
-                    dy = dxin
-                continue
-            dc = self._ln_bwd(lt["c"], None, dy, f"{p}.2.weight", f"{p}.2.bias", M, filt, bias_name=f"{p}.0.module.bias", relu_mask=True,
-                              drop=drop)
-            o.wgrad(dc, lt["xin"], G[f"{p}.0.module.weight"], None, M, filt, lt["cin"], taps=k, S=S)
-            if j == 0:
-                o.dgrad(dc, W[f"{p}.0.module.weight"], M, filt, lt["cin"], taps=k, S=S, out=dx_out, accumulate=True, wt=self._wt(f"{p}.0.module.weight"))
-            else:
-                dy = o.dgrad(dc, W[f"{p}.0.module.weight"], M, filt, lt["cin"], taps=k, S=S, wt=self._wt(f"{p}.0.module.weight"))
+                    o.add_(dx_out, dy)
+            else:  # the first layer's data gradient is added to dx_out in the product's own launch where that applies
+                o.wgrad(dc, lt["xin"], G[f"{lin}.weight"], None, M, filt, lt["cin"], taps=k, S=S)
+                dy = o.dgrad(dc, W[f"{lin}.weight"], M, filt, lt["cin"], taps=k, S=S, out=dx_out if j == 0 else None, accumulate=j == 0,
+                             wt=self._wt(f"{lin}.weight"))
 
     def _loss_soft_dtw(self, name, pred, truth, truth_kind, mask, rows, inner):
         """get_loss with loss == "soft_dtw" (loss.py:62-81): pads zero-filled in prediction and target, the time axis cut into
@@ -1138,7 +1108,7 @@ class Trainer:
             if self.gradient_clip_val is not None:
                 _lib.check(o.lib.fs2_op_sum_sq(self.flat_g, self.n_flat, self._nsq_ws, self._nsq, o.st()), None, "sum_sq")
                 nsq = self._nsq
-            shadow = self.flat_w if o.dt != F32 and os.environ.get("FS2_TRAIN_ADAMW_SHADOW", "1") != "0" else None  # (A/B switch)
+            shadow = self.flat_w if o.dt != F32 and self.adamw_shadow else None
             _lib.check(o.lib.fs2_op_adamw_shadow(self.flat_p, self.flat_g, self.flat_m, self.flat_v, shadow, self.n_flat, lr, self.betas[0],
                                                  self.betas[1], self.eps, self.weight_decay, self.steps + 1, nsq,
                                                  self.gradient_clip_val or 0.0, 1.0 / (self._accum * world), o.st()), None, "adamw")

@@ -285,8 +285,8 @@ def test_fused_tape_switches_agree_with_their_fallbacks(monkeypatch, switch):
     (p, seed, key) and the element index, so both sides compute the same function of the same weights: one fp32 step of the WIDE
     case (where tests/test_tape_route_cpu.py shows the fused forms launch) with every dropout site on must give the same losses
     (1e-5) and gradients (GRAD_TOL), and - other kernels, another summation order - not the same bits, which is also what shows
-    that a switch the step reads from the environment as it goes (FS2_TRAIN_GATE) took effect.  No switch is left out: at this
-    size each one changes the launches of at least one GEMM."""
+    that a switch took effect (each one is read once, when the Trainer is built).  No switch is left out: at this size each one
+    changes the launches of at least one GEMM."""
     name, value, took_effect = switch
     tr0, l0, g0, flat0 = _wide_dropout_step()
     assert tr0.ops.fuse_ln and tr0.ops.fuse_ln_drop and tr0.ops.fuse_add and tr0.use_forward_dgrad
