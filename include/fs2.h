@@ -155,6 +155,20 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
  * = targets["priors_<prior_names[p]>"] (fastspeech2.py:687-692; PriorEmbedding, model.py:146-164).
  * Required before every fs2_encode when n_priors > 0. */
 int fs2_set_priors(fs2_engine* e, const float* priors_device, int32_t B);
+/* duration_stochastic=True (model.py:196-207, 258-268, 299-305): the stochastic duration predictor (fs2_sdp_* below) where the
+ * conv + LayerNorm duration predictor runs, and its rounding rule (fs2_op_durations_stochastic).  Legal only between fs2_create and
+ * the first fs2_load_weight (FS2_ERR_STATE later).  n_flows = dur_nlayers, hidden_channels = dur_filter, kernel_size = dur_kernel of
+ * the config; dur_depthwise != 0 is refused (FS2_ERR_SHAPE, as the reference refuses it), and so is a shape fs2_sdp_supported
+ * does not cover (hidden > 256 among them).  The conv predictor's rule dur_filter == hidden for dur_nlayers > 1 does not apply to this
+ * predictor: fs2_create accepts such a config and the rule is judged at the first fs2_load_weight / at fs2_finalize of an engine that
+ * was NOT switched (FS2_ERR_SHAPE there).  The engine then expects "variance_adaptor.duration_predictor.sdp.*" (training-only tensors accepted and
+ * dropped) in place of the deterministic predictor's tensors.  fs2_clone shares the weights.  With fs2_set_graphs the encode phase
+ * of a stochastic engine takes the plain path (the noise is a one-shot pointer of the call); the decode phase may still replay. */
+int fs2_set_stochastic_duration(fs2_engine* e, int32_t on);
+/* The noise of the NEXT fs2_encode of a stochastic engine (one-shot, like fs2_set_priors): (B, 2, L) fp32 device, standard normal
+ * already scaled by noise_scale (sdp.py:335-338).  Required before every fs2_encode of a stochastic engine, forced durations or
+ * not (FS2_ERR_STATE from fs2_encode otherwise); fs2_encode copies it into the engine's own buffer on its stream. */
+int fs2_set_duration_noise(fs2_engine* e, const float* noise_device, int32_t B, int32_t L);
 /* Per-utterance frame totals (untruncated) and zero-duration-guard flags of the last fs2_encode. */
 int fs2_last_totals(const fs2_engine* e, int32_t* totals_host, int32_t* guard_host, int32_t B);
 /* Phase 2: length regulator + variance encoders + decoder + mel linear, into caller buffers. */
@@ -752,6 +766,51 @@ int fs2_op_contour_finish(const float* values, const int32_t* frames, const int3
                           int32_t* frames_out, float* prior, void* hip_stream);
 int fs2_op_masked_row_mean(const float* values, const int32_t* counts, const int32_t* skip, int32_t B, int32_t N, float* out,
                            void* hip_stream);
+
+/* ================================================================================================
+ * Stochastic duration predictor at inference (duration_stochastic=True: the VITS spline-flow predictor of
+ * litfass/third_party/stochastic_duration_predictor/sdp.py:249-349 with reverse=True, as StochasticDurationPredictorWrapper calls it,
+ * litfass/fastspeech2/model.py:463-479).  A handle of its own, in the pattern of fs2_mel_*: create validates on the host alone.
+ *   fs2_sdp_create: H = in_channels (the encoder width), F = hidden_channels, k = kernel_size, n_flows = the wrapper's nlayers.
+ *    Supported: F == 256, k == 3, 1 <= n_flows <= 8, H a multiple of 16 in 16 .. 256 (`pre` runs inside the conditioning launch);
+ *    anything else is FS2_ERR_SHAPE and fs2_sdp_supported answers 0.  A bad abi_version is FS2_ERR_ARG.  As with fs2_mel_create the
+ *    handle is returned on failure too, for fs2_sdp_last_error; destroy it.
+ *   fs2_sdp_load_weight: fp32 HOST data under the reference's state_dict names relative to "variance_adaptor.duration_predictor."
+ *    ("sdp.pre.weight", "sdp.convs.convs_sep.0.weight", "sdp.convs.norms_1.0.gamma", "sdp.flows.0.translation",
+ *    "sdp.flows.2.proj.weight", ...) with the reference's shapes.  The training-only tensors (sdp.post_pre / post_convs / post_proj /
+ *    post_flows.*, and sdp.flows.1.*, the ConvFlow the inference loop drops) are shape-checked and dropped.  An unknown name or a wrong
+ *    shape is FS2_ERR_WEIGHT.
+ *   fs2_sdp_finalize packs and uploads; FS2_ERR_WEIGHT names the first on-path tensor that is missing.
+ *   fs2_sdp_forward: x (B, L, H) of x_dtype (FS2_F32, FS2_BF16, FS2_F16; converted to fp32 as the rows are read), pad_mask (B, L)
+ *    1 = pad, noise (B, 2, L) fp32 standard normal ALREADY scaled by noise_scale, logw (B, L) fp32 out, 0 at pads; all device.
+ *    workspace: fs2_sdp_workspace_bytes(h, B, L) device bytes, 16-byte aligned (FS2_ERR_NOMEM if short; n_flows == 1 needs none).
+ *    Launches: one for the text conditioning, one per ConvFlow that runs (n_flows - 1 of them: CF_n .. CF_2), the ElementwiseAffine
+ *    folded into the last; n_flows == 1 is a single row launch.  fs2_sdp_launches reports the count.  All arithmetic is fp32 (1x1 convs
+ *    on the fp32 MFMA) with accurate exp / log / erf / sqrt, whatever x_dtype.  The bits of an utterance's logw do not depend on B, on
+ *    L, or on where its rows fall in a tile.  Allocates nothing, never synchronises.
+ *   fs2_sdp_tile_rows: the finished rows per workgroup (tiles start at its multiples from an utterance's first row).
+ *   fs2_op_rq_spline_inverse: out[i] = the inverse of the unconstrained rational-quadratic spline with linear tails (tail_bound 5,
+ *    10 bins; transforms.py:51-191) at x1[i] with parameters h29[i][0..28] (widths and heights are divided by sqrt(F)); the device
+ *    function of the flow launch.  Where the reference asserts a non-negative discriminant this clamps it at 0.
+ *   fs2_op_durations_stochastic: fs2_op_durations with the stochastic model's rule (model.py:302-309):
+ *    d = int(clamp(ceil(exp(logw + 1e-9)), 0)) in float32 as written, 0 where logw == 0; then the same zero-duration guard, forced
+ *    durations and prefix sums.  A value beyond int32 SATURATES at INT32_MAX and NaN gives 0, as in fs2_op_durations.
+ * ================================================================================================ */
+typedef struct fs2_sdp fs2_sdp;
+int fs2_sdp_supported(int32_t H, int32_t F, int32_t k, int32_t n_flows);
+int fs2_sdp_create(int32_t abi_version, int32_t H, int32_t F, int32_t k, int32_t n_flows, fs2_sdp** out);
+int fs2_sdp_destroy(fs2_sdp* h);
+const char* fs2_sdp_last_error(const fs2_sdp* h);
+int32_t fs2_sdp_tile_rows(const fs2_sdp* h);
+int fs2_sdp_launches(const fs2_sdp* h);
+int fs2_sdp_load_weight(fs2_sdp* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim);
+int fs2_sdp_finalize(fs2_sdp* h);
+int fs2_sdp_workspace_bytes(const fs2_sdp* h, int32_t B, int32_t L, size_t* bytes);
+int fs2_sdp_forward(fs2_sdp* h, int32_t x_dtype, const void* x, const uint8_t* pad_mask, const float* noise, float* logw,
+                    void* workspace, size_t workspace_bytes, int32_t B, int32_t L, void* hip_stream);
+int fs2_op_rq_spline_inverse(const float* x1, const float* h29, int32_t F, float* out, int32_t rows, void* hip_stream);
+int fs2_op_durations_stochastic(const float* logw, const uint8_t* src_mask, const int32_t* forced, int32_t* dur, int32_t* cum,
+                                int32_t* totals, int32_t* guard, int32_t B, int32_t L, void* hip_stream);
 
 /* ================================================================================================
  * HiFi-GAN generator: the step right after the mel forward.  Replaces

@@ -49,6 +49,9 @@ class Fs2Config:
     duration_kernel_size: int = 3
     duration_filter_size: int = 256
     duration_depthwise_conv: bool = True
+    # StochasticDurationPredictorWrapper in place of the conv + LayerNorm predictor (model.py:196-207); duration_nlayers = its flows.
+    # NOTE: to_dict() / to_json() carry this field only when it is True (see to_dict): do not iterate the dataclass fields against them.
+    duration_stochastic: bool = False
     n_mels: int = 80
     sampling_rate: int = 22050
     hop_length: int = 256
@@ -111,7 +114,19 @@ class Fs2Config:
                                  "(every layer is built in_channels->filter, model.py:497-501)")
             if v not in self.stats:
                 raise ValueError(f"stats missing for variance {v!r}")
-        if self.duration_nlayers > 1 and self.duration_filter_size != H:
+        if self.duration_stochastic:
+            if self.duration_depthwise_conv:  # model.py:196-200 raises NotImplementedError
+                raise ValueError("duration_stochastic=True with duration_depthwise_conv=True: the reference does not build "
+                                 "a depth-wise flow-based duration predictor (model.py:196-200)")
+            # what the kernel is built for (fs2_sdp_supported, csrc/sdp.hip): refused here as the engine refuses it
+            if self.duration_filter_size != 256 or self.duration_kernel_size != 3:
+                raise ValueError("duration_stochastic=True runs with duration_filter_size=256 and duration_kernel_size=3 only")
+            if not 1 <= self.duration_nlayers <= 8:
+                raise ValueError("duration_stochastic=True needs 1 <= duration_nlayers <= 8 (its number of flows)")
+            if H > 256 or H % 16:
+                raise ValueError("duration_stochastic=True needs encoder_hidden <= 256, a multiple of 16: the predictor's "
+                                 "input projection runs inside its conditioning launch")
+        elif self.duration_nlayers > 1 and self.duration_filter_size != H:
             raise ValueError("duration_filter_size must equal hidden when nlayers>1")
         for pr in self.priors:
             # PriorEmbedding(H, variance_nbins, stats[f"{prior}_prior"]) (fastspeech2.py:416-424)
@@ -128,7 +143,12 @@ class Fs2Config:
         return self.variance_levels[i] == "phone"
 
     def to_dict(self) -> dict:
-        return asdict(self)
+        d = asdict(self)
+        if not d["duration_stochastic"]:
+            # written only when set: the dict (and to_json, which fixtures store and compare) of every deterministic config stays
+            # what it was before the field existed; from_dict's default reads the absence back as False
+            del d["duration_stochastic"]
+        return d
 
     def to_json(self) -> str:
         return json.dumps(self.to_dict(), sort_keys=True)

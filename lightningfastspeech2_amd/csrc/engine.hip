@@ -178,6 +178,9 @@ struct Model {
     float* mel_wg = nullptr;
     bool mel_fold = false;
     std::vector<VarianceW> priors_w;  // bins + relu(embedding) per prior (predictor unused)
+    // duration_stochastic=True (fs2_set_stochastic_duration): the stochastic duration predictor's handle (sdp.hip) stands in for `dur`
+    bool dur_stochastic = false;
+    std::shared_ptr<fs2_sdp> sdp;
 };
 struct Switches {
     bool fuse_predictor = true;
@@ -204,6 +207,9 @@ struct fs2_engine : Model, Switches {
     std::map<std::string, HostTensor> host;  // fs2_load_weight's tensors, until fs2_finalize has packed them
     const float* priors_dev = nullptr;
     int priors_B = 0;
+    bool weight_seen = false;          // a fs2_load_weight has been accepted: the architecture switches are closed
+    const float* noise_dev = nullptr;  // fs2_set_duration_noise: the next encode's (B, 2, L) noise, one-shot
+    int noise_B = 0, noise_L = 0;
     Arena persist, scratch, dbg, dbg_enc;
     int B = 0, L = 0, T = 0;
     bool encoded = false;
@@ -294,7 +300,8 @@ void build_spec(fs2_engine* e) {
     for (int i = 0; i < c.dec_layers; ++i)
         conformer_spec(e, "decoder.layers." + std::to_string(i), H, c.dec_filter, c.dec_kernels[i], c.dec_depthwise);
     e->spec["positional_encoding.pe"] = {1, c.pe_len, H};
-    predictor_spec(e, "variance_adaptor.duration_predictor", c.dur_nlayers, H, c.dur_filter, c.dur_kernel, c.dur_depthwise);
+    if (!e->dur_stochastic)  // (a stochastic predictor's tensors are the sdp handle's: fs2_load_weight hands them on)
+        predictor_spec(e, "variance_adaptor.duration_predictor", c.dur_nlayers, H, c.dur_filter, c.dur_kernel, c.dur_depthwise);
     for (int v = 0; v < c.n_variances; ++v) {
         const std::string p = std::string("variance_adaptor.encoders.") + c.var_names[v];
         e->spec[p + ".bins"] = {c.var_nbins - 1};
@@ -348,7 +355,6 @@ int check_config(fs2_engine* e) {
     if (c.var_filter % 64 || c.dur_filter % 64 || c.var_filter > 1024 || c.dur_filter > 1024)
         return fail(e, FS2_ERR_SHAPE, "predictor filter sizes must be multiples of 64, <= 1024");
     if (c.dur_nlayers < 1) return fail(e, FS2_ERR_SHAPE, "duration_nlayers < 1");
-    if (c.dur_nlayers > 1 && c.dur_filter != H) return fail(e, FS2_ERR_SHAPE, "duration_filter_size != hidden with nlayers > 1");
     if (!(c.dur_kernel & 1) || c.dur_kernel > 31) return fail(e, FS2_ERR_SHAPE, "duration kernel must be odd, <= 31");
     for (int v = 0; v < c.n_variances; ++v) {
         if (c.var_nlayers[v] < 1) return fail(e, FS2_ERR_SHAPE, "variance_nlayers < 1");
@@ -361,6 +367,15 @@ int check_config(fs2_engine* e) {
     if (c.var_nbins < 2 && c.n_variances) return fail(e, FS2_ERR_SHAPE, "variance_nbins < 2");
     if (c.n_mels <= 0 || c.n_mels % 4) return fail(e, FS2_ERR_SHAPE, "n_mels must be a positive multiple of 4");
     if (c.dvec_dim <= 0 || c.max_frames <= 0 || c.pe_len <= 0 || c.n_phones <= 0) return fail(e, FS2_ERR_ARG, "non-positive size");
+    return FS2_OK;
+}
+
+// The conv + LayerNorm duration predictor chains its layers in_channels -> filter (model.py:497-501).  Judged when the first weight
+// arrives, not in fs2_create: until then fs2_set_stochastic_duration may still replace that predictor by one that maps hidden -> filter itself.
+int check_deterministic_duration(fs2_engine* e) {
+    const fs2_config& c = e->cfg;
+    if (!e->dur_stochastic && c.dur_nlayers > 1 && c.dur_filter != c.hidden)
+        return fail(e, FS2_ERR_SHAPE, "duration_filter_size != hidden with nlayers > 1");
     return FS2_OK;
 }
 
@@ -1068,6 +1083,9 @@ bool layout_persist(const fs2_engine* e, Arena& ar, int B, int L, PersistBufs* p
 struct EncodeScratch {
     LayerScratch sc;
     float* spec12 = nullptr;  // the CWT head's (M, 12) spectrogram: one buffer that every phone-level CWT variance reuses (encode_body)
+    float* sdp_noise = nullptr;  // stochastic durations: the engine's copy of the call's (B, 2, L) noise ...
+    void* sdp_ws = nullptr;      // ... and fs2_sdp_forward's workspace
+    size_t sdp_ws_bytes = 0;
 };
 bool layout_encode_scratch(const fs2_engine* e, Arena& ar, int B, int L, EncodeScratch* s) {
     const fs2_config& c = e->cfg;
@@ -1075,6 +1093,11 @@ bool layout_encode_scratch(const fs2_engine* e, Arena& ar, int B, int L, EncodeS
     bool phone_cwt = false;
     for (int v = 0; v < c.n_variances; ++v) phone_cwt = phone_cwt || (c.var_level[v] && c.var_cwt[v]);
     s->spec12 = phone_cwt ? (float*)ar.take((size_t)B * L * 12 * 4) : nullptr;
+    if (e->dur_stochastic) {
+        s->sdp_noise = (float*)ar.take((size_t)B * 2 * L * 4);
+        if (fs2_sdp_workspace_bytes(e->sdp.get(), B, L, &s->sdp_ws_bytes) != FS2_OK) s->sdp_ws_bytes = 0;
+        s->sdp_ws = ar.take(s->sdp_ws_bytes);
+    }
     return !ar.overflow;
 }
 
@@ -1237,6 +1260,14 @@ int fs2_destroy(fs2_engine* e) {
 int fs2_load_weight(fs2_engine* e, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
     if (!e || !name || !data || !shape || ndim < 0) return FS2_ERR_ARG;
     if (e->finalized) return fail(e, FS2_ERR_STATE, "weights already finalized");
+    static const char kDur[] = "variance_adaptor.duration_predictor.";
+    if (e->dur_stochastic && !strncmp(name, kDur, sizeof(kDur) - 1)) {
+        const int r = fs2_sdp_load_weight(e->sdp.get(), name + sizeof(kDur) - 1, data, shape, ndim);
+        if (r != FS2_OK) return fail(e, r, "%s (stochastic duration predictor: '%s')", fs2_sdp_last_error(e->sdp.get()), name);
+        e->weight_seen = true;
+        return FS2_OK;
+    }
+    CHK(check_deterministic_duration(e));
     auto it = e->spec.find(name);
     if (it == e->spec.end()) return fail(e, FS2_ERR_WEIGHT, "unexpected weight '%s' for this config", name);
     const std::vector<int64_t>& want = it->second;
@@ -1248,12 +1279,14 @@ int fs2_load_weight(fs2_engine* e, const char* name, const float* data, const in
     t.shape.assign(shape, shape + ndim);
     t.data.assign(data, data + n);
     e->host[name] = std::move(t);
+    e->weight_seen = true;
     return FS2_OK;
 }
 
 int fs2_finalize(fs2_engine* e) {
     if (!e) return FS2_ERR_ARG;
     if (e->finalized) return FS2_OK;
+    CHK(check_deterministic_duration(e));
     for (auto& kv : e->spec)
         if (!e->host.count(kv.first)) return fail(e, FS2_ERR_WEIGHT, "missing weight '%s'", kv.first.c_str());
     const fs2_config& c = e->cfg;
@@ -1278,7 +1311,12 @@ int fs2_finalize(fs2_engine* e) {
         for (int i = 1; i < c.enc_layers && c.enc_depthwise && e->fdt == FS2_BF16; ++i) CHK(fold_in_proj("encoder.layers.", i, &e->enc[i]));
         for (int i = 1; i < c.dec_layers && c.dec_depthwise && is_16bit(e->bdt); ++i) CHK(fold_in_proj("decoder.layers.", i, &e->dec[i]));
     }
-    CHK(make_predictor(e, "variance_adaptor.duration_predictor", c.dur_nlayers, c.dur_filter, c.dur_depthwise, &e->dur, e->fdt));
+    if (e->dur_stochastic) {
+        const int r = fs2_sdp_finalize(e->sdp.get());
+        if (r != FS2_OK) return fail(e, r, "stochastic duration predictor: %s", fs2_sdp_last_error(e->sdp.get()));
+    } else {
+        CHK(make_predictor(e, "variance_adaptor.duration_predictor", c.dur_nlayers, c.dur_filter, c.dur_depthwise, &e->dur, e->fdt));
+    }
     e->vars.resize(c.n_variances);
     for (int v = 0; v < c.n_variances; ++v) {
         const std::string p = std::string("variance_adaptor.encoders.") + c.var_names[v];
@@ -1428,6 +1466,8 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
     if (!e || !phones || !speaker || !T_out || B <= 0 || L <= 0) return e ? fail(e, FS2_ERR_ARG, "bad encode argument") : FS2_ERR_ARG;
     if (!e->finalized) return fail(e, FS2_ERR_STATE, "fs2_finalize not called");
     if (L > e->cfg.pe_len) return fail(e, FS2_ERR_SHAPE, "L=%d exceeds positional table %d", L, e->cfg.pe_len);
+    if (e->dur_stochastic && (!e->noise_dev || e->noise_B != B || e->noise_L != L))
+        return fail(e, FS2_ERR_STATE, "fs2_set_duration_noise(B=%d, L=%d) required before fs2_encode of a stochastic engine", B, L);
     hipStream_t st = (hipStream_t)stream;
     const fs2_config& c = e->cfg;
     e->encoded = false;
@@ -1456,7 +1496,8 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
         std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)e->persist.base, (uint64_t)e->scratch.base, (uint64_t)phones,
                                      (uint64_t)speaker, (uint64_t)forced, (uint64_t)e->h_pinned, (uint64_t)e->fuse_predictor, (uint64_t)e->tune.gen,
                                      (uint64_t)e->defer_ln, (uint64_t)e->front_split, (uint64_t)e->fold_ln};
-        const bool plain = c.n_priors != 0 || pv_forced;  // a prior tensor / a phone-level forced target is a one-shot pointer of the call
+        // a prior tensor / a phone-level forced target / the duration noise is a one-shot pointer of the call
+        const bool plain = c.n_priors != 0 || pv_forced || e->dur_stochastic;
         CHK(run_phase(e, e->egraphs, key, plain, st, [&](hipStream_t s2) { return encode_body(e, phones, speaker, forced, es, s2); }));
     }
     HIPCHK(e, hipStreamSynchronize(st));  // the one host sync of the forward (output shape)
@@ -1504,7 +1545,14 @@ static int encode_body(fs2_engine* e, const int64_t* phones, const float* speake
         e->priors_dev = nullptr;  // one-shot
     }
     // duration predictor + rounding + prefix sums                          model.py:259,299-309
-    CHK(predictor(e, st, e->dur, ps.xA, B, L, ps.src_mask, ps.dur_pred, sc));
+    if (e->dur_stochastic) {  // model.py:260-268: the flow predictor on encoder_out.detach(), noise from the caller (sdp.py:335-338)
+        HIPCHK(e, hipMemcpyAsync(es.sdp_noise, e->noise_dev, (size_t)B * 2 * L * 4, hipMemcpyDeviceToDevice, st));
+        e->noise_dev = nullptr;  // one-shot
+        const int r = fs2_sdp_forward(e->sdp.get(), e->fdt, ps.xA, ps.src_mask, es.sdp_noise, ps.dur_pred, es.sdp_ws, es.sdp_ws_bytes, B, L, st);
+        if (r != FS2_OK) return fail(e, r, "stochastic duration predictor: %s", fs2_sdp_last_error(e->sdp.get()));
+    } else {
+        CHK(predictor(e, st, e->dur, ps.xA, B, L, ps.src_mask, ps.dur_pred, sc));
+    }
     // phone-level variance encoders (variance_levels[i] == "phone"), in list order, AFTER the duration predictor has seen x and BEFORE
     // the length regulator: each adds its embedding to the rows that get regulated                      model.py:276-294
     // The rows ping-pong between xA and xB through local pointers (variance_stage swaps them where the embedding rode in the predictor
@@ -1518,7 +1566,8 @@ static int encode_body(fs2_engine* e, const int64_t* phones, const float* speake
         e->forced_idx[v] = nullptr, e->forced_tgt[v] = nullptr;  // one-shot, consumed here
     }
     if (x != ps.xA) HIPCHK(e, hipMemcpyAsync(ps.xA, x, ML * H * esz, hipMemcpyDeviceToDevice, st));  // an odd number of swaps
-    DurationArgs da{ps.dur_pred, ps.src_mask, forced, ps.d_dur, ps.d_cum, ps.d_totals, ps.d_guard, B, L};
+    // stochastic: ceil(exp(logw)), 0 where logw == 0 (model.py:302-305) in front of the same guard and prefix sums
+    DurationArgs da{ps.dur_pred, ps.src_mask, forced, ps.d_dur, ps.d_cum, ps.d_totals, ps.d_guard, B, L, e->dur_stochastic ? 1 : 0};
     if (launch_durations(da, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "durations launch failed");
     HIPCHK(e, hipMemcpyAsync(e->h_pinned, ps.d_totals, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st));
     return FS2_OK;
@@ -1529,6 +1578,37 @@ int fs2_set_priors(fs2_engine* e, const float* priors_device, int32_t B) {
     if (e->cfg.n_priors == 0) return fail(e, FS2_ERR_STATE, "this engine was configured without priors");
     e->priors_dev = priors_device;
     e->priors_B = B;
+    return FS2_OK;
+}
+
+int fs2_set_stochastic_duration(fs2_engine* e, int32_t on) {
+    if (!e) return FS2_ERR_ARG;
+    if (e->finalized || e->weight_seen)
+        return fail(e, FS2_ERR_STATE, "fs2_set_stochastic_duration is legal only between fs2_create and the first fs2_load_weight");
+    if (e->spec.empty()) return fail(e, FS2_ERR_STATE, "fs2_create did not succeed");
+    const fs2_config& c = e->cfg;
+    std::shared_ptr<fs2_sdp> h;
+    if (on) {
+        if (c.dur_depthwise)
+            return fail(e, FS2_ERR_SHAPE, "duration_stochastic with duration_depthwise_conv: the reference builds no such predictor (model.py:196-200)");
+        fs2_sdp* raw = nullptr;
+        const int r = fs2_sdp_create(FS2_ABI_VERSION, c.hidden, c.dur_filter, c.dur_kernel, c.dur_nlayers, &raw);
+        h.reset(raw, [](fs2_sdp* p) { if (p) (void)fs2_sdp_destroy(p); });
+        if (r != FS2_OK) return fail(e, r, "stochastic duration predictor: %s", raw ? fs2_sdp_last_error(raw) : "out of memory");
+    }
+    e->dur_stochastic = on != 0;
+    e->sdp = h;
+    e->spec.clear();
+    build_spec(e);
+    return FS2_OK;
+}
+
+int fs2_set_duration_noise(fs2_engine* e, const float* noise_device, int32_t B, int32_t L) {
+    if (!e || !noise_device || B <= 0 || L <= 0) return FS2_ERR_ARG;
+    if (!e->dur_stochastic) return fail(e, FS2_ERR_STATE, "this engine's duration predictor is not stochastic (fs2_set_stochastic_duration)");
+    e->noise_dev = noise_device;
+    e->noise_B = B;
+    e->noise_L = L;
     return FS2_OK;
 }
 

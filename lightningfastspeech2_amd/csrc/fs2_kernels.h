@@ -421,6 +421,7 @@ struct DurationArgs {
     int32_t* totals;          // (B)
     int32_t* guard;           // (B) 1 if the zero-duration guard fired
     int B, L;
+    int stochastic = 0;       // 1: dur_pred is a stochastic predictor's logw, rounded by ceil(exp(logw + 1e-9)), 0 where logw == 0 (model.py:302-305)
 };
 int launch_durations(const DurationArgs& a, hipStream_t stream);
 

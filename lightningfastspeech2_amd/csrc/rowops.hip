@@ -501,12 +501,21 @@ int launch_mask_bits(const MaskBitsArgs& a, hipStream_t stream) {
 // Duration rounding + zero-duration guard + prefix sum (model.py:299-309 and the lengths the
 // LengthRegulator derives, model.py:350-354).  One workgroup per utterance.
 //   d = int(clamp(round_half_even(exp(p) - 1), 0));  if sum_valid d <= n_valid // 2: d[valid] = 1
+// STOCHASTIC (duration_stochastic=True, model.py:302-305): d = int(clamp(ceil(exp(p + 1e-9)), 0)), 0 where p == 0; the rest is shared.
 // =============================================================================================
+template <bool STOCHASTIC>
 __device__ inline int dur_from_pred(float p) {
-    const float v = rintf(__fsub_rn(expf(p), 1.0f));  // torch.round = half-to-even
-    return v > 0.f ? (int)v : 0;
+    float v;
+    if constexpr (STOCHASTIC) {
+        if (p == 0.f) return 0;
+        v = ceilf(expf(__fadd_rn(p, 1e-9f)));  // float32 as written: the addend vanishes unless |p| is tiny
+    } else {
+        v = rintf(__fsub_rn(expf(p), 1.0f));  // torch.round = half-to-even
+    }
+    return v > 0.f ? (int)v : 0;  // NaN -> 0; beyond int32 the conversion saturates
 }
 
+template <bool STOCHASTIC>
 __global__ __launch_bounds__(256) void durations_kernel(DurationArgs p) {
     __shared__ int red[2][4];
     __shared__ int wsum[4];
@@ -519,7 +528,7 @@ __global__ __launch_bounds__(256) void durations_kernel(DurationArgs p) {
     if (!forced) {
         int sd = 0, nv = 0;
         for (int l = tid; l < p.L; l += 256) {
-            if (!mk[l]) { sd += dur_from_pred(dp[l]); nv += 1; }
+            if (!mk[l]) { sd += dur_from_pred<STOCHASTIC>(dp[l]); nv += 1; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o, 64); nv += __shfl_xor(nv, o, 64); }
@@ -539,7 +548,7 @@ __global__ __launch_bounds__(256) void durations_kernel(DurationArgs p) {
         int d = 0;
         if (l < p.L) {
             if (forced) d = forced[l];
-            else d = (guard && !mk[l]) ? 1 : dur_from_pred(dp[l]);
+            else d = (guard && !mk[l]) ? 1 : dur_from_pred<STOCHASTIC>(dp[l]);
             if (d < 0) d = 0;
         }
         int inc = d;  // inclusive scan inside the wave
@@ -567,7 +576,8 @@ __global__ __launch_bounds__(256) void durations_kernel(DurationArgs p) {
 
 int launch_durations(const DurationArgs& a, hipStream_t stream) {
     if (a.B <= 0) return FS2_OK;
-    hipLaunchKernelGGL(durations_kernel, dim3(a.B), dim3(256), 0, stream, a);
+    if (a.stochastic) hipLaunchKernelGGL(durations_kernel<true>, dim3(a.B), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(durations_kernel<false>, dim3(a.B), dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 

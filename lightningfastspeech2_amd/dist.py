@@ -77,6 +77,9 @@ def shard_batch(batch: Dict[str, torch.Tensor], world: int, rank: int, *, trim: 
             if k != "phones" and bool((torch.as_tensor(v)[:, Lr:] != 0).any()):
                 raise ValueError(f"batch[{k!r}] has non-zero entries beyond the shard's longest utterance")
             out[k] = v[:, :Lr].contiguous()
+        zn = out.get("duration_noise")  # (B, 2, L): a stochastic duration predictor's noise follows its utterances' rows and phones
+        if zn is not None and hasattr(zn, "shape") and len(zn.shape) == 3 and zn.shape[2] == L:
+            out["duration_noise"] = zn[:, :, :Lr].contiguous()
         dur = out.get("duration")
         mel_t = out.get("mel")
         if dur is not None and hasattr(dur, "shape") and len(dur.shape) == 2:
@@ -211,10 +214,19 @@ def forward_sharded(forward_fn: Callable[..., Dict[str, torch.Tensor]], batch: D
     empty mel.  ``device``: where the control tensors of the collectives (and an empty shard's mel) live; default =
     what the group's backend needs (``collective_device``: the current GPU under nccl, also for a host-side batch).
     ``dst``: gather onto that rank only (``gather_mels_async``); the other ranks get ``(None, None, local)``.
+    A stochastic duration predictor (``duration_stochastic=True``): the noise is ONE ``(B, 2, L)`` draw for the whole batch, of which a
+    shard takes its rows.  Hand it over as ``batch["duration_noise"]`` (the same tensor on every rank); without it, and with a bound
+    model method as ``forward_fn``, every rank draws the whole batch's noise from ITS OWN CPU generator - the shards then equal the
+    one-device result only if all ranks seeded ``torch.manual_seed`` alike and have drawn nothing else since.
     Returns (mel_all, frames, local_result or None)."""
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     B = batch["phones"].shape[0]
     Bs = [hi - lo for lo, hi in (shard_bounds(B, world, r) for r in range(world))]
+    owner = getattr(forward_fn, "__self__", None)
+    if "duration_noise" not in batch and getattr(getattr(owner, "cfg", None), "duration_stochastic", False):
+        # a stochastic model's one draw is the WHOLE batch's (B, 2, L), as on one device; the shard takes its rows of it.  A plain
+        # function or lambda as forward_fn cannot be asked: hand batch["duration_noise"] over there.
+        batch = {**batch, "duration_noise": owner.draw_duration_noise(B, batch["phones"].shape[1])}
     local_batch = shard_batch(batch, world, rank, trim=not global_pad)
     sp_ = batch.get("speaker")
     dev = torch.device(device) if device is not None else collective_device(group, sp_ if isinstance(sp_, torch.Tensor) else None)

@@ -57,6 +57,8 @@ class Engine:
             st = self.lib.fs2_create(C.byref(cc), C.byref(self.handle))
             try:
                 _lib.check(st, self.handle, "create")
+                if cfg.duration_stochastic:  # before the first weight: the engine then expects ...duration_predictor.sdp.*
+                    _lib.check(self.lib.fs2_set_stochastic_duration(self.handle, 1), self.handle, "set_stochastic_duration")
                 self._load(state_dict)
             except Exception:
                 self.close()
@@ -119,11 +121,13 @@ class Engine:
         _lib.check(self.lib.fs2_set_debug(self.handle, int(on)), self.handle, "set_debug")
 
     def encode(self, phones: torch.Tensor, speaker: torch.Tensor, forced_durations: Optional[torch.Tensor] = None,
-               priors: Optional[torch.Tensor] = None) -> int:
+               priors: Optional[torch.Tensor] = None, duration_noise: Optional[torch.Tensor] = None) -> int:
         B, L = phones.shape
         T = C.c_int32(0)
         if priors is not None:  # (n_priors, B) fp32 on the device
             _lib.check(self.lib.fs2_set_priors(self.handle, priors, B), self.handle, "set_priors")
+        if duration_noise is not None:  # (B, 2, L) fp32 on the device, already scaled: a stochastic duration predictor's draw
+            _lib.check(self.lib.fs2_set_duration_noise(self.handle, duration_noise, B, L), self.handle, "set_duration_noise")
         with torch.cuda.device(self.device):
             if self.torch_workspace:  # sized for the frame count this (B, L) produced last time, if any
                 self._ensure_workspace(B, L, self._t_hint.get((B, L), 0))
@@ -303,13 +307,21 @@ class FastSpeech2:
         hp.pop("stats", None)
         hp.pop("n_phones", None)
         hp.update(dict(speaker_embedding_every_layer=False, prior_embedding_every_layer=False,
-                       fastdiff_variances=False, fastdiff_speakers=False, duration_stochastic=False))
+                       fastdiff_variances=False, fastdiff_speakers=False, duration_stochastic=cfg.duration_stochastic))
         hp.update(extra_hparams or {})
         self.hparams = SimpleNamespace(**hp)
         self.engine = Engine(cfg, state_dict, precision=precision, device=device)
         self.device = self.engine.device
         self.training = False
         self._t_guess = {}
+        # the reference's `sigma` (StochasticDurationPredictorWrapper.forward, model.py:475-476): scales a stochastic model's noise
+        self.duration_noise_scale = 1.0
+
+    def draw_duration_noise(self, B: int, L: int) -> torch.Tensor:
+        """The draw of a stochastic duration predictor, where and how the reference makes it (sdp.py:335-338): one
+        ``torch.randn(B, 2, L)`` on the CPU default generator, times ``duration_noise_scale`` - reproducible from
+        ``torch.manual_seed``."""
+        return torch.randn(B, 2, L) * self.duration_noise_scale
 
     def replicate(self) -> "FastSpeech2":
         """Another model object over the same weights (its own engine: own workspace, own host state) - what ForwardPipeline
@@ -367,6 +379,9 @@ class FastSpeech2:
         """``frames_hook(T_local) -> T`` (optional) runs between the two phases and may raise the frame count
         this batch is padded to (data-parallel global-pad mode: an all-reduce MAX over the ranks)."""
         teacher = not inference and force_durations is None
+        if teacher and self.cfg.duration_stochastic:
+            raise NotImplementedError("the teacher-forced forward of a stochastic duration predictor is its training NLL "
+                                      "(sdp.py:276-331): only inference runs on the device")
         if teacher:
             # FastSpeech2.forward(batch) as the Lightning hooks call it (fastspeech2.py:787,800):
             # target durations (model.py:296-297) and target variances (model.py:317-325) are teacher
@@ -430,7 +445,14 @@ class FastSpeech2:
                 if tuple(idx.shape) != (B, L):
                     raise ValueError(f"force_buckets[{var!r}] (phone level) must be (B, L)=({B}, {L})")
                 self.engine.force_buckets(vi, idx)
-        T = self.engine.encode(phones, speaker, forced, priors)
+        noise = None
+        if self.cfg.duration_stochastic:
+            noise = targets.get("duration_noise")  # given: used as it is (already scaled); else the reference's draw
+            noise = self.draw_duration_noise(B, L) if noise is None else torch.as_tensor(noise)
+            if tuple(noise.shape) != (B, 2, L):
+                raise ValueError(f"duration_noise must be (B, 2, L) = ({B}, 2, {L}), got {tuple(noise.shape)}")
+            noise = noise.to(self.device, dtype=torch.float32).contiguous()
+        T = self.engine.encode(phones, speaker, forced, priors, noise)
         if frames_hook is not None:
             Tg = int(frames_hook(T))
             if Tg != T:
@@ -605,6 +627,11 @@ class ForwardPipeline:
 
     def _start(self, batch):
         """Queue one batch on the next replica; the future of ``_run``'s ``(out, done event)`` (SpeechPipeline takes these one by one)."""
+        if self.models[0].cfg.duration_stochastic and "duration_noise" not in batch:
+            # the draw happens HERE, on the calling thread and in submission order: the replicas' threads would race for the
+            # generator, and the results would stop being those of one-at-a-time calls under the same seed
+            B, L = batch["phones"].shape
+            batch = {**batch, "duration_noise": self.models[0].draw_duration_noise(B, L)}
         k = self.n % len(self.models)
         self.n += 1
         ready = torch.cuda.Event()

@@ -367,6 +367,8 @@ class Trainer:
         # (model.py:276-333).  The reference's own FastSpeech2Loss reads self.mse_loss for a CWT variance's mean / std terms
         # (loss.py:141,148) and never sets it; plain nn.MSELoss() over the B utterance values is what the name stands for, and what
         # the fixtures were produced with (tools/gen_golden_train_variances.py).
+        if cfg.duration_stochastic:  # its training forward is the flow's NLL with its own backward (sdp.py:276-331): inference only
+            raise NotImplementedError("training step: a stochastic duration predictor (duration_stochastic=True) is not trained here")
         for i, v in enumerate(cfg.variances):
             # Fs2Config has already checked the level and transform names; the CWT head operators take these widths only
             if cfg.is_cwt(i) and (cfg.variance_filter_size % 64 or not 64 <= cfg.variance_filter_size <= 1024):

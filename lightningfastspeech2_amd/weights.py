@@ -67,6 +67,58 @@ def _predictor_spec(prefix, nlayers, cin, filt, k, depthwise, out, n_out=1):
     out[f"{prefix}.linear.bias"] = (n_out,)
 
 
+SDP_SPLINE_PARAMS = 29  # ConvFlow.proj: num_bins * 3 - 1 with num_bins = 10 (sdp.py:129-131)
+
+
+def _sdp_spec(prefix, n_flows, cin, filt, k, out):
+    """StochasticDurationPredictorWrapper(nlayers, in_channels, filter_size, kernel_size, dropout).state_dict() (model.py:463-473,
+    sdp.py:197-241), in the module's own order.  The post_* half and flows.1 are training-only but part of every checkpoint."""
+    def dds(p):  # DilatedDepthSeparableConv(filt, k, num_layers=3), sdp.py:33-52
+        for i in range(3):
+            out[f"{p}.convs_sep.{i}.weight"] = (filt, 1, k)
+            out[f"{p}.convs_sep.{i}.bias"] = (filt,)
+        for i in range(3):
+            out[f"{p}.convs_1x1.{i}.weight"] = (filt, filt, 1)
+            out[f"{p}.convs_1x1.{i}.bias"] = (filt,)
+        for nm in ("norms_1", "norms_2"):
+            for i in range(3):
+                out[f"{p}.{nm}.{i}.gamma"] = (filt,)
+                out[f"{p}.{nm}.{i}.beta"] = (filt,)
+
+    def flows(p):  # [ElementwiseAffine(2)] + n x ConvFlow(2, filt, k, num_layers=3)
+        out[f"{p}.0.translation"] = (2, 1)
+        out[f"{p}.0.log_scale"] = (2, 1)
+        for j in range(1, n_flows + 1):
+            out[f"{p}.{j}.pre.weight"] = (filt, 1, 1)
+            out[f"{p}.{j}.pre.bias"] = (filt,)
+            dds(f"{p}.{j}.convs")
+            out[f"{p}.{j}.proj.weight"] = (SDP_SPLINE_PARAMS, filt, 1)
+            out[f"{p}.{j}.proj.bias"] = (SDP_SPLINE_PARAMS,)
+
+    s = f"{prefix}.sdp"
+    out[f"{s}.pre.weight"] = (filt, cin, 1)
+    out[f"{s}.pre.bias"] = (filt,)
+    dds(f"{s}.convs")
+    out[f"{s}.proj.weight"] = (filt, filt, 1)
+    out[f"{s}.proj.bias"] = (filt,)
+    flows(f"{s}.flows")
+    out[f"{s}.post_pre.weight"] = (filt, 1, 1)
+    out[f"{s}.post_pre.bias"] = (filt,)
+    dds(f"{s}.post_convs")
+    out[f"{s}.post_proj.weight"] = (filt, filt, 1)
+    out[f"{s}.post_proj.bias"] = (filt,)
+    flows(f"{s}.post_flows")
+
+
+SDP_PREFIX = "variance_adaptor.duration_predictor."
+
+
+def sdp_on_path(name: str) -> bool:
+    """Whether an ``sdp.*`` tensor (name relative to the duration predictor) is read at inference: not the posterior encoder, and
+    not flows.1, the ConvFlow the reversed loop drops (sdp.py:333-334)."""
+    return not (name.startswith("sdp.post_") or name.startswith("sdp.flows.1."))
+
+
 def state_dict_spec(cfg: Fs2Config) -> "OrderedDict[str, tuple]":
     H = cfg.hidden
     out: "OrderedDict[str, tuple]" = OrderedDict()
@@ -75,8 +127,12 @@ def state_dict_spec(cfg: Fs2Config) -> "OrderedDict[str, tuple]":
         _conformer_layer_spec(f"encoder.layers.{i}", H, cfg.encoder_head, cfg.encoder_conv_filter_size,
                               cfg.encoder_kernel_sizes[i], cfg.encoder_depthwise_conv, out)
     out["positional_encoding.pe"] = (1, PE_MAX_LEN, H)
-    _predictor_spec("variance_adaptor.duration_predictor", cfg.duration_nlayers, H,
-                    cfg.duration_filter_size, cfg.duration_kernel_size, cfg.duration_depthwise_conv, out)
+    if cfg.duration_stochastic:
+        _sdp_spec("variance_adaptor.duration_predictor", cfg.duration_nlayers, H, cfg.duration_filter_size,
+                  cfg.duration_kernel_size, out)
+    else:
+        _predictor_spec("variance_adaptor.duration_predictor", cfg.duration_nlayers, H,
+                        cfg.duration_filter_size, cfg.duration_kernel_size, cfg.duration_depthwise_conv, out)
     for vi, var in enumerate(cfg.variances):
         p = f"variance_adaptor.encoders.{var}"
         out[f"{p}.bins"] = (cfg.variance_nbins - 1,)
@@ -157,6 +213,24 @@ def synth_state_dict(cfg: Fs2Config, seed: int = 0, *, randomize_norm: bool = Fa
             sd[name] = w
             continue
         leaf = name.rsplit(".", 1)[1]
+        if ".duration_predictor.sdp." in name:
+            # The reference zero-initialises every ConvFlow.proj (sdp.py:132-133): the spline would be the identity and a test
+            # would see none of it.  So: proj of a flow ~ N(0, (2 / sqrt(F))^2) / N(0, 0.5^2), LayerNorm parameters and the
+            # ElementwiseAffine perturbed; every other conv by torch's default rule below.
+            if leaf in ("gamma", "beta"):
+                sd[name] = ((1.0 if leaf == "gamma" else 0.0) + 0.2 * rs.standard_normal(shape)).astype(np.float32)
+                continue
+            if leaf in ("translation", "log_scale"):
+                sd[name] = (0.5 * rs.standard_normal(shape)).astype(np.float32)
+                continue
+            if shape[0] == SDP_SPLINE_PARAMS:
+                scale = 2.0 / math.sqrt(cfg.duration_filter_size) if leaf == "weight" else 0.5
+                sd[name] = (scale * rs.standard_normal(shape)).astype(np.float32)
+                continue
+            if leaf == "weight":
+                fan_in = int(np.prod(shape[1:]))  # remembered for the bias that follows: the spec lists a module's weight, then its bias
+            sd[name] = rs.uniform(-1.0 / math.sqrt(fan_in), 1.0 / math.sqrt(fan_in), shape).astype(np.float32)
+            continue
         is_norm = ".norm1." in name or ".norm2." in name or name.rsplit(".", 2)[1] == "2"
         if is_norm:
             if leaf == "weight":
@@ -185,6 +259,8 @@ def synth_state_dict(cfg: Fs2Config, seed: int = 0, *, randomize_norm: bool = Fa
         bound = 1.0 / math.sqrt(fan_in)
         sd[name] = rs.uniform(-bound, bound, shape).astype(np.float32)
     if duration_bias is not None:
+        if cfg.duration_stochastic:
+            raise ValueError("duration_bias overrides the conv predictor's head: a stochastic duration predictor has none")
         p = "variance_adaptor.duration_predictor.linear"
         sd[f"{p}.weight"] = (sd[f"{p}.weight"] * np.float32(duration_weight_scale)).astype(np.float32)
         sd[f"{p}.bias"] = np.full((1,), duration_bias, np.float32)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Micro-benchmarks of single operators through the C ABI (device-resident, HIP-event timed).
-    python tools/bench_ops.py [gemm|attn|all] [--variant V] [--reps R]
+    python tools/bench_ops.py [gemm|attn|sdp|all] [--variant V] [--reps R]
 Shapes are the C2 (FS2-27M, B=32, L=256, T=1536) launches of the forward."""
 import argparse
 import ctypes as C
@@ -281,6 +281,58 @@ def dwconv_case(name, B, S, Cc, k, reps):
     print(f"{name:28s} B={B} S={S} C={Cc} k={k:2d}   {t * 1e6:8.1f} us   {by / t / 1e12:6.2f} TB/s  ({by / t / 8e12 * 100:4.1f}% of 8 TB/s)", flush=True)
 
 
+def sdp_case(B, L, n, reps):
+    """The stochastic duration predictor (fs2_sdp_forward, csrc/sdp.hip) at the C2 encoder shape, the deterministic duration
+    predictor's single launch beside it in the same process, and the whole C2-shaped forward with duration_stochastic off and on.
+    Fastest of five timed loops each."""
+    import _sdp_ref as R
+    from lightningfastspeech2_amd.config import preset
+    from lightningfastspeech2_amd.model import FastSpeech2
+    from lightningfastspeech2_amd.sdp import StochasticDurationPredictor
+    from lightningfastspeech2_amd.weights import synth_inputs, synth_state_dict
+    p = StochasticDurationPredictor(256, 256, 3, n, R.sdp_state_dict(R.module_config(n), 1), device=DEV)
+    x = torch.randn(B, L, 256, device=DEV)
+    pad = torch.zeros(B, L, dtype=torch.bool, device=DEV)
+    noise = torch.randn(B, 2, L, device=DEV)
+    out = torch.empty(B, L, device=DEV)
+    p(x, pad, noise, out)  # sizes the workspace
+    ws, h, mask = p._ws, p.handle, pad.to(torch.uint8)
+    best = min(timeit(lambda st: lib.fs2_sdp_forward(h, _lib.FS2_F32, x, mask, noise, out, ws, ws.numel(), B, L, st), reps) for _ in range(5))
+    nl = p.launches
+    fl = 2.0 * B * L * 256 * 256 * (5 + 3 * (n - 1)) + 2.0 * B * L * 256 * 32 * (n - 1)
+    print(f"{'stochastic duration predictor':28s} B={B} L={L} flows={n}  {best * 1e6:8.1f} us  {nl} launches, {best * 1e6 / nl:6.1f} us per launch  "
+          f"{fl / 1e9:5.2f} GFLOP of useful 1x1 convs, {fl / best / 1e12:5.1f} TF", flush=True)
+    # the launch it replaces (bf16 operands, as the bf16 engine runs it)
+    H, k, nd = 256, 3, 2
+    xb = torch.randn(B * L, H, device=DEV).to(torch.bfloat16)
+    w = (torch.randn(nd, H, k * H, device=DEV) * (k * H) ** -0.5).to(torch.bfloat16)
+    b, g, be = (torch.randn(nd, H, device=DEV) for _ in range(3))
+    hw = torch.randn(H, device=DEV)
+    pred = torch.empty(B * L, device=DEV)
+    scratch = torch.empty(nd * H * k * H * 2, dtype=torch.uint8, device=DEV)
+    det = min(timeit(lambda st: lib.fs2_op_predictor(BF16, xb, w, b, g, be, hw, 0.1, None, pred, scratch, B, L, H, nd, k, st), reps) for _ in range(5))
+    print(f"{'deterministic duration pred.':28s} B={B} L={L} layers={nd}  {det * 1e6:8.1f} us (incl. {nd} weight-pack launches)", flush=True)
+    for sto in (False, True):
+        cfg = preset("c2")
+        if sto:
+            cfg.duration_stochastic = True
+            cfg.validate()
+        sd = synth_state_dict(cfg, 0)
+        if not sto:  # bench.py's durations: weight 0, bias ln 7 -> 6 frames per phone
+            sd = synth_state_dict(cfg, 0, duration_bias=1.9459101, duration_weight_scale=0.0)
+        m = FastSpeech2(cfg, sd, precision="bf16", device=DEV)
+        inp = synth_inputs(cfg, B, L, seed=3)
+        batch = {"phones": torch.from_numpy(inp["phones"]).to(DEV), "speaker": torch.from_numpy(inp["speaker"]).to(DEV)}
+        forced = torch.full((B, L), 6, dtype=torch.int32, device=DEV)  # the same 1536 frames in both models
+        if sto:
+            batch["duration_noise"] = torch.randn(B, 2, L, device=DEV)
+
+        def step(st):
+            m.forward(batch, force_durations=forced)
+        t = min(timeit(step, max(reps // 2, 3)) for _ in range(5))
+        print(f"{'C2 forward, bf16, T = 1536':28s} duration_stochastic={sto!s:5s}  {t * 1e3:8.3f} ms per batch of {B}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
@@ -371,6 +423,8 @@ def main():
         flash_bwd_case("c2 encoder attention backward", 32, 256, 256, 2, a.reps)
     if a.what in ("bwd",):
         bwd_cases(a.reps)
+    if a.what in ("sdp",):
+        sdp_case(32, 256, 2, a.reps)
     if a.what in ("pred", "all"):
         predictor_case("variance predictor fused", 32, 1536, 5, a.reps)
         predictor_case("duration predictor fused", 32, 256, 2, a.reps)

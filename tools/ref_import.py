@@ -125,7 +125,7 @@ def build_reference_model(cfg, state_dict):
         cfg.stats, list(cfg.variances), list(cfg.variance_levels[:nv]), list(cfg.variance_transforms[:nv]),
         list(cfg.variance_nlayers[:nv]), list(cfg.variance_kernel_size[:nv]), [0.5] * nv,
         cfg.variance_filter_size, cfg.variance_nbins, cfg.variance_depthwise_conv,
-        cfg.duration_nlayers, False, cfg.duration_kernel_size, 0.5, cfg.duration_filter_size,
+        cfg.duration_nlayers, bool(getattr(cfg, "duration_stochastic", False)), cfg.duration_kernel_size, 0.5, cfg.duration_filter_size,
         cfg.duration_depthwise_conv, H, cfg.max_length * cfg.sampling_rate / cfg.hop_length)
     obj.decoder = Enc110([layer(cfg.decoder_head, cfg.decoder_conv_filter_size,
                                 cfg.decoder_kernel_sizes[i], cfg.decoder_depthwise_conv)
