@@ -858,6 +858,73 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
  * fp32 (B, T * up_i, C_i) into a device buffer */
 int fs2_voc_debug_copy(fs2_vocoder* v, int32_t stage, float* dst, void* hip_stream);
 
+/* ================================================================================================
+ * FastDiff vocoder at inference (litfass/third_party/fastdiff/FastDiff.py:91-195, module/modules.py:116-343,
+ * module/util.py:158-237, 305-343): SpeechGenerator(fastdiff=True)'s model.fastdiff_model.inference(mel, N).  A handle of its own in the
+ * pattern of fs2_sdp_*: create validates on the host alone and returns the handle on failure too (fs2_fd_last_error, then destroy).
+ *   Architecture: the reference's defaults ONLY - inner_channels 32, cond_channels 80, upsample_ratios {8, 8, 4}, 4 LVC layers of kernel
+ *    3, kpnet_hidden 64, kpnet_conv 3, step embedding 128 / 512 / 512.  Anything else: fs2_fd_supported answers 0, create FS2_ERR_SHAPE.
+ *   dtype: FS2_F32 (parity mode: fp32 MFMA, accurate exp / tanh) or FS2_BF16 (the packed conv weights, the predicted kernels and biases,
+ *    the conditioning and every 32 / 64-channel stream between launches are stored in bf16, each MFMA operand is rounded to bf16 after its
+ *    input LeakyReLU; accumulation, first_audio_conv, final_conv, the gate, the diffusion state x, the noise, eps, the sampler update and
+ *    the peak scale stay fp32).  Other dtypes: FS2_ERR_ARG.
+ *   fs2_fd_load_weight: host fp32 under the reference's state_dict names after remove_weight_norm ("first_audio_conv.weight",
+ *    "fc_t1.weight", "downsample.0.conv.1.bias", "lvc_blocks.2.kernel_predictor.kernel_conv.weight", "lvc_blocks.0.upsample.weight"
+ *    (Cin, Cout, 2r), "lvc_blocks.1.fc_t.weight", "final_conv.0.weight" ...).  Unknown name / wrong shape: FS2_ERR_WEIGHT.
+ *   fs2_fd_finalize packs (MFMA fragment order; kernel_conv's rows permuted into the order the LVC launch reads) and uploads.
+ *   Every utterance is computed alone, with zero padding at its own ends in every layer (generator.py:163-168); lengths (B) int32 device
+ *    valid frames or NULL (= T).  The bits of an utterance's result do not depend on B, T or its place in the batch: every launch tiles
+ *    an utterance in fs2_fd_tile_rows rows from its own first row.  The batch is walked in chunks of utterances so that the workspace
+ *    stays under a cap: fs2_fd_set_chunk(h, n) limits a chunk to n utterances (0 = the default, as many as fit 2 GiB, at least one);
+ *    fs2_fd_workspace_bytes reports the bytes for (B, T) under the current limit (device, 256-byte aligned; FS2_ERR_NOMEM if short).
+ *   fs2_fd_denoise: one eps evaluation, FastDiff.forward(x, c, ts): x (B, T*hop) fp32, mel (B, T, 80) fp32, step = the (fractional)
+ *    diffusion step, eps (B, T*hop) fp32 out; rows past an utterance's length are left untouched.
+ *   fs2_fd_sample: FastDiff.inference(c, N), ddim off, N in {3, 4, 6, 8} (others FS2_ERR_SHAPE): noise (N, B, T*hop) fp32 -
+ *    noise[0] is x_T, noise[j] (j >= 1) the draw added after reverse step n = N - j (the reference's order of drawing) - and
+ *    wav (B, T*hop) fp32 = x_0 / max|x_0| over the utterance's own samples; samples past its length are left untouched.
+ *   fs2_fd_launches(h, N): kernel launches per chunk of fs2_fd_sample with N steps; N = 0: of fs2_fd_denoise.
+ *   fs2_fd_schedule (host only): beta, alpha-bar, sigma and the mapped fractional steps of N, float32 as the reference computes them.
+ *   All launches go to the caller's stream; nothing is allocated and nothing synchronises on the call path.  Every argument, the
+ *   schedule and the workspace size are judged on the host before the first launch.
+ *   Pieces for tests:
+ *   fs2_fd_predict_kernels: block's kernel predictor on mel + fc_t(step embedding): kernels (B, T, 24576) and bias (B, T, 256) in the
+ *    handle's dtype, kernels in the LVC launch's order: fs2_fd_kernel_index(dtype, layer, in, out, k) is the position of the reference's
+ *    kernels[layer, in, out, k] inside a frame's 24576; bias is in the reference's order (layer * 64 + out).
+ *   fs2_op_lvc: one location-variable convolution with gate and residual (modules.py:214-217): with l = t / hop,
+ *    o[t, n] = bias[l, layer*64 + n] + sum_{c < 32, k < 3} y[t + k - 1, c] * K[l, layer, c, n, k]  (y = 0 outside the utterance only),
+ *    out[t, c] = x[t, c] + sigmoid(o[t, c]) * tanh(o[t, 32 + c]) (+ add[t, c] when add is not NULL); y, x, add, out (B, T*hop, 32),
+ *    kernels, bias as above, all of dtype; hop in {8, 64, 256}; out may alias x.
+ *   fs2_op_fd_dblock: DiffusionDBlock `block` (0, 1, 2: factors 4, 8, 8) of the handle: x (B, S, 32) -> out (B, S / f, 32) in the
+ *    handle's dtype, S = T * 256 / {1, 4, 32}, an utterance's rows = lengths * that; tmp: 3 * B * (S / f) * 32 elements.
+ * ================================================================================================ */
+typedef struct fs2_fd fs2_fd;
+int fs2_fd_supported(int32_t inner_channels, int32_t cond_channels, const int32_t* upsample_ratios, int32_t n_ratios, int32_t lvc_layers,
+                     int32_t lvc_kernel, int32_t kpnet_hidden, int32_t kpnet_conv, int32_t embed_in, int32_t embed_mid, int32_t embed_out);
+int fs2_fd_create(int32_t abi_version, int32_t dtype, int32_t inner_channels, int32_t cond_channels, const int32_t* upsample_ratios,
+                  int32_t n_ratios, int32_t lvc_layers, int32_t lvc_kernel, int32_t kpnet_hidden, int32_t kpnet_conv, int32_t embed_in,
+                  int32_t embed_mid, int32_t embed_out, fs2_fd** out);
+int fs2_fd_destroy(fs2_fd* h);
+const char* fs2_fd_last_error(const fs2_fd* h);
+int fs2_fd_load_weight(fs2_fd* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim);
+int fs2_fd_finalize(fs2_fd* h);
+int32_t fs2_fd_hop(const fs2_fd* h);
+int32_t fs2_fd_tile_rows(const fs2_fd* h);
+int fs2_fd_launches(const fs2_fd* h, int32_t N);
+int fs2_fd_set_chunk(fs2_fd* h, int32_t max_utterances);
+int fs2_fd_workspace_bytes(const fs2_fd* h, int32_t B, int32_t T, size_t* bytes);
+int fs2_fd_schedule(int32_t N, float* beta, float* alpha, float* sigma, float* step);
+int fs2_fd_denoise(fs2_fd* h, const float* x, const float* mel, const int32_t* lengths, float step, float* eps, void* workspace,
+                   size_t workspace_bytes, int32_t B, int32_t T, void* hip_stream);
+int fs2_fd_sample(fs2_fd* h, const float* mel, const int32_t* lengths, const float* noise, int32_t N, float* wav, void* workspace,
+                  size_t workspace_bytes, int32_t B, int32_t T, void* hip_stream);
+int fs2_fd_predict_kernels(fs2_fd* h, int32_t block, const float* mel, const int32_t* lengths, float step, void* kernels, void* bias,
+                           void* workspace, size_t workspace_bytes, int32_t B, int32_t T, void* hip_stream);
+int64_t fs2_fd_kernel_index(int32_t dtype, int32_t layer, int32_t in_channel, int32_t out_channel, int32_t k);
+int fs2_op_lvc(int32_t dtype, int32_t hop, int32_t layer, const void* y, const void* kernels, const void* bias, const void* x,
+               const void* add, void* out, const int32_t* lengths, int32_t B, int32_t T, void* hip_stream);
+int fs2_op_fd_dblock(fs2_fd* h, int32_t block, const void* x, void* out, void* tmp, const int32_t* lengths, int32_t B, int32_t T,
+                     void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@ from .config import Fs2Config, preset  # noqa: F401
 from .weights import state_dict_spec, synth_state_dict, synth_inputs  # noqa: F401
 
 __all__ = ["Fs2Config", "preset", "state_dict_spec", "synth_state_dict", "synth_inputs", "FastSpeech2", "Trainer", "MelAnalyzer",
-           "slaney_mel_basis", "finish_contour", "masked_row_mean"]
+           "slaney_mel_basis", "finish_contour", "masked_row_mean", "FastDiff", "FastDiffConfig"]
 
 
 def __getattr__(name):
@@ -14,6 +14,9 @@ def __getattr__(name):
     if name == "Trainer":  # the training step: forward tape + backward + clip + AdamW / Noam
         from .training import Trainer
         return Trainer
+    if name in ("FastDiff", "FastDiffConfig"):  # the FastDiff vocoder at inference (fs2_fd_*)
+        from . import fastdiff
+        return getattr(fastdiff, name)
     # the analysis front end: waveform -> log-mel + energy + training targets on the device
     if name in ("MelAnalyzer", "slaney_mel_basis", "finish_contour", "masked_row_mean"):
         from . import analysis

@@ -15,6 +15,7 @@ from typing import Dict, List
 import numpy as np
 import torch
 
+from .fastdiff import FastDiff
 from .hifigan import HifiGan
 from .model import FastSpeech2, ForwardPipeline
 
@@ -35,9 +36,15 @@ class SpeechGenerator:
     (generator.py:151-223): ``audios`` is a list of float32 arrays, one per utterance, each the
     int16-quantised generator output rescaled by 1/32767 exactly as the reference does
     (Synthesiser.__call__ then int16_samples_to_float32).  Either object carries its own precision: the reference's mel and the
-    reference's waveform at 16-bit speed are ``FastSpeech2(precision="mixed16")`` with ``HifiGan(precision="fp16")``."""
+    reference's waveform at 16-bit speed are ``FastSpeech2(precision="mixed16")`` with ``HifiGan(precision="fp16")``.
 
-    def __init__(self, model: FastSpeech2, vocoder: HifiGan, g2p_model=None):
+    ``vocoder`` may be a ``FastDiff`` instead (the reference's ``SpeechGenerator(fastdiff=True)``, generator.py:48-57, 166-168:
+    ``model.fastdiff_model.inference(mel, N=4)``): ``audios`` are then the float32 samples themselves, UNQUANTISED
+    (int16_samples_to_float32 passes a float32 tensor through), drawn from torch's CPU generator utterance after utterance as the
+    reference draws them; ``audio_dtype="int16"`` is refused.  The reference adds ``fastdiff_var`` to the mel first
+    (generator.py:167); the engine does not expose it, so this is the mel alone."""
+
+    def __init__(self, model: FastSpeech2, vocoder: "HifiGan | FastDiff", g2p_model=None):
         self.model, self.synth, self.g2p = model, vocoder, g2p_model
         self.model.eval()
 
