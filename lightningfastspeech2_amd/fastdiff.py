@@ -12,6 +12,7 @@ reference adds it to the mel before vocoding; a caller adds it to ``mel`` themse
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -150,28 +151,39 @@ def synth_state_dict(cfg: FastDiffConfig, seed: int = 0) -> Dict[str, np.ndarray
     return sd
 
 
-def inference_schedule(N: int) -> Dict[str, torch.Tensor]:
-    """``beta``, ``alpha`` (the cumulative sqrt(prod(1 - beta))), ``sigma`` and the fractional ``steps`` of FastDiff.inference(N),
-    float32 with the reference's own tensor operations in its order (FastDiff.py:88-89, util.py:187-204, 276-316).
+def _sqrt_rounded(t: torch.Tensor) -> torch.Tensor:
+    """The correctly rounded float32 square root, element by element: the float64 square root (IEEE, through math.sqrt) rounded once to
+    float32 is the correctly rounded float32 root (53 >= 2 x 24 + 2 significand bits)."""
+    return torch.tensor([math.sqrt(v) for v in t.tolist()], dtype=torch.float64).to(torch.float32)
 
-    The engine computes the same in scalar float arithmetic (fs2_fd_schedule) with a correctly rounded sqrtf.  torch's CPU sqrt is not
-    correctly rounded for every input: for N = 3, 4 and 8 the two agree bit for bit (3 and 4 are pinned by a test); for N = 6 the
-    cumulative alpha of step 4 is a near-tie (0.948683411...) that torch rounds the other way, which moves that step's 144.46 by six
-    float32 ulps."""
+
+def inference_schedule(N: int, sqrt=_sqrt_rounded) -> Dict[str, torch.Tensor]:
+    """``beta``, ``alpha`` (the cumulative sqrt(prod(1 - beta))), ``sigma`` and the fractional ``steps`` of FastDiff.inference(N),
+    float32 with the reference's own tensor operations in its order (FastDiff.py:88-89, util.py:187-204, 276-316), except that the
+    three square roots are correctly rounded, as the engine's are (fs2_fd_schedule: the same in scalar float arithmetic with sqrtf);
+    the two agree bit for bit for every N, on every host.
+
+    ``sqrt=torch.sqrt`` gives what the reference computes ON THIS HOST.  torch's CPU sqrt is not correctly rounded, and how far off it
+    is depends on the CPU's vector path: measured, one x86 host rounds 4 of the 1000 training alphas and one near-tie the other way,
+    another 218 of the 1000 and a fifth of all small inputs, which moves the fractional steps of every N by up to 1e-2.  On the host
+    that recorded tests/golden/fastdiff/ the reference's schedules for N = 3, 4 and 8 ARE the correctly rounded ones, bit for bit;
+    for N = 6 the cumulative alpha of step 4 is a near-tie (0.948683411...) that its torch rounded down: the engine's alpha[4] is one
+    float32 ulp above the recorded one, which moves that step's 144.46 down by six float32 ulps (9.2e-5); every other entry agrees
+    bit for bit.  All of this is pinned by tests/test_fastdiff_cpu.py; the N = 6 waveform moves by 2.4e-7 at most."""
     if N not in _BETAS:
         raise ValueError("Reverse step should be 3, 4, 6 or 8 (200 and 1000 are not supported).")
     train = torch.linspace(1e-6, 0.01, 1000)
     alpha_t = 1 - train
     for t in range(1, 1000):
         alpha_t[t] *= alpha_t[t - 1]
-    alpha_t = torch.sqrt(alpha_t)
+    alpha_t = sqrt(alpha_t)
     beta = torch.FloatTensor(_BETAS[N])
     alpha = 1 - beta
     sigma = beta + 0
     for n in range(1, N):
         alpha[n] *= alpha[n - 1]
         sigma[n] *= (1 - alpha[n - 1]) / (1 - alpha[n])
-    alpha, sigma = torch.sqrt(alpha), torch.sqrt(sigma)
+    alpha, sigma = sqrt(alpha), sqrt(sigma)
     steps = []
     for n in range(N):
         a = alpha[n]

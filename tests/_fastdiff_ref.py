@@ -145,6 +145,38 @@ class FastDiffRef:
         return x / x.abs().max()
 
 
+def lvc_op_inputs(hop, lengths, T, seed=None, bf16=False):
+    """y, x, add (B, T*hop, 32), K (B, T, 4, 32, 64, 3) in the reference's order and bias (B, T, 4, 64) of the fs2_op_lvc tests,
+    float32; ``bf16``: rounded to bf16 values, so that they are exact in float32, float64 and on the device alike"""
+    rs = np.random.RandomState(hop if seed is None else seed)
+    B, S = len(lengths), T * hop
+    y, x, add = (rs.standard_normal((B, S, 32)) for _ in range(3))
+    K = rs.standard_normal((B, T, 4, 32, 64, 3)) * (1 / 96) ** 0.5
+    bias = rs.standard_normal((B, T, 4, 64)) * 0.3
+    arrs = [a.astype(np.float32) for a in (y, x, add, K, bias)]
+    return [bf16_round(torch.as_tensor(a)).numpy() for a in arrs] if bf16 else arrs
+
+
+def lvc_op_ref(inputs, b, frames, hop, layer, dtype):
+    """utterance b of the fs2_op_lvc launch in ``dtype``: x + sigmoid(o[:32]) * tanh(o[32:]) without and with ``add``, each
+    (frames * hop, 32) in ``dtype`` (the caller casts: a float32 result is the yardstick AND what a bf16 store would round)"""
+    y, x, add, K, bias = inputs
+    n = frames * hop
+    t = lambda a: torch.as_tensor(a).to(dtype)
+    o = FastDiffRef.lvc(t(y[b, :n].T), t(K[b, :frames, layer]).permute(1, 2, 3, 0), t(bias[b, :frames, layer].T), hop)
+    v = t(x[b, :n].T) + torch.sigmoid(o[:32]) * torch.tanh(o[32:])
+    return v.T.contiguous(), (v + t(add[b, :n].T)).T.contiguous()
+
+
+def bf16_elementwise_excess(got, truth, yard, margin):
+    """The elementwise rule for ONE round-to-nearest bf16 store of a float32 evaluation:
+    |got - truth| <= 2^-8 |truth| + margin * max(yard, 2^-23 max|truth|), 2^-8 = bf16's unit roundoff (8 significand bits), yard = the
+    float32 restatement's own max error.  Returns max over elements of (error - bound): <= 0 passes."""
+    truth = np.asarray(truth, np.float64)
+    bound = 2.0 ** -8 * np.abs(truth) + margin * max(yard, 2.0 ** -23 * float(np.abs(truth).max()))
+    return float((np.abs(np.asarray(got, np.float64) - truth) - bound).max())
+
+
 def fixture_mels(seed, frames):
     """The synthetic mels of the fixtures: standard normal, (frames_i, 80) float32 each, numpy RandomState"""
     rs = np.random.RandomState(seed)

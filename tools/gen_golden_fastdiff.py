@@ -1,7 +1,10 @@
 #!/usr/bin/env python
-"""tests/golden/fastdiff/fastdiff_{ragged,long}.npz: what the REAL FastDiff of the reference returns (build container only, CPU).
+"""tests/golden/fastdiff/fastdiff_{ragged,long,ragged_n68}.npz: what the REAL FastDiff of the reference returns (build container only,
+CPU).
 
-    python tools/gen_golden_fastdiff.py
+    python tools/gen_golden_fastdiff.py [ragged] [long] [ragged_n68]     (no name: all three)
+
+A file whose recorded arrays come out bit for bit as they are on disk is left alone (a zip archive carries the time of writing).
 
 The reference's default FastDiff() with lightningfastspeech2_amd.fastdiff.synth_state_dict(seed) loaded after remove_weight_norm, on
 the synthetic mels of tests/_fastdiff_ref.fixture_mels:
@@ -13,6 +16,10 @@ run (torch.manual_seed, nothing handed in, utterance after utterance), the N = 3
 shapes.  Every output is recorded twice over: float32 as the reference computes it, and the maximum absolute difference to a float64
 run of the same modules on the same inputs (``*_err64``), the yardstick the tests derive their bounds from.  No weights: they are
 regenerated from the seed.
+
+  ragged_n68  the mels, lengths and weights of ``ragged`` under the two longer tabulated schedules: eight handed-in draws per
+              utterance (N = 6 uses the first six), inference(N = 6) and inference(N = 8) with their ``_err64``, and the N = 6 / 8
+              schedules.  A file of its own, so that the two above stay byte-identical.
 
 std_normal is replaced while noise is handed in, and it hands in CLONES: sampling_given_noise_schedule updates its draw in place
 (util.py:211, 228) and would otherwise corrupt the recorded input.
@@ -89,7 +96,7 @@ def run_case(name, mel_seed, frames, sd):
     out = {"mel": np.zeros((B, T, 80), np.float32), "lengths": np.asarray(frames, np.int32), "noise": noise}
     for b, f in enumerate(frames):
         out["mel"][b, :f] = mels[b]
-    sched = {N: FD.inference_schedule(N) for N in (3, 4)}
+    sched = {N: FD.inference_schedule(N, sqrt=torch.sqrt) for N in (3, 4)}  # the reference's own, with this host's torch.sqrt
     eps_steps = [float(sched[4]["steps"][2]), float(sched[4]["steps"][3])]
     out["eps_steps"] = np.asarray(eps_steps, np.float32)
     res = {k: np.zeros((B, S), np.float32) for k in ("eps_0", "eps_1", "wav_n4", "wav_n3", "wav_seeded")}
@@ -129,27 +136,98 @@ def run_case(name, mel_seed, frames, sd):
     for N in (3, 4):
         for k, v in sched[N].items():
             out[f"sched{N}_{k}"] = v.numpy()
-    # the schedule as the reference's own sampler derives it (util.py:187-204), against inference_schedule
-    import litfass.third_party.fastdiff.module.util as util
-    for N, betas in ((4, [3.2176e-04, 2.5743e-03, 2.5376e-02, 7.0414e-01]), (3, [9.0000e-05, 9.0000e-03, 6.0000e-01])):
-        a = 1 - torch.FloatTensor(betas)
-        for n in range(1, N):
-            a[n] *= a[n - 1]
-        a = torch.sqrt(a)
-        steps = torch.FloatTensor([util.map_noise_scale_to_time_step(a[n], m32.diffusion_hyperparams["alpha"]) for n in range(N)])
-        assert torch.equal(steps, sched[N]["steps"]) and torch.equal(a, sched[N]["alpha"]), (N, steps, sched[N]["steps"])
+    check_schedules(m32, sched, {4: [3.2176e-04, 2.5743e-03, 2.5376e-02, 7.0414e-01], 3: [9.0000e-05, 9.0000e-03, 6.0000e-01]})
     meta = {"weight_seed": WEIGHT_SEED, "run_seed": RUN_SEED, "mel_seed": mel_seed, "frames": frames,
             "config": {k: getattr(FD.FastDiffConfig(), k) for k in FD.FastDiffConfig.__dataclass_fields__},
             "state_dict": {k: list(v.shape) for k, v in m32.state_dict().items()},
             "eps_std": [float(res["eps_0"][b, :f * 256].std()) for b, f in enumerate(frames)]}
     out["meta"] = np.asarray(json.dumps(meta))
+    save(name, out)
+    print(name, {k: f"{v:.2e}" for k, v in err.items()}, "eps std", meta["eps_std"])
+
+
+def check_schedules(m32, sched, betas):
+    """the schedule as the reference's own sampler derives it (util.py:187-204), against inference_schedule(N, sqrt=torch.sqrt).  The
+    recorded schedules are this host's: torch's CPU sqrt is not correctly rounded and differs between CPUs (inference_schedule's
+    docstring), so regenerate on the host that recorded the committed files, or expect sched*_ and the waveforms to move."""
+    import litfass.third_party.fastdiff.module.util as util
+    for N, b in betas.items():
+        a = 1 - torch.FloatTensor(b)
+        for n in range(1, N):
+            a[n] *= a[n - 1]
+        a = torch.sqrt(a)
+        steps = torch.FloatTensor([util.map_noise_scale_to_time_step(a[n], m32.diffusion_hyperparams["alpha"]) for n in range(N)])
+        assert torch.equal(steps, sched[N]["steps"]) and torch.equal(a, sched[N]["alpha"]), (N, steps, sched[N]["steps"])
+
+
+def save(name, out):
     os.makedirs(OUT_DIR, exist_ok=True)
     path = os.path.join(OUT_DIR, f"fastdiff_{name}.npz")
+    if os.path.exists(path):
+        old = np.load(path)
+        if sorted(old.files) == sorted(out) and all(
+                old[k].dtype == np.asarray(v).dtype and old[k].shape == np.asarray(v).shape and old[k].tobytes() == np.asarray(v).tobytes()
+                for k, v in out.items()):
+            print(name, "unchanged: file left as it is")
+            return
     np.savez_compressed(path, **out)
-    print(name, os.path.getsize(path), "bytes", {k: f"{v:.2e}" for k, v in err.items()}, "eps std", meta["eps_std"])
+    print(name, os.path.getsize(path), "bytes written")
+
+
+@torch.no_grad()
+def run_n68(sd):
+    """ragged_n68: the ragged utterances through the reference's inference(N = 6) and inference(N = 8), noise handed in"""
+    mel_seed, frames = CASES["ragged"]
+    m32, ref, _ = reference_model(sd)
+    m64, _, emb64 = reference_model(sd, double=True)
+    mels = R.fixture_mels(mel_seed, frames)
+    B, T = len(frames), max(frames)
+    S = T * 256
+    rs = np.random.RandomState(mel_seed + 200)
+    noise = np.zeros((8, B, S), np.float32)
+    for b, f in enumerate(frames):
+        noise[:, b, :f * 256] = rs.standard_normal((8, f * 256)).astype(np.float32)
+    out = {"mel": np.zeros((B, T, 80), np.float32), "lengths": np.asarray(frames, np.int32), "noise": noise}
+    for b, f in enumerate(frames):
+        out["mel"][b, :f] = mels[b]
+    sched = {N: FD.inference_schedule(N, sqrt=torch.sqrt) for N in (6, 8)}  # the reference's own, with this host's torch.sqrt
+    check_schedules(m32, sched, {N: FD._BETAS[N] for N in (6, 8)})
+    saved_emb = ref.calc_diffusion_step_embedding
+    err = {}
+    for N in (6, 8):
+        wav = np.zeros((B, S), np.float32)
+        err[N] = 0.0
+        for b, f in enumerate(frames):
+            n = f * 256
+            c = torch.as_tensor(mels[b])  # (frames, 80), as generator.py:164-168 hands it over
+            draws = [torch.as_tensor(noise[j, b, :n]) for j in range(N)]
+            with HandIn(ref, torch.float32) as h:
+                h.queue = list(draws)
+                w32 = m32.inference(c, N=N)
+                assert not h.queue
+            with HandIn(ref, torch.float64) as h:
+                h.queue = list(draws)
+                ref.calc_diffusion_step_embedding = emb64
+                w64 = m64.inference(c.double(), N=N)
+                ref.calc_diffusion_step_embedding = saved_emb
+                assert not h.queue
+            wav[b, :n] = w32.numpy()
+            err[N] = max(err[N], float((w32.double() - w64).abs().max()))
+        out[f"wav_n{N}"] = wav
+        out[f"wav_n{N}_err64"] = np.float64(err[N])
+        for k, v in sched[N].items():
+            out[f"sched{N}_{k}"] = v.numpy()
+    meta = {"weight_seed": WEIGHT_SEED, "mel_seed": mel_seed, "noise_seed": mel_seed + 200, "frames": frames}
+    out["meta"] = np.asarray(json.dumps(meta))
+    save("ragged_n68", out)
+    print("ragged_n68", {f"wav_n{N}": f"{v:.2e}" for N, v in err.items()})
 
 
 if __name__ == "__main__":
+    names = sys.argv[1:] or list(CASES) + ["ragged_n68"]
     sd = FD.synth_state_dict(FD.FastDiffConfig(), WEIGHT_SEED)
-    for name, (seed, frames) in CASES.items():
-        run_case(name, seed, frames, sd)
+    for name in names:
+        if name == "ragged_n68":
+            run_n68(sd)
+        else:
+            run_case(name, *CASES[name], sd)
