@@ -93,7 +93,10 @@ __device__ inline float half_sum(float x) {
 // (small terms first; the dropped lo*lo is 2^-16 of the product), P split the same way in registers.  Softmax, running max, the
 // denominator and O stay fp32.  Against the fp32-MFMA form of this kernel (32x32x2, 1/16 of the bf16 rate): 3/16 of the matrix
 // time; the decoder launch at C2 went 714 us -> see profiles/HISTORY.md §5.
-template <typename T, int D, int NW, bool X3 = false>
+// TR (the training path, bf16: lse2 is handed to a backward that recomputes P from the UNSCALED q): Q enters the MFMA as it is and
+// the fp32 scores are scaled afterwards, one fma per score - rounding q log2(e)/sqrt(d) to bf16 moved lse2 by 1e-4 .. 1e-1 log2 units
+// from the log-sum-exp of the scores the backward forms (profiles/attention_train.md)
+template <typename T, int D, int NW, bool X3 = false, bool TR = false>
 __global__ __launch_bounds__(NW * 64, (sizeof(T) == 2 && D == 128) ? 2 : 1) void attention_kernel(AttnArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)  // buffer-resource builtins exist in the device pass only
     constexpr int KVB = sizeof(T) == 2 ? 64 : 32;      // keys per tile
@@ -215,8 +218,10 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 2 && D == 128) ? 2 : 1) void
                 for (int e = 0; e < Vec16<T>::N; ++e) r[e] = f[e] - g[e];
                 qfl[c] = Vec16<T>::pack(r);
             } else {
+            if constexpr (!TR) {
 #pragma unroll
             for (int e = 0; e < Vec16<T>::N; ++e) f[e] *= p.scale_log2e;
+            }
             qf[c] = Vec16<T>::pack(f);
             }
         }
@@ -254,7 +259,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 2 && D == 128) ? 2 : 1) void
     #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
     #pragma unroll
-                for (int r = 0; r < 16; ++r) sacc[kb][r] = m_init;  // accumulate (s - m) directly
+                for (int r = 0; r < 16; ++r) sacc[kb][r] = TR ? 0.f : m_init;  // accumulate (s - m) directly
             // chunk-outer / key-block-inner: consecutive MFMAs hit DIFFERENT accumulators, so the
             // accumulate latency of one chain hides under the other
             {   // rolling prefetch: PD K fragments are in flight ahead of the MFMA that consumes them, so a
@@ -282,6 +287,12 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 2 && D == 128) ? 2 : 1) void
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
+            }
+            if constexpr (TR) {  // raw q . k -> s log2(e)/sqrt(d) - m_eff, in fp32
+    #pragma unroll
+                for (int kb = 0; kb < NKB; ++kb)
+    #pragma unroll
+                    for (int r = 0; r < 16; ++r) sacc[kb][r] = __builtin_fmaf(sacc[kb][r], p.scale_log2e, m_init);
             }
             // ---- key-padding mask (only tiles that contain a padded key pay for it) ----
             const unsigned long long full = KVB == 64 ? ~0ull : 0xffffffffull;
@@ -846,6 +857,13 @@ static int launch_td(const AttnArgs& a, hipStream_t stream) {
     // (192-query / 6-wave workgroups - 512 of them for the C2 decoder, two per CU, a third less K/V streamed - need three
     // waves per SIMD, i.e. <= 168 VGPRs; this kernel holds 234 (O^T 64, S^T 32, Q 32, K/V/P fragments 56 ...) and with the cap
     // spills 84 of them: 195 us against 101 us for the 128-query form.  Measured r02, removed.)
+    if constexpr (std::is_same<T, bf16>::value && D == 128) {
+        if (a.lse2) {  // the training path: scores scaled in fp32 (TR)
+            if (blocks4 >= 512) hipLaunchKernelGGL((attention_kernel<T, D, 4, false, true>), dim3(((a.S + 127) / 128) * BH8), dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((attention_kernel<T, D, 2, false, true>), dim3(((a.S + 63) / 64) * BH8), dim3(128), 0, stream, a);
+            return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
+        }
+    }
     if (blocks4 >= 512) {
         hipLaunchKernelGGL((attention_kernel<T, D, 4>), dim3(((a.S + 127) / 128) * BH8), dim3(256), 0, stream, a);
     } else {

@@ -128,7 +128,10 @@ struct PipeState {
 // cycles per item.
 constexpr float kBound = 0x1p100f, kLow = 0x1p-100f;
 
-template <int NQB, bool ACC>
+// TRAIN (lse2 is handed to a backward that recomputes P from the UNSCALED q): Q enters the MFMA as it is, the chains start from 0
+// and a unit forms exp2(s log2(e)/sqrt(d) - reference) with one fp32 fma per score - rounding q log2(e)/sqrt(d) to bf16 moved lse2
+// by 1e-4 .. 1e-1 log2 units from the log-sum-exp of the scores the backward forms (profiles/attention_train.md)
+template <int NQB, bool ACC, bool TRAIN>
 __device__ __forceinline__ bool run_item(const AttnArgs& p, unsigned char* smem, int bh, int q0, int wave, int lane) {
     static_assert(NQB != 3 || ACC, "96 queries per wave need the whole register file");
     constexpr int NQR = NQB == 3 ? 2 : NQB;  // query blocks whose Q fragments stay in registers
@@ -247,7 +250,7 @@ __device__ __forceinline__ bool run_item(const AttnArgs& p, unsigned char* smem,
             float f[8];
             Vec16<bf16>::unpack(qraw[qb][c], f);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] *= p.scale_log2e;
+            for (int e = 0; e < 8; ++e) f[e] *= TRAIN ? 1.f : p.scale_log2e;
             const uint4 pk = Vec16<bf16>::pack(f);
             if (qb < NQR) {
                 qf[qb < NQR ? qb : 0][c] = u32x4_t{pk.x, pk.y, pk.z, pk.w};
@@ -276,8 +279,8 @@ __device__ __forceinline__ bool run_item(const AttnArgs& p, unsigned char* smem,
     auto unit = [&](f32x16_t (&S)[NQB], uint32_t (&P)[NQB][8], int u) {
         if (kProbe & 1) return;
         const int k = u / NQB, qb = u % NQB;
-        const float e0 = __builtin_amdgcn_exp2f(S[qb][2 * k]);
-        const float e1 = __builtin_amdgcn_exp2f(S[qb][2 * k + 1]);
+        const float e0 = __builtin_amdgcn_exp2f(TRAIN ? __builtin_fmaf(S[qb][2 * k], p.scale_log2e, -st.mref[qb]) : S[qb][2 * k]);
+        const float e1 = __builtin_amdgcn_exp2f(TRAIN ? __builtin_fmaf(S[qb][2 * k + 1], p.scale_log2e, -st.mref[qb]) : S[qb][2 * k + 1]);
         st.lsum[qb][0] += e0;
         st.lsum[qb][1] += e1;
         P[qb][k] = pack_bf16x2(e0, e1);
@@ -498,7 +501,7 @@ __device__ __forceinline__ bool run_item(const AttnArgs& p, unsigned char* smem,
         for (int qb = 0; qb < NQB; ++qb) {
             st.mref[qb] = pass == 0 ? 0.f : st.mnext[qb];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) st.minit[qb][r] = -st.mref[qb];
+            for (int r = 0; r < 16; ++r) st.minit[qb][r] = TRAIN ? 0.f : -st.mref[qb];
 #pragma unroll
             for (int nd = 0; nd < 4; ++nd)
 #pragma unroll
@@ -617,7 +620,7 @@ __device__ __forceinline__ bool run_item(const AttnArgs& p, unsigned char* smem,
     return false;
 }
 
-template <int NQBMAX>
+template <int NQBMAX, bool TRAIN>
 __global__ __launch_bounds__(256, NQBMAX >= 2 ? 1 : 2) void attention_pipe_kernel(AttnArgs p, int nu, int U) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(32768))) unsigned char smem[5 * kTileB + (NQBMAX == 3 ? 32768 : 0)];
@@ -632,19 +635,19 @@ __global__ __launch_bounds__(256, NQBMAX >= 2 ? 1 : 2) void attention_pipe_kerne
         if constexpr (NQBMAX == 3) {
             if (!(kProbe & 128) && uu + 3 <= nu && u + 3 <= u1) {
                 // 384 queries, 96 per wave, one pass; a row outside the reference-free range sends the three units to the paths below
-                if (run_item<3, true>(p, smem, bh, uu * 128, wave, lane)) {
-                    run_item<2, true>(p, smem, bh, uu * 128, wave, lane);
-                    run_item<1, true>(p, smem, bh, (uu + 2) * 128, wave, lane);
+                if (run_item<3, true, TRAIN>(p, smem, bh, uu * 128, wave, lane)) {
+                    run_item<2, true, TRAIN>(p, smem, bh, uu * 128, wave, lane);
+                    run_item<1, true, TRAIN>(p, smem, bh, (uu + 2) * 128, wave, lane);
                 }
                 u += 3;
                 continue;
             }
         }
         if (NQBMAX >= 2 && !(kProbe & 128) && uu + 2 <= nu && u + 2 <= u1) {
-            run_item<2, true>(p, smem, bh, uu * 128, wave, lane);
+            run_item<2, true, TRAIN>(p, smem, bh, uu * 128, wave, lane);
             u += 2;
         } else {
-            run_item<1, NQBMAX >= 2>(p, smem, bh, uu * 128, wave, lane);
+            run_item<1, NQBMAX >= 2, TRAIN>(p, smem, bh, uu * 128, wave, lane);
             u += 1;
         }
     }
@@ -666,13 +669,13 @@ int launch_attention_pipe(const AttnArgs& a, int variant, hipStream_t stream) {
     const int nu = (a.S + 127) / 128;
     const long long U = (long long)a.B * a.heads * nu;
     if (U > 0x7fffffffll) return FS2_ERR_SHAPE;
-    if (variant == 3) {
-        hipLaunchKernelGGL((attention_pipe_kernel<3>), dim3(256), dim3(256), 0, stream, a, nu, (int)U);
-    } else if (variant == 2) {
-        hipLaunchKernelGGL((attention_pipe_kernel<2>), dim3(256), dim3(256), 0, stream, a, nu, (int)U);
-    } else {
-        hipLaunchKernelGGL((attention_pipe_kernel<1>), dim3(512), dim3(256), 0, stream, a, nu, (int)U);
-    }
+#define FS2_AP(NQ, GRID) \
+    if (a.lse2) hipLaunchKernelGGL((attention_pipe_kernel<NQ, true>), dim3(GRID), dim3(256), 0, stream, a, nu, (int)U); \
+    else hipLaunchKernelGGL((attention_pipe_kernel<NQ, false>), dim3(GRID), dim3(256), 0, stream, a, nu, (int)U)
+    if (variant == 3) { FS2_AP(3, 256); }
+    else if (variant == 2) { FS2_AP(2, 256); }
+    else { FS2_AP(1, 512); }
+#undef FS2_AP
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
