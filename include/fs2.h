@@ -290,10 +290,34 @@ int fs2_profile_read(fs2_engine* e, int32_t kernel_class, double* total_ms, int6
 int fs2_op_set_gemm_variant(int32_t variant);
 /* The two vocoder knobs below are PER CALLING THREAD, like fs2_op_set_gemm_variant: fs2_voc_synthesize reads the switches of the thread
  * that calls it - a value set on the main thread does not reach a vocoder driven from a pipeline / executor worker thread (set it there).
- * tuning knob: cap (KiB) on the LDS operand slab of a vocoder conv workgroup; 0 = built-in heuristic */
+ * tuning knob: cap (KiB) on the LDS operand slab of a vocoder conv workgroup: the conv kernel takes the tallest of its tile heights
+ * (14, 8, 4, 2 sixteen-row fragments per wave) whose slab fits; the shortest is taken up to the 150 KiB a workgroup can have whatever the
+ * cap says.  0 = built-in heuristic (110 KiB), 1..150 = that cap; anything else FS2_ERR_ARG (the knob is left as it was). */
 int fs2_op_set_vocoder_lds_limit(int32_t kib);
-/* A/B knob: 1 (default) = whole resblocks of the 32/64-channel stages as one LDS-resident launch, 0 = conv by conv */
+/* A/B knob: which resblocks of the 32 / 64 / 128-channel stages run on LDS-resident tiles (vocoder_resblock.hip) and in which form.
+ * A form is 100 * waves + sixteen-row fragments per wave: 408 = 4 waves on <= 76 KiB (two workgroups per CU), 808 / 804 = 8 waves on
+ * <= 150 KiB at full / half height; a form is taken only while at least 80 % (408: 85 %) of its rows are outside the halo.
+ *   0        conv by conv everywhere: no resident launch
+ *   1        (default) a whole block in one launch where taps * channels <= 224, pair by pair otherwise; 408 first, then 808, then 804;
+ *            between two resident launches, and behind the upsampler of a stage whose every pair is resident, the stream is stored
+ *            as LeakyReLU(x)
+ *   2        as 1, pairs only: never a whole block per launch
+ *   4        as 1 without 408: the 8-wave forms only
+ *   7        as 1 without the taps * channels <= 224 rule: a whole block per launch wherever it fits
+ *   9        as 1 with every stream between launches stored raw
+ *   50..100  as 1 with that percentage in place of 408's 85 (1 is the same as 85)
+ * Anything else (negatives, 3, 5, 6, 8, 10..49, above 100) is FS2_ERR_ARG and leaves the knob as it was. */
 int fs2_op_set_vocoder_fused_resblock(int32_t on);
+/* The two choices the vocoder engine makes per layer, as pure shape functions (host only, no device needed); both read the calling
+ * thread's two knobs above.  dtype: FS2_F32, FS2_BF16 or FS2_F16.
+ * fs2_op_vocoder_resblock_form: the form (408 / 808 / 804, above) a whole block (npairs = 3, dilations[0..2]) or one (c1, c2) pair
+ *   (npairs = 1, dilations[0]) of `channels` channels and `taps` taps runs in; 0 = not on resident tiles; negative = bad argument.
+ * fs2_op_vocoder_conv_tile: the tile height (14 / 8 / 4 / 2) of the conv kernel for a layer of n output and cin input channels
+ *   (shift != 0: the two tap windows of a transposed conv; post != 0: conv_post), 0 = no slab fits; *cin_pad (may be NULL) receives the
+ *   padded channel stride: 32 / 64 / 128 / 256 / 512 run a compile-time-stride build, anything else the runtime-stride one. */
+int32_t fs2_op_vocoder_resblock_form(int32_t dtype, int32_t channels, int32_t taps, const int32_t* dilations, int32_t npairs);
+int32_t fs2_op_vocoder_conv_tile(int32_t dtype, int32_t n, int32_t cin, int32_t taps, int32_t dil, int32_t shift, int32_t post,
+                                 int32_t* cin_pad);
 int fs2_op_gemm(int32_t dtype, int32_t out_dtype, const void* x, const void* w, const float* bias, void* c,
                 int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t relu, void* hip_stream);
 /* c = dropout(relu(x w^T + bias)) with fs2_op_dropout's mask over the (M, N) product in the store (the FFN's hidden tensor in training
@@ -857,6 +881,16 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
 /* parity tap: copy stage output `stage` (0 = conv_pre, i = after upsample stage i) of the last call as
  * fp32 (B, T * up_i, C_i) into a device buffer */
 int fs2_voc_debug_copy(fs2_vocoder* v, int32_t stage, float* dst, void* hip_stream);
+/* Which kernel instantiation every launch of the last fs2_voc_synthesize was, in launch order (host only; written by the launchers
+ * where they pick the instantiation).  Returns the number of launches and copies the first min(count, cap) codes to `codes` (host
+ * memory; may be NULL with cap 0); negative = bad argument.  A code, from bit 0:
+ *   bit 0        0 = vocoder_conv_kernel<T, MI16, CP>, 1 = vocoder_resblock_kernel<T, MI16, CH, NW, MID>
+ *   bits 1-3     T as FS2_F32 / FS2_BF16 / FS2_F16
+ *   conv:        bits 4-7 MI16 (14 / 8 / 4 / 2); bits 8-17 CP (0 = the runtime-stride build); bit 18 the input is the fp32 mel (conv_pre);
+ *                bit 19 conv_post; bit 20 two tap windows (a transposed conv)
+ *   resblock:    bits 4-13 the form 100 * NW + MI16 (408 / 808 / 804); bits 14-21 CH; bits 22-23 pairs in the launch (3 / 1);
+ *                bit 24 MID (the result is stored activated); bit 25 the input stream is stored activated */
+int32_t fs2_voc_last_launches(const fs2_vocoder* v, int32_t* codes, int32_t cap);
 
 /* ================================================================================================
  * FastDiff vocoder at inference (litfass/third_party/fastdiff/FastDiff.py:91-195, module/modules.py:116-343,

@@ -145,11 +145,15 @@ int fs2_op_masked_loss(const float* pred, const void* truth, int32_t truth_kind,
 }
 
 int fs2_op_set_vocoder_fused_resblock(int32_t on) {
+    // the values voc_resblock_mi16 and fs2_voc_synthesize give a meaning to (include/fs2.h)
+    const bool defined = on == 0 || on == 1 || on == 2 || on == 4 || on == 7 || on == 9 || (on >= 50 && on <= 100);
+    if (!defined) return FS2_ERR_ARG;
     fs2::op_tuning().voc_fused_resblock = on;
     return FS2_OK;
 }
 
 int fs2_op_set_vocoder_lds_limit(int32_t kib) {
+    if (kib < 0 || kib > 150) return FS2_ERR_ARG;  // 150 KiB: the most a workgroup's slab can have
     fs2::op_tuning().voc_lds_limit = kib;
     return FS2_OK;
 }

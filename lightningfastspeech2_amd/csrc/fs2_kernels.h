@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/fs2.h"
 
 namespace fs2 {
@@ -35,7 +37,7 @@ struct Tuning {
     int colsum_fused = 0;      // column sums in one launch (device-scope fences: slower) / two
     int bgemm_full = 1, bgemm_xcd = 1, bgemm_tn256 = 1;
     int voc_lds_limit = 0;     // KiB cap on a vocoder conv workgroup's slab; 0 = heuristic
-    int voc_fused_resblock = 1;
+    int voc_fused_resblock = 1;  // resident resblock forms: 0, 1, 2, 4, 7, 9, 50..100 (fs2_op_set_vocoder_fused_resblock, include/fs2.h)
     unsigned long long gen = 0;  // bumped by every accepted change: part of an engine's hipGraph keys
 };
 Tuning& op_tuning();                       // the calling thread's (capi_ops.hip)
@@ -305,9 +307,23 @@ int launch_soft_dtw_grad(const SoftDtwArgs& a, float* grad_x, void* scratch, siz
 size_t masked_loss_ws_bytes();
 int launch_masked_loss(const LossArgs& a, hipStream_t stream);
 int voc_resblock_mi16(const VocResblockArgs& a, int dtype);  // 0 = shape not covered
-int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t stream);
+// launched (both launchers; may be null): the code of the instantiation that was launched, as fs2_voc_last_launches documents it
+// (include/fs2.h); written by the function that names the template arguments, left alone where nothing is launched
+int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t stream, int32_t* launched = nullptr);
 int voc_steps_padded(int taps, int cin_pad, int dtype);
-int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream);
+int voc_pick_mi16(const VocConvArgs& a, int esz, size_t* smem);  // rows per wave (x16) this layer's slab leaves room for; 0 = none
+int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream, int32_t* launched = nullptr);
+struct bf16;
+struct f16;  // fs2_common.h
+template <typename T> constexpr int voc_dtype_of() {  // the storage dtype a vocoder kernel's T stands for
+    return std::is_same<T, float>::value ? FS2_F32 : std::is_same<T, f16>::value ? FS2_F16 : FS2_BF16;
+}
+inline int32_t voc_conv_code(int dtype, int mi16, int cp, const VocConvArgs& a) {
+    return (int32_t)(dtype << 1 | mi16 << 4 | cp << 8 | (a.in_fp32 ? 1 : 0) << 18 | (a.post ? 1 : 0) << 19 | (a.shift_from ? 1 : 0) << 20);
+}
+inline int32_t voc_resblock_code(int dtype, int form, int ch, const VocResblockArgs& a, bool mid) {
+    return (int32_t)(1 | dtype << 1 | form << 4 | ch << 14 | a.npairs << 22 | (mid ? 1 : 0) << 24 | (a.x_act ? 1 : 0) << 25);
+}
 
 struct ConvertArgs {
     const void* src;

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(512) void vocoder_conv_kernel(VocConvArgs p) {
 // (Tuning::voc_lds_limit: KiB; 0 = heuristic - fs2_op_set_vocoder_lds_limit)
 
 // rows per wave (x16) the slab of this layer leaves room for
-static int voc_pick_mi16(const VocConvArgs& a, int esz, size_t* smem) {
+int voc_pick_mi16(const VocConvArgs& a, int esz, size_t* smem) {
     static const int cand[4] = {14, 8, 4, 2};
     const int WM = 8 / a.wn;
     // One maximal slab per CU leaves a workgroup alone with its fill -> multiply -> store chain; a cap
@@ -353,7 +353,7 @@ static int voc_pick_mi16(const VocConvArgs& a, int esz, size_t* smem) {
 }
 
 template <typename T, int MI16, int CP>
-static int voc_launch_c(const VocConvArgs& a, size_t smem, hipStream_t stream) {
+static int voc_launch_c(const VocConvArgs& a, size_t smem, hipStream_t stream, int32_t* launched) {
     static size_t attr = 0;
     if (smem > attr) {
         if (hipFuncSetAttribute((const void*)vocoder_conv_kernel<T, MI16, CP>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -366,18 +366,19 @@ static int voc_launch_c(const VocConvArgs& a, size_t smem, hipStream_t stream) {
     const int ntiles = a.post ? 1 : (a.n + a.wn * 32 - 1) / (a.wn * 32);
     hipLaunchKernelGGL((vocoder_conv_kernel<T, MI16, CP>), dim3((unsigned)(tiles * a.B), (unsigned)ntiles), dim3(512), smem,
                        stream, a);
+    if (launched) *launched = voc_conv_code(voc_dtype_of<T>(), MI16, CP, a);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
 template <typename T, int MI16>
-static int voc_launch_t(const VocConvArgs& a, size_t smem, hipStream_t stream) {
+static int voc_launch_t(const VocConvArgs& a, size_t smem, hipStream_t stream, int32_t* launched) {
     switch (a.cin_pad) {  // the V1 / V2 / V3 generators' widths; anything else takes the runtime-stride build
-        case 32: return voc_launch_c<T, MI16, 32>(a, smem, stream);
-        case 64: return voc_launch_c<T, MI16, 64>(a, smem, stream);
-        case 128: return voc_launch_c<T, MI16, 128>(a, smem, stream);
-        case 256: return voc_launch_c<T, MI16, 256>(a, smem, stream);
-        case 512: return voc_launch_c<T, MI16, 512>(a, smem, stream);
-        default: return voc_launch_c<T, MI16, 0>(a, smem, stream);
+        case 32: return voc_launch_c<T, MI16, 32>(a, smem, stream, launched);
+        case 64: return voc_launch_c<T, MI16, 64>(a, smem, stream, launched);
+        case 128: return voc_launch_c<T, MI16, 128>(a, smem, stream, launched);
+        case 256: return voc_launch_c<T, MI16, 256>(a, smem, stream, launched);
+        case 512: return voc_launch_c<T, MI16, 512>(a, smem, stream, launched);
+        default: return voc_launch_c<T, MI16, 0>(a, smem, stream, launched);
     }
 }
 
@@ -386,7 +387,7 @@ int voc_steps_padded(int taps, int cin_pad, int dtype) {
     return (taps * (cin_pad / ke) + 3) & ~3;
 }
 
-int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream) {
+int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream, int32_t* launched) {
     if (!is_storage_dtype(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32, bf16 or binary16
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
     if (a.wn != 1 && a.wn != 2 && a.wn != 4 && a.wn != 8) return FS2_ERR_SHAPE;
@@ -398,21 +399,21 @@ int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream) {
     const int mi = voc_pick_mi16(a, (int)elem_bytes(dtype), &smem);
     if (!mi) return FS2_ERR_SHAPE;
     if (dtype == FS2_BF16) {
-        if (mi == 14) return voc_launch_t<bf16, 14>(a, smem, stream);
-        if (mi == 8) return voc_launch_t<bf16, 8>(a, smem, stream);
-        if (mi == 4) return voc_launch_t<bf16, 4>(a, smem, stream);
-        return voc_launch_t<bf16, 2>(a, smem, stream);
+        if (mi == 14) return voc_launch_t<bf16, 14>(a, smem, stream, launched);
+        if (mi == 8) return voc_launch_t<bf16, 8>(a, smem, stream, launched);
+        if (mi == 4) return voc_launch_t<bf16, 4>(a, smem, stream, launched);
+        return voc_launch_t<bf16, 2>(a, smem, stream, launched);
     }
     if (dtype == FS2_F16) {  // bf16's tiles, LDS sizes and grids: the two differ in Vec16 / Mma16 only
-        if (mi == 14) return voc_launch_t<f16, 14>(a, smem, stream);
-        if (mi == 8) return voc_launch_t<f16, 8>(a, smem, stream);
-        if (mi == 4) return voc_launch_t<f16, 4>(a, smem, stream);
-        return voc_launch_t<f16, 2>(a, smem, stream);
+        if (mi == 14) return voc_launch_t<f16, 14>(a, smem, stream, launched);
+        if (mi == 8) return voc_launch_t<f16, 8>(a, smem, stream, launched);
+        if (mi == 4) return voc_launch_t<f16, 4>(a, smem, stream, launched);
+        return voc_launch_t<f16, 2>(a, smem, stream, launched);
     }
-    if (mi == 14) return voc_launch_t<float, 14>(a, smem, stream);
-    if (mi == 8) return voc_launch_t<float, 8>(a, smem, stream);
-    if (mi == 4) return voc_launch_t<float, 4>(a, smem, stream);
-    return voc_launch_t<float, 2>(a, smem, stream);
+    if (mi == 14) return voc_launch_t<float, 14>(a, smem, stream, launched);
+    if (mi == 8) return voc_launch_t<float, 8>(a, smem, stream, launched);
+    if (mi == 4) return voc_launch_t<float, 4>(a, smem, stream, launched);
+    return voc_launch_t<float, 2>(a, smem, stream, launched);
 }
 
 }  // namespace fs2

@@ -65,6 +65,7 @@ struct fs2_vocoder {
     size_t ws_bytes = 0;
     std::vector<void*> stage_out;  // x after conv_pre and after each stage
     int lastB = 0, lastT = 0;
+    std::vector<int32_t> launches;  // fs2_voc_last_launches: one code per kernel launch of the last synthesize
 };
 
 namespace {
@@ -97,6 +98,12 @@ int next_pow2(int x) {
     int p = 32;
     while (p < x) p <<= 1;
     return p;
+}
+
+// wave columns of a conv to n channels (n a multiple of 32; conv_post: one column)
+int wave_cols(int n, bool post) {
+    const int n32 = post ? 1 : n / 32;
+    return (n32 % 8 == 0) ? 8 : (n32 % 4 == 0) ? 4 : (n32 % 2 == 0) ? 2 : 1;
 }
 
 // W (n, cin, taps) fp32 host (conv form: out[t] = sum_tap x[t - pad + tap*dil] . W[:, :, tap]) ->
@@ -150,9 +157,8 @@ int pack_layer(fs2_vocoder* v, const std::vector<float>& W, const std::vector<fl
     L->taps = taps;
     L->dil = dil;
     L->pad = pad;
-    const int n32 = post ? 1 : n / 32;
     if (!post && n % 32) return vfail(v, FS2_ERR_SHAPE, "channel count %d is not a multiple of 32", n);
-    L->wn = (n32 % 8 == 0) ? 8 : (n32 % 4 == 0) ? 4 : (n32 % 2 == 0) ? 2 : 1;
+    L->wn = wave_cols(n, post);
     std::vector<float> stage;
     frag_order(v->dt, W, n, cin, L->cin_pad, taps, L->wn, post, &stage);
     VCHK(upload_frags(v, stage, &L->w));
@@ -228,7 +234,9 @@ int run_conv(fs2_vocoder* v, hipStream_t st, const VocLayer& L, const void* x, v
     a.wn = L.wn; a.in_slope = in_slope; a.scale = scale; a.accumulate = accumulate ? 1 : 0;
     a.in_fp32 = in_fp32 ? 1 : 0; a.post = post ? 1 : 0;
     a.shift_from = L.shift_from;
-    const int r = launch_vocoder_conv(a, v->dt, st);
+    int32_t code = -1;
+    const int r = launch_vocoder_conv(a, v->dt, st, &code);
+    if (code >= 0) v->launches.push_back(code);
     if (r != FS2_OK) return vfail(v, r, "vocoder conv launch failed (cin=%d n=%d k=%d dil=%d S=%d)", L.cin, L.n, L.taps, L.dil, S);
     return FS2_OK;
 }
@@ -395,6 +403,7 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
     void* r2 = base + 3 * big;
     v->lastB = B;
     v->lastT = T;
+    v->launches.clear();
 
     VCHK(run_conv(v, st, v->pre, mel, v->stage_out[0], nullptr, lengths, 1, B, T, 1.f, 1.f, false, /*in_fp32=*/true));
     const float inv = 1.0f / (float)c.n_kernels;
@@ -435,7 +444,9 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
                 ra.slope = 0.1f; ra.scale = inv; ra.accumulate = j > 0 ? 1 : 0;
                 ra.x_act = stage_act ? 1 : 0;
                 if (voc_resblock_mi16(ra, v->dt)) {  // the whole block in one launch
-                    const int rr = launch_vocoder_resblock(ra, v->dt, st);
+                    int32_t code = -1;
+                    const int rr = launch_vocoder_resblock(ra, v->dt, st, &code);
+                    if (code >= 0) v->launches.push_back(code);
                     if (rr != FS2_OK) return vfail(v, rr, "fused resblock launch failed (C=%d k=%d)", ra.C, ra.taps);
                     continue;
                 }
@@ -464,7 +475,9 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
                     pa.x_act = (m == 0 ? stage_act : (resident[m - 1] && resident[m] && g_voc_fused_resblock != 9)) ? 1 : 0;
                     pa.out_act = m < 2 && resident[m] && resident[m + 1] && g_voc_fused_resblock != 9;
                     if (resident[m]) {
-                        const int rr = launch_vocoder_resblock(pa, v->dt, st);
+                        int32_t code = -1;
+                        const int rr = launch_vocoder_resblock(pa, v->dt, st, &code);
+                        if (code >= 0) v->launches.push_back(code);
                         if (rr != FS2_OK) return vfail(v, rr, "fused conv pair launch failed (C=%d k=%d)", ra.C, ra.taps);
                     } else {
                         const size_t idx = ((size_t)i * c.n_kernels + j) * 3 + m;
@@ -504,6 +517,37 @@ int fs2_voc_debug_copy(fs2_vocoder* v, int32_t stage, float* dst, void* stream) 
     const int r = launch_convert(a, v->dt, FS2_F32, (hipStream_t)stream);
     if (r != FS2_OK) return vfail(v, r, "convert failed");
     return FS2_OK;
+}
+
+int32_t fs2_voc_last_launches(const fs2_vocoder* v, int32_t* codes, int32_t cap) {
+    if (!v || cap < 0 || (cap > 0 && !codes)) return -FS2_ERR_ARG;
+    const size_t n = v->launches.size();
+    for (size_t i = 0; i < n && i < (size_t)cap; ++i) codes[i] = v->launches[i];
+    return (int32_t)n;
+}
+
+int32_t fs2_op_vocoder_resblock_form(int32_t dtype, int32_t channels, int32_t taps, const int32_t* dilations, int32_t npairs) {
+    if (!is_storage_dtype(dtype) || !dilations || (npairs != 1 && npairs != 3) || channels <= 0 || taps <= 0) return -FS2_ERR_ARG;
+    VocResblockArgs a{};
+    a.C = channels; a.taps = taps; a.wn = channels / 32; a.npairs = npairs;
+    for (int m = 0; m < npairs; ++m) {
+        if (dilations[m] < 1) return -FS2_ERR_ARG;
+        a.dil[m] = dilations[m];
+    }
+    a.tune = &op_tuning();
+    return voc_resblock_mi16(a, dtype);
+}
+
+int32_t fs2_op_vocoder_conv_tile(int32_t dtype, int32_t n, int32_t cin, int32_t taps, int32_t dil, int32_t shift, int32_t post,
+                                 int32_t* cin_pad) {
+    if (!is_storage_dtype(dtype) || n <= 0 || cin <= 0 || taps <= 0 || dil <= 0 || (!post && n % 32)) return -FS2_ERR_ARG;
+    VocConvArgs a{};
+    a.cin = cin; a.cin_pad = next_pow2(cin); a.n = n; a.taps = taps; a.dil = dil;
+    a.wn = wave_cols(n, post != 0); a.post = post ? 1 : 0; a.shift_from = shift ? 32 : 0;
+    a.tune = &op_tuning();
+    if (cin_pad) *cin_pad = a.cin_pad;
+    size_t smem = 0;
+    return voc_pick_mi16(a, (int)elem_bytes(dtype), &smem);
 }
 
 }  // extern "C"

@@ -423,7 +423,9 @@ __global__ __launch_bounds__(NW * 64, 2) void vocoder_resblock_kernel(VocResbloc
     }
 }
 
-// (Tuning::voc_fused_resblock - fs2_op_set_vocoder_fused_resblock: 0 off, 1 auto, 2 pairs only, 4 = full-height 8-wave tiles only)
+// (Tuning::voc_fused_resblock - fs2_op_set_vocoder_fused_resblock: 0 off, 1 auto, 2 pairs only, 4 = 8-wave tiles only, 7 = whole blocks
+// whatever taps * C, 9 = 1 with raw streams between launches (vocoder_engine.hip), 50..100 = 1 with that percentage for the 4-wave
+// form; the list a caller reads is in include/fs2.h, the setter refuses everything else)
 
 static void rb_geom(const VocResblockArgs& a, int nw, int mi16, int* R, int* H, int* G) {
     const int c = (a.taps - 1) / 2;
@@ -475,7 +477,7 @@ int voc_resblock_mi16(const VocResblockArgs& a, int dtype) {
 }
 
 template <typename T, int MI16, int CH, int NW, bool MID>
-static int rb_launch_c(const VocResblockArgs& a, size_t smem, hipStream_t stream) {
+static int rb_launch_c(const VocResblockArgs& a, size_t smem, hipStream_t stream, int32_t* launched) {
     static bool attr = false;
     if (!attr) {
         if (hipFuncSetAttribute((const void*)vocoder_resblock_kernel<T, MI16, CH, NW, MID>,
@@ -489,19 +491,20 @@ static int rb_launch_c(const VocResblockArgs& a, size_t smem, hipStream_t stream
     const int tiles = (a.S + V - 1) / V;
     hipLaunchKernelGGL((vocoder_resblock_kernel<T, MI16, CH, NW, MID>), dim3((unsigned)(tiles * a.B)), dim3(NW * 64), smem,
                        stream, a);
+    if (launched) *launched = voc_resblock_code(voc_dtype_of<T>(), NW * 100 + MI16, CH, a, MID);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
 template <typename T, int MI16, int NW>
-static int rb_launch_t(const VocResblockArgs& a, size_t smem, hipStream_t stream) {
+static int rb_launch_t(const VocResblockArgs& a, size_t smem, hipStream_t stream, int32_t* launched) {
     const bool mid = a.out_act != 0;
     if (mid && (a.npairs != 1 || a.scale != 1.f || a.accumulate)) return FS2_ERR_ARG;
-    if (a.C == 32) return mid ? rb_launch_c<T, MI16, 32, NW, true>(a, smem, stream) : rb_launch_c<T, MI16, 32, NW, false>(a, smem, stream);
-    if (a.C == 64) return mid ? rb_launch_c<T, MI16, 64, NW, true>(a, smem, stream) : rb_launch_c<T, MI16, 64, NW, false>(a, smem, stream);
-    return mid ? rb_launch_c<T, MI16, 128, NW, true>(a, smem, stream) : rb_launch_c<T, MI16, 128, NW, false>(a, smem, stream);
+    if (a.C == 32) return mid ? rb_launch_c<T, MI16, 32, NW, true>(a, smem, stream, launched) : rb_launch_c<T, MI16, 32, NW, false>(a, smem, stream, launched);
+    if (a.C == 64) return mid ? rb_launch_c<T, MI16, 64, NW, true>(a, smem, stream, launched) : rb_launch_c<T, MI16, 64, NW, false>(a, smem, stream, launched);
+    return mid ? rb_launch_c<T, MI16, 128, NW, true>(a, smem, stream, launched) : rb_launch_c<T, MI16, 128, NW, false>(a, smem, stream, launched);
 }
 
-int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t stream) {
+int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t stream, int32_t* launched) {
     if (!is_storage_dtype(dtype)) return FS2_ERR_ARG;  // the vocoder runs in fp32, bf16 or binary16
     if (a.B <= 0 || a.S <= 0) return FS2_OK;
     const int cfg = voc_resblock_mi16(a, dtype);
@@ -509,15 +512,15 @@ int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t str
     const int nw = cfg / 100, mi = cfg % 100;
     const size_t smem = rb_lds_bytes(a, nw, mi, (int)elem_bytes(dtype));
     if (dtype == FS2_BF16) {
-        if (nw == 4) return rb_launch_t<bf16, 8, 4>(a, smem, stream);
-        return mi == 8 ? rb_launch_t<bf16, 8, 8>(a, smem, stream) : rb_launch_t<bf16, 4, 8>(a, smem, stream);
+        if (nw == 4) return rb_launch_t<bf16, 8, 4>(a, smem, stream, launched);
+        return mi == 8 ? rb_launch_t<bf16, 8, 8>(a, smem, stream, launched) : rb_launch_t<bf16, 4, 8>(a, smem, stream, launched);
     }
     if (dtype == FS2_F16) {  // bf16's tiles, LDS sizes and grids
-        if (nw == 4) return rb_launch_t<f16, 8, 4>(a, smem, stream);
-        return mi == 8 ? rb_launch_t<f16, 8, 8>(a, smem, stream) : rb_launch_t<f16, 4, 8>(a, smem, stream);
+        if (nw == 4) return rb_launch_t<f16, 8, 4>(a, smem, stream, launched);
+        return mi == 8 ? rb_launch_t<f16, 8, 8>(a, smem, stream, launched) : rb_launch_t<f16, 4, 8>(a, smem, stream, launched);
     }
-    if (nw == 4) return rb_launch_t<float, 8, 4>(a, smem, stream);
-    return mi == 8 ? rb_launch_t<float, 8, 8>(a, smem, stream) : rb_launch_t<float, 4, 8>(a, smem, stream);
+    if (nw == 4) return rb_launch_t<float, 8, 4>(a, smem, stream, launched);
+    return mi == 8 ? rb_launch_t<float, 8, 8>(a, smem, stream, launched) : rb_launch_t<float, 4, 8>(a, smem, stream, launched);
 }
 
 }  // namespace fs2

@@ -138,6 +138,19 @@ _PRECISIONS = {"bf16": _lib.FS2_BF16, "fp32": _lib.FS2_F32, "fp16": _lib.FS2_F16
 _WAV_KINDS = {"int16": (_lib.FS2_WAV_I16, torch.int16), "float32": (_lib.FS2_WAV_F32, torch.float32)}
 
 
+_DTYPE_NAMES = {v: k for k, v in _PRECISIONS.items()}
+
+
+def decode_launch(code: int) -> tuple:
+    """One code of fs2_voc_last_launches (include/fs2.h) -> ("conv", precision, MI16, CP, in_fp32, post, shift) or
+    ("resblock", precision, form, channels, npairs, out_act, x_act): the template arguments of the kernel that ran and the
+    argument flags that select its paths; precision as HifiGan spells it, flags as bools."""
+    dt = _DTYPE_NAMES[(code >> 1) & 7]
+    if code & 1:
+        return ("resblock", dt, (code >> 4) & 1023, (code >> 14) & 255, (code >> 22) & 3, bool(code >> 24 & 1), bool(code >> 25 & 1))
+    return ("conv", dt, (code >> 4) & 15, (code >> 8) & 1023, bool(code >> 18 & 1), bool(code >> 19 & 1), bool(code >> 20 & 1))
+
+
 def wav_pack(wav: torch.Tensor, lengths: Optional[torch.Tensor], hop: int, dtype: str = "float32",
              out: Optional[torch.Tensor] = None):
     """fs2_op_wav_pack (include/fs2.h) on the current stream: wav (B, T*hop) fp32 device, lengths (B,) int32 device frame counts or
@@ -244,6 +257,16 @@ class HifiGan:
         The frame counts are never read by the host."""
         wav, ld = self._generate(mel, lengths, False)  # the pads are neither read nor written behind it: no memset
         return wav_pack(wav, ld, self.hop, dtype, out)
+
+    def last_launches(self) -> list:
+        """The kernel instantiation of every launch of the last ``synthesize``, in launch order (fs2_voc_last_launches), each as
+        ``decode_launch`` spells it."""
+        n = int(self.lib.fs2_voc_last_launches(self.handle, None, 0))
+        if n < 0:
+            raise RuntimeError("fs2_voc_last_launches failed")
+        codes = (C.c_int32 * max(n, 1))()
+        self.lib.fs2_voc_last_launches(self.handle, codes, n)
+        return [decode_launch(codes[i]) for i in range(n)]
 
     def debug_stage(self, stage: int) -> torch.Tensor:
         B, T = self._last

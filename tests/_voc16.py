@@ -20,8 +20,9 @@ the engine stores them under fs2_op_set_vocoder_fused_resblock(1), the default:
 
 Accumulation is fp32 everywhere (torch's conv1d on fp32 tensors holding 16-bit values).  Parameterised by torch.float32 /
 torch.bfloat16 / torch.float16: with float32 nothing is rounded, the residual is carried instead of recovered and the stage mean
-is the oracle's (sum) / n, so the model IS the oracle, bit for bit (tests/test_hifigan_fp16_cpu.py).  `knob` = 0 / 9 model the
-two other launch forms (conv by conv everywhere / resident tiles with raw streams between launches).
+is the oracle's (sum) / n, so the model IS the oracle, bit for bit (tests/test_hifigan_fp16_cpu.py).  `knob` = any other value of
+fs2_op_set_vocoder_fused_resblock models that launch form: 0 conv by conv everywhere, 9 resident tiles with raw streams between
+launches, 2 / 4 / 7 / 50..100 another set of resident pairs and blocks (`resident_form`) and with it other streams stored activated.
 Per-utterance zero padding follows hifigan_cpu.synthesize: every utterance runs alone on its first lengths[b] frames."""
 import numpy as np
 import torch
@@ -43,20 +44,29 @@ def _rb_lds(C, taps, dils, nw, mi16, esz):
     return ((R + 2 * G) + (R + 2 * ((taps - 1) // 2))) * C * esz
 
 
-def resident(C, taps, dils, knob=1, esz=2):
-    """voc_resblock_mi16 (vocoder_resblock.hip) for a 2-byte type: does this block (3 dilations) / pair (1) run on LDS tiles?"""
-    if not knob or C not in (32, 64, 128) or not taps & 1 or len(dils) not in (1, 3):
-        return False
-    if len(dils) == 3 and taps * C > 224:
-        return False
-    R, H, _ = _rb_geom(C, taps, dils, 4, 8)
-    if _rb_lds(C, taps, dils, 4, 8, esz) <= 76 * 1024 and (R - 2 * H) * 100 >= R * 85:
-        return True
+def resident_form(C, taps, dils, knob=1, esz=2):
+    """voc_resblock_mi16 (vocoder_resblock.hip) restated: the form - 408 / 808 / 804 = 100 * waves + 16-row fragments per wave - this
+    block (3 dilations) / pair (1) runs in on LDS tiles, 0 = conv by conv.  knob: fs2_op_set_vocoder_fused_resblock's values (0 off,
+    1 default, 2 pairs only, 4 no 4-wave form, 7 whole blocks whatever taps * C, 9 = 1 here, 50..100 = the 4-wave form's threshold in
+    percent); esz: bytes per stored element.  tests/test_voc_forms_cpu.py holds it to the library's own picker."""
+    if not knob or (knob == 2 and len(dils) != 1) or C not in (32, 64, 128) or not taps & 1 or len(dils) not in (1, 3):
+        return 0
+    if len(dils) == 3 and taps * C > 224 and knob != 7:
+        return 0
+    if knob != 4:
+        R, H, _ = _rb_geom(C, taps, dils, 4, 8)
+        if _rb_lds(C, taps, dils, 4, 8, esz) <= 76 * 1024 and (R - 2 * H) * 100 >= R * (knob if knob >= 50 else 85):
+            return 408
     for mi in (8, 4):
         R, H, _ = _rb_geom(C, taps, dils, 8, mi)
         if _rb_lds(C, taps, dils, 8, mi, esz) <= 150 * 1024 and (R - 2 * H) * 5 >= R * 4:
-            return True
-    return False
+            return 800 + mi
+    return 0
+
+
+def resident(C, taps, dils, knob=1, esz=2):
+    """does this block (3 dilations) / pair (1) run on LDS tiles?"""
+    return resident_form(C, taps, dils, knob, esz) != 0
 
 
 class _Stream:

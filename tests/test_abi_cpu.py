@@ -299,6 +299,32 @@ def test_knob_setter_rejects_undefined_values(lib):
         assert lib.fs2_op_set_gemm_variant(ok) == FS2_OK, ok
 
 
+def test_vocoder_knob_setters_reject_undefined_values(lib):
+    """fs2_op_set_vocoder_fused_resblock takes the values the engine gives a meaning to (0, 1, 2, 4, 7, 9, 50..100),
+    fs2_op_set_vocoder_lds_limit 0..150 KiB; anything else is FS2_ERR_ARG and leaves the knob as it was (read back through the
+    host-side picker, which reads the calling thread's knobs)."""
+    FS2_OK, FS2_ERR_ARG = _lib.FS2_OK, _lib.FS2_ERR_ARG
+    d = (C.c_int32 * 3)(1, 3, 5)
+    form = lambda: lib.fs2_op_vocoder_resblock_form(_lib.FS2_BF16, 64, 3, d, 3)
+    tile = lambda: lib.fs2_op_vocoder_conv_tile(_lib.FS2_BF16, 256, 256, 11, 5, 0, 0, None)
+    try:
+        assert lib.fs2_op_set_vocoder_fused_resblock(4) == FS2_OK and form() == 808
+        for bad in (-1, -50, 3, 5, 6, 8, 10, 25, 49, 101, 150, 1000, 2 ** 31 - 1, -2 ** 31):
+            assert lib.fs2_op_set_vocoder_fused_resblock(bad) == FS2_ERR_ARG, bad
+            assert form() == 808, bad
+        for ok in (0, 1, 2, 4, 7, 9, 50, 60, 85, 100):
+            assert lib.fs2_op_set_vocoder_fused_resblock(ok) == FS2_OK, ok
+        assert lib.fs2_op_set_vocoder_lds_limit(150) == FS2_OK and tile() == 14
+        for bad in (-1, -150, 151, 152, 1024, 2 ** 31 - 1, -2 ** 31):
+            assert lib.fs2_op_set_vocoder_lds_limit(bad) == FS2_ERR_ARG, bad
+            assert tile() == 14, bad
+        for ok in (0, 1, 12, 76, 110, 149, 150):
+            assert lib.fs2_op_set_vocoder_lds_limit(ok) == FS2_OK, ok
+    finally:
+        assert lib.fs2_op_set_vocoder_fused_resblock(1) == FS2_OK and lib.fs2_op_set_vocoder_lds_limit(0) == FS2_OK
+    assert form() == 408 and tile() == 8
+
+
 def test_library_has_no_mutable_tuning_globals():
     """SURVEY 8b "no global state (one handle per device)" / VERDICT r04 item 6: the A/B switches live in a per-engine / per-thread
     `fs2::Tuning`, not in process-wide `int g_*` variables every engine and pipeline thread reads unsynchronised.  By `nm`: no
