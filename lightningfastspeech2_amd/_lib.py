@@ -12,7 +12,8 @@ import os
 import re
 from types import SimpleNamespace
 
-import torch  # noqa: F401  (must precede the dlopen below)
+import numpy as np
+import torch  # (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FS2_LIB: alternative build of the same ABI (kernel A/B experiments); default = the in-tree library
@@ -159,18 +160,71 @@ def load():
     return lib
 
 
-def check(status: int, engine=None, what: str = "", last_error=None):
+def check(status: int, engine=None, what: str = "", last_error=None, lib=None):
     """Raise on a status other than FS2_OK.  engine = the handle whose message to append; last_error = the name of the
     entry point that returns it, for handles other than the engine's ("fs2_voc_last_error", "fs2_mel_last_error")."""
     if status == FS2_OK:
         return
-    lib = load()
+    lib = lib or load()
     msg = lib.fs2_status_string(status).decode()
     if engine:
         detail = getattr(lib, last_error or "fs2_last_error")(engine).decode()
         if detail:
             msg = f"{msg}: {detail}"
     raise RuntimeError(f"fs2 {what} failed ({status}): {msg}")
+
+
+class Handle:
+    """Base of the five wrappers that own an opaque handle of include/fs2.h.  A subclass names its family (``_prefix``: "fs2",
+    "fs2_voc", "fs2_sdp", "fs2_mel", "fs2_fd" - the base finds ``<prefix>_last_error`` / ``_load_weight`` / ``_finalize`` /
+    ``_destroy`` from it), makes its own ``<prefix>_create`` call into ``self.handle`` and, when anything after that call fails,
+    calls ``close()`` before it re-raises.  ``_label`` and ``_load_what`` only word the RuntimeError of ``_check``."""
+    _prefix = "fs2"
+    _label = ""
+    _load_what = "load_weight({})"
+
+    def __init__(self, lib=None):
+        self.lib = lib or load()
+        self.handle = C.c_void_p()
+        self._ws = None
+
+    def _fn(self, what):
+        return getattr(self.lib, f"{self._prefix}_{what}")
+
+    def _check(self, status, what):
+        check(status, self.handle, self._label + what, f"{self._prefix}_last_error", self.lib)
+
+    def close(self):
+        """Destroy the handle; harmless when called again (or on an object whose constructor never got that far)."""
+        if getattr(self, "handle", None):
+            handle, self.handle = self.handle, C.c_void_p()
+            self._fn("destroy")(handle)  # (fs2_voc_destroy returns void: no result is looked at for any family)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load_weights(self, names, state_dict):
+        """``<prefix>_load_weight`` for every name (tensors and arrays alike go in as contiguous float32), then
+        ``<prefix>_finalize``."""
+        load_weight = self._fn("load_weight")
+        for name in names:
+            v = state_dict[name]
+            if isinstance(v, torch.Tensor):
+                v = v.detach().cpu().float().numpy()
+            a = np.ascontiguousarray(v, dtype=np.float32)
+            shape = (C.c_int64 * a.ndim)(*a.shape)
+            self._check(load_weight(self.handle, name.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim), self._load_what.format(name))
+        self._check(self._fn("finalize")(self.handle), "finalize")
+
+    def _workspace(self, nbytes: int):
+        """The handle's grow-only device workspace (uint8 on ``self.device``), at least ``nbytes`` long."""
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None  # (released before the larger one is asked for)
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
 
 
 def config_to_c(cfg, dtype: int) -> Fs2ConfigC:

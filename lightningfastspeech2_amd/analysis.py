@@ -157,10 +157,11 @@ def masked_row_mean(values: torch.Tensor, counts=None, skip=None) -> torch.Tenso
     return out
 
 
-class MelAnalyzer:
+class MelAnalyzer(_lib.Handle):
     """Waveforms -> {"mel", "mel_lengths", "energy", "energy_lengths"} on the device.  The defaults are ``TTSDataset``'s
     (datasets.py:183-199); ``log="ln", clip=1e-5`` is the HiFi-GAN convention, ``log="none"`` returns the mel itself, unclamped.  ``mel_basis`` (n_mels, n_fft // 2 + 1) replaces
     the built-in :func:`slaney_mel_basis` (which is not pinned against librosa's output, see there)."""
+    _prefix = "fs2_mel"
 
     def __init__(self, sampling_rate: int = 22050, n_fft: int = 1024, win_length: int = 1024, hop_length: int = 256, n_mels: int = 80,
                  fmin: float = 0.0, fmax: Optional[float] = 8000.0, log: str = "log10", clip: float = 1e-6, mel_basis=None,
@@ -170,7 +171,7 @@ class MelAnalyzer:
             raise RuntimeError("the analysis front end runs on an MI355X only (no CPU fallback)")
         if log not in _LOG_KINDS:
             raise ValueError(f"log must be one of {sorted(_LOG_KINDS)}, got {log!r}")
-        self.lib = _lib.load()
+        _lib.Handle.__init__(self)
         self.sampling_rate, self.n_fft, self.win_length, self.hop_length, self.n_mels = sampling_rate, n_fft, win_length, hop_length, n_mels
         self.log, self.clip = log, float(clip)
         if mel_basis is None:
@@ -179,19 +180,22 @@ class MelAnalyzer:
         if basis.shape != (n_mels, n_fft // 2 + 1):
             raise ValueError(f"mel_basis must be {(n_mels, n_fft // 2 + 1)}, got {basis.shape}")
         self.mel_basis = basis
-        self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
             st = self.lib.fs2_mel_create(_lib.FS2_ABI_VERSION, n_fft, win_length, hop_length, n_mels, self.clip, _LOG_KINDS[log],
                                          basis.ctypes.data_as(C.c_void_p), C.byref(self.handle))
         if st != _lib.FS2_OK:  # the handle comes back on failure too, for its message
             try:
-                _lib.check(st, self.handle, "fs2_mel_create", "fs2_mel_last_error")
+                self._check(st, "fs2_mel_create")
             finally:
                 self.close()
         self.tile_frames = int(self.lib.fs2_mel_tile_frames(self.handle))
         self.wada_table = None
         if wada_table is not None:
-            self.set_wada_table(wada_table)
+            try:
+                self.set_wada_table(wada_table)
+            except Exception:
+                self.close()
+                raise
 
     def set_wada_table(self, table, db_lo: float = -20.0):
         """The WADA table ``snr`` looks its statistic up in: g[i] for db_lo + i dB, 2 to 512 finite values (the reference's:
@@ -199,19 +203,8 @@ class MelAnalyzer:
         table = np.ascontiguousarray(table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table, np.float64).reshape(-1)
         with torch.cuda.device(self.device):
             st = self.lib.fs2_mel_set_snr_table(self.handle, table.ctypes.data_as(C.c_void_p), len(table), db_lo)
-        _lib.check(st, self.handle, "fs2_mel_set_snr_table", "fs2_mel_last_error")
+        self._check(st, "fs2_mel_set_snr_table")
         self.wada_table = table
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.fs2_mel_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _batch(self, wav, lengths):
         if isinstance(wav, (list, tuple)):
@@ -252,7 +245,7 @@ class MelAnalyzer:
         with torch.cuda.device(dev):
             st = self.lib.fs2_mel_run(self.handle, wav, lengths, B, S, int(bool(peak_normalize)), mel, T_max, en, Te_max, mel_len, en_len,
                                       ws, ws_bytes, torch.cuda.current_stream(dev))
-        _lib.check(st, self.handle, "fs2_mel_run", "fs2_mel_last_error")
+        self._check(st, "fs2_mel_run")
         return {"mel": mel, "mel_lengths": mel_len, "energy": en, "energy_lengths": en_len}
 
     def targets(self, wavs: Sequence, durations: Sequence, stats: Optional[dict] = None, energy_level: str = "frame",
@@ -304,7 +297,7 @@ class MelAnalyzer:
         with torch.cuda.device(dev):
             st = self.lib.fs2_mel_snr(self.handle, wav, lengths, B, S, int(bool(peak_normalize)), out, Te_max, out_len, ws, ws_bytes,
                                       torch.cuda.current_stream(dev))
-        _lib.check(st, self.handle, "fs2_mel_snr", "fs2_mel_last_error")
+        self._check(st, "fs2_mel_snr")
         return {"snr": out, "snr_lengths": out_len}
 
     def items(self, wavs: Sequence, durations: Sequence, silent: Optional[Sequence] = None, pitch: Optional[Sequence] = None,

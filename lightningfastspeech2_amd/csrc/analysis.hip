@@ -18,14 +18,11 @@
 //      t < T_b; rows past the utterance's count are written as zeros.
 // The order of every sum depends on (t mod TM, bin, mel) only, never on the batch: results are bitwise batch-invariant.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <new>
 #include <vector>
 
-#include "fs2_common.h"
-#include "fs2_kernels.h"
+#include "fs2_host.h"
 
 namespace fs2 {
 
@@ -570,30 +567,22 @@ static size_t mel_lds_bytes(int n_fft, int hop, int tm, int nt) {
 
 using namespace fs2;
 
-struct fs2_mel {
+struct fs2_mel : ErrorBase {
     int n_fft = 0, win = 0, hop = 0, lh = 0, n_mels = 0, log_kind = 0;
     float clip = 0.0f;
     int f_lo = 0, nbt = 0, tm = 0, mt = 0, nt = 0;
     size_t lds = 0;
     MelKernelFn kernel = nullptr;
+    DevAllocs tables, snr_alloc;  // owners of table + btab / of snr_table (replaced whole by fs2_mel_set_snr_table)
     float4* table = nullptr;
     float4* btab = nullptr;
     double* snr_table = nullptr;  // the WADA table (fs2_mel_set_snr_table), snr_k entries for db_lo, db_lo + 1, ...
     int snr_k = 0;
     float snr_db_lo = 0.0f;
     bool ready = false;
-    char err[256] = {0};
 };
 
 namespace {
-
-int mfail(fs2_mel* m, int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(m->err, sizeof(m->err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 size_t mel_ws_need(int B) { return (((size_t)B * sizeof(uint32_t)) + 255) & ~(size_t)255; }
 
@@ -608,21 +597,21 @@ int fs2_mel_create(int32_t abi_version, int32_t n_fft, int32_t win_length, int32
     fs2_mel* m = new (std::nothrow) fs2_mel();
     if (!m) return FS2_ERR_NOMEM;
     *out = m;  // returned even on failure so the caller can read fs2_mel_last_error, then destroy
-    if (abi_version != FS2_ABI_VERSION) return mfail(m, FS2_ERR_ARG, "abi_version %d, this library is %d", abi_version, FS2_ABI_VERSION);
-    if (!mel_basis_host) return mfail(m, FS2_ERR_ARG, "mel_basis is null");
+    if (abi_version != FS2_ABI_VERSION) return m->fail(FS2_ERR_ARG, "abi_version %d, this library is %d", abi_version, FS2_ABI_VERSION);
+    if (!mel_basis_host) return m->fail(FS2_ERR_ARG, "mel_basis is null");
     if (log_kind != FS2_MEL_LOG10 && log_kind != FS2_MEL_LN && log_kind != FS2_MEL_LINEAR)
-        return mfail(m, FS2_ERR_ARG, "log_kind %d is none of FS2_MEL_LOG10, FS2_MEL_LN, FS2_MEL_LINEAR", log_kind);
-    if (!(clip > 0.0f) || !isfinite(clip)) return mfail(m, FS2_ERR_ARG, "clip must be a positive finite number");
-    if (n_fft < 256 || n_fft > 2048 || (n_fft & (n_fft - 1))) return mfail(m, FS2_ERR_SHAPE, "n_fft %d is not a power of two in [256, 2048]", n_fft);
-    if (win_length < 1 || win_length > n_fft) return mfail(m, FS2_ERR_SHAPE, "win_length %d is outside [1, n_fft = %d]", win_length, n_fft);
-    if (hop < 1 || n_fft % hop) return mfail(m, FS2_ERR_SHAPE, "hop %d does not divide n_fft %d", hop, n_fft);
-    if (n_mels < 1 || n_mels > 128) return mfail(m, FS2_ERR_SHAPE, "n_mels %d is outside [1, 128]", n_mels);
+        return m->fail(FS2_ERR_ARG, "log_kind %d is none of FS2_MEL_LOG10, FS2_MEL_LN, FS2_MEL_LINEAR", log_kind);
+    if (!(clip > 0.0f) || !isfinite(clip)) return m->fail(FS2_ERR_ARG, "clip must be a positive finite number");
+    if (n_fft < 256 || n_fft > 2048 || (n_fft & (n_fft - 1))) return m->fail(FS2_ERR_SHAPE, "n_fft %d is not a power of two in [256, 2048]", n_fft);
+    if (win_length < 1 || win_length > n_fft) return m->fail(FS2_ERR_SHAPE, "win_length %d is outside [1, n_fft = %d]", win_length, n_fft);
+    if (hop < 1 || n_fft % hop) return m->fail(FS2_ERR_SHAPE, "hop %d does not divide n_fft %d", hop, n_fft);
+    if (n_mels < 1 || n_mels > 128) return m->fail(FS2_ERR_SHAPE, "n_mels %d is outside [1, 128]", n_mels);
     const int nbins = n_fft / 2 + 1;
     int f_lo = nbins, f_hi = -1;
     for (int i = 0; i < n_mels; ++i)
         for (int f = 0; f < nbins; ++f) {
             const float w = mel_basis_host[(size_t)i * nbins + f];
-            if (!isfinite(w)) return mfail(m, FS2_ERR_ARG, "mel_basis[%d][%d] is not finite", i, f);
+            if (!isfinite(w)) return m->fail(FS2_ERR_ARG, "mel_basis[%d][%d] is not finite", i, f);
             if (w != 0.0f) {
                 f_lo = f < f_lo ? f : f_lo;
                 f_hi = f > f_hi ? f : f_hi;
@@ -636,7 +625,7 @@ int fs2_mel_create(int32_t abi_version, int32_t n_fft, int32_t win_length, int32
     m->nt = (n_mels + 31) / 32;
     for (int tm = 64; tm >= 16 && !m->tm; tm >>= 1)  // the tallest tile whose span fits the CU's LDS
         if (mel_lds_bytes(n_fft, hop, tm, m->nt) <= MEL_LDS_LIMIT) m->tm = tm;
-    if (!m->tm) return mfail(m, FS2_ERR_SHAPE, "n_fft %d with hop %d does not fit a 16-frame tile into LDS", n_fft, hop);
+    if (!m->tm) return m->fail(FS2_ERR_SHAPE, "n_fft %d with hop %d does not fit a 16-frame tile into LDS", n_fft, hop);
     m->mt = m->tm > 32 ? 2 : 1;
     m->lds = mel_lds_bytes(n_fft, hop, m->tm, m->nt);
     m->kernel = mel_kernel_for(m->mt, m->nt);
@@ -649,7 +638,7 @@ int fs2_mel_create(int32_t abi_version, int32_t n_fft, int32_t win_length, int32
         table.resize((size_t)m->nbt * KC * 2 * 64 * 4);
         btab.resize((size_t)m->nbt * 4 * m->nt * 64 * 4);
     } catch (const std::bad_alloc&) {  // no exception crosses the C ABI
-        return mfail(m, FS2_ERR_NOMEM, "out of host memory for the DFT table");
+        return m->fail(FS2_ERR_NOMEM, "out of host memory for the DFT table");
     }
     const double two_pi = 6.283185307179586476925286766559;
     const int left = (n_fft - win_length) / 2;  // torch.stft centres a short window
@@ -674,23 +663,16 @@ int fs2_mel_create(int32_t abi_version, int32_t n_fft, int32_t win_length, int32
                         btab[(((((size_t)bt * 4 + kc) * m->nt + nt) * 64) + lane) * 4 + e] =
                             (f <= f_hi && mel < n_mels) ? mel_basis_host[(size_t)mel * nbins + f] : 0.0f;
                     }
-    if (hipMalloc((void**)&m->table, table.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&m->btab, btab.size() * sizeof(float)) != hipSuccess)
-        return mfail(m, FS2_ERR_HIP, "hipMalloc of the DFT table failed: %s", hipGetErrorString(hipGetLastError()));
-    if (hipMemcpy(m->table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->btab, btab.data(), btab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return mfail(m, FS2_ERR_HIP, "upload of the DFT table failed: %s", hipGetErrorString(hipGetLastError()));
+    FS2_TRY(upload_as(*m, m->tables, table.data(), table.size(), FS2_F32, (void**)&m->table, FS2_ERR_HIP));
+    FS2_TRY(upload_as(*m, m->tables, btab.data(), btab.size(), FS2_F32, (void**)&m->btab, FS2_ERR_HIP));
     if (hipFuncSetAttribute((const void*)m->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds) != hipSuccess)
-        return mfail(m, FS2_ERR_HIP, "cannot reserve %zu bytes of LDS: %s", m->lds, hipGetErrorString(hipGetLastError()));
+        return m->fail(FS2_ERR_HIP, "cannot reserve %zu bytes of LDS: %s", m->lds, hipGetErrorString(hipGetLastError()));
     m->ready = true;
     return FS2_OK;
 }
 
 int fs2_mel_destroy(fs2_mel* m) {
     if (!m) return FS2_ERR_ARG;
-    if (m->table) (void)hipFree(m->table);
-    if (m->btab) (void)hipFree(m->btab);
-    if (m->snr_table) (void)hipFree(m->snr_table);
     delete m;
     return FS2_OK;
 }
@@ -715,21 +697,21 @@ int fs2_mel_run(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B,
                 int32_t T_max, float* energy, int32_t Te_max, int32_t* mel_frames, int32_t* energy_frames, void* ws, size_t ws_bytes,
                 void* hip_stream) {
     if (!m) return FS2_ERR_ARG;
-    if (!m->ready) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");
-    if (!wav || !lengths || !mel || !mel_frames) return mfail(m, FS2_ERR_ARG, "wav, lengths, mel and mel_frames must not be null");
-    if (B < 1 || S < 1) return mfail(m, FS2_ERR_ARG, "B = %d, S = %d: both must be at least 1", B, S);
-    if (B > 65535) return mfail(m, FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
-    if (T_max < 1 + S / m->hop) return mfail(m, FS2_ERR_ARG, "T_max = %d < 1 + S / hop = %d", T_max, 1 + S / m->hop);
+    if (!m->ready) return m->fail(FS2_ERR_STATE, "fs2_mel_create did not succeed");
+    if (!wav || !lengths || !mel || !mel_frames) return m->fail(FS2_ERR_ARG, "wav, lengths, mel and mel_frames must not be null");
+    if (B < 1 || S < 1) return m->fail(FS2_ERR_ARG, "B = %d, S = %d: both must be at least 1", B, S);
+    if (B > 65535) return m->fail(FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
+    if (T_max < 1 + S / m->hop) return m->fail(FS2_ERR_ARG, "T_max = %d < 1 + S / hop = %d", T_max, 1 + S / m->hop);
     const int te_need = (int)(((long long)S + m->hop - 1) / m->hop);
-    if (energy && Te_max < te_need) return mfail(m, FS2_ERR_ARG, "Te_max = %d < ceil(S / hop) = %d", Te_max, te_need);
-    if ((long long)T_max * m->n_mels > 0x7fffffffLL) return mfail(m, FS2_ERR_SHAPE, "T_max * n_mels exceeds 2^31");
+    if (energy && Te_max < te_need) return m->fail(FS2_ERR_ARG, "Te_max = %d < ceil(S / hop) = %d", Te_max, te_need);
+    if ((long long)T_max * m->n_mels > 0x7fffffffLL) return m->fail(FS2_ERR_SHAPE, "T_max * n_mels exceeds 2^31");
     if (!ws || ws_bytes < mel_ws_need(B))  // asked for in every mode: a caller sizes one buffer, whatever it switches later
-        return mfail(m, FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, mel_ws_need(B));
+        return m->fail(FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, mel_ws_need(B));
     hipStream_t st = (hipStream_t)hip_stream;
     uint32_t* peak = nullptr;
     if (peak_normalize) {
         peak = (uint32_t*)ws;
-        if (hipMemsetAsync(peak, 0, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return mfail(m, FS2_ERR_HIP, "hipMemsetAsync failed");
+        if (hipMemsetAsync(peak, 0, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return m->fail(FS2_ERR_HIP, "hipMemsetAsync failed");
         int chunks = (S + 4095) / 4096;
         chunks = chunks > 64 ? 64 : chunks;
         hipLaunchKernelGGL(mel_peak_kernel, dim3(chunks, B), dim3(256), 0, st, wav, lengths, peak, S);
@@ -738,9 +720,9 @@ int fs2_mel_run(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B,
                     m->n_mels, m->nbt, m->tm, m->log_kind, m->clip};
     void* kargs[] = {&a};
     if (hipLaunchKernel((const void*)m->kernel, dim3((T_max + m->tm - 1) / m->tm, B), dim3(MEL_THREADS), kargs, m->lds, st) != hipSuccess)
-        return mfail(m, FS2_ERR_HIP, "launch of the STFT kernel failed: %s", hipGetErrorString(hipGetLastError()));
+        return m->fail(FS2_ERR_HIP, "launch of the STFT kernel failed: %s", hipGetErrorString(hipGetLastError()));
     if (energy) hipLaunchKernelGGL(mel_energy_kernel, dim3((Te_max + 3) / 4, B), dim3(256), 0, st, wav, lengths, peak, energy, S, Te_max, m->hop, m->win);
-    if (hipGetLastError() != hipSuccess) return mfail(m, FS2_ERR_HIP, "a launch of fs2_mel_run failed");
+    if (hipGetLastError() != hipSuccess) return m->fail(FS2_ERR_HIP, "a launch of fs2_mel_run failed");
     return FS2_OK;
 }
 
@@ -755,20 +737,16 @@ int fs2_op_segment_mean(const float* values, const int32_t* frames, const int32_
 
 int fs2_mel_set_snr_table(fs2_mel* m, const double* table_host, int32_t n, float db_lo) {
     if (!m) return FS2_ERR_ARG;
-    if (!table_host) return mfail(m, FS2_ERR_ARG, "the SNR table is null");
-    if (n < 2 || n > SNR_MAX_TABLE) return mfail(m, FS2_ERR_ARG, "the SNR table has %d entries, outside [2, %d]", n, SNR_MAX_TABLE);
-    if (!isfinite(db_lo)) return mfail(m, FS2_ERR_ARG, "db_lo is not finite");
+    if (!table_host) return m->fail(FS2_ERR_ARG, "the SNR table is null");
+    if (n < 2 || n > SNR_MAX_TABLE) return m->fail(FS2_ERR_ARG, "the SNR table has %d entries, outside [2, %d]", n, SNR_MAX_TABLE);
+    if (!isfinite(db_lo)) return m->fail(FS2_ERR_ARG, "db_lo is not finite");
     for (int i = 0; i < n; ++i)
-        if (!isfinite(table_host[i])) return mfail(m, FS2_ERR_ARG, "SNR table entry %d is not finite", i);
-    if (!m->ready) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");
+        if (!isfinite(table_host[i])) return m->fail(FS2_ERR_ARG, "SNR table entry %d is not finite", i);
+    if (!m->ready) return m->fail(FS2_ERR_STATE, "fs2_mel_create did not succeed");
     double* dev = nullptr;
-    if (hipMalloc((void**)&dev, (size_t)n * sizeof(double)) != hipSuccess)
-        return mfail(m, FS2_ERR_HIP, "hipMalloc of the SNR table failed: %s", hipGetErrorString(hipGetLastError()));
-    if (hipMemcpy(dev, table_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dev);
-        return mfail(m, FS2_ERR_HIP, "upload of the SNR table failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (m->snr_table) (void)hipFree(m->snr_table);  // waits for launches that still read the old one
+    DevAllocs fresh;  // (a failed upload leaves the old table in place)
+    FS2_TRY(upload_bytes(*m, fresh, table_host, (size_t)n * sizeof(double), (void**)&dev, FS2_ERR_HIP));
+    m->snr_alloc.swap(fresh);  // the old table goes with `fresh`: its hipFree waits for launches that still read it
     m->snr_table = dev, m->snr_k = n, m->snr_db_lo = db_lo;
     return FS2_OK;
 }
@@ -776,22 +754,22 @@ int fs2_mel_set_snr_table(fs2_mel* m, const double* table_host, int32_t n, float
 int fs2_mel_snr(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B, int32_t S, int32_t peak_normalize, float* snr,
                 int32_t Te_max, int32_t* snr_frames, void* ws, size_t ws_bytes, void* hip_stream) {
     if (!m) return FS2_ERR_ARG;
-    if (m->hop < 1) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");  // no geometry to judge
-    if (m->win % m->hop) return mfail(m, FS2_ERR_SHAPE, "win_length %d is not a multiple of hop %d: the windowed SNR needs one", m->win, m->hop);
-    if (!m->ready) return mfail(m, FS2_ERR_STATE, "fs2_mel_create did not succeed");
-    if (!m->snr_table) return mfail(m, FS2_ERR_STATE, "no SNR table: call fs2_mel_set_snr_table first (the library ships none)");
-    if (!wav || !lengths || !snr) return mfail(m, FS2_ERR_ARG, "wav, lengths and snr must not be null");
-    if (B < 1 || S < 1) return mfail(m, FS2_ERR_ARG, "B = %d, S = %d: both must be at least 1", B, S);
-    if (B > 65535) return mfail(m, FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
+    if (m->hop < 1) return m->fail(FS2_ERR_STATE, "fs2_mel_create did not succeed");  // no geometry to judge
+    if (m->win % m->hop) return m->fail(FS2_ERR_SHAPE, "win_length %d is not a multiple of hop %d: the windowed SNR needs one", m->win, m->hop);
+    if (!m->ready) return m->fail(FS2_ERR_STATE, "fs2_mel_create did not succeed");
+    if (!m->snr_table) return m->fail(FS2_ERR_STATE, "no SNR table: call fs2_mel_set_snr_table first (the library ships none)");
+    if (!wav || !lengths || !snr) return m->fail(FS2_ERR_ARG, "wav, lengths and snr must not be null");
+    if (B < 1 || S < 1) return m->fail(FS2_ERR_ARG, "B = %d, S = %d: both must be at least 1", B, S);
+    if (B > 65535) return m->fail(FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
     const int te_need = (int)(((long long)S + m->hop - 1) / m->hop);
-    if (Te_max < te_need) return mfail(m, FS2_ERR_ARG, "Te_max = %d < ceil(S / hop) = %d", Te_max, te_need);
+    if (Te_max < te_need) return m->fail(FS2_ERR_ARG, "Te_max = %d < ceil(S / hop) = %d", Te_max, te_need);
     if (!ws || ws_bytes < mel_ws_need(B))
-        return mfail(m, FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, mel_ws_need(B));
+        return m->fail(FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, mel_ws_need(B));
     hipStream_t st = (hipStream_t)hip_stream;
     uint32_t* peak = nullptr;
     if (peak_normalize) {
         peak = (uint32_t*)ws;
-        if (hipMemsetAsync(peak, 0, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return mfail(m, FS2_ERR_HIP, "hipMemsetAsync failed");
+        if (hipMemsetAsync(peak, 0, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return m->fail(FS2_ERR_HIP, "hipMemsetAsync failed");
         int chunks = (S + 4095) / 4096;
         chunks = chunks > 64 ? 64 : chunks;
         hipLaunchKernelGGL(mel_peak_kernel, dim3(chunks, B), dim3(256), 0, st, wav, lengths, peak, S);
@@ -799,7 +777,7 @@ int fs2_mel_snr(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B,
     const size_t lds = snr_lds_bytes(SNR_TILE + m->win / m->hop - 1, m->snr_k);
     hipLaunchKernelGGL(mel_snr_kernel, dim3((Te_max + SNR_TILE - 1) / SNR_TILE, B), dim3(256), lds, st, wav, lengths, peak, m->snr_table,
                        m->snr_k, snr, snr_frames, S, Te_max, m->hop, m->win);
-    if (hipGetLastError() != hipSuccess) return mfail(m, FS2_ERR_HIP, "a launch of fs2_mel_snr failed");
+    if (hipGetLastError() != hipSuccess) return m->fail(FS2_ERR_HIP, "a launch of fs2_mel_snr failed");
     return FS2_OK;
 }
 

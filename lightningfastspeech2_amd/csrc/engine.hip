@@ -5,8 +5,6 @@
 // and VarianceAdaptor.forward (litfass/fastspeech2/model.py:249-341); see DESIGN.md for the
 // kernel-by-kernel map.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <functional>
@@ -16,61 +14,11 @@
 #include <string>
 #include <vector>
 
-#include "fs2_common.h"
-#include "fs2_kernels.h"
+#include "fs2_host.h"
 
 using namespace fs2;
 
 namespace {
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
-
-struct Arena {
-    char* base = nullptr;
-    size_t cap = 0, off = 0;
-    bool external = false;  // caller-owned memory (fs2_set_workspace): never freed or grown here
-    bool overflow = false;  // a take() since the last reserve() did not fit (a null result cannot say so: offset 0 of a counting arena is null)
-    // An arena that only counts: no memory behind it, every take() fits and hands out no pointer; a layout function run on it leaves
-    // the size of its region in `off`.
-    static Arena counting() {
-        Arena a;
-        a.cap = ~(size_t)0;
-        return a;
-    }
-    int reserve(size_t bytes) {
-        off = 0;
-        overflow = false;
-        if (bytes <= cap) return FS2_OK;
-        if (external) return FS2_ERR_NOMEM;
-        if (base) (void)hipFree(base);
-        base = nullptr;
-        cap = 0;
-        bytes += bytes / 8;  // slack so slowly growing shapes do not reallocate every call
-        if (hipMalloc((void**)&base, bytes) != hipSuccess) return FS2_ERR_NOMEM;
-        cap = bytes;
-        return FS2_OK;
-    }
-    void* take(size_t bytes) {
-        const size_t a = (off + 255) & ~(size_t)255;
-        if (a + bytes > cap) { overflow = true; return nullptr; }
-        off = a + bytes;
-        return base ? base + a : nullptr;
-    }
-    void release() {
-        if (base && !external) (void)hipFree(base);
-        base = nullptr;
-        cap = off = 0;
-        external = false;
-    }
-    void adopt(void* p, size_t bytes) {  // p == nullptr: back to an engine-owned, grow-only arena
-        release();
-        if (p) { base = (char*)p; cap = bytes; external = true; }
-    }
-};
-inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct ConvW {     // dense conv or pointwise: W (N, taps*Cin) in its side's dtype, bias fp32
     void* w = nullptr;
@@ -161,12 +109,7 @@ struct Model {
                                        // and of the back (decoder + mel head); they differ in the FS2_MIXED* modes (back: bf16 or f16)
     size_t esz = 4;            // bytes per activation element, the larger of the two (arena sizing)
     bool front_split = false;  // FS2_MIXED_X3 / FS2_F32_X3: the fp32 GEMMs / convs (the front's / all of them) run as bf16 x 3 split products
-    std::map<std::string, std::vector<int64_t>> spec;
     // device weight blocks: owned jointly by an engine and its fs2_clone()s (freed with the last of them)
-    struct DevAllocs {
-        std::vector<void*> p;
-        ~DevAllocs() { for (void* q : p) (void)hipFree(q); }
-    };
     std::shared_ptr<DevAllocs> dev_allocs = std::make_shared<DevAllocs>();
     // device weights
     float *phone_table = nullptr, *pe = nullptr, *spk_w = nullptr, *spk_b = nullptr;
@@ -194,8 +137,7 @@ struct Switches {
 
 }  // namespace
 
-struct fs2_engine : Model, Switches {
-    char err[512];
+struct fs2_engine : Model, Switches, ErrorBase {
     bool finalized = false;
     bool debug = false;        // (not inherited by a clone)
     struct GraphEntry { std::vector<uint64_t> key; hipGraphExec_t exec = nullptr; uint64_t stamp = 0; bool bad = false; };
@@ -204,7 +146,7 @@ struct fs2_engine : Model, Switches {
     hipEvent_t gev_in = nullptr, gev_out = nullptr;
     uint64_t gclock = 0;
     long graph_replays = 0;
-    std::map<std::string, HostTensor> host;  // fs2_load_weight's tensors, until fs2_finalize has packed them
+    WeightStore w;  // the expected tensors (empty: fs2_create did not succeed) and fs2_load_weight's values, until fs2_finalize has packed them
     const float* priors_dev = nullptr;
     int priors_B = 0;
     bool weight_seen = false;          // a fs2_load_weight has been accepted: the architecture switches are closed
@@ -226,147 +168,128 @@ struct fs2_engine : Model, Switches {
 
 namespace {
 
-int fail(fs2_engine* e, int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(e->err, sizeof(e->err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIPCHK(e, call)                                                                        \
-    do {                                                                                       \
-        hipError_t _s = (call);                                                                \
-        if (_s != hipSuccess) return fail(e, FS2_ERR_HIP, "%s: %s", #call, hipGetErrorString(_s)); \
-    } while (0)
-#define CHK(call)                       \
-    do {                                \
-        int _r = (call);                \
-        if (_r != FS2_OK) return _r;    \
-    } while (0)
-
 // ---- expected tensors (mirror of lightningfastspeech2_amd/weights.py:state_dict_spec) -----------
 void conformer_spec(fs2_engine* e, const std::string& p, int H, int F, int k, bool dw) {
-    auto& s = e->spec;
-    s[p + ".self_attn.in_proj_weight"] = {3 * H, H};
-    s[p + ".self_attn.in_proj_bias"] = {3 * H};
-    s[p + ".self_attn.out_proj.weight"] = {H, H};
-    s[p + ".self_attn.out_proj.bias"] = {H};
-    s[p + ".norm1.weight"] = {H};
-    s[p + ".norm1.bias"] = {H};
-    s[p + ".norm2.weight"] = {H};
-    s[p + ".norm2.bias"] = {H};
+    auto& s = e->w;
+    s.expect(p + ".self_attn.in_proj_weight", {3 * H, H});
+    s.expect(p + ".self_attn.in_proj_bias", {3 * H});
+    s.expect(p + ".self_attn.out_proj.weight", {H, H});
+    s.expect(p + ".self_attn.out_proj.bias", {H});
+    s.expect(p + ".norm1.weight", {H});
+    s.expect(p + ".norm1.bias", {H});
+    s.expect(p + ".norm2.weight", {H});
+    s.expect(p + ".norm2.bias", {H});
     if (dw) {
-        s[p + ".conv1.0.weight"] = {H, 1, k};
-        s[p + ".conv1.0.bias"] = {H};
-        s[p + ".conv1.1.weight"] = {F, H, 1};
-        s[p + ".conv1.1.bias"] = {F};
-        s[p + ".conv2.0.weight"] = {F, F / H, 1};
-        s[p + ".conv2.0.bias"] = {F};
-        s[p + ".conv2.1.weight"] = {H, F, 1};
-        s[p + ".conv2.1.bias"] = {H};
+        s.expect(p + ".conv1.0.weight", {H, 1, k});
+        s.expect(p + ".conv1.0.bias", {H});
+        s.expect(p + ".conv1.1.weight", {F, H, 1});
+        s.expect(p + ".conv1.1.bias", {F});
+        s.expect(p + ".conv2.0.weight", {F, F / H, 1});
+        s.expect(p + ".conv2.0.bias", {F});
+        s.expect(p + ".conv2.1.weight", {H, F, 1});
+        s.expect(p + ".conv2.1.bias", {H});
     } else {
-        s[p + ".conv1.weight"] = {F, H, k};
-        s[p + ".conv1.bias"] = {F};
-        s[p + ".conv2.weight"] = {H, F, 1};
-        s[p + ".conv2.bias"] = {H};
+        s.expect(p + ".conv1.weight", {F, H, k});
+        s.expect(p + ".conv1.bias", {F});
+        s.expect(p + ".conv2.weight", {H, F, 1});
+        s.expect(p + ".conv2.bias", {H});
     }
 }
 void predictor_spec(fs2_engine* e, const std::string& p, int nl, int cin, int filt, int k, bool dw, int n_out = 1) {
-    auto& s = e->spec;
+    auto& s = e->w;
     for (int j = 0; j < nl; ++j) {
         const std::string q = p + ".layers." + std::to_string(j) + ".layers";
         if (dw) {
-            s[q + ".0.module.0.weight"] = {cin, 1, k};
-            s[q + ".0.module.0.bias"] = {cin};
-            s[q + ".0.module.1.weight"] = {filt, cin, 1};
-            s[q + ".0.module.1.bias"] = {filt};
+            s.expect(q + ".0.module.0.weight", {cin, 1, k});
+            s.expect(q + ".0.module.0.bias", {cin});
+            s.expect(q + ".0.module.1.weight", {filt, cin, 1});
+            s.expect(q + ".0.module.1.bias", {filt});
         } else {
-            s[q + ".0.module.weight"] = {filt, cin, k};
-            s[q + ".0.module.bias"] = {filt};
+            s.expect(q + ".0.module.weight", {filt, cin, k});
+            s.expect(q + ".0.module.bias", {filt});
         }
-        s[q + ".2.weight"] = {filt};
-        s[q + ".2.bias"] = {filt};
+        s.expect(q + ".2.weight", {filt});
+        s.expect(q + ".2.bias", {filt});
     }
-    s[p + ".linear.weight"] = {n_out, filt};
-    s[p + ".linear.bias"] = {n_out};
+    s.expect(p + ".linear.weight", {n_out, filt});
+    s.expect(p + ".linear.bias", {n_out});
 }
 void build_spec(fs2_engine* e) {
     const fs2_config& c = e->cfg;
     const int H = c.hidden;
-    e->spec["phone_embedding.weight"] = {c.n_phones, H};
+    e->w.expect("phone_embedding.weight", {c.n_phones, H});
     for (int i = 0; i < c.enc_layers; ++i)
         conformer_spec(e, "encoder.layers." + std::to_string(i), H, c.enc_filter, c.enc_kernels[i], c.enc_depthwise);
     for (int i = 0; i < c.dec_layers; ++i)
         conformer_spec(e, "decoder.layers." + std::to_string(i), H, c.dec_filter, c.dec_kernels[i], c.dec_depthwise);
-    e->spec["positional_encoding.pe"] = {1, c.pe_len, H};
+    e->w.expect("positional_encoding.pe", {1, c.pe_len, H});
     if (!e->dur_stochastic)  // (a stochastic predictor's tensors are the sdp handle's: fs2_load_weight hands them on)
         predictor_spec(e, "variance_adaptor.duration_predictor", c.dur_nlayers, H, c.dur_filter, c.dur_kernel, c.dur_depthwise);
     for (int v = 0; v < c.n_variances; ++v) {
         const std::string p = std::string("variance_adaptor.encoders.") + c.var_names[v];
-        e->spec[p + ".bins"] = {c.var_nbins - 1};
-        e->spec[p + ".embedding.weight"] = {c.var_nbins, H};
+        e->w.expect(p + ".bins", {c.var_nbins - 1});
+        e->w.expect(p + ".embedding.weight", {c.var_nbins, H});
         predictor_spec(e, p + ".predictor", c.var_nlayers[v], H, c.var_filter, c.var_kernel[v], c.var_depthwise, c.var_cwt[v] ? 10 : 1);
         if (c.var_cwt[v]) {
-            e->spec[p + ".mean_std_linear.weight"] = {2, c.var_filter};
-            e->spec[p + ".mean_std_linear.bias"] = {2};
+            e->w.expect(p + ".mean_std_linear.weight", {2, c.var_filter});
+            e->w.expect(p + ".mean_std_linear.bias", {2});
         }
     }
-    e->spec["linear.weight"] = {c.n_mels, H};
-    e->spec["linear.bias"] = {c.n_mels};
-    e->spec["speaker_embedding.projection.weight"] = {H, c.dvec_dim};
-    e->spec["speaker_embedding.projection.bias"] = {H};
+    e->w.expect("linear.weight", {c.n_mels, H});
+    e->w.expect("linear.bias", {c.n_mels});
+    e->w.expect("speaker_embedding.projection.weight", {H, c.dvec_dim});
+    e->w.expect("speaker_embedding.projection.bias", {H});
     for (int p = 0; p < c.n_priors; ++p) {
         const std::string q = std::string("prior_embeddings.") + c.prior_names[p];
-        e->spec[q + ".bins"] = {c.var_nbins - 1};
-        e->spec[q + ".embedding.weight"] = {c.var_nbins, H};
+        e->w.expect(q + ".bins", {c.var_nbins - 1});
+        e->w.expect(q + ".embedding.weight", {c.var_nbins, H});
     }
 }
 
 int check_config(fs2_engine* e) {
     const fs2_config& c = e->cfg;
-    if (c.abi_version != FS2_ABI_VERSION) return fail(e, FS2_ERR_ARG, "abi_version %d != %d", c.abi_version, FS2_ABI_VERSION);
+    if (c.abi_version != FS2_ABI_VERSION) return e->fail(FS2_ERR_ARG, "abi_version %d != %d", c.abi_version, FS2_ABI_VERSION);
     if (c.dtype != FS2_F32 && c.dtype != FS2_BF16 && c.dtype != FS2_MIXED && c.dtype != FS2_MIXED_X3 && c.dtype != FS2_F32_X3 &&
         c.dtype != FS2_MIXED_F16_X3)  // (FS2_F16 alone is a storage dtype of the operators, not an engine mode)
-        return fail(e, FS2_ERR_ARG, "bad dtype");
+        return e->fail(FS2_ERR_ARG, "bad dtype");
     const int H = c.hidden;
-    if (H <= 0 || H % 64 || H > 1024) return fail(e, FS2_ERR_SHAPE, "hidden=%d must be a multiple of 64, <= 1024", H);
+    if (H <= 0 || H % 64 || H > 1024) return e->fail(FS2_ERR_SHAPE, "hidden=%d must be a multiple of 64, <= 1024", H);
     if (c.enc_layers < 0 || c.enc_layers > FS2_MAX_LAYERS || c.dec_layers < 0 || c.dec_layers > FS2_MAX_LAYERS)
-        return fail(e, FS2_ERR_SHAPE, "layer count out of range");
-    if (c.n_variances < 0 || c.n_variances > FS2_MAX_VARIANCES) return fail(e, FS2_ERR_SHAPE, "n_variances out of range");
-    if (c.n_priors < 0 || c.n_priors > FS2_MAX_PRIORS) return fail(e, FS2_ERR_SHAPE, "n_priors out of range");
-    if (c.n_priors && c.var_nbins < 2) return fail(e, FS2_ERR_SHAPE, "variance_nbins < 2");
+        return e->fail(FS2_ERR_SHAPE, "layer count out of range");
+    if (c.n_variances < 0 || c.n_variances > FS2_MAX_VARIANCES) return e->fail(FS2_ERR_SHAPE, "n_variances out of range");
+    if (c.n_priors < 0 || c.n_priors > FS2_MAX_PRIORS) return e->fail(FS2_ERR_SHAPE, "n_priors out of range");
+    if (c.n_priors && c.var_nbins < 2) return e->fail(FS2_ERR_SHAPE, "variance_nbins < 2");
     const int heads[2] = {c.enc_heads, c.dec_heads};
     for (int i = 0; i < 2; ++i) {
-        if (heads[i] <= 0 || H % heads[i]) return fail(e, FS2_ERR_SHAPE, "heads must divide hidden");
+        if (heads[i] <= 0 || H % heads[i]) return e->fail(FS2_ERR_SHAPE, "heads must divide hidden");
         const int d = H / heads[i];
-        if (d != 32 && d != 64 && d != 128) return fail(e, FS2_ERR_SHAPE, "head dim %d not in {32,64,128}", d);
+        if (d != 32 && d != 64 && d != 128) return e->fail(FS2_ERR_SHAPE, "head dim %d not in {32,64,128}", d);
     }
     const int F[2] = {c.enc_filter, c.dec_filter};
     const int dw[2] = {c.enc_depthwise, c.dec_depthwise};
     for (int i = 0; i < 2; ++i) {
-        if (F[i] <= 0 || F[i] % 64) return fail(e, FS2_ERR_SHAPE, "conv_filter_size must be a multiple of 64");
-        if (dw[i] && F[i] % H) return fail(e, FS2_ERR_SHAPE, "depth-wise FFN needs filter %% hidden == 0");
+        if (F[i] <= 0 || F[i] % 64) return e->fail(FS2_ERR_SHAPE, "conv_filter_size must be a multiple of 64");
+        if (dw[i] && F[i] % H) return e->fail(FS2_ERR_SHAPE, "depth-wise FFN needs filter %% hidden == 0");
     }
     for (int i = 0; i < c.enc_layers; ++i)
-        if (c.enc_kernels[i] < 1 || c.enc_kernels[i] > 31 || !(c.enc_kernels[i] & 1)) return fail(e, FS2_ERR_SHAPE, "encoder kernel sizes must be odd, <= 31");
+        if (c.enc_kernels[i] < 1 || c.enc_kernels[i] > 31 || !(c.enc_kernels[i] & 1)) return e->fail(FS2_ERR_SHAPE, "encoder kernel sizes must be odd, <= 31");
     for (int i = 0; i < c.dec_layers; ++i)
-        if (c.dec_kernels[i] < 1 || c.dec_kernels[i] > 31 || !(c.dec_kernels[i] & 1)) return fail(e, FS2_ERR_SHAPE, "decoder kernel sizes must be odd, <= 31");
+        if (c.dec_kernels[i] < 1 || c.dec_kernels[i] > 31 || !(c.dec_kernels[i] & 1)) return e->fail(FS2_ERR_SHAPE, "decoder kernel sizes must be odd, <= 31");
     if (c.var_filter % 64 || c.dur_filter % 64 || c.var_filter > 1024 || c.dur_filter > 1024)
-        return fail(e, FS2_ERR_SHAPE, "predictor filter sizes must be multiples of 64, <= 1024");
-    if (c.dur_nlayers < 1) return fail(e, FS2_ERR_SHAPE, "duration_nlayers < 1");
-    if (!(c.dur_kernel & 1) || c.dur_kernel > 31) return fail(e, FS2_ERR_SHAPE, "duration kernel must be odd, <= 31");
+        return e->fail(FS2_ERR_SHAPE, "predictor filter sizes must be multiples of 64, <= 1024");
+    if (c.dur_nlayers < 1) return e->fail(FS2_ERR_SHAPE, "duration_nlayers < 1");
+    if (!(c.dur_kernel & 1) || c.dur_kernel > 31) return e->fail(FS2_ERR_SHAPE, "duration kernel must be odd, <= 31");
     for (int v = 0; v < c.n_variances; ++v) {
-        if (c.var_nlayers[v] < 1) return fail(e, FS2_ERR_SHAPE, "variance_nlayers < 1");
-        if (c.var_level[v] != 0 && c.var_level[v] != 1) return fail(e, FS2_ERR_ARG, "var_level must be 0 (frame) or 1 (phone)");
+        if (c.var_nlayers[v] < 1) return e->fail(FS2_ERR_SHAPE, "variance_nlayers < 1");
+        if (c.var_level[v] != 0 && c.var_level[v] != 1) return e->fail(FS2_ERR_ARG, "var_level must be 0 (frame) or 1 (phone)");
         if (c.var_cwt[v] && (c.var_mean[v] != 0.f || c.var_std[v] != 1.f))
-            return fail(e, FS2_ERR_ARG, "a CWT variance is bucketised as it is: var_mean / var_std must be 0 / 1");
-        if (c.var_nlayers[v] > 1 && c.var_filter != H) return fail(e, FS2_ERR_SHAPE, "variance_filter_size != hidden with nlayers > 1");
-        if (!(c.var_kernel[v] & 1) || c.var_kernel[v] > 31) return fail(e, FS2_ERR_SHAPE, "variance kernel must be odd, <= 31");
+            return e->fail(FS2_ERR_ARG, "a CWT variance is bucketised as it is: var_mean / var_std must be 0 / 1");
+        if (c.var_nlayers[v] > 1 && c.var_filter != H) return e->fail(FS2_ERR_SHAPE, "variance_filter_size != hidden with nlayers > 1");
+        if (!(c.var_kernel[v] & 1) || c.var_kernel[v] > 31) return e->fail(FS2_ERR_SHAPE, "variance kernel must be odd, <= 31");
     }
-    if (c.var_nbins < 2 && c.n_variances) return fail(e, FS2_ERR_SHAPE, "variance_nbins < 2");
-    if (c.n_mels <= 0 || c.n_mels % 4) return fail(e, FS2_ERR_SHAPE, "n_mels must be a positive multiple of 4");
-    if (c.dvec_dim <= 0 || c.max_frames <= 0 || c.pe_len <= 0 || c.n_phones <= 0) return fail(e, FS2_ERR_ARG, "non-positive size");
+    if (c.var_nbins < 2 && c.n_variances) return e->fail(FS2_ERR_SHAPE, "variance_nbins < 2");
+    if (c.n_mels <= 0 || c.n_mels % 4) return e->fail(FS2_ERR_SHAPE, "n_mels must be a positive multiple of 4");
+    if (c.dvec_dim <= 0 || c.max_frames <= 0 || c.pe_len <= 0 || c.n_phones <= 0) return e->fail(FS2_ERR_ARG, "non-positive size");
     return FS2_OK;
 }
 
@@ -375,32 +298,17 @@ int check_config(fs2_engine* e) {
 int check_deterministic_duration(fs2_engine* e) {
     const fs2_config& c = e->cfg;
     if (!e->dur_stochastic && c.dur_nlayers > 1 && c.dur_filter != c.hidden)
-        return fail(e, FS2_ERR_SHAPE, "duration_filter_size != hidden with nlayers > 1");
+        return e->fail(FS2_ERR_SHAPE, "duration_filter_size != hidden with nlayers > 1");
     return FS2_OK;
 }
 
 // ---- upload helpers ---------------------------------------------------------------------------
-int dev_alloc(fs2_engine* e, void** p, size_t bytes) {
-    if (hipMalloc(p, bytes ? bytes : 256) != hipSuccess) return fail(e, FS2_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
-    e->dev_allocs->p.push_back(*p);
-    return FS2_OK;
-}
-int upload_f32(fs2_engine* e, const float* h, size_t n, float** out) {
-    CHK(dev_alloc(e, (void**)out, n * 4));
-    HIPCHK(e, hipMemcpy(*out, h, n * 4, hipMemcpyHostToDevice));
-    return FS2_OK;
-}
+int dev_alloc(fs2_engine* e, void** p, size_t bytes) { return fs2::dev_alloc(*e, *e->dev_allocs, p, bytes, FS2_ERR_NOMEM); }
 int upload_mat(fs2_engine* e, const float* h, size_t n, void** out, int dt) {
-    if (dt == FS2_F32) return upload_f32(e, h, n, (float**)out);
-    if (!is_16bit(dt)) return fail(e, FS2_ERR_ARG, "upload_mat: not a storage dtype");
-    std::vector<unsigned short> tmp(n);
-    if (dt == FS2_F16) for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_f16_sat(h[i]).v;  // the device stores' rule, bit for bit
-    else for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_bf16(h[i]).v;
-    CHK(dev_alloc(e, out, n * 2));
-    HIPCHK(e, hipMemcpy(*out, tmp.data(), n * 2, hipMemcpyHostToDevice));
-    return FS2_OK;
+    return upload_as(*e, *e->dev_allocs, h, n, dt, out, FS2_ERR_NOMEM);
 }
-const HostTensor& W(fs2_engine* e, const std::string& n) { return e->host.at(n); }
+int upload_f32(fs2_engine* e, const float* h, size_t n, float** out) { return upload_mat(e, h, n, (void**)out, FS2_F32); }
+const WeightStore::Entry& W(fs2_engine* e, const std::string& n) { return e->w.at(n); }
 
 // conv weight (N, Cin, k) -> (N, k*Cin) tap-major
 // GEMM weights of the split-arithmetic modes (FS2_F32_X3, the front of FS2_MIXED_X3): every launch of an fp32-weight layer splits each
@@ -409,15 +317,15 @@ const HostTensor& W(fs2_engine* e, const std::string& n) { return e->host.at(n);
 int upload_gemm_w(fs2_engine* e, const float* h, int N, int K, ConvW* out, int dt) {
     out->presplit = dt == FS2_F32 && e->front_split && gemm_presplit_eligible(N, K);
     if (!out->presplit) return upload_mat(e, h, (size_t)N * K, &out->w, dt);
-    CHK(upload_f32(e, h, (size_t)N * K, (float**)&out->w));
-    if (launch_presplit_pack((const float*)out->w, out->w, (size_t)N * K, nullptr) != FS2_OK) return fail(e, FS2_ERR_HIP, "weight split launch failed");
-    HIPCHK(e, hipStreamSynchronize(nullptr));
+    FS2_TRY(upload_f32(e, h, (size_t)N * K, (float**)&out->w));
+    if (launch_presplit_pack((const float*)out->w, out->w, (size_t)N * K, nullptr) != FS2_OK) return e->fail(FS2_ERR_HIP, "weight split launch failed");
+    FS2_HIP(e, hipStreamSynchronize(nullptr));
     return FS2_OK;
 }
 
 int make_conv(fs2_engine* e, const std::string& wname, const std::string& bname, ConvW* out, int dt) {
     out->dt = dt;
-    const HostTensor& w = W(e, wname);
+    const auto& w = W(e, wname);
     const int N = (int)w.shape[0], Cin = (int)w.shape[1], k = w.shape.size() > 2 ? (int)w.shape[2] : 1;
     std::vector<float> packed((size_t)N * Cin * k);
     for (int n = 0; n < N; ++n)
@@ -426,16 +334,16 @@ int make_conv(fs2_engine* e, const std::string& wname, const std::string& bname,
     out->N = N;
     out->Cin = Cin;
     out->taps = k;
-    CHK(upload_gemm_w(e, packed.data(), N, Cin * k, out, dt));
-    const HostTensor& b = W(e, bname);
+    FS2_TRY(upload_gemm_w(e, packed.data(), N, Cin * k, out, dt));
+    const auto& b = W(e, bname);
     return upload_f32(e, b.data.data(), b.data.size(), &out->b);
 }
 int make_dw(fs2_engine* e, const std::string& wname, const std::string& bname, DwW* out) {
-    const HostTensor& w = W(e, wname);  // (C, 1, k)
+    const auto& w = W(e, wname);  // (C, 1, k)
     out->C = (int)w.shape[0];
     out->k = (int)w.shape[2];
-    CHK(upload_f32(e, w.data.data(), w.data.size(), &out->w));
-    const HostTensor& b = W(e, bname);
+    FS2_TRY(upload_f32(e, w.data.data(), w.data.size(), &out->w));
+    const auto& b = W(e, bname);
     return upload_f32(e, b.data.data(), b.data.size(), &out->b);
 }
 // conv2 = Sequential(grouped k=1 conv (groups=H over F channels), pointwise F->H) has no
@@ -443,10 +351,10 @@ int make_dw(fs2_engine* e, const std::string& wname, const std::string& bname, D
 // b' = W21 * bg + b21.  Folded once here in double precision.
 int make_folded_conv2(fs2_engine* e, const std::string& p, int H, int F, ConvW* out, int dt) {
     out->dt = dt;
-    const HostTensor& G = W(e, p + ".conv2.0.weight");   // (F, F/H, 1)
-    const HostTensor& bg = W(e, p + ".conv2.0.bias");    // (F)
-    const HostTensor& W2 = W(e, p + ".conv2.1.weight");  // (H, F, 1)
-    const HostTensor& b2 = W(e, p + ".conv2.1.bias");    // (H)
+    const auto& G = W(e, p + ".conv2.0.weight");   // (F, F/H, 1)
+    const auto& bg = W(e, p + ".conv2.0.bias");    // (F)
+    const auto& W2 = W(e, p + ".conv2.1.weight");  // (H, F, 1)
+    const auto& b2 = W(e, p + ".conv2.1.bias");    // (H)
     const int gs = F / H;
     std::vector<float> Wf((size_t)H * F), bf(H);
     for (int o = 0; o < H; ++o) {
@@ -466,34 +374,34 @@ int make_folded_conv2(fs2_engine* e, const std::string& p, int H, int F, ConvW* 
     out->N = H;
     out->Cin = F;
     out->taps = 1;
-    CHK(upload_gemm_w(e, Wf.data(), H, F, out, dt));
+    FS2_TRY(upload_gemm_w(e, Wf.data(), H, F, out, dt));
     return upload_f32(e, bf.data(), bf.size(), &out->b);
 }
 int up_vec(fs2_engine* e, const std::string& n, float** out) {
-    const HostTensor& t = W(e, n);
+    const auto& t = W(e, n);
     return upload_f32(e, t.data.data(), t.data.size(), out);
 }
 int make_layer(fs2_engine* e, const std::string& p, int H, int F, bool dw, LayerW* L, int dt) {
     L->depthwise = dw;
-    CHK(make_conv(e, p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", &L->in_proj, dt));
-    CHK(make_conv(e, p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias", &L->out_proj, dt));
-    CHK(up_vec(e, p + ".norm1.weight", &L->g1));
-    CHK(up_vec(e, p + ".norm1.bias", &L->b1));
-    CHK(up_vec(e, p + ".norm2.weight", &L->g2));
-    CHK(up_vec(e, p + ".norm2.bias", &L->b2));
+    FS2_TRY(make_conv(e, p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", &L->in_proj, dt));
+    FS2_TRY(make_conv(e, p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias", &L->out_proj, dt));
+    FS2_TRY(up_vec(e, p + ".norm1.weight", &L->g1));
+    FS2_TRY(up_vec(e, p + ".norm1.bias", &L->b1));
+    FS2_TRY(up_vec(e, p + ".norm2.weight", &L->g2));
+    FS2_TRY(up_vec(e, p + ".norm2.bias", &L->b2));
     if (dw) {
-        CHK(make_dw(e, p + ".conv1.0.weight", p + ".conv1.0.bias", &L->dw));
-        CHK(make_conv(e, p + ".conv1.1.weight", p + ".conv1.1.bias", &L->c1, dt));
-        CHK(make_folded_conv2(e, p, H, F, &L->c2, dt));
+        FS2_TRY(make_dw(e, p + ".conv1.0.weight", p + ".conv1.0.bias", &L->dw));
+        FS2_TRY(make_conv(e, p + ".conv1.1.weight", p + ".conv1.1.bias", &L->c1, dt));
+        FS2_TRY(make_folded_conv2(e, p, H, F, &L->c2, dt));
     } else {
-        CHK(make_conv(e, p + ".conv1.weight", p + ".conv1.bias", &L->c1, dt));
-        CHK(make_conv(e, p + ".conv2.weight", p + ".conv2.bias", &L->c2, dt));
+        FS2_TRY(make_conv(e, p + ".conv1.weight", p + ".conv1.bias", &L->c1, dt));
+        FS2_TRY(make_conv(e, p + ".conv2.weight", p + ".conv2.bias", &L->c2, dt));
     }
     const bool is_enc = p.compare(0, 8, "encoder.") == 0;
     if (is_16bit(dt) && H == 256 && (is_enc ? e->cfg.enc_heads : e->cfg.dec_heads) == 2) {  // attn_out_ln_kernel's weight stream (a 16-bit shuffle)
-        CHK(dev_alloc(e, &L->wo_pk, predictor_packed_bytes_per_layer(1)));
-        CHK(launch_pack_predictor_weights(L->out_proj.w, L->wo_pk, nullptr, 1));
-        HIPCHK(e, hipStreamSynchronize(nullptr));
+        FS2_TRY(dev_alloc(e, &L->wo_pk, predictor_packed_bytes_per_layer(1)));
+        FS2_TRY(launch_pack_predictor_weights(L->out_proj.w, L->wo_pk, nullptr, 1));
+        FS2_HIP(e, hipStreamSynchronize(nullptr));
     }
     return FS2_OK;
 }
@@ -502,10 +410,10 @@ int make_layer(fs2_engine* e, const std::string& p, int H, int F, bool dw, Layer
 // depth-wise blocks only (the blocks whose LayerNorms are deferred, conformer()): a block's in-projection behind the previous block's
 // norm2, the mel head behind the last decoder block's.
 int make_norm_folded(fs2_engine* e, const std::string& lw, const std::string& lb, const std::string& norm, ConvW* out, float** wg_out, int dt) {
-    const HostTensor& w = W(e, lw);
-    const HostTensor& b = W(e, lb);
-    const HostTensor& g = W(e, norm + ".weight");
-    const HostTensor& be = W(e, norm + ".bias");
+    const auto& w = W(e, lw);
+    const auto& b = W(e, lb);
+    const auto& g = W(e, norm + ".weight");
+    const auto& be = W(e, norm + ".bias");
     const int N = (int)w.shape[0], H = (int)w.shape[1];
     std::vector<float> wf((size_t)N * H), bf(N), wg(N);
     for (int n = 0; n < N; ++n) {
@@ -520,8 +428,8 @@ int make_norm_folded(fs2_engine* e, const std::string& lw, const std::string& lb
         wg[n] = (float)gacc;
     }
     out->N = N; out->Cin = H; out->taps = 1; out->dt = dt;
-    CHK(upload_mat(e, wf.data(), wf.size(), &out->w, dt));
-    CHK(upload_f32(e, bf.data(), bf.size(), &out->b));
+    FS2_TRY(upload_mat(e, wf.data(), wf.size(), &out->w, dt));
+    FS2_TRY(upload_f32(e, bf.data(), bf.size(), &out->b));
     return upload_f32(e, wg.data(), wg.size(), wg_out);
 }
 
@@ -536,8 +444,8 @@ int upload_stacked_vectors(fs2_engine* e, const std::string& p, int nl, const ch
         g.insert(g.end(), hg.begin(), hg.end());
         b.insert(b.end(), hbe.begin(), hbe.end());
     }
-    CHK(upload_f32(e, bias.data(), bias.size(), &P->bias_all));
-    CHK(upload_f32(e, g.data(), g.size(), &P->g_all));
+    FS2_TRY(upload_f32(e, bias.data(), bias.size(), &P->bias_all));
+    FS2_TRY(upload_f32(e, g.data(), g.size(), &P->g_all));
     return upload_f32(e, b.data(), b.size(), &P->b_all);
 }
 
@@ -551,26 +459,26 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
         PredLayerW& Lw = P->layers[j];
         Lw.depthwise = dw;
         if (dw) {
-            CHK(make_dw(e, q + ".0.module.0.weight", q + ".0.module.0.bias", &Lw.dw));
-            CHK(make_conv(e, q + ".0.module.1.weight", q + ".0.module.1.bias", &Lw.c, dt));
+            FS2_TRY(make_dw(e, q + ".0.module.0.weight", q + ".0.module.0.bias", &Lw.dw));
+            FS2_TRY(make_conv(e, q + ".0.module.1.weight", q + ".0.module.1.bias", &Lw.c, dt));
         } else {
-            CHK(make_conv(e, q + ".0.module.weight", q + ".0.module.bias", &Lw.c, dt));
+            FS2_TRY(make_conv(e, q + ".0.module.weight", q + ".0.module.bias", &Lw.c, dt));
         }
-        CHK(up_vec(e, q + ".2.weight", &Lw.g));
-        CHK(up_vec(e, q + ".2.bias", &Lw.b));
+        FS2_TRY(up_vec(e, q + ".2.weight", &Lw.g));
+        FS2_TRY(up_vec(e, q + ".2.bias", &Lw.b));
     }
     if (cwt) {  // Linear(filter, 10): a small GEMM (rows padded to 12 for 16-byte fp32 stores)
-        const HostTensor& hw = W(e, p + ".linear.weight");
-        const HostTensor& hb = W(e, p + ".linear.bias");
+        const auto& hw = W(e, p + ".linear.weight");
+        const auto& hb = W(e, p + ".linear.bias");
         std::vector<float> wp((size_t)12 * filt, 0.f), bp(12, 0.f);
         memcpy(wp.data(), hw.data.data(), (size_t)10 * filt * 4);
         memcpy(bp.data(), hb.data.data(), 10 * 4);
         P->head_mat.N = 12; P->head_mat.Cin = filt; P->head_mat.taps = 1; P->head_mat.dt = dt;
-        CHK(upload_mat(e, wp.data(), wp.size(), &P->head_mat.w, dt));
-        CHK(upload_f32(e, bp.data(), bp.size(), &P->head_mat.b));
+        FS2_TRY(upload_mat(e, wp.data(), wp.size(), &P->head_mat.w, dt));
+        FS2_TRY(upload_f32(e, bp.data(), bp.size(), &P->head_mat.b));
         return FS2_OK;  // never the single-launch kernel: its head is the scalar one
     }
-    CHK(up_vec(e, p + ".linear.weight", &P->head_w));
+    FS2_TRY(up_vec(e, p + ".linear.weight", &P->head_w));
     P->head_b = W(e, p + ".linear.bias").data[0];
     if (dw && nl && filt > 256) {
         const std::string q = p + ".layers." + std::to_string(nl - 1) + ".layers";
@@ -582,35 +490,35 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
             sg += (double)gw[n];
             cst += (double)hbe[n] * hw[n];
         }
-        CHK(upload_f32(e, gw.data(), gw.size(), &P->head_gw));
+        FS2_TRY(upload_f32(e, gw.data(), gw.size(), &P->head_gw));
         P->head_sum_gw = (float)sg;
         P->head_cst = (float)cst;
     }
     const int taps = nl ? P->layers[0].c.taps : 0, cin = nl ? P->layers[0].c.Cin : 0;
     if (!dw && nl && cin == filt && predictor_fused_supported(dt, filt, taps, nl, 1)) {
         const size_t lb = predictor_packed_bytes_per_layer();
-        CHK(dev_alloc(e, &P->wpk, lb * nl));
-        for (int j = 0; j < nl; ++j) CHK(launch_pack_predictor_weights(P->layers[j].c.w, (char*)P->wpk + lb * j, nullptr));
-        HIPCHK(e, hipStreamSynchronize(nullptr));
-        CHK(upload_stacked_vectors(e, p, nl, ".0.module.bias", P));
+        FS2_TRY(dev_alloc(e, &P->wpk, lb * nl));
+        for (int j = 0; j < nl; ++j) FS2_TRY(launch_pack_predictor_weights(P->layers[j].c.w, (char*)P->wpk + lb * j, nullptr));
+        FS2_HIP(e, hipStreamSynchronize(nullptr));
+        FS2_TRY(upload_stacked_vectors(e, p, nl, ".0.module.bias", P));
     } else if (dw && nl && cin == filt && P->layers[0].dw.k == 3 && P->layers[0].dw.C == filt && predictor_fused_supported(dt, filt, 3, nl, 1)) {
         // depth-wise layers in the single launch (predictor_fused_kernel<..., DW>): the pointwise weights in fragment order (one tap),
         // the depth-wise taps as (layer, tap, channel) fp32
         const size_t lb = predictor_packed_bytes_per_layer(1);
-        CHK(dev_alloc(e, &P->wpk, lb * nl));
+        FS2_TRY(dev_alloc(e, &P->wpk, lb * nl));
         std::vector<float> dww((size_t)nl * 3 * filt), dwb;
         for (int j = 0; j < nl; ++j) {
             const std::string q = p + ".layers." + std::to_string(j) + ".layers";
-            CHK(launch_pack_predictor_weights(P->layers[j].c.w, (char*)P->wpk + lb * j, nullptr, 1));
+            FS2_TRY(launch_pack_predictor_weights(P->layers[j].c.w, (char*)P->wpk + lb * j, nullptr, 1));
             const auto &hw = W(e, q + ".0.module.0.weight").data, &hdb = W(e, q + ".0.module.0.bias").data;  // (filt, 1, 3), (filt)
             for (int c2 = 0; c2 < filt; ++c2)
                 for (int t = 0; t < 3; ++t) dww[((size_t)j * 3 + t) * filt + c2] = hw[(size_t)c2 * 3 + t];
             dwb.insert(dwb.end(), hdb.begin(), hdb.end());
         }
-        HIPCHK(e, hipStreamSynchronize(nullptr));
-        CHK(upload_stacked_vectors(e, p, nl, ".0.module.1.bias", P));
-        CHK(upload_f32(e, dww.data(), dww.size(), &P->dw_all));
-        CHK(upload_f32(e, dwb.data(), dwb.size(), &P->dwb_all));
+        FS2_HIP(e, hipStreamSynchronize(nullptr));
+        FS2_TRY(upload_stacked_vectors(e, p, nl, ".0.module.1.bias", P));
+        FS2_TRY(upload_f32(e, dww.data(), dww.size(), &P->dw_all));
+        FS2_TRY(upload_f32(e, dwb.data(), dwb.size(), &P->dwb_all));
     } else if (!dw && nl && cin == filt && dt == FS2_F32 && e->front_split && predictor_fused_x3_supported(filt, taps, nl, 1)) {
         // the same launch in the split arithmetic: the weights' bf16 heads and tails in the kernel's fragment order
         // [layer][step = tap * 8 + kb][32-channel group][2][lane] x 8 values (pack_predictor_weights_kernel's map), packed here
@@ -618,7 +526,7 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
         std::vector<unsigned short> hi(per * nl), lo(per * nl);
         for (int j = 0; j < nl; ++j) {
             const std::string q = p + ".layers." + std::to_string(j) + ".layers";
-            const HostTensor& w = W(e, q + ".0.module.weight");  // (filt, filt, 3)
+            const auto& w = W(e, q + ".0.module.weight");  // (filt, filt, 3)
             for (int step = 0; step < 24; ++step) {
                 const int tap = step / 8, kb = step % 8;
                 for (int grp = 0; grp < 8; ++grp)
@@ -637,11 +545,11 @@ int make_predictor(fs2_engine* e, const std::string& p, int nl, int filt, bool d
                         }
             }
         }
-        CHK(dev_alloc(e, &P->wpk, hi.size() * 2));
-        CHK(dev_alloc(e, &P->wpk_lo, lo.size() * 2));
-        HIPCHK(e, hipMemcpy(P->wpk, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(P->wpk_lo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
-        CHK(upload_stacked_vectors(e, p, nl, ".0.module.bias", P));
+        FS2_TRY(dev_alloc(e, &P->wpk, hi.size() * 2));
+        FS2_TRY(dev_alloc(e, &P->wpk_lo, lo.size() * 2));
+        FS2_HIP(e, hipMemcpy(P->wpk, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
+        FS2_HIP(e, hipMemcpy(P->wpk_lo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
+        FS2_TRY(upload_stacked_vectors(e, p, nl, ".0.module.bias", P));
     }
     return FS2_OK;
 }
@@ -757,7 +665,7 @@ int gemm(fs2_engine* e, hipStream_t st, const ConvW& w, const void* x, void* c, 
     Bracket br(e, w.taps > 1 ? FS2_K_CONV_GEMM : FS2_K_GEMM, st, fl, by);
     Bracket br2(e, o.extra_class >= 0 ? o.extra_class : FS2_K_COUNT - 1, st, fl, by, o.extra_class >= 0);
     const int r = launch_gemm(a, w.dt, out_dt, st);
-    if (r != FS2_OK) return fail(e, r, "gemm launch failed (M=%d N=%d K=%d)", M, a.N, a.K);
+    if (r != FS2_OK) return e->fail(r, "gemm launch failed (M=%d N=%d K=%d)", M, a.N, a.K);
     return FS2_OK;
 }
 struct LnOnLoad { const float* stats; const float* g; const float* b; };  // x of a dwconv is a pre-norm tensor
@@ -770,7 +678,7 @@ int dwconv(fs2_engine* e, hipStream_t st, const DwW& w, const void* x, void* y, 
     a.B = B; a.S = S; a.C = w.C; a.k = w.k; a.pad = (w.k - 1) / 2;
     Bracket br(e, FS2_K_ROWOPS, st, 2.0 * B * S * (double)w.C * w.k, 2.0 * B * S * (double)w.C * (double)elem_bytes(dt));
     const int r = launch_dwconv(a, dt, st);
-    if (r != FS2_OK) return fail(e, r, "dwconv launch failed");
+    if (r != FS2_OK) return e->fail(r, "dwconv launch failed");
     return FS2_OK;
 }
 
@@ -782,7 +690,7 @@ int norm_only(fs2_engine* e, hipStream_t st, int dt, const void* v, const float*
     l.dot_w = dot_w; l.dot_b = dot_b; l.mask = mask; l.pred = pred;
     l.M = M; l.H = H; l.eps = 1e-5f;
     Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * M * (double)H * (double)elem_bytes(dt));
-    if (launch_layernorm(l, dt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "normalise-only LayerNorm launch failed");
+    if (launch_layernorm(l, dt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "normalise-only LayerNorm launch failed");
     return FS2_OK;
 }
 
@@ -815,21 +723,21 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
     const bool x3 = e->front_split && dt == FS2_F32 && e->tune.attn_x3;
     void* qkv_lo = x3 ? (void*)((char*)sc.qkv + (size_t)M * 3 * H * 2) : nullptr;
     if (prenorm_in) {
-        if (!w.has_fold || !(w.depthwise && H > 256 && e->defer_ln)) return fail(e, FS2_ERR_STATE, "pre-norm block input without folded weights");
+        if (!w.has_fold || !(w.depthwise && H > 256 && e->defer_ln)) return e->fail(FS2_ERR_STATE, "pre-norm block input without folded weights");
         const RowScale rs{sc.rsf, w.in_wg};
-        CHK(gemm(e, st, w.in_proj_f, x, sc.qkv, M, M, false, dt, {.rowscale = &rs}));
+        FS2_TRY(gemm(e, st, w.in_proj_f, x, sc.qkv, M, M, false, dt, {.rowscale = &rs}));
     } else {
-        CHK(gemm(e, st, w.in_proj, x, sc.qkv, M, M, false, dt, {.c_lo = qkv_lo}));
+        FS2_TRY(gemm(e, st, w.in_proj, x, sc.qkv, M, M, false, dt, {.c_lo = qkv_lo}));
     }
     const int ffn_class = is_decoder ? FS2_K_DEC_FFN_CONV1 : -1;
     // the block's second half on tmp = LN1(x + out_proj(att)): x = LN2(tmp + conv2(relu(conv1([dwconv] tmp))))
     const auto ffn = [&]() -> int {
         const void* in = tmp;
         if (w.depthwise) {
-            CHK(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt));
+            FS2_TRY(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt));
             in = sc.u;
         }
-        CHK(gemm(e, st, w.c1, in, sc.hid, M, S, true, dt, {.extra_class = ffn_class}));
+        FS2_TRY(gemm(e, st, w.c1, in, sc.hid, M, S, true, dt, {.extra_class = ffn_class}));
         LnFuse ln;
         ln.res = tmp; ln.g = w.g2; ln.b = w.b2; ln.tmp = sc.proj;
         return gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, {.ln = &ln});
@@ -853,7 +761,7 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
         {
             Bracket br(e, FS2_K_ATTENTION, st, 4.0 * B * (double)S * S * H + 2.0 * M * (double)H * H, 5.0 * M * H * dsz + (double)H * H * dsz);
             const int r = launch_attn_out_ln(ao, dt, st);
-            if (r != FS2_OK) return fail(e, r, "fused attention + out-projection launch failed");
+            if (r != FS2_OK) return e->fail(r, "fused attention + out-projection launch failed");
         }
         mha.reset();
         return ffn();
@@ -861,13 +769,13 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
     {
         Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * M * H * dsz);
         const int r = x3 ? FS2_OK : launch_transpose_v(a, dt, st);  // (the split form reads V row-major, like the bf16 one)
-        if (r != FS2_OK) return fail(e, r, "transpose_v launch failed");
+        if (r != FS2_OK) return e->fail(r, "transpose_v launch failed");
     }
     {
         Bracket br(e, FS2_K_ATTENTION, st, 4.0 * B * (double)S * S * H, 4.0 * M * H * dsz);
         Bracket br2(e, FS2_K_DEC_ATTENTION, st, 4.0 * B * (double)S * S * H, 4.0 * M * H * dsz, is_decoder);
         const int r = launch_attention(a, dt, st);
-        if (r != FS2_OK) return fail(e, r, "attention launch failed");
+        if (r != FS2_OK) return e->fail(r, "attention launch failed");
     }
     if (w.depthwise && H > 256 && e->defer_ln) {
         // Rows wider than one GEMM tile cannot have LayerNorm fused behind the GEMM, and in the depth-wise block every
@@ -877,16 +785,16 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
         Deferred d1;
         d1.res = x; d1.stats_out = sc.st1;
         if (prenorm_in) { d1.res_stats = sc.st2; d1.res_g = pg; d1.res_b = pb; }                      // x = LN2_prev(v2_prev), on load
-        CHK(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, {.deferred = &d1}));               // tmp = v1
+        FS2_TRY(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, {.deferred = &d1}));               // tmp = v1
         mha.reset();
         LnOnLoad l1{sc.st1, w.g1, w.b1};
-        CHK(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt, &l1));
-        CHK(gemm(e, st, w.c1, sc.u, sc.hid, M, S, true, dt, {.extra_class = ffn_class}));
+        FS2_TRY(dwconv(e, st, w.dw, tmp, sc.u, B, S, dt, &l1));
+        FS2_TRY(gemm(e, st, w.c1, sc.u, sc.hid, M, S, true, dt, {.extra_class = ffn_class}));
         Deferred d2;
         d2.res = tmp; d2.res_stats = sc.st1; d2.res_g = w.g1; d2.res_b = w.b1; d2.stats_out = sc.st2;
-        CHK(gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, {.deferred = &d2}));                        // x = v2 (x is free by now)
+        FS2_TRY(gemm(e, st, w.c2, sc.hid, x, M, S, false, dt, {.deferred = &d2}));                        // x = v2 (x is free by now)
         if (leave_prenorm) {  // the next block folds LN2 in: its in-projection wants (rstd, rstd * mean) per row
-            if (launch_rowstats_finish(sc.st2, ln_parts(H), H, 1e-5f, sc.rsf, M, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "row statistics launch failed");
+            if (launch_rowstats_finish(sc.st2, ln_parts(H), H, 1e-5f, sc.rsf, M, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "row statistics launch failed");
             return FS2_OK;
         }
         return norm_only(e, st, dt, x, sc.st2, w.g2, w.b2, x, M, H);                                   // x = LN2(v2), in place
@@ -894,7 +802,7 @@ int conformer(fs2_engine* e, hipStream_t st, const LayerW& w, void* x, void* tmp
     {   // tmp = LN1(x + out_proj(att))
         LnFuse ln;
         ln.res = x; ln.g = w.g1; ln.b = w.b1; ln.tmp = sc.proj;
-        CHK(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, {.ln = &ln}));
+        FS2_TRY(gemm(e, st, w.out_proj, sc.att, tmp, M, M, false, dt, {.ln = &ln}));
         mha.reset();
     }
     return ffn();
@@ -911,7 +819,7 @@ int run_stack(fs2_engine* e, hipStream_t st, const std::vector<LayerW>& Ls, void
         const LayerW& w = Ls[i];
         const bool deferred = w.depthwise && H > 256 && e->defer_ln;
         const bool leave = e->fold_ln && deferred && (i + 1 < Ls.size() ? Ls[i + 1].has_fold && Ls[i + 1].depthwise : leave_last);
-        CHK(conformer(e, st, w, x, tmp, B, S, heads, sc, is_decoder, pre, pre ? Ls[i - 1].g2 : nullptr, pre ? Ls[i - 1].b2 : nullptr, leave));
+        FS2_TRY(conformer(e, st, w, x, tmp, B, S, heads, sc, is_decoder, pre, pre ? Ls[i - 1].g2 : nullptr, pre ? Ls[i - 1].b2 : nullptr, leave));
         pre = leave;
     }
     if (left) *left = pre;  // the stack's output is the last block's pre-norm v2 (+ finished statistics in sc.rsf): the caller folds norm2 in
@@ -937,9 +845,9 @@ struct EmbedTail {  // the VarianceEncoder's bucketize + embedding add (+ pe + s
 
 // The CWT ending on the last layer's activations (model.py:412-431): 10-scale head, utterance-level mean / std, recomposition
 int cwt_head(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* act, const CwtOut& cw, const uint8_t* mask, float* pred, int B, int S) {
-    CHK(gemm(e, st, P.head_mat, act, cw.spec12, B * S, B * S, false, FS2_F32));
+    FS2_TRY(gemm(e, st, P.head_mat, act, cw.spec12, B * S, B * S, false, FS2_F32));
     CwtArgs ca{act, cw.spec12, 12, mask, P.ms_w, P.ms_b, cw.mean_std, pred, cw.spec_out, B, S, P.filt};
-    if (launch_cwt_head(ca, P.dt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "cwt head launch failed");
+    if (launch_cwt_head(ca, P.dt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "cwt head launch failed");
     return FS2_OK;
 }
 
@@ -947,7 +855,7 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
               float* pred, const LayerScratch& sc, const CwtOut* cw = nullptr, const EmbedTail* tail = nullptr, bool* tail_done = nullptr) {
     const int M = B * S;
     if (tail_done) *tail_done = false;
-    if (P.cwt && !cw) return fail(e, FS2_ERR_STATE, "CWT predictor without its output buffers");
+    if (P.cwt && !cw) return e->fail(FS2_ERR_STATE, "CWT predictor without its output buffers");
     // the whole predictor as one launch (predictor_fused.hip): in the split arithmetic (fp32 rows in, and out of the embedding tail), or in bf16
     const int nl = (int)P.layers.size(), taps = P.dw_all ? 3 : P.layers[0].c.taps;
     const bool one_x3 = P.wpk && P.wpk_lo && e->fuse_predictor && P.dt == FS2_F32 && e->front_split && predictor_fused_x3_supported(P.filt, taps, nl, S);
@@ -968,7 +876,7 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
         Bracket br(e, FS2_K_CONV_GEMM, st, fl, by);
         Bracket brp(e, FS2_K_PREDICTOR, st, fl, by, x != e->ps.xA && x != e->ps.xB);
         const int r = one_x3 ? launch_predictor_fused_x3(a, st) : launch_predictor_fused(a, st);
-        if (r != FS2_OK) return fail(e, r, "fused predictor%s launch failed (B=%d S=%d)", one_x3 ? " (split arithmetic)" : "", B, S);
+        if (r != FS2_OK) return e->fail(r, "fused predictor%s launch failed (B=%d S=%d)", one_x3 ? " (split arithmetic)" : "", B, S);
         if (with_tail) *tail_done = true;
         return FS2_OK;
     }
@@ -984,11 +892,11 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
             const PredLayerW& Lw = P.layers[j];
             void* out = (j & 1) ? sc.proj : sc.att;
             LnOnLoad lp{stats[(j + 1) & 1], prev ? prev->g : nullptr, prev ? prev->b : nullptr};
-            CHK(dwconv(e, st, Lw.dw, src, sc.u, B, S, P.dt, prev ? &lp : nullptr));
+            FS2_TRY(dwconv(e, st, Lw.dw, src, sc.u, B, S, P.dt, prev ? &lp : nullptr));
             Deferred d;
             d.stats_out = stats[j & 1];
             if (j + 1 == P.layers.size() && !P.cwt && P.head_gw) { d.head_gw = P.head_gw; d.head_out = sc.hd; d.head_done = &head_done; }
-            CHK(gemm(e, st, Lw.c, sc.u, out, M, S, true, P.dt, {.deferred = &d}));
+            FS2_TRY(gemm(e, st, Lw.c, sc.u, out, M, S, true, P.dt, {.deferred = &d}));
             src = out;
             prev = &Lw;
         }
@@ -996,11 +904,11 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
         if (head_done) {  // the last LayerNorm + head: a row-sized pass over the epilogue's sums
             Bracket br(e, FS2_K_ROWOPS, st, 0, (double)M * ln_parts(P.filt) * 12);
             if (launch_head_finish(stl, sc.hd, ln_parts(P.filt), P.filt, 1e-5f, P.head_sum_gw, P.head_cst, mask, pred, M, st) != FS2_OK)
-                return fail(e, FS2_ERR_HIP, "head finish launch failed");
+                return e->fail(FS2_ERR_HIP, "head finish launch failed");
             return FS2_OK;
         }
         if (!P.cwt) return norm_only(e, st, P.dt, src, stl, prev->g, prev->b, nullptr, M, P.filt, P.head_w, P.head_b, mask, pred);
-        CHK(norm_only(e, st, P.dt, src, stl, prev->g, prev->b, (void*)src, M, P.filt));
+        FS2_TRY(norm_only(e, st, P.dt, src, stl, prev->g, prev->b, (void*)src, M, P.filt));
         return cwt_head(e, st, P, src, *cw, mask, pred, B, S);
     }
     const void* src = x;
@@ -1017,12 +925,12 @@ int predictor(fs2_engine* e, hipStream_t st, const PredictorW& P, const void* x,
         const bool keep = !last || P.cwt;  // the CWT head needs the last layer's activations themselves
         if (last && !P.cwt) { ln.dot_w = P.head_w; ln.dot_b = P.head_b; ln.mask = mask; ln.pred = pred; }
         if (Lw.depthwise) {
-            CHK(dwconv(e, st, Lw.dw, src, sc.u, B, S, P.dt));
+            FS2_TRY(dwconv(e, st, Lw.dw, src, sc.u, B, S, P.dt));
             ln.tmp = other;  // src (= other for j > 0) is dead once the depth-wise conv has run
-            CHK(gemm(e, st, Lw.c, sc.u, keep ? out : nullptr, M, S, true, P.dt, {.ln = &ln}));
+            FS2_TRY(gemm(e, st, Lw.c, sc.u, keep ? out : nullptr, M, S, true, P.dt, {.ln = &ln}));
         } else {
             ln.tmp = sc.u;
-            CHK(gemm(e, st, Lw.c, src, keep ? out : nullptr, M, S, true, P.dt, {.ln = &ln}));
+            FS2_TRY(gemm(e, st, Lw.c, src, keep ? out : nullptr, M, S, true, P.dt, {.ln = &ln}));
         }
         src = out;
     }
@@ -1152,9 +1060,9 @@ size_t decode_scratch_need(const fs2_engine* e, int B, int T) {
 }
 // Grow-only engine arena, or the caller's buffer (fs2_set_workspace) which must already be large enough.
 int ensure_arena(fs2_engine* e, Arena& ar, size_t need, const char* what) {
-    if (need > ar.cap && !ar.external) HIPCHK(e, hipDeviceSynchronize());  // earlier work may still read the old block
+    if (need > ar.cap && !ar.external) FS2_HIP(e, hipDeviceSynchronize());  // earlier work may still read the old block
     if (ar.reserve(need) != FS2_OK)
-        return fail(e, FS2_ERR_NOMEM, ar.external ? "caller workspace too small: %s needs %zu bytes (fs2_workspace_bytes)"
+        return e->fail(FS2_ERR_NOMEM, ar.external ? "caller workspace too small: %s needs %zu bytes (fs2_workspace_bytes)"
                                                   : "%s arena: hipMalloc of %zu bytes failed", what, need);
     return FS2_OK;
 }
@@ -1162,10 +1070,10 @@ int ensure_arena(fs2_engine* e, Arena& ar, size_t need, const char* what) {
 int tap_store(fs2_engine* e, hipStream_t st, const std::string& name, const void* src, size_t n, int src_dt,
               Arena* arena = nullptr) {
     void* dst = (arena ? arena : &e->dbg)->take(n * 4);
-    if (!dst) return fail(e, FS2_ERR_NOMEM, "debug arena too small");
+    if (!dst) return e->fail(FS2_ERR_NOMEM, "debug arena too small");
     ConvertArgs a{src, dst, n};
     const int r = launch_convert(a, src_dt, FS2_F32, st);
-    if (r != FS2_OK) return fail(e, r, "convert launch failed");
+    if (r != FS2_OK) return e->fail(r, "convert launch failed");
     e->taps[name] = {dst, n * 4};
     return FS2_OK;
 }
@@ -1209,7 +1117,6 @@ int fs2_create(const fs2_config* cfg, fs2_engine** out) {
     if (!cfg || !out) return FS2_ERR_ARG;
     fs2_engine* e = new fs2_engine();
     e->cfg = *cfg;
-    e->err[0] = 0;
     *out = e;  // returned even on failure so the caller can read fs2_last_error, then destroy
     const int r = check_config(e);
     if (r != FS2_OK) return r;
@@ -1232,7 +1139,6 @@ int fs2_clone(const fs2_engine* src, fs2_engine** out) {
     fs2_engine* e = new fs2_engine();
     static_cast<Model&>(*e) = *src;     // shared: the weights stay where they are (dev_allocs counts the owners)
     static_cast<Switches&>(*e) = *src;  // inherited
-    e->err[0] = 0;
     e->finalized = true;
     *out = e;
     return FS2_OK;
@@ -1259,26 +1165,16 @@ int fs2_destroy(fs2_engine* e) {
 
 int fs2_load_weight(fs2_engine* e, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
     if (!e || !name || !data || !shape || ndim < 0) return FS2_ERR_ARG;
-    if (e->finalized) return fail(e, FS2_ERR_STATE, "weights already finalized");
+    if (e->finalized) return e->fail(FS2_ERR_STATE, "weights already finalized");
     static const char kDur[] = "variance_adaptor.duration_predictor.";
     if (e->dur_stochastic && !strncmp(name, kDur, sizeof(kDur) - 1)) {
         const int r = fs2_sdp_load_weight(e->sdp.get(), name + sizeof(kDur) - 1, data, shape, ndim);
-        if (r != FS2_OK) return fail(e, r, "%s (stochastic duration predictor: '%s')", fs2_sdp_last_error(e->sdp.get()), name);
+        if (r != FS2_OK) return e->fail(r, "%s (stochastic duration predictor: '%s')", fs2_sdp_last_error(e->sdp.get()), name);
         e->weight_seen = true;
         return FS2_OK;
     }
-    CHK(check_deterministic_duration(e));
-    auto it = e->spec.find(name);
-    if (it == e->spec.end()) return fail(e, FS2_ERR_WEIGHT, "unexpected weight '%s' for this config", name);
-    const std::vector<int64_t>& want = it->second;
-    bool ok = (size_t)ndim == want.size();
-    size_t n = 1;
-    for (int i = 0; ok && i < ndim; ++i) { ok = shape[i] == want[i]; n *= (size_t)shape[i]; }
-    if (!ok) return fail(e, FS2_ERR_WEIGHT, "shape mismatch for '%s'", name);
-    HostTensor t;
-    t.shape.assign(shape, shape + ndim);
-    t.data.assign(data, data + n);
-    e->host[name] = std::move(t);
+    FS2_TRY(check_deterministic_duration(e));
+    FS2_TRY(e->w.load(*e, name, data, shape, ndim));
     e->weight_seen = true;
     return FS2_OK;
 }
@@ -1286,66 +1182,65 @@ int fs2_load_weight(fs2_engine* e, const char* name, const float* data, const in
 int fs2_finalize(fs2_engine* e) {
     if (!e) return FS2_ERR_ARG;
     if (e->finalized) return FS2_OK;
-    CHK(check_deterministic_duration(e));
-    for (auto& kv : e->spec)
-        if (!e->host.count(kv.first)) return fail(e, FS2_ERR_WEIGHT, "missing weight '%s'", kv.first.c_str());
+    FS2_TRY(check_deterministic_duration(e));
+    if (const char* missing = e->w.first_missing()) return e->fail(FS2_ERR_WEIGHT, "missing weight '%s'", missing);
     const fs2_config& c = e->cfg;
     const int H = c.hidden;
-    CHK(up_vec(e, "phone_embedding.weight", &e->phone_table));
-    CHK(up_vec(e, "positional_encoding.pe", &e->pe));
-    CHK(up_vec(e, "speaker_embedding.projection.weight", &e->spk_w));
-    CHK(up_vec(e, "speaker_embedding.projection.bias", &e->spk_b));
+    FS2_TRY(up_vec(e, "phone_embedding.weight", &e->phone_table));
+    FS2_TRY(up_vec(e, "positional_encoding.pe", &e->pe));
+    FS2_TRY(up_vec(e, "speaker_embedding.projection.weight", &e->spk_w));
+    FS2_TRY(up_vec(e, "speaker_embedding.projection.bias", &e->spk_b));
     e->enc.resize(c.enc_layers);
     for (int i = 0; i < c.enc_layers; ++i)
-        CHK(make_layer(e, "encoder.layers." + std::to_string(i), H, c.enc_filter, c.enc_depthwise, &e->enc[i], e->fdt));
+        FS2_TRY(make_layer(e, "encoder.layers." + std::to_string(i), H, c.enc_filter, c.enc_depthwise, &e->enc[i], e->fdt));
     e->dec.resize(c.dec_layers);
     for (int i = 0; i < c.dec_layers; ++i)
-        CHK(make_layer(e, "decoder.layers." + std::to_string(i), H, c.dec_filter, c.dec_depthwise, &e->dec[i], e->bdt));
+        FS2_TRY(make_layer(e, "decoder.layers." + std::to_string(i), H, c.dec_filter, c.dec_depthwise, &e->dec[i], e->bdt));
     if (H > 256) {  // stacks of wide depth-wise 16-bit (bf16 / f16) blocks: norm2 of block i - 1 folded into the in-projection of block i
         const auto fold_in_proj = [&](const std::string& stack, int i, LayerW* L) -> int {
             const std::string p = stack + std::to_string(i) + ".self_attn.in_proj_";
-            CHK(make_norm_folded(e, p + "weight", p + "bias", stack + std::to_string(i - 1) + ".norm2", &L->in_proj_f, &L->in_wg, L->in_proj.dt));
+            FS2_TRY(make_norm_folded(e, p + "weight", p + "bias", stack + std::to_string(i - 1) + ".norm2", &L->in_proj_f, &L->in_wg, L->in_proj.dt));
             L->has_fold = true;
             return FS2_OK;
         };
-        for (int i = 1; i < c.enc_layers && c.enc_depthwise && e->fdt == FS2_BF16; ++i) CHK(fold_in_proj("encoder.layers.", i, &e->enc[i]));
-        for (int i = 1; i < c.dec_layers && c.dec_depthwise && is_16bit(e->bdt); ++i) CHK(fold_in_proj("decoder.layers.", i, &e->dec[i]));
+        for (int i = 1; i < c.enc_layers && c.enc_depthwise && e->fdt == FS2_BF16; ++i) FS2_TRY(fold_in_proj("encoder.layers.", i, &e->enc[i]));
+        for (int i = 1; i < c.dec_layers && c.dec_depthwise && is_16bit(e->bdt); ++i) FS2_TRY(fold_in_proj("decoder.layers.", i, &e->dec[i]));
     }
     if (e->dur_stochastic) {
         const int r = fs2_sdp_finalize(e->sdp.get());
-        if (r != FS2_OK) return fail(e, r, "stochastic duration predictor: %s", fs2_sdp_last_error(e->sdp.get()));
+        if (r != FS2_OK) return e->fail(r, "stochastic duration predictor: %s", fs2_sdp_last_error(e->sdp.get()));
     } else {
-        CHK(make_predictor(e, "variance_adaptor.duration_predictor", c.dur_nlayers, c.dur_filter, c.dur_depthwise, &e->dur, e->fdt));
+        FS2_TRY(make_predictor(e, "variance_adaptor.duration_predictor", c.dur_nlayers, c.dur_filter, c.dur_depthwise, &e->dur, e->fdt));
     }
     e->vars.resize(c.n_variances);
     for (int v = 0; v < c.n_variances; ++v) {
         const std::string p = std::string("variance_adaptor.encoders.") + c.var_names[v];
-        CHK(make_predictor(e, p + ".predictor", c.var_nlayers[v], c.var_filter, c.var_depthwise, &e->vars[v].pred, e->fdt, c.var_cwt[v] != 0));
+        FS2_TRY(make_predictor(e, p + ".predictor", c.var_nlayers[v], c.var_filter, c.var_depthwise, &e->vars[v].pred, e->fdt, c.var_cwt[v] != 0));
         if (c.var_cwt[v]) {
-            CHK(up_vec(e, p + ".mean_std_linear.weight", &e->vars[v].pred.ms_w));
-            CHK(up_vec(e, p + ".mean_std_linear.bias", &e->vars[v].pred.ms_b));
+            FS2_TRY(up_vec(e, p + ".mean_std_linear.weight", &e->vars[v].pred.ms_w));
+            FS2_TRY(up_vec(e, p + ".mean_std_linear.bias", &e->vars[v].pred.ms_b));
         }
-        CHK(up_vec(e, p + ".bins", &e->vars[v].bins));
-        CHK(up_vec(e, p + ".embedding.weight", &e->vars[v].emb));
+        FS2_TRY(up_vec(e, p + ".bins", &e->vars[v].bins));
+        FS2_TRY(up_vec(e, p + ".embedding.weight", &e->vars[v].emb));
     }
-    CHK(make_conv(e, "linear.weight", "linear.bias", &e->mel, e->bdt));
+    FS2_TRY(make_conv(e, "linear.weight", "linear.bias", &e->mel, e->bdt));
     // (the row-scaled product with an fp32 store exists for narrow heads only - route_gemm's GF_RS_NARROW row: N < 192 -; a wider mel head keeps the
     //  normalise-only pass + the plain mel GEMM)
     if (H > 256 && c.dec_layers > 0 && c.dec_depthwise && is_16bit(e->bdt) && c.n_mels < 192) {
         // mel = Linear(LN2_last(v2)) evaluated on v2
-        CHK(make_norm_folded(e, "linear.weight", "linear.bias", "decoder.layers." + std::to_string(c.dec_layers - 1) + ".norm2", &e->mel_f, &e->mel_wg, e->bdt));
+        FS2_TRY(make_norm_folded(e, "linear.weight", "linear.bias", "decoder.layers." + std::to_string(c.dec_layers - 1) + ".norm2", &e->mel_f, &e->mel_wg, e->bdt));
         e->mel_fold = true;
     }
     e->priors_w.resize(c.n_priors);
     for (int p = 0; p < c.n_priors; ++p) {
         const std::string q = std::string("prior_embeddings.") + c.prior_names[p];
-        CHK(up_vec(e, q + ".bins", &e->priors_w[p].bins));
+        FS2_TRY(up_vec(e, q + ".bins", &e->priors_w[p].bins));
         // relu(Embedding[idx]) (model.py:161) == Embedding'[idx] with the table rectified once here
         std::vector<float> t = W(e, q + ".embedding.weight").data;
         for (float& v : t) v = v > 0.f ? v : 0.f;
-        CHK(upload_f32(e, t.data(), t.size(), &e->priors_w[p].emb));
+        FS2_TRY(upload_f32(e, t.data(), t.size(), &e->priors_w[p].emb));
     }
-    e->host.clear();
+    e->w.drop();
     e->finalized = true;
     return FS2_OK;
 }
@@ -1376,9 +1271,9 @@ int fs2_set_tuning(fs2_engine* e, int32_t knob) {
     // calling thread only; here they would label a default-configuration measurement as switched
     const bool op_only = (knob >= 900 && knob <= 909) || knob == 1000 || knob == 1001 || knob == 1100 || knob == 1101 ||
                          knob == 700 || knob == 701 || knob == 800 || knob == 801 || knob == 500 || knob == 501;
-    if (op_only) return fail(e, FS2_ERR_ARG, "fs2_set_tuning(%d): an operator-level switch no engine launch reads (use fs2_op_set_gemm_variant on the calling thread)", (int)knob);
+    if (op_only) return e->fail(FS2_ERR_ARG, "fs2_set_tuning(%d): an operator-level switch no engine launch reads (use fs2_op_set_gemm_variant on the calling thread)", (int)knob);
     const int r = apply_knob(e->tune, knob);
-    if (r != FS2_OK) return fail(e, r, "fs2_set_tuning(%d): not a defined switch", (int)knob);
+    if (r != FS2_OK) return e->fail(r, "fs2_set_tuning(%d): not a defined switch", (int)knob);
     return FS2_OK;
 }
 
@@ -1405,10 +1300,10 @@ int fs2_workspace_bytes(const fs2_engine* e, int32_t B, int32_t L, int32_t T, si
 }
 
 int fs2_set_workspace(fs2_engine* e, void* persist, size_t persist_bytes_, void* scratch, size_t scratch_bytes_) {
-    if (!e || (persist == nullptr) != (scratch == nullptr)) return e ? fail(e, FS2_ERR_ARG, "give both buffers or neither") : FS2_ERR_ARG;
-    if (((uintptr_t)persist | (uintptr_t)scratch) & 255) return fail(e, FS2_ERR_ARG, "workspace buffers must be 256-byte aligned");
+    if (!e || (persist == nullptr) != (scratch == nullptr)) return e ? e->fail(FS2_ERR_ARG, "give both buffers or neither") : FS2_ERR_ARG;
+    if (((uintptr_t)persist | (uintptr_t)scratch) & 255) return e->fail(FS2_ERR_ARG, "workspace buffers must be 256-byte aligned");
     if (e->mid_forward && (char*)persist != e->persist.base)
-        return fail(e, FS2_ERR_STATE, "the persist buffer holds the encoder state between fs2_encode and fs2_decode: only scratch may change there");
+        return e->fail(FS2_ERR_STATE, "the persist buffer holds the encoder state between fs2_encode and fs2_decode: only scratch may change there");
     if (!e->mid_forward) e->persist.adopt(persist, persist_bytes_);
     e->scratch.adopt(scratch, scratch_bytes_);
     return FS2_OK;
@@ -1416,9 +1311,9 @@ int fs2_set_workspace(fs2_engine* e, void* persist, size_t persist_bytes_, void*
 
 int fs2_set_frames(fs2_engine* e, int32_t T) {
     if (!e) return FS2_ERR_ARG;
-    if (!e->encoded) return fail(e, FS2_ERR_STATE, "fs2_set_frames without a preceding successful fs2_encode");
-    if (T < e->T) return fail(e, FS2_ERR_ARG, "fs2_set_frames can only pad: T=%d < this batch's %d", T, e->T);
-    if (T > e->cfg.max_frames || T > e->cfg.pe_len) return fail(e, FS2_ERR_SHAPE, "T=%d exceeds max_frames/positional table", T);
+    if (!e->encoded) return e->fail(FS2_ERR_STATE, "fs2_set_frames without a preceding successful fs2_encode");
+    if (T < e->T) return e->fail(FS2_ERR_ARG, "fs2_set_frames can only pad: T=%d < this batch's %d", T, e->T);
+    if (T > e->cfg.max_frames || T > e->cfg.pe_len) return e->fail(FS2_ERR_SHAPE, "T=%d exceeds max_frames/positional table", T);
     e->T = T;
     return FS2_OK;
 }
@@ -1440,7 +1335,7 @@ static int variance_stage(fs2_engine* e, hipStream_t st, int v, void*& x, void*&
     const EmbedTail tl{xalt, e->vars[v].bins, e->vars[v].emb, c.var_nbins, c.var_std[v], c.var_mean[v],
                        add_pe_spk ? e->pe : nullptr, add_pe_spk ? e->ps.spk : nullptr};
     bool tail_done = false;
-    CHK(predictor(e, st, e->vars[v].pred, x, B, S, mask, vpred, sc, cwo, tail_ok ? &tl : nullptr, &tail_done));
+    FS2_TRY(predictor(e, st, e->vars[v].pred, x, B, S, mask, vpred, sc, cwo, tail_ok ? &tl : nullptr, &tail_done));
     if (tail_done) {
         std::swap(x, xalt);
         return FS2_OK;
@@ -1448,14 +1343,14 @@ static int variance_stage(fs2_engine* e, hipStream_t st, int v, void*& x, void*&
     int32_t* idx = nullptr;
     if (e->debug) {
         idx = (int32_t*)dbg.take(M * 4);
-        if (!idx) return fail(e, FS2_ERR_NOMEM, "debug arena too small");
+        if (!idx) return e->fail(FS2_ERR_NOMEM, "debug arena too small");
         e->taps[std::string("bucket_") + c.var_names[v]] = {idx, M * 4};
     }
     Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * M * H * esz);
     BucketArgs ba{x, vpred, e->vars[v].bins, e->vars[v].emb, c.var_nbins, c.var_std[v], c.var_mean[v],
                   add_pe_spk ? e->pe : nullptr, add_pe_spk ? e->ps.spk : nullptr, x, idx, B, S, (int)H,
                   e->forced_idx[v], 0, e->forced_tgt[v]};
-    if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "bucket_embed launch failed");
+    if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "bucket_embed launch failed");
     return FS2_OK;
 }
 static int run_phase(fs2_engine* e, std::vector<fs2_engine::GraphEntry>& cache, const std::vector<uint64_t>& key, bool plain,
@@ -1463,11 +1358,11 @@ static int run_phase(fs2_engine* e, std::vector<fs2_engine::GraphEntry>& cache, 
 
 int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32_t B, int32_t L,
                const int32_t* forced, void* stream, int32_t* T_out) {
-    if (!e || !phones || !speaker || !T_out || B <= 0 || L <= 0) return e ? fail(e, FS2_ERR_ARG, "bad encode argument") : FS2_ERR_ARG;
-    if (!e->finalized) return fail(e, FS2_ERR_STATE, "fs2_finalize not called");
-    if (L > e->cfg.pe_len) return fail(e, FS2_ERR_SHAPE, "L=%d exceeds positional table %d", L, e->cfg.pe_len);
+    if (!e || !phones || !speaker || !T_out || B <= 0 || L <= 0) return e ? e->fail(FS2_ERR_ARG, "bad encode argument") : FS2_ERR_ARG;
+    if (!e->finalized) return e->fail(FS2_ERR_STATE, "fs2_finalize not called");
+    if (L > e->cfg.pe_len) return e->fail(FS2_ERR_SHAPE, "L=%d exceeds positional table %d", L, e->cfg.pe_len);
     if (e->dur_stochastic && (!e->noise_dev || e->noise_B != B || e->noise_L != L))
-        return fail(e, FS2_ERR_STATE, "fs2_set_duration_noise(B=%d, L=%d) required before fs2_encode of a stochastic engine", B, L);
+        return e->fail(FS2_ERR_STATE, "fs2_set_duration_noise(B=%d, L=%d) required before fs2_encode of a stochastic engine", B, L);
     hipStream_t st = (hipStream_t)stream;
     const fs2_config& c = e->cfg;
     e->encoded = false;
@@ -1477,17 +1372,17 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
     e->taps.clear();
     // the arenas are reused across calls: earlier work on this stream that still reads them is
     // ordered before the kernels below; a (rare) growth reallocates after a device sync
-    CHK(ensure_arena(e, e->persist, persist_need(e, B, L), "persist"));
-    CHK(ensure_arena(e, e->scratch, encode_scratch_need(e, B, L), "scratch"));
-    if (!layout_persist(e, e->persist, B, L, &e->ps)) return fail(e, FS2_ERR_NOMEM, "persist arena too small");
+    FS2_TRY(ensure_arena(e, e->persist, persist_need(e, B, L), "persist"));
+    FS2_TRY(ensure_arena(e, e->scratch, encode_scratch_need(e, B, L), "scratch"));
+    if (!layout_persist(e, e->persist, B, L, &e->ps)) return e->fail(FS2_ERR_NOMEM, "persist arena too small");
     EncodeScratch es;
-    if (!layout_encode_scratch(e, e->scratch, B, L, &es)) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
+    if (!layout_encode_scratch(e, e->scratch, B, L, &es)) return e->fail(FS2_ERR_NOMEM, "scratch arena too small");
     bool pv_forced = false;
     for (int v = 0; v < c.n_variances; ++v) pv_forced = pv_forced || (c.var_level[v] && (e->forced_idx[v] || e->forced_tgt[v]));
     if (e->h_pinned_cap < 2 * B) {
         if (e->h_pinned) (void)hipHostFree(e->h_pinned);
         e->h_pinned = nullptr;
-        HIPCHK(e, hipHostMalloc((void**)&e->h_pinned, (size_t)2 * B * 4, hipHostMallocDefault));
+        FS2_HIP(e, hipHostMalloc((void**)&e->h_pinned, (size_t)2 * B * 4, hipHostMallocDefault));
         e->h_pinned_cap = 2 * B;
         drop_graphs(e);  // captured copies point at the old pinned block
     }
@@ -1498,15 +1393,15 @@ int fs2_encode(fs2_engine* e, const int64_t* phones, const float* speaker, int32
                                      (uint64_t)e->defer_ln, (uint64_t)e->front_split, (uint64_t)e->fold_ln};
         // a prior tensor / a phone-level forced target / the duration noise is a one-shot pointer of the call
         const bool plain = c.n_priors != 0 || pv_forced || e->dur_stochastic;
-        CHK(run_phase(e, e->egraphs, key, plain, st, [&](hipStream_t s2) { return encode_body(e, phones, speaker, forced, es, s2); }));
+        FS2_TRY(run_phase(e, e->egraphs, key, plain, st, [&](hipStream_t s2) { return encode_body(e, phones, speaker, forced, es, s2); }));
     }
-    HIPCHK(e, hipStreamSynchronize(st));  // the one host sync of the forward (output shape)
+    FS2_HIP(e, hipStreamSynchronize(st));  // the one host sync of the forward (output shape)
     e->totals.assign(e->h_pinned, e->h_pinned + B);
     e->guard.assign(e->h_pinned + B, e->h_pinned + 2 * B);
     int mx = 0;
     for (int b = 0; b < B; ++b) mx = e->totals[b] > mx ? e->totals[b] : mx;
     e->T = mx < c.max_frames ? mx : c.max_frames;                            // model.py:355
-    if (e->T > c.pe_len) return fail(e, FS2_ERR_SHAPE, "T=%d exceeds positional table %d", e->T, c.pe_len);
+    if (e->T > c.pe_len) return e->fail(FS2_ERR_SHAPE, "T=%d exceeds positional table %d", e->T, c.pe_len);
     *T_out = e->T;
     e->encoded = true;
     e->mid_forward = true;
@@ -1522,36 +1417,36 @@ static int encode_body(fs2_engine* e, const int64_t* phones, const float* speake
     {   // speaker projection + phone embedding + PE                       fastspeech2.py:651-660
         Bracket br(e, FS2_K_ROWOPS, st, 0, ML * H * esz);
         SpkProjArgs sp{speaker, e->spk_w, e->spk_b, ps.spk, B, (int)H, c.dvec_dim};
-        if (launch_spk_proj(sp, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "spk_proj launch failed");
+        if (launch_spk_proj(sp, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "spk_proj launch failed");
         EmbedArgs em{phones, e->phone_table, e->pe, ps.spk, ps.xA, ps.src_mask, B, L, (int)H, c.n_phones};
-        if (launch_embed(em, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "embed launch failed");
+        if (launch_embed(em, e->fdt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "embed launch failed");
         MaskBitsArgs mb{ps.src_mask, sc.bits, B, L, sc.nw64};
-        if (launch_mask_bits(mb, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "mask_bits launch failed");
+        if (launch_mask_bits(mb, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "mask_bits launch failed");
     }
-    CHK(run_stack(e, st, e->enc, ps.xA, ps.xB, B, L, c.enc_heads, sc, false));  // fastspeech2.py:685
+    FS2_TRY(run_stack(e, st, e->enc, ps.xA, ps.xB, B, L, c.enc_heads, sc, false));  // fastspeech2.py:685
     if (e->debug) {  // the reference's encoder output, i.e. before the prior embeddings are added
         const size_t need_d = al(ML * H * 4) + (size_t)c.n_variances * al(ML * 4) + 4096;
-        if (need_d > e->dbg_enc.cap) HIPCHK(e, hipDeviceSynchronize());
-        if (e->dbg_enc.reserve(need_d) != FS2_OK) return fail(e, FS2_ERR_NOMEM, "debug arena");
-        CHK(tap_store(e, st, "encoder_out", ps.xA, ML * H, e->fdt, &e->dbg_enc));
+        if (need_d > e->dbg_enc.cap) FS2_HIP(e, hipDeviceSynchronize());
+        if (e->dbg_enc.reserve(need_d) != FS2_OK) return e->fail(FS2_ERR_NOMEM, "debug arena");
+        FS2_TRY(tap_store(e, st, "encoder_out", ps.xA, ML * H, e->fdt, &e->dbg_enc));
     }
     if (c.n_priors) {                                                        // fastspeech2.py:687-692
-        if (!e->priors_dev || e->priors_B != B) return fail(e, FS2_ERR_STATE, "fs2_set_priors(B=%d) required before fs2_encode", B);
+        if (!e->priors_dev || e->priors_B != B) return e->fail(FS2_ERR_STATE, "fs2_set_priors(B=%d) required before fs2_encode", B);
         for (int p = 0; p < c.n_priors; ++p) {
             BucketArgs ba{ps.xA, e->priors_dev + (size_t)p * B, e->priors_w[p].bins, e->priors_w[p].emb, c.var_nbins,
                           1.0f, 0.0f, nullptr, nullptr, ps.xA, nullptr, B, L, (int)H, nullptr, 1};
-            if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "prior embedding launch failed");
+            if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "prior embedding launch failed");
         }
         e->priors_dev = nullptr;  // one-shot
     }
     // duration predictor + rounding + prefix sums                          model.py:259,299-309
     if (e->dur_stochastic) {  // model.py:260-268: the flow predictor on encoder_out.detach(), noise from the caller (sdp.py:335-338)
-        HIPCHK(e, hipMemcpyAsync(es.sdp_noise, e->noise_dev, (size_t)B * 2 * L * 4, hipMemcpyDeviceToDevice, st));
+        FS2_HIP(e, hipMemcpyAsync(es.sdp_noise, e->noise_dev, (size_t)B * 2 * L * 4, hipMemcpyDeviceToDevice, st));
         e->noise_dev = nullptr;  // one-shot
         const int r = fs2_sdp_forward(e->sdp.get(), e->fdt, ps.xA, ps.src_mask, es.sdp_noise, ps.dur_pred, es.sdp_ws, es.sdp_ws_bytes, B, L, st);
-        if (r != FS2_OK) return fail(e, r, "stochastic duration predictor: %s", fs2_sdp_last_error(e->sdp.get()));
+        if (r != FS2_OK) return e->fail(r, "stochastic duration predictor: %s", fs2_sdp_last_error(e->sdp.get()));
     } else {
-        CHK(predictor(e, st, e->dur, ps.xA, B, L, ps.src_mask, ps.dur_pred, sc));
+        FS2_TRY(predictor(e, st, e->dur, ps.xA, B, L, ps.src_mask, ps.dur_pred, sc));
     }
     // phone-level variance encoders (variance_levels[i] == "phone"), in list order, AFTER the duration predictor has seen x and BEFORE
     // the length regulator: each adds its embedding to the rows that get regulated                      model.py:276-294
@@ -1562,20 +1457,20 @@ static int encode_body(fs2_engine* e, const int64_t* phones, const float* speake
     for (int v = 0; v < c.n_variances; ++v) {
         if (!c.var_level[v]) continue;
         const CwtOut cwo{es.spec12, ps.pv_ms[v], ps.pv_spec[v]};
-        CHK(variance_stage(e, st, v, x, xalt, B, L, ps.src_mask, ps.pv_pred[v], sc, c.var_cwt[v] ? &cwo : nullptr, false, e->dbg_enc));
+        FS2_TRY(variance_stage(e, st, v, x, xalt, B, L, ps.src_mask, ps.pv_pred[v], sc, c.var_cwt[v] ? &cwo : nullptr, false, e->dbg_enc));
         e->forced_idx[v] = nullptr, e->forced_tgt[v] = nullptr;  // one-shot, consumed here
     }
-    if (x != ps.xA) HIPCHK(e, hipMemcpyAsync(ps.xA, x, ML * H * esz, hipMemcpyDeviceToDevice, st));  // an odd number of swaps
+    if (x != ps.xA) FS2_HIP(e, hipMemcpyAsync(ps.xA, x, ML * H * esz, hipMemcpyDeviceToDevice, st));  // an odd number of swaps
     // stochastic: ceil(exp(logw)), 0 where logw == 0 (model.py:302-305) in front of the same guard and prefix sums
     DurationArgs da{ps.dur_pred, ps.src_mask, forced, ps.d_dur, ps.d_cum, ps.d_totals, ps.d_guard, B, L, e->dur_stochastic ? 1 : 0};
-    if (launch_durations(da, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "durations launch failed");
-    HIPCHK(e, hipMemcpyAsync(e->h_pinned, ps.d_totals, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st));
+    if (launch_durations(da, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "durations launch failed");
+    FS2_HIP(e, hipMemcpyAsync(e->h_pinned, ps.d_totals, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st));
     return FS2_OK;
 }
 
 int fs2_set_priors(fs2_engine* e, const float* priors_device, int32_t B) {
     if (!e || !priors_device || B <= 0) return FS2_ERR_ARG;
-    if (e->cfg.n_priors == 0) return fail(e, FS2_ERR_STATE, "this engine was configured without priors");
+    if (e->cfg.n_priors == 0) return e->fail(FS2_ERR_STATE, "this engine was configured without priors");
     e->priors_dev = priors_device;
     e->priors_B = B;
     return FS2_OK;
@@ -1584,28 +1479,28 @@ int fs2_set_priors(fs2_engine* e, const float* priors_device, int32_t B) {
 int fs2_set_stochastic_duration(fs2_engine* e, int32_t on) {
     if (!e) return FS2_ERR_ARG;
     if (e->finalized || e->weight_seen)
-        return fail(e, FS2_ERR_STATE, "fs2_set_stochastic_duration is legal only between fs2_create and the first fs2_load_weight");
-    if (e->spec.empty()) return fail(e, FS2_ERR_STATE, "fs2_create did not succeed");
+        return e->fail(FS2_ERR_STATE, "fs2_set_stochastic_duration is legal only between fs2_create and the first fs2_load_weight");
+    if (e->w.empty()) return e->fail(FS2_ERR_STATE, "fs2_create did not succeed");
     const fs2_config& c = e->cfg;
     std::shared_ptr<fs2_sdp> h;
     if (on) {
         if (c.dur_depthwise)
-            return fail(e, FS2_ERR_SHAPE, "duration_stochastic with duration_depthwise_conv: the reference builds no such predictor (model.py:196-200)");
+            return e->fail(FS2_ERR_SHAPE, "duration_stochastic with duration_depthwise_conv: the reference builds no such predictor (model.py:196-200)");
         fs2_sdp* raw = nullptr;
         const int r = fs2_sdp_create(FS2_ABI_VERSION, c.hidden, c.dur_filter, c.dur_kernel, c.dur_nlayers, &raw);
         h.reset(raw, [](fs2_sdp* p) { if (p) (void)fs2_sdp_destroy(p); });
-        if (r != FS2_OK) return fail(e, r, "stochastic duration predictor: %s", raw ? fs2_sdp_last_error(raw) : "out of memory");
+        if (r != FS2_OK) return e->fail(r, "stochastic duration predictor: %s", raw ? fs2_sdp_last_error(raw) : "out of memory");
     }
     e->dur_stochastic = on != 0;
     e->sdp = h;
-    e->spec.clear();
+    e->w.clear();
     build_spec(e);
     return FS2_OK;
 }
 
 int fs2_set_duration_noise(fs2_engine* e, const float* noise_device, int32_t B, int32_t L) {
     if (!e || !noise_device || B <= 0 || L <= 0) return FS2_ERR_ARG;
-    if (!e->dur_stochastic) return fail(e, FS2_ERR_STATE, "this engine's duration predictor is not stochastic (fs2_set_stochastic_duration)");
+    if (!e->dur_stochastic) return e->fail(FS2_ERR_STATE, "this engine's duration predictor is not stochastic (fs2_set_stochastic_duration)");
     e->noise_dev = noise_device;
     e->noise_B = B;
     e->noise_L = L;
@@ -1627,66 +1522,66 @@ static int decode_body(fs2_engine* e, const fs2_outputs* out, hipStream_t st) {
     // launches - three hipMemcpyAsync cost the host ~15 us each, which the GPU would otherwise spend idle at the seam
     const PersistBufs& ps = e->ps;
     auto phone_outputs = [&]() -> int {
-        if (out->duration_prediction) HIPCHK(e, hipMemcpyAsync(out->duration_prediction, ps.dur_pred, ML * 4, hipMemcpyDeviceToDevice, st));
-        if (out->duration_rounded) HIPCHK(e, hipMemcpyAsync(out->duration_rounded, ps.d_dur, ML * 4, hipMemcpyDeviceToDevice, st));
-        if (out->src_mask) HIPCHK(e, hipMemcpyAsync(out->src_mask, ps.src_mask, ML, hipMemcpyDeviceToDevice, st));
+        if (out->duration_prediction) FS2_HIP(e, hipMemcpyAsync(out->duration_prediction, ps.dur_pred, ML * 4, hipMemcpyDeviceToDevice, st));
+        if (out->duration_rounded) FS2_HIP(e, hipMemcpyAsync(out->duration_rounded, ps.d_dur, ML * 4, hipMemcpyDeviceToDevice, st));
+        if (out->src_mask) FS2_HIP(e, hipMemcpyAsync(out->src_mask, ps.src_mask, ML, hipMemcpyDeviceToDevice, st));
         for (int v = 0; v < c.n_variances; ++v) {  // phone-level variances: (B, L) outputs, produced by the encode phase
             if (!c.var_level[v]) continue;
-            if (out->variances[v]) HIPCHK(e, hipMemcpyAsync(out->variances[v], ps.pv_pred[v], ML * 4, hipMemcpyDeviceToDevice, st));
-            if (c.var_cwt[v] && out->var_spectrogram[v]) HIPCHK(e, hipMemcpyAsync(out->var_spectrogram[v], ps.pv_spec[v], ML * 10 * 4, hipMemcpyDeviceToDevice, st));
-            if (c.var_cwt[v] && out->var_mean_std[v]) HIPCHK(e, hipMemcpyAsync(out->var_mean_std[v], ps.pv_ms[v], (size_t)B * 8, hipMemcpyDeviceToDevice, st));
+            if (out->variances[v]) FS2_HIP(e, hipMemcpyAsync(out->variances[v], ps.pv_pred[v], ML * 4, hipMemcpyDeviceToDevice, st));
+            if (c.var_cwt[v] && out->var_spectrogram[v]) FS2_HIP(e, hipMemcpyAsync(out->var_spectrogram[v], ps.pv_spec[v], ML * 10 * 4, hipMemcpyDeviceToDevice, st));
+            if (c.var_cwt[v] && out->var_mean_std[v]) FS2_HIP(e, hipMemcpyAsync(out->var_mean_std[v], ps.pv_ms[v], (size_t)B * 8, hipMemcpyDeviceToDevice, st));
         }
         return FS2_OK;
     };
     if (T == 0) { e->encoded = false; e->mid_forward = false; return phone_outputs(); }
 
-    CHK(ensure_arena(e, e->scratch, decode_scratch_need(e, B, T), "scratch"));  // too small: the caller may retry with more
+    FS2_TRY(ensure_arena(e, e->scratch, decode_scratch_need(e, B, T), "scratch"));  // too small: the caller may retry with more
     e->mid_forward = false;  // from here on the encoder state is consumed by this call
     DecodeScratch ds;
-    if (!layout_decode_scratch(e, e->scratch, B, T, out, &ds)) return fail(e, FS2_ERR_NOMEM, "scratch arena too small");
+    if (!layout_decode_scratch(e, e->scratch, B, T, out, &ds)) return e->fail(FS2_ERR_NOMEM, "scratch arena too small");
     void *yA = ds.yA, *yB = ds.yB;  // swapped below: locals (run_phase's rule for a body)
     uint8_t* const tmask = ds.tmask;
     const LayerScratch& sc = ds.sc;
     if (e->debug) {
         const size_t need_d = 3 * al(MT * H * 4) + (size_t)c.n_variances * al(MT * 4) + 4096;
-        if (need_d > e->dbg.cap) HIPCHK(e, hipDeviceSynchronize());
-        if (e->dbg.reserve(need_d) != FS2_OK) return fail(e, FS2_ERR_NOMEM, "debug arena");
+        if (need_d > e->dbg.cap) FS2_HIP(e, hipDeviceSynchronize());
+        if (e->dbg.reserve(need_d) != FS2_OK) return e->fail(FS2_ERR_NOMEM, "debug arena");
     }
 
     {   // length regulator                                                  model.py:311,349-370
         Bracket br(e, FS2_K_ROWOPS, st, 0, 2.0 * MT * H * esz);
         RegulateArgs ra{ps.xA, ps.d_cum, ps.d_totals, yA, tmask, B, L, T, (int)H};
-        if (launch_regulate(ra, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "regulate launch failed");
+        if (launch_regulate(ra, e->fdt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "regulate launch failed");
         MaskBitsArgs mb{tmask, sc.bits, B, T, sc.nw64};
-        if (launch_mask_bits(mb, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "mask_bits launch failed");
+        if (launch_mask_bits(mb, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "mask_bits launch failed");
     }
-    if (e->debug) CHK(tap_store(e, st, "regulated", yA, MT * H, e->fdt));
+    if (e->debug) FS2_TRY(tap_store(e, st, "regulated", yA, MT * H, e->fdt));
     // frame-level variance encoders, sequential                            model.py:315-333
     const bool fuse_pe = !e->debug;
     for (int v = 0; v < c.n_variances; ++v) {
         if (c.var_level[v]) continue;  // phone level: done by the encode phase
         const CwtOut cwo{ds.cw_spec, out->var_mean_std[v] ? out->var_mean_std[v] : ds.cw_ms, out->var_spectrogram[v]};
-        CHK(variance_stage(e, st, v, yA, yB, B, T, tmask, ds.vpred[v], sc, c.var_cwt[v] ? &cwo : nullptr, v == ds.last_frame_v && fuse_pe, e->dbg));
+        FS2_TRY(variance_stage(e, st, v, yA, yB, B, T, tmask, ds.vpred[v], sc, c.var_cwt[v] ? &cwo : nullptr, v == ds.last_frame_v && fuse_pe, e->dbg));
     }
-    if (e->debug) CHK(tap_store(e, st, "adaptor_out", yA, MT * H, e->fdt));
+    if (e->debug) FS2_TRY(tap_store(e, st, "adaptor_out", yA, MT * H, e->fdt));
     if (!fuse_pe || ds.last_frame_v < 0) {  // y = (x + pe) + spk            fastspeech2.py:705-718
         BucketArgs ba{yA, nullptr, nullptr, nullptr, 0, 0.f, 0.f, e->pe, ps.spk, yA, nullptr, B, T, (int)H, nullptr};
-        if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "pe/spk add launch failed");
+        if (launch_bucket_embed(ba, e->fdt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "pe/spk add launch failed");
     }
     if (e->fdt != e->bdt) {  // FS2_MIXED: the decoder's input, rounded once to the back dtype (yB is free until layer 0 writes it)
         ConvertArgs ca{yA, yB, MT * H};
-        if (launch_convert(ca, e->fdt, e->bdt, st) != FS2_OK) return fail(e, FS2_ERR_HIP, "front -> back conversion failed");
+        if (launch_convert(ca, e->fdt, e->bdt, st) != FS2_OK) return e->fail(FS2_ERR_HIP, "front -> back conversion failed");
         std::swap(yA, yB);
     }
     // (the mel head takes the last block's norm2 folded in where it can: nothing else reads the decoder's normalised output)
     bool dec_pre = false;
-    CHK(run_stack(e, st, e->dec, yA, yB, B, T, c.dec_heads, sc, true, e->mel_fold && out->mel && !e->debug, &dec_pre));  // fastspeech2.py:719-721
-    if (e->debug) CHK(tap_store(e, st, "decoder_out", yA, MT * H, e->bdt));
+    FS2_TRY(run_stack(e, st, e->dec, yA, yB, B, T, c.dec_heads, sc, true, e->mel_fold && out->mel && !e->debug, &dec_pre));  // fastspeech2.py:719-721
+    if (e->debug) FS2_TRY(tap_store(e, st, "decoder_out", yA, MT * H, e->bdt));
     if (out->mel && dec_pre) {                                               // fastspeech2.py:723
         const RowScale rs{sc.rsf, e->mel_wg};
-        CHK(gemm(e, st, e->mel_f, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, {.zero_rows = e->zero_pad_mel ? tmask : nullptr, .rowscale = &rs}));
+        FS2_TRY(gemm(e, st, e->mel_f, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, {.zero_rows = e->zero_pad_mel ? tmask : nullptr, .rowscale = &rs}));
     } else if (out->mel) {
-        CHK(gemm(e, st, e->mel, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, {.zero_rows = e->zero_pad_mel ? tmask : nullptr}));
+        FS2_TRY(gemm(e, st, e->mel, yA, out->mel, (int)MT, (int)MT, false, FS2_F32, {.zero_rows = e->zero_pad_mel ? tmask : nullptr}));
     }
     for (int v = 0; v < FS2_MAX_VARIANCES; ++v) e->forced_idx[v] = nullptr, e->forced_tgt[v] = nullptr;  // one-shot
     return phone_outputs();
@@ -1751,25 +1646,25 @@ static int run_phase(fs2_engine* e, std::vector<fs2_engine::GraphEntry>& cache, 
         }
         (void)hipGraphDestroy(graph);
     }
-    HIPCHK(e, hipEventRecord(e->gev_in, st));
-    HIPCHK(e, hipStreamWaitEvent(e->gstream, e->gev_in, 0));
-    HIPCHK(e, hipGraphLaunch(g->exec, e->gstream));
-    HIPCHK(e, hipEventRecord(e->gev_out, e->gstream));
-    HIPCHK(e, hipStreamWaitEvent(st, e->gev_out, 0));
+    FS2_HIP(e, hipEventRecord(e->gev_in, st));
+    FS2_HIP(e, hipStreamWaitEvent(e->gstream, e->gev_in, 0));
+    FS2_HIP(e, hipGraphLaunch(g->exec, e->gstream));
+    FS2_HIP(e, hipEventRecord(e->gev_out, e->gstream));
+    FS2_HIP(e, hipStreamWaitEvent(st, e->gev_out, 0));
     e->graph_replays++;
     return FS2_OK;
 }
 
 int fs2_decode(fs2_engine* e, const fs2_outputs* out, void* stream) {
     if (!e || !out) return FS2_ERR_ARG;
-    if (!e->encoded) return fail(e, FS2_ERR_STATE, "fs2_decode without a preceding successful fs2_encode");
+    if (!e->encoded) return e->fail(FS2_ERR_STATE, "fs2_decode without a preceding successful fs2_encode");
     hipStream_t st = (hipStream_t)stream;
     bool plain = !e->use_graph || e->debug || e->T == 0;
     for (int v = 0; v < FS2_MAX_VARIANCES && !plain; ++v) plain = e->forced_idx[v] || e->forced_tgt[v];
     if (plain) return decode_body(e, out, st);
     // the arena may grow (device sync + hipMalloc) only outside a capture; the body's own call is then a no-op
     const char* base0 = e->scratch.base;
-    CHK(ensure_arena(e, e->scratch, decode_scratch_need(e, e->B, e->T), "scratch"));
+    FS2_TRY(ensure_arena(e, e->scratch, decode_scratch_need(e, e->B, e->T), "scratch"));
     if (e->scratch.base != base0) drop_graphs(e);
     std::vector<uint64_t> key = {(uint64_t)e->B, (uint64_t)e->L, (uint64_t)e->T, (uint64_t)e->scratch.base, (uint64_t)e->persist.base,
                                  (uint64_t)e->ps.xA, (uint64_t)e->ps.d_cum, (uint64_t)e->ps.spk,(uint64_t)e->zero_pad_mel, (uint64_t)e->fuse_predictor, (uint64_t)e->tune.gen,
@@ -1809,8 +1704,8 @@ int fs2_force_variance_targets(fs2_engine* e, int32_t variance_index, const floa
 int fs2_debug_copy(fs2_engine* e, const char* what, void* dst, void* stream) {
     if (!e || !what || !dst) return FS2_ERR_ARG;
     auto it = e->taps.find(what);
-    if (it == e->taps.end()) return fail(e, FS2_ERR_STATE, "no debug tap '%s' (fs2_set_debug before encode?)", what);
-    HIPCHK(e, hipMemcpyAsync(dst, it->second.first, it->second.second, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (it == e->taps.end()) return e->fail(FS2_ERR_STATE, "no debug tap '%s' (fs2_set_debug before encode?)", what);
+    FS2_HIP(e, hipMemcpyAsync(dst, it->second.first, it->second.second, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return FS2_OK;
 }
 
@@ -1831,8 +1726,8 @@ int fs2_profile_reserve(fs2_engine* e, int32_t cls, int32_t pairs) {
     ProfSlot& s = e->prof[cls];
     while ((int)s.ev.size() < pairs) {
         hipEvent_t a, b;
-        HIPCHK(e, hipEventCreate(&a));
-        if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return fail(e, FS2_ERR_HIP, "hipEventCreate failed"); }
+        FS2_HIP(e, hipEventCreate(&a));
+        if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return e->fail(FS2_ERR_HIP, "hipEventCreate failed"); }
         s.ev.emplace_back(a, b);
     }
     return FS2_OK;
@@ -1843,9 +1738,9 @@ int fs2_profile_read(fs2_engine* e, int32_t cls, double* total_ms, int64_t* laun
     ProfSlot& s = e->prof[cls];
     double ms = 0;
     for (size_t i = 0; i < s.used; ++i) {
-        HIPCHK(e, hipEventSynchronize(s.ev[i].second));
+        FS2_HIP(e, hipEventSynchronize(s.ev[i].second));
         float t = 0;
-        HIPCHK(e, hipEventElapsedTime(&t, s.ev[i].first, s.ev[i].second));
+        FS2_HIP(e, hipEventElapsedTime(&t, s.ev[i].first, s.ev[i].second));
         ms += t;
     }
     if (total_ms) *total_ms = ms;

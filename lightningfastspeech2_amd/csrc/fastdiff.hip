@@ -35,12 +35,9 @@
 // frame zeroed in the sample operand (K concatenation: 2 x 96), so both frames share the MFMA tile instead of leaving half of it idle.
 // That doubles the MFMA work of the hop-8 block, which is 1/32 of the rows of the hop-256 block: +3 % of the LVC's arithmetic, in
 // exchange for one code path and full-width loads of the kernels.
-#include "fs2_common.h"
-#include "fs2_kernels.h"
+#include "fs2_host.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <new>
@@ -477,14 +474,6 @@ int fd_lvc_launch(int dtype, const FdLvcArgs& a, int hop, hipStream_t st) {
 }
 
 // ---- host side: weights ----
-struct FdTensor {
-    std::vector<int> shape;
-    bool loaded = false;
-    std::vector<float> data;
-};
-
-size_t fd_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // position of the reference's kernels[layer, c, o, k] inside a frame's FD_KW values: fragment order of fd_lvc_kernel
 // ([layer][step = k * NKC + c / KE][n-tile][lane = ((c % KE) / E16) * 16 + row][c % E16]); output channel o = half * 32 + q * 8 + j * 4 + r
 // sits in n-tile half * 2 + j at row q * 4 + r, so that a lane ends with 8 consecutive channels of both gate halves
@@ -532,12 +521,13 @@ const int kFdDown[3] = {4, 8, 8};  // upsample_ratios reversed (FastDiff.py:69)
 
 using namespace fs2;
 
-struct fs2_fd {
+struct fs2_fd : ErrorBase {
     int dtype = FS2_F32;
     bool ready = false, finalized = false;
     int chunk_limit = 0;
-    std::map<std::string, FdTensor> t;
-    unsigned char* dev = nullptr;
+    WeightStore w;
+    DevAllocs allocs;
+    unsigned char* dev = nullptr;  // one block: every packed tensor
     // packed convs
     FdConvW db_res[3], db_conv[3][3];
     FdConvW kp_in[3], kp_res[3][6], kp_kernel[3], kp_bias[3];
@@ -546,18 +536,9 @@ struct fs2_fd {
     // the step conditioning stays on the host (fc_t1, fc_t2, fc_t): 240 constants of (weights, step)
     std::vector<float> fc1_w, fc1_b, fc2_w, fc2_b, fct_w[3], fct_b[3];
     std::map<int, std::vector<FdOffsets>> sched_offsets;  // N -> per step n, per block
-    char err[256] = {0};
 };
 
 namespace {
-
-int ffail(fs2_fd* h, int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(h->err, sizeof(h->err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 bool fd_config_ok(int inner, int cond, const int32_t* ratios, int n_ratios, int layers, int lvc_k, int hid, int kp_k, int e_in, int e_mid,
                   int e_out) {
@@ -566,8 +547,8 @@ bool fd_config_ok(int inner, int cond, const int32_t* ratios, int n_ratios, int 
 }
 
 void fd_add_conv(fs2_fd* h, const std::string& name, int n, int cin, int k) {
-    h->t[name + ".weight"].shape = {n, cin, k};
-    h->t[name + ".bias"].shape = {n};
+    h->w.expect(name + ".weight", {n, cin, k});
+    h->w.expect(name + ".bias", {n});
 }
 
 // fc_t(swish(fc_t2(swish(fc_t1(emb(step)))))) per LVC block, in double (FastDiff.py:120-123, util.py:318-343, modules.py:202)
@@ -664,7 +645,7 @@ FdWs fd_layout(int dtype, size_t Bc, size_t T) {
     const size_t e = elem_bytes(dtype), S = T * FD_HOP;
     FdWs w{};
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += fd_align(bytes, 256); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += al(bytes); return o; };
     w.cond = take(Bc * T * FD_MELP * e);
     w.kpa = take(Bc * T * FD_HID * e);
     w.kpb = take(Bc * T * FD_HID * e);
@@ -703,17 +684,15 @@ FdConvArgs fd_conv_args(const fs2_fd* h, const FdConvW& w, const void* x, void* 
     return a;
 }
 
-#define FD_TRY(expr) do { const int st_ = (expr); if (st_ != FS2_OK) return st_; } while (0)
-
 // DiffusionDBlock (modules.py:127-138): x (B, rows_out * f, 32) -> out (B, rows_out, 32); tmp = 3 x (B, rows_out, 32)
 int fd_dblock(const fs2_fd* h, int blk, const void* x, void* out, void* tmp, const int* lengths, int B, int T, int rows_out,
               int len_scale, hipStream_t st) {
     const int f = kFdDown[blk], rows_in = rows_out * f;
     const size_t tb = (size_t)B * rows_out * FD_CH * elem_bytes(h->dtype);
     void* r = tmp; void* a = (char*)tmp + tb; void* b = (char*)tmp + 2 * tb;
-    FD_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->db_res[blk], x, r, lengths, B, T, rows_in, rows_out, len_scale, f, 1, 1.f, 1.f), FD_CH, st));
-    FD_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->db_conv[blk][0], x, a, lengths, B, T, rows_in, rows_out, len_scale, f, 1, 0.2f, 1.f), FD_CH, st));
-    FD_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->db_conv[blk][1], a, b, lengths, B, T, rows_out, rows_out, len_scale, 1, 2, 0.2f, 1.f), FD_CH, st));
+    FS2_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->db_res[blk], x, r, lengths, B, T, rows_in, rows_out, len_scale, f, 1, 1.f, 1.f), FD_CH, st));
+    FS2_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->db_conv[blk][0], x, a, lengths, B, T, rows_in, rows_out, len_scale, f, 1, 0.2f, 1.f), FD_CH, st));
+    FS2_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->db_conv[blk][1], a, b, lengths, B, T, rows_out, rows_out, len_scale, 1, 2, 0.2f, 1.f), FD_CH, st));
     FdConvArgs c = fd_conv_args(h, h->db_conv[blk][2], b, out, lengths, B, T, rows_out, rows_out, len_scale, 1, 4, 0.2f, 1.f);
     c.add1 = r;
     return fd_conv_launch(h->dtype, c, FD_CH, st);
@@ -736,13 +715,13 @@ int fd_predict(const fs2_fd* h, int n, const float* mel, const FdOffsets& off, c
         return fd_conv_launch(h->dtype, a, cin, st);
     };
     void* ka = ws + L.kpa; void* kp[2] = {ws + L.kpb, ws + L.kpc};
-    FD_TRY(conv(h->kp_in[n], ws + L.cond, ka, 0.1f, nullptr, FD_MELP));
+    FS2_TRY(conv(h->kp_in[n], ws + L.cond, ka, 0.1f, nullptr, FD_MELP));
     const void* cur = ka;
     for (int i = 0; i < 6; ++i) {
-        FD_TRY(conv(h->kp_res[n][i], cur, kp[i & 1], 0.1f, i == 5 ? ka : nullptr, FD_HID));
+        FS2_TRY(conv(h->kp_res[n][i], cur, kp[i & 1], 0.1f, i == 5 ? ka : nullptr, FD_HID));
         cur = kp[i & 1];
     }
-    FD_TRY(conv(h->kp_kernel[n], cur, K, 1.f, nullptr, FD_HID));
+    FS2_TRY(conv(h->kp_kernel[n], cur, K, 1.f, nullptr, FD_HID));
     return conv(h->kp_bias[n], cur, kb, 1.f, nullptr, FD_HID);
 }
 
@@ -764,25 +743,25 @@ int fd_eps(const fs2_fd* h, const float* x, const float* mel, const int* lengths
     const bool b16 = h->dtype == FS2_BF16;
     if (b16) fd_ends_launch<bf16>(true, h, x, ws + L.h0, lengths, B, T, st);
     else fd_ends_launch<float>(true, h, x, ws + L.h0, lengths, B, T, st);
-    FD_TRY(fd_dblock(h, 0, ws + L.h0, ws + L.h1, ws + L.d0, lengths, B, T, S / 4, 64, st));
-    FD_TRY(fd_dblock(h, 1, ws + L.h1, ws + L.h2, ws + L.d0, lengths, B, T, S / 32, 8, st));
-    FD_TRY(fd_dblock(h, 2, ws + L.h2, ws + L.h3, ws + L.d0, lengths, B, T, T, 1, st));
+    FS2_TRY(fd_dblock(h, 0, ws + L.h0, ws + L.h1, ws + L.d0, lengths, B, T, S / 4, 64, st));
+    FS2_TRY(fd_dblock(h, 1, ws + L.h1, ws + L.h2, ws + L.d0, lengths, B, T, S / 32, 8, st));
+    FS2_TRY(fd_dblock(h, 2, ws + L.h2, ws + L.h3, ws + L.d0, lengths, B, T, T, 1, st));
     const void* cur = ws + L.h3;
     int cur_scale = 1;  // rows of `cur` per frame
     void* const xbuf[3] = {ws + L.xa, ws + L.xb, ws + L.xa};
     void* const down[3] = {ws + L.h2, ws + L.h1, ws + L.h0};  // reversed(downsample), FastDiff.py:131
     for (int n = 0; n < 3; ++n) {
         const int hop = kFdHops[n], rows = T * hop;
-        FD_TRY(fd_predict(h, n, mel, off[n], lengths, B, T, ws, L, ws + L.K, ws + L.kb, st));
+        FS2_TRY(fd_predict(h, n, mel, off[n], lengths, B, T, ws, L, ws + L.K, ws + L.kb, st));
         // x = upsample(lrelu(x)); x += audio_down (the first of the four adds)
         FdConvArgs u = fd_conv_args(h, h->up[n], cur, xbuf[n], lengths, B, T, T * cur_scale, T * cur_scale, cur_scale, 1, 1, 0.2f, 1.f);
         u.add1 = down[n];
-        FD_TRY(fd_conv_launch(h->dtype, u, FD_CH, st));
+        FS2_TRY(fd_conv_launch(h->dtype, u, FD_CH, st));
         for (int i = 0, dil = 1; i < 4; ++i, dil *= 3) {
-            FD_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->lvc_conv[n][i], xbuf[n], ws + L.y, lengths, B, T, rows, rows, hop, 1, dil, 0.2f, 0.2f),
+            FS2_TRY(fd_conv_launch(h->dtype, fd_conv_args(h, h->lvc_conv[n][i], xbuf[n], ws + L.y, lengths, B, T, rows, rows, hop, 1, dil, 0.2f, 0.2f),
                                   FD_CH, st));
             FdLvcArgs a{ws + L.y, ws + L.K, ws + L.kb, xbuf[n], i < 3 ? down[n] : nullptr, xbuf[n], lengths, B, T, i};
-            FD_TRY(fd_lvc_launch(h->dtype, a, hop, st));
+            FS2_TRY(fd_lvc_launch(h->dtype, a, hop, st));
         }
         cur = xbuf[n];
         cur_scale = hop;
@@ -793,14 +772,14 @@ int fd_eps(const fs2_fd* h, const float* x, const float* mel, const int* lengths
 }
 
 int fd_call_checks(fs2_fd* h, const char* what, const void* ws, size_t ws_bytes, int B, int T) {
-    if (!h->finalized) return ffail(h, FS2_ERR_STATE, "%s before fs2_fd_finalize", what);
-    if (B < 1 || T < 1) return ffail(h, FS2_ERR_ARG, "B = %d, T = %d: both must be at least 1", B, T);
-    if (T > 8192) return ffail(h, FS2_ERR_SHAPE, "T = %d frames: at most 8192 per utterance", T);
+    if (!h->finalized) return h->fail(FS2_ERR_STATE, "%s before fs2_fd_finalize", what);
+    if (B < 1 || T < 1) return h->fail(FS2_ERR_ARG, "B = %d, T = %d: both must be at least 1", B, T);
+    if (T > 8192) return h->fail(FS2_ERR_SHAPE, "T = %d frames: at most 8192 per utterance", T);
     const int Bc = fd_chunk(h, B, T);
     const size_t need = fd_layout(h->dtype, (size_t)Bc, (size_t)T).total;
-    if ((size_t)Bc * ((T * FD_HOP + 31) / 32) > 0x7fffffffull) return ffail(h, FS2_ERR_SHAPE, "a chunk of %d utterances x %d frames exceeds the grid", Bc, T);
+    if ((size_t)Bc * ((T * FD_HOP + 31) / 32) > 0x7fffffffull) return h->fail(FS2_ERR_SHAPE, "a chunk of %d utterances x %d frames exceeds the grid", Bc, T);
     if (!ws || ws_bytes < need || ((uintptr_t)ws & 255))
-        return ffail(h, FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed (256-byte aligned)", ws_bytes, need);
+        return h->fail(FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed (256-byte aligned)", ws_bytes, need);
     return FS2_OK;
 }
 
@@ -822,28 +801,28 @@ int fs2_fd_create(int32_t abi_version, int32_t dtype, int32_t inner_channels, in
     fs2_fd* h = new (std::nothrow) fs2_fd();
     if (!h) return FS2_ERR_NOMEM;
     *out = h;
-    if (abi_version != FS2_ABI_VERSION) return ffail(h, FS2_ERR_ARG, "abi_version %d, this library is %d", abi_version, FS2_ABI_VERSION);
-    if (dtype != FS2_F32 && dtype != FS2_BF16) return ffail(h, FS2_ERR_ARG, "dtype %d: FS2_F32 or FS2_BF16", dtype);
+    if (abi_version != FS2_ABI_VERSION) return h->fail(FS2_ERR_ARG, "abi_version %d, this library is %d", abi_version, FS2_ABI_VERSION);
+    if (dtype != FS2_F32 && dtype != FS2_BF16) return h->fail(FS2_ERR_ARG, "dtype %d: FS2_F32 or FS2_BF16", dtype);
     if (!fd_config_ok(inner_channels, cond_channels, upsample_ratios, n_ratios, lvc_layers, lvc_kernel, kpnet_hidden, kpnet_conv, embed_in,
                       embed_mid, embed_out))
-        return ffail(h, FS2_ERR_SHAPE,
+        return h->fail(FS2_ERR_SHAPE,
                      "the FastDiff kernels cover the reference's default architecture only: inner 32, cond 80, upsample_ratios [8, 8, 4], "
                      "4 LVC layers of kernel 3, kpnet 64 / 3, step embedding 128 / 512 / 512");
     h->dtype = dtype;
     fd_add_conv(h, "first_audio_conv", FD_CH, 1, 7);
-    h->t["fc_t1.weight"].shape = {512, 128}; h->t["fc_t1.bias"].shape = {512};
-    h->t["fc_t2.weight"].shape = {512, 512}; h->t["fc_t2.bias"].shape = {512};
+    h->w.expect("fc_t1.weight", {512, 128}); h->w.expect("fc_t1.bias", {512});
+    h->w.expect("fc_t2.weight", {512, 512}); h->w.expect("fc_t2.bias", {512});
     for (int n = 0; n < 3; ++n) {
         const std::string d = "downsample." + std::to_string(n), l = "lvc_blocks." + std::to_string(n);
         fd_add_conv(h, d + ".residual_dense", FD_CH, FD_CH, 1);
         for (int i = 0; i < 3; ++i) fd_add_conv(h, d + ".conv." + std::to_string(i), FD_CH, FD_CH, 3);
-        h->t[l + ".upsample.weight"].shape = {FD_CH, FD_CH, 2 * kFdRatios[n]};
-        h->t[l + ".upsample.bias"].shape = {FD_CH};
+        h->w.expect(l + ".upsample.weight", {FD_CH, FD_CH, 2 * kFdRatios[n]});
+        h->w.expect(l + ".upsample.bias", {FD_CH});
         fd_add_conv(h, l + ".kernel_predictor.input_conv.0", FD_HID, FD_MEL, 5);
         for (int i : {1, 3, 6, 8, 11, 13}) fd_add_conv(h, l + ".kernel_predictor.residual_conv." + std::to_string(i), FD_HID, FD_HID, 3);
         fd_add_conv(h, l + ".kernel_predictor.kernel_conv", FD_KW, FD_HID, 3);
         fd_add_conv(h, l + ".kernel_predictor.bias_conv", FD_NB, FD_HID, 3);
-        h->t[l + ".fc_t.weight"].shape = {FD_MEL, 512}; h->t[l + ".fc_t.bias"].shape = {FD_MEL};
+        h->w.expect(l + ".fc_t.weight", {FD_MEL, 512}); h->w.expect(l + ".fc_t.bias", {FD_MEL});
         for (int i = 0; i < 4; ++i) fd_add_conv(h, l + ".convs." + std::to_string(i), FD_CH, FD_CH, 3);
     }
     fd_add_conv(h, "final_conv.0", 1, FD_CH, 7);
@@ -853,7 +832,6 @@ int fs2_fd_create(int32_t abi_version, int32_t dtype, int32_t inner_channels, in
 
 int fs2_fd_destroy(fs2_fd* h) {
     if (!h) return FS2_ERR_ARG;
-    if (h->dev) (void)hipFree(h->dev);
     delete h;
     return FS2_OK;
 }
@@ -862,35 +840,23 @@ const char* fs2_fd_last_error(const fs2_fd* h) { return h ? h->err : "null fastd
 
 int fs2_fd_load_weight(fs2_fd* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim) {
     if (!h) return FS2_ERR_ARG;
-    if (!h->ready) return ffail(h, FS2_ERR_STATE, "fs2_fd_create did not succeed");
-    if (h->finalized) return ffail(h, FS2_ERR_STATE, "fs2_fd_load_weight after fs2_fd_finalize");
-    if (!name || !host_data || !shape || ndim < 1) return ffail(h, FS2_ERR_ARG, "name, host_data and shape must not be null");
-    auto it = h->t.find(name);
-    if (it == h->t.end()) return ffail(h, FS2_ERR_WEIGHT, "unknown weight name '%s'", name);
-    FdTensor& t = it->second;
-    bool same = (size_t)ndim == t.shape.size();
-    size_t n = 1;
-    for (int i = 0; same && i < ndim; ++i) {
-        same = shape[i] == t.shape[i];
-        n *= (size_t)t.shape[i];
-    }
-    if (!same) return ffail(h, FS2_ERR_WEIGHT, "shape mismatch for '%s'", name);
-    t.loaded = true;
-    t.data.assign(host_data, host_data + n);
-    return FS2_OK;
+    if (!h->ready) return h->fail(FS2_ERR_STATE, "fs2_fd_create did not succeed");
+    if (h->finalized) return h->fail(FS2_ERR_STATE, "fs2_fd_load_weight after fs2_fd_finalize");
+    if (!name || !host_data || !shape || ndim < 1) return h->fail(FS2_ERR_ARG, "name, host_data and shape must not be null");
+    return h->w.load(*h, name, host_data, shape, ndim);
 }
 
 int fs2_fd_finalize(fs2_fd* h) {
     if (!h) return FS2_ERR_ARG;
-    if (!h->ready) return ffail(h, FS2_ERR_STATE, "fs2_fd_create did not succeed");
-    if (h->finalized) return ffail(h, FS2_ERR_STATE, "fs2_fd_finalize called twice");
-    for (const auto& kv : h->t)
-        if (!kv.second.loaded) return ffail(h, FS2_ERR_WEIGHT, "missing weight '%s'", kv.first.c_str());
+    if (!h->ready) return h->fail(FS2_ERR_STATE, "fs2_fd_create did not succeed");
+    if (h->finalized) return h->fail(FS2_ERR_STATE, "fs2_fd_finalize called twice");
+    if (const char* missing = h->w.first_missing()) return h->fail(FS2_ERR_WEIGHT, "missing weight '%s'", missing);
     const int dt = h->dtype;
     const size_t e = elem_bytes(dt);
-    std::vector<unsigned char> blk;
-    auto grow = [&](size_t bytes) { const size_t at = blk.size(); blk.resize(at + fd_align(bytes, 256)); return at; };
-    auto W = [&](const std::string& n) -> const std::vector<float>& { return h->t[n].data; };
+    WeightBlock wb;
+    std::vector<unsigned char>& blk = wb.host;
+    auto grow = [&](size_t bytes) { return wb.grow(bytes, 256); };
+    auto W = [&](const std::string& n) -> const std::vector<float>& { return h->w.at(n).data; };
     // rows[i] = the source row (of w and bias) that packed row i holds
     auto pack = [&](const float* w, const float* bias, int n, int cin, int cin_pad, int taps) {
         FdConvW c;
@@ -954,16 +920,13 @@ int fs2_fd_finalize(fs2_fd* h) {
     // the offsets of the four tabulated schedules: constants of (weights, N)
     for (int N : {3, 4, 6, 8}) {
         float steps[8];
-        if (fd_schedule(N, nullptr, nullptr, nullptr, steps) != FS2_OK) return ffail(h, FS2_ERR_SHAPE, "schedule N = %d does not map to steps", N);
+        if (fd_schedule(N, nullptr, nullptr, nullptr, steps) != FS2_OK) return h->fail(FS2_ERR_SHAPE, "schedule N = %d does not map to steps", N);
         std::vector<FdOffsets> v((size_t)N * 3);
         for (int n = 0; n < N; ++n) fd_step_offsets(h, steps[n], &v[(size_t)n * 3]);
         h->sched_offsets[N] = v;
     }
-    if (hipMalloc((void**)&h->dev, blk.size()) != hipSuccess)
-        return ffail(h, FS2_ERR_HIP, "hipMalloc of %zu weight bytes failed: %s", blk.size(), hipGetErrorString(hipGetLastError()));
-    if (hipMemcpy(h->dev, blk.data(), blk.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return ffail(h, FS2_ERR_HIP, "weight upload failed: %s", hipGetErrorString(hipGetLastError()));
-    for (auto& kv : h->t) std::vector<float>().swap(kv.second.data);
+    FS2_TRY(wb.upload(*h, h->allocs, (void**)&h->dev));
+    h->w.drop();
     h->finalized = true;
     return FS2_OK;
 }
@@ -979,7 +942,7 @@ int fs2_fd_launches(const fs2_fd* h, int32_t N) {
 
 int fs2_fd_set_chunk(fs2_fd* h, int32_t max_utterances) {
     if (!h) return FS2_ERR_ARG;
-    if (max_utterances < 0) return ffail(h, FS2_ERR_ARG, "max_utterances = %d", max_utterances);
+    if (max_utterances < 0) return h->fail(FS2_ERR_ARG, "max_utterances = %d", max_utterances);
     h->chunk_limit = max_utterances;
     return FS2_OK;
 }
@@ -995,9 +958,9 @@ int fs2_fd_schedule(int32_t N, float* beta, float* alpha, float* sigma, float* s
 int fs2_fd_denoise(fs2_fd* h, const float* x, const float* mel, const int32_t* lengths, float step, float* eps, void* workspace,
                    size_t workspace_bytes, int32_t B, int32_t T, void* hip_stream) {
     if (!h) return FS2_ERR_ARG;
-    FD_TRY(fd_call_checks(h, "fs2_fd_denoise", workspace, workspace_bytes, B, T));
-    if (!x || !mel || !eps) return ffail(h, FS2_ERR_ARG, "x, mel and eps must not be null");
-    if (!(step >= 0.f) || !std::isfinite(step)) return ffail(h, FS2_ERR_ARG, "step must be finite and non-negative");
+    FS2_TRY(fd_call_checks(h, "fs2_fd_denoise", workspace, workspace_bytes, B, T));
+    if (!x || !mel || !eps) return h->fail(FS2_ERR_ARG, "x, mel and eps must not be null");
+    if (!(step >= 0.f) || !std::isfinite(step)) return h->fail(FS2_ERR_ARG, "step must be finite and non-negative");
     FdOffsets off[3];
     fd_step_offsets(h, step, off);
     const int Bc = fd_chunk(h, B, T);
@@ -1007,7 +970,7 @@ int fs2_fd_denoise(fs2_fd* h, const float* x, const float* mel, const int32_t* l
         const int nb = B - b0 < Bc ? B - b0 : Bc;
         const int st = fd_eps(h, x + b0 * S, mel + (size_t)b0 * T * FD_MEL, lengths ? lengths + b0 : nullptr, off, eps + b0 * S,
                               (char*)workspace, L, nb, T, (hipStream_t)hip_stream);
-        if (st != FS2_OK) return ffail(h, st, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (st != FS2_OK) return h->fail(st, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     }
     return FS2_OK;
 }
@@ -1017,9 +980,9 @@ int fs2_fd_sample(fs2_fd* h, const float* mel, const int32_t* lengths, const flo
     if (!h) return FS2_ERR_ARG;
     float beta[8], alpha[8], sigma[8], steps[8];
     if (fd_schedule(N, beta, alpha, sigma, steps) != FS2_OK)
-        return ffail(h, FS2_ERR_SHAPE, "N = %d reverse steps: the tabulated schedules are 3, 4, 6 and 8", N);
-    FD_TRY(fd_call_checks(h, "fs2_fd_sample", workspace, workspace_bytes, B, T));
-    if (!mel || !noise || !wav) return ffail(h, FS2_ERR_ARG, "mel, noise and wav must not be null");
+        return h->fail(FS2_ERR_SHAPE, "N = %d reverse steps: the tabulated schedules are 3, 4, 6 and 8", N);
+    FS2_TRY(fd_call_checks(h, "fs2_fd_sample", workspace, workspace_bytes, B, T));
+    if (!mel || !noise || !wav) return h->fail(FS2_ERR_ARG, "mel, noise and wav must not be null");
     const std::vector<FdOffsets>& offs = h->sched_offsets[N];
     hipStream_t st = (hipStream_t)hip_stream;
     const int Bc = fd_chunk(h, B, T);
@@ -1035,7 +998,7 @@ int fs2_fd_sample(fs2_fd* h, const float* mel, const int32_t* lengths, const flo
         const float* xin = noise + b0 * S;  // x_T
         for (int n = N - 1; n >= 0; --n) {
             const int s = fd_eps(h, xin, cmel, len, &offs[(size_t)n * 3], eps, ws, L, nb, T, st);
-            if (s != FS2_OK) return ffail(h, s, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+            if (s != FS2_OK) return h->fail(s, "launch failed: %s", hipGetErrorString(hipGetLastError()));
             float c1, d;
             {
 #pragma clang fp contract(off)
@@ -1050,14 +1013,14 @@ int fs2_fd_sample(fs2_fd* h, const float* mel, const int32_t* lengths, const flo
         }
         hipLaunchKernelGGL(fd_peak_scale_kernel, dim3((unsigned)nb), dim3(1024), 0, st, xs, wav + b0 * S, len, T);
     }
-    return hipGetLastError() == hipSuccess ? FS2_OK : ffail(h, FS2_ERR_HIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return hipGetLastError() == hipSuccess ? FS2_OK : h->fail(FS2_ERR_HIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
 }
 
 int fs2_fd_predict_kernels(fs2_fd* h, int32_t block, const float* mel, const int32_t* lengths, float step, void* kernels, void* bias,
                            void* workspace, size_t workspace_bytes, int32_t B, int32_t T, void* hip_stream) {
     if (!h) return FS2_ERR_ARG;
-    FD_TRY(fd_call_checks(h, "fs2_fd_predict_kernels", workspace, workspace_bytes, B, T));
-    if (block < 0 || block > 2 || !mel || !kernels || !bias) return ffail(h, FS2_ERR_ARG, "block 0 .. 2; mel, kernels and bias must not be null");
+    FS2_TRY(fd_call_checks(h, "fs2_fd_predict_kernels", workspace, workspace_bytes, B, T));
+    if (block < 0 || block > 2 || !mel || !kernels || !bias) return h->fail(FS2_ERR_ARG, "block 0 .. 2; mel, kernels and bias must not be null");
     FdOffsets off[3];
     fd_step_offsets(h, step, off);
     const int Bc = fd_chunk(h, B, T);
@@ -1067,7 +1030,7 @@ int fs2_fd_predict_kernels(fs2_fd* h, int32_t block, const float* mel, const int
         const int nb = B - b0 < Bc ? B - b0 : Bc;
         const int st = fd_predict(h, block, mel + (size_t)b0 * T * FD_MEL, off[block], lengths ? lengths + b0 : nullptr, nb, T, (char*)workspace, L,
                                   (char*)kernels + (size_t)b0 * T * FD_KW * e, (char*)bias + (size_t)b0 * T * FD_NB * e, (hipStream_t)hip_stream);
-        if (st != FS2_OK) return ffail(h, st, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (st != FS2_OK) return h->fail(st, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     }
     return FS2_OK;
 }
@@ -1092,8 +1055,8 @@ int fs2_op_lvc(int32_t dtype, int32_t hop, int32_t layer, const void* y, const v
 int fs2_op_fd_dblock(fs2_fd* h, int32_t block, const void* x, void* out, void* tmp, const int32_t* lengths, int32_t B, int32_t T,
                      void* hip_stream) {
     if (!h) return FS2_ERR_ARG;
-    if (!h->finalized) return ffail(h, FS2_ERR_STATE, "fs2_op_fd_dblock before fs2_fd_finalize");
-    if (block < 0 || block > 2 || !x || !out || !tmp || B < 1 || T < 1 || T > 8192) return ffail(h, FS2_ERR_ARG, "block 0 .. 2, x / out / tmp not null, B, T >= 1");
+    if (!h->finalized) return h->fail(FS2_ERR_STATE, "fs2_op_fd_dblock before fs2_fd_finalize");
+    if (block < 0 || block > 2 || !x || !out || !tmp || B < 1 || T < 1 || T > 8192) return h->fail(FS2_ERR_ARG, "block 0 .. 2, x / out / tmp not null, B, T >= 1");
     static const int rows_per_frame[3] = {64, 8, 1};  // output rows per frame
     return fd_dblock(h, block, x, out, tmp, lengths, B, T, T * rows_per_frame[block], rows_per_frame[block], (hipStream_t)hip_stream);
 }

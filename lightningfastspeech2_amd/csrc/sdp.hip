@@ -24,14 +24,10 @@
 // LDS: 2 planes x 64 rows x 260 floats (1040-byte rows: the MFMA operand reads of 16 rows spread over the banks) = 133 KB, + 3 KB.
 // That, not the register file, bounds the tile height: 80 rows x 2 planes would be 166 KB.
 // fp32 storage, accurate expf / logf / log1pf / erff / sqrtf everywhere: a duration is a decision.
-#include "fs2_common.h"
-#include "fs2_kernels.h"
+#include "fs2_host.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <map>
 #include <new>
 #include <string>
 #include <vector>
@@ -472,11 +468,11 @@ void pack_1x1(const float* W, int rows_src, int rows, int K, float* out) {
             }
 }
 
-struct Tensor {
-    std::vector<int> shape;
-    bool on_path = false;
-    bool loaded = false;
-    std::vector<float> data;  // kept for on-path tensors only
+// The weight block indexed in floats.  The bytes of `host` are read as float: the vector's storage comes from operator new (aligned
+// for any scalar) and every offset is a multiple of 16 bytes; a float reference is valid until the next grow().
+struct SdpBlock : WeightBlock {
+    size_t grow(size_t floats) { return WeightBlock::grow(floats * 4, 16) / 4; }
+    float& operator[](size_t i) { return ((float*)host.data())[i]; }
 };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -486,11 +482,12 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 using namespace fs2;
 
-struct fs2_sdp {
+struct fs2_sdp : ErrorBase {
     int H = 0, F = 0, k = 0, n = 0;
     bool ready = false;  // create succeeded
     bool finalized = false;
-    std::map<std::string, Tensor> t;
+    WeightStore w;  // the training-only tensors with keep = false: checked, dropped, not required
+    DevAllocs allocs;
     float* dev = nullptr;  // one block: every packed tensor
     // offsets (floats) into dev
     struct Dds { size_t dw_w, dw_b, g1, b1, pw, pb, g2, b2; };
@@ -499,51 +496,42 @@ struct fs2_sdp {
     Dds enc{};
     std::vector<Flow> flows;  // index j - 2 <-> flows.j, j = 2 .. n
     float ea_t = 0.f, ea_ls = 0.f;
-    char err[256] = {0};
 };
 
 namespace {
 
-int sfail(fs2_sdp* h, int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(h->err, sizeof(h->err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 void add_dds(fs2_sdp* h, const std::string& p, int F, int k, bool on) {
     for (int i = 0; i < 3; ++i) {
         const std::string s = std::to_string(i);
-        h->t[p + ".convs_sep." + s + ".weight"] = Tensor{{F, 1, k}, on};
-        h->t[p + ".convs_sep." + s + ".bias"] = Tensor{{F}, on};
-        h->t[p + ".convs_1x1." + s + ".weight"] = Tensor{{F, F, 1}, on};
-        h->t[p + ".convs_1x1." + s + ".bias"] = Tensor{{F}, on};
+        h->w.expect(p + ".convs_sep." + s + ".weight", {F, 1, k}, on);
+        h->w.expect(p + ".convs_sep." + s + ".bias", {F}, on);
+        h->w.expect(p + ".convs_1x1." + s + ".weight", {F, F, 1}, on);
+        h->w.expect(p + ".convs_1x1." + s + ".bias", {F}, on);
         for (const char* nm : {".norms_1.", ".norms_2."}) {
-            h->t[p + nm + s + ".gamma"] = Tensor{{F}, on};
-            h->t[p + nm + s + ".beta"] = Tensor{{F}, on};
+            h->w.expect(p + nm + s + ".gamma", {F}, on);
+            h->w.expect(p + nm + s + ".beta", {F}, on);
         }
     }
 }
 
 void add_flows(fs2_sdp* h, const std::string& p, int F, int k, int n, bool inference_set) {
-    h->t[p + ".0.translation"] = Tensor{{2, 1}, inference_set};
-    h->t[p + ".0.log_scale"] = Tensor{{2, 1}, inference_set};
+    h->w.expect(p + ".0.translation", {2, 1}, inference_set);
+    h->w.expect(p + ".0.log_scale", {2, 1}, inference_set);
     for (int j = 1; j <= n; ++j) {
         const bool on = inference_set && j >= 2;  // flows.1 is the ConvFlow the inference loop drops (sdp.py:333-334)
         const std::string q = p + "." + std::to_string(j);
-        h->t[q + ".pre.weight"] = Tensor{{F, 1, 1}, on};
-        h->t[q + ".pre.bias"] = Tensor{{F}, on};
+        h->w.expect(q + ".pre.weight", {F, 1, 1}, on);
+        h->w.expect(q + ".pre.bias", {F}, on);
         add_dds(h, q + ".convs", F, k, on);
-        h->t[q + ".proj.weight"] = Tensor{{SNP, F, 1}, on};
-        h->t[q + ".proj.bias"] = Tensor{{SNP}, on};
+        h->w.expect(q + ".proj.weight", {SNP, F, 1}, on);
+        h->w.expect(q + ".proj.bias", {SNP}, on);
     }
 }
 
 // one DDS's tensors into the block at `at` (floats); returns the end
-size_t pack_dds(fs2_sdp* h, const std::string& p, std::vector<float>& blk, fs2_sdp::Dds& o) {
-    auto T = [&](const std::string& n) -> const std::vector<float>& { return h->t[p + n].data; };
-    auto grow = [&](size_t n) { const size_t at = blk.size(); blk.resize(at + align_up(n, 4)); return at; };
+size_t pack_dds(fs2_sdp* h, const std::string& p, SdpBlock& blk, fs2_sdp::Dds& o) {
+    auto T = [&](const std::string& n) -> const std::vector<float>& { return h->w.at(p + n).data; };
+    auto grow = [&](size_t n) { return blk.grow(n); };
     o.dw_w = grow(3 * 3 * SF); o.dw_b = grow(3 * SF); o.g1 = grow(3 * SF); o.b1 = grow(3 * SF);
     o.pw = grow((size_t)3 * SF * SF); o.pb = grow(3 * SF); o.g2 = grow(3 * SF); o.b2 = grow(3 * SF);
     for (int i = 0; i < 3; ++i) {
@@ -559,7 +547,7 @@ size_t pack_dds(fs2_sdp* h, const std::string& p, std::vector<float>& blk, fs2_s
         std::memcpy(&blk[o.g2 + i * SF], T(".norms_2." + s + ".gamma").data(), SF * 4);
         std::memcpy(&blk[o.b2 + i * SF], T(".norms_2." + s + ".beta").data(), SF * 4);
     }
-    return blk.size();
+    return blk.host.size() / 4;
 }
 
 DdsW dds_ptrs(const float* dev, const fs2_sdp::Dds& o) {
@@ -585,25 +573,25 @@ int fs2_sdp_create(int32_t abi_version, int32_t H, int32_t F, int32_t k, int32_t
     fs2_sdp* h = new (std::nothrow) fs2_sdp();
     if (!h) return FS2_ERR_NOMEM;
     *out = h;  // returned even on failure so the caller can read fs2_sdp_last_error, then destroy
-    if (abi_version != FS2_ABI_VERSION) return sfail(h, FS2_ERR_ARG, "abi_version %d, this library is %d", abi_version, FS2_ABI_VERSION);
-    if (F != SF) return sfail(h, FS2_ERR_SHAPE, "filter size %d: the stochastic duration predictor's kernel is built for 256 channels", F);
-    if (k != 3) return sfail(h, FS2_ERR_SHAPE, "kernel size %d: the kernel's dilations 1 / 3 / 9 and its 13-row halo are those of k = 3", k);
-    if (n_flows < 1 || n_flows > 8) return sfail(h, FS2_ERR_SHAPE, "n_flows = %d: 1 .. 8 are supported", n_flows);
+    if (abi_version != FS2_ABI_VERSION) return h->fail(FS2_ERR_ARG, "abi_version %d, this library is %d", abi_version, FS2_ABI_VERSION);
+    if (F != SF) return h->fail(FS2_ERR_SHAPE, "filter size %d: the stochastic duration predictor's kernel is built for 256 channels", F);
+    if (k != 3) return h->fail(FS2_ERR_SHAPE, "kernel size %d: the kernel's dilations 1 / 3 / 9 and its 13-row halo are those of k = 3", k);
+    if (n_flows < 1 || n_flows > 8) return h->fail(FS2_ERR_SHAPE, "n_flows = %d: 1 .. 8 are supported", n_flows);
     if (H < 16 || H > SF || H % 16)
-        return sfail(h, FS2_ERR_SHAPE, "in_channels %d: `pre` runs inside the encoder launch for multiples of 16 up to 256", H);
+        return h->fail(FS2_ERR_SHAPE, "in_channels %d: `pre` runs inside the encoder launch for multiples of 16 up to 256", H);
     h->H = H; h->F = F; h->k = k; h->n = n_flows;
-    h->t["sdp.pre.weight"] = Tensor{{F, H, 1}, true};
-    h->t["sdp.pre.bias"] = Tensor{{F}, true};
+    h->w.expect("sdp.pre.weight", {F, H, 1}, true);
+    h->w.expect("sdp.pre.bias", {F}, true);
     add_dds(h, "sdp.convs", F, k, true);
-    h->t["sdp.proj.weight"] = Tensor{{F, F, 1}, true};
-    h->t["sdp.proj.bias"] = Tensor{{F}, true};
+    h->w.expect("sdp.proj.weight", {F, F, 1}, true);
+    h->w.expect("sdp.proj.bias", {F}, true);
     add_flows(h, "sdp.flows", F, k, n_flows, true);
     // the training-only half: the posterior encoder
-    h->t["sdp.post_pre.weight"] = Tensor{{F, 1, 1}, false};
-    h->t["sdp.post_pre.bias"] = Tensor{{F}, false};
+    h->w.expect("sdp.post_pre.weight", {F, 1, 1}, false);
+    h->w.expect("sdp.post_pre.bias", {F}, false);
     add_dds(h, "sdp.post_convs", F, k, false);
-    h->t["sdp.post_proj.weight"] = Tensor{{F, F, 1}, false};
-    h->t["sdp.post_proj.bias"] = Tensor{{F}, false};
+    h->w.expect("sdp.post_proj.weight", {F, F, 1}, false);
+    h->w.expect("sdp.post_proj.bias", {F}, false);
     add_flows(h, "sdp.post_flows", F, k, n_flows, false);
     h->ready = true;
     return FS2_OK;
@@ -611,7 +599,6 @@ int fs2_sdp_create(int32_t abi_version, int32_t H, int32_t F, int32_t k, int32_t
 
 int fs2_sdp_destroy(fs2_sdp* h) {
     if (!h) return FS2_ERR_ARG;
-    if (h->dev) (void)hipFree(h->dev);
     delete h;
     return FS2_OK;
 }
@@ -622,63 +609,48 @@ int32_t fs2_sdp_tile_rows(const fs2_sdp* h) { return h && h->ready ? SV : 0; }
 
 int fs2_sdp_load_weight(fs2_sdp* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim) {
     if (!h) return FS2_ERR_ARG;
-    if (!h->ready) return sfail(h, FS2_ERR_STATE, "fs2_sdp_create did not succeed");
-    if (h->finalized) return sfail(h, FS2_ERR_STATE, "fs2_sdp_load_weight after fs2_sdp_finalize");
-    if (!name || !host_data || !shape || ndim < 1) return sfail(h, FS2_ERR_ARG, "name, host_data and shape must not be null");
-    auto it = h->t.find(name);
-    if (it == h->t.end()) return sfail(h, FS2_ERR_WEIGHT, "unknown weight name '%s'", name);
-    Tensor& t = it->second;
-    bool same = (size_t)ndim == t.shape.size();
-    size_t n = 1;
-    for (int i = 0; same && i < ndim; ++i) {
-        same = shape[i] == t.shape[i];
-        n *= (size_t)t.shape[i];
-    }
-    if (!same) return sfail(h, FS2_ERR_WEIGHT, "shape mismatch for '%s'", name);
-    t.loaded = true;
-    if (t.on_path) t.data.assign(host_data, host_data + n);  // training-only tensors are checked and dropped
-    return FS2_OK;
+    if (!h->ready) return h->fail(FS2_ERR_STATE, "fs2_sdp_create did not succeed");
+    if (h->finalized) return h->fail(FS2_ERR_STATE, "fs2_sdp_load_weight after fs2_sdp_finalize");
+    if (!name || !host_data || !shape || ndim < 1) return h->fail(FS2_ERR_ARG, "name, host_data and shape must not be null");
+    return h->w.load(*h, name, host_data, shape, ndim);
 }
 
 int fs2_sdp_finalize(fs2_sdp* h) {
     if (!h) return FS2_ERR_ARG;
-    if (!h->ready) return sfail(h, FS2_ERR_STATE, "fs2_sdp_create did not succeed");
-    if (h->finalized) return sfail(h, FS2_ERR_STATE, "fs2_sdp_finalize called twice");
-    for (const auto& kv : h->t)
-        if (kv.second.on_path && !kv.second.loaded) return sfail(h, FS2_ERR_WEIGHT, "missing weight '%s'", kv.first.c_str());
-    std::vector<float> blk;
-    auto grow = [&](size_t n) { const size_t at = blk.size(); blk.resize(at + align_up(n, 4)); return at; };
+    if (!h->ready) return h->fail(FS2_ERR_STATE, "fs2_sdp_create did not succeed");
+    if (h->finalized) return h->fail(FS2_ERR_STATE, "fs2_sdp_finalize called twice");
+    if (const char* missing = h->w.first_missing()) return h->fail(FS2_ERR_WEIGHT, "missing weight '%s'", missing);
+    SdpBlock blk;
+    auto grow = [&](size_t n) { return blk.grow(n); };
+    auto W = [&](const std::string& n) -> const std::vector<float>& { return h->w.at(n).data; };
     h->pre_w = grow((size_t)SF * h->H);
-    pack_1x1(h->t["sdp.pre.weight"].data.data(), SF, SF, h->H, &blk[h->pre_w]);
+    pack_1x1(W("sdp.pre.weight").data(), SF, SF, h->H, &blk[h->pre_w]);
     h->pre_b = grow(SF);
-    std::memcpy(&blk[h->pre_b], h->t["sdp.pre.bias"].data.data(), SF * 4);
+    std::memcpy(&blk[h->pre_b], W("sdp.pre.bias").data(), SF * 4);
     pack_dds(h, "sdp.convs", blk, h->enc);
     h->proj_w = grow((size_t)SF * SF);
-    pack_1x1(h->t["sdp.proj.weight"].data.data(), SF, SF, SF, &blk[h->proj_w]);
+    pack_1x1(W("sdp.proj.weight").data(), SF, SF, SF, &blk[h->proj_w]);
     h->proj_b = grow(SF);
-    std::memcpy(&blk[h->proj_b], h->t["sdp.proj.bias"].data.data(), SF * 4);
+    std::memcpy(&blk[h->proj_b], W("sdp.proj.bias").data(), SF * 4);
     h->flows.clear();
     for (int j = 2; j <= h->n; ++j) {
         const std::string q = "sdp.flows." + std::to_string(j);
         fs2_sdp::Flow f{};
         f.pre_w = grow(SF);
-        std::memcpy(&blk[f.pre_w], h->t[q + ".pre.weight"].data.data(), SF * 4);
+        std::memcpy(&blk[f.pre_w], W(q + ".pre.weight").data(), SF * 4);
         f.pre_b = grow(SF);
-        std::memcpy(&blk[f.pre_b], h->t[q + ".pre.bias"].data.data(), SF * 4);
+        std::memcpy(&blk[f.pre_b], W(q + ".pre.bias").data(), SF * 4);
         pack_dds(h, q + ".convs", blk, f.d);
         f.proj_w = grow((size_t)32 * SF);
-        pack_1x1(h->t[q + ".proj.weight"].data.data(), SNP, 32, SF, &blk[f.proj_w]);
+        pack_1x1(W(q + ".proj.weight").data(), SNP, 32, SF, &blk[f.proj_w]);
         f.proj_b = grow(32);
-        std::memcpy(&blk[f.proj_b], h->t[q + ".proj.bias"].data.data(), SNP * 4);
+        std::memcpy(&blk[f.proj_b], W(q + ".proj.bias").data(), SNP * 4);
         h->flows.push_back(f);
     }
-    h->ea_t = h->t["sdp.flows.0.translation"].data[0];
-    h->ea_ls = h->t["sdp.flows.0.log_scale"].data[0];
-    if (hipMalloc((void**)&h->dev, blk.size() * 4) != hipSuccess)
-        return sfail(h, FS2_ERR_HIP, "hipMalloc of %zu weight bytes failed: %s", blk.size() * 4, hipGetErrorString(hipGetLastError()));
-    if (hipMemcpy(h->dev, blk.data(), blk.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return sfail(h, FS2_ERR_HIP, "weight upload failed: %s", hipGetErrorString(hipGetLastError()));
-    for (auto& kv : h->t) std::vector<float>().swap(kv.second.data);
+    h->ea_t = W("sdp.flows.0.translation")[0];
+    h->ea_ls = W("sdp.flows.0.log_scale")[0];
+    FS2_TRY(blk.upload(*h, h->allocs, (void**)&h->dev));
+    h->w.drop();
     h->finalized = true;
     return FS2_OK;
 }
@@ -695,21 +667,21 @@ int fs2_sdp_launches(const fs2_sdp* h) { return h && h->ready ? (h->n == 1 ? 1 :
 int fs2_sdp_forward(fs2_sdp* h, int32_t x_dtype, const void* x, const uint8_t* pad_mask, const float* noise, float* logw, void* workspace,
                     size_t workspace_bytes, int32_t B, int32_t L, void* hip_stream) {
     if (!h) return FS2_ERR_ARG;
-    if (!h->finalized) return sfail(h, FS2_ERR_STATE, "fs2_sdp_forward before fs2_sdp_finalize");
-    if (!x || !pad_mask || !noise || !logw) return sfail(h, FS2_ERR_ARG, "x, pad_mask, noise and logw must not be null");
-    if (x_dtype != FS2_F32 && x_dtype != FS2_BF16 && x_dtype != FS2_F16) return sfail(h, FS2_ERR_ARG, "x_dtype %d: FS2_F32, FS2_BF16 or FS2_F16", x_dtype);
-    if (B < 1 || L < 1) return sfail(h, FS2_ERR_ARG, "B = %d, L = %d: both must be at least 1", B, L);
-    if (B > 65535) return sfail(h, FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
-    if ((uintptr_t)x & 15) return sfail(h, FS2_ERR_ARG, "x must be 16-byte aligned");
+    if (!h->finalized) return h->fail(FS2_ERR_STATE, "fs2_sdp_forward before fs2_sdp_finalize");
+    if (!x || !pad_mask || !noise || !logw) return h->fail(FS2_ERR_ARG, "x, pad_mask, noise and logw must not be null");
+    if (x_dtype != FS2_F32 && x_dtype != FS2_BF16 && x_dtype != FS2_F16) return h->fail(FS2_ERR_ARG, "x_dtype %d: FS2_F32, FS2_BF16 or FS2_F16", x_dtype);
+    if (B < 1 || L < 1) return h->fail(FS2_ERR_ARG, "B = %d, L = %d: both must be at least 1", B, L);
+    if (B > 65535) return h->fail(FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
+    if ((uintptr_t)x & 15) return h->fail(FS2_ERR_ARG, "x must be 16-byte aligned");
     hipStream_t st = (hipStream_t)hip_stream;
     if (h->n == 1) {  // ElementwiseAffine alone: no conditioning is read
         const size_t n = (size_t)B * L;
         hipLaunchKernelGGL(sdp_affine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, noise, pad_mask, logw, h->ea_t, h->ea_ls, B, L);
-        return hipGetLastError() == hipSuccess ? FS2_OK : sfail(h, FS2_ERR_HIP, "launch failed");
+        return hipGetLastError() == hipSuccess ? FS2_OK : h->fail(FS2_ERR_HIP, "launch failed");
     }
     const size_t need = sdp_ws_need(B, L);
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))
-        return sfail(h, FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed (16-byte aligned)", workspace_bytes, need);
+        return h->fail(FS2_ERR_NOMEM, "workspace of %zu bytes, %zu needed (16-byte aligned)", workspace_bytes, need);
     float* g = (float*)workspace;
     float* z[2];
     z[0] = (float*)((char*)workspace + align_up((size_t)B * L * SF * 4, 256));
@@ -731,7 +703,7 @@ int fs2_sdp_forward(fs2_sdp* h, int32_t x_dtype, const void* x, const uint8_t* p
         hipLaunchKernelGGL(sdp_flow_kernel, grid, dim3(256), 0, st, a);
         zin = a.zout;
     }
-    return hipGetLastError() == hipSuccess ? FS2_OK : sfail(h, FS2_ERR_HIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return hipGetLastError() == hipSuccess ? FS2_OK : h->fail(FS2_ERR_HIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
 }
 
 int fs2_op_rq_spline_inverse(const float* x1, const float* h29, int32_t F, float* out, int32_t rows, void* hip_stream) {

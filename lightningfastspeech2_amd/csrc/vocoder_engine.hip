@@ -15,18 +15,12 @@
 //   y[q*s + f] = sum_m x[q - m] . Wt[:, :, m*s + f + p]   (0 <= m*s + f + p < k)
 // is a plain conv of x to s*Cout channels (phase-major), whose (T, s*Cout) row-major output is the
 // (T*s, Cout) tensor the next layer reads - no scatter, no zero insertion.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "../../include/fs2.h"
-#include "fs2_common.h"
-#include "fs2_kernels.h"
+#include "fs2_host.h"
 
 using namespace fs2;
 
@@ -38,22 +32,16 @@ struct VocLayer {     // one conv in kernel form
     int cin = 0, cin_pad = 0, n = 0, taps = 1, dil = 1, pad = 0, wn = 1;
     int shift_from = 0;  // VocConvArgs::shift_from
 };
-struct HostT {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
 
 }  // namespace
 
-struct fs2_vocoder {
+struct fs2_vocoder : ErrorBase {
     fs2_voc_config cfg;
     int dt = FS2_BF16;
     size_t esz = 2;
-    char err[512] = {0};
     bool finalized = false;
-    std::map<std::string, std::vector<int64_t>> spec;
-    std::map<std::string, HostT> host;
-    std::vector<void*> allocs;
+    WeightStore w;
+    DevAllocs allocs;
     VocLayer pre, post;
     std::vector<VocLayer> ups;
     std::vector<VocLayer> c1, c2;  // [(stage * n_kernels + j) * 3 + m]
@@ -70,28 +58,9 @@ struct fs2_vocoder {
 
 namespace {
 
-int vfail(fs2_vocoder* v, int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(v->err, sizeof(v->err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define VHIP(v, call)                                                                           \
-    do {                                                                                        \
-        hipError_t _s = (call);                                                                 \
-        if (_s != hipSuccess) return vfail(v, FS2_ERR_HIP, "%s: %s", #call, hipGetErrorString(_s)); \
-    } while (0)
-#define VCHK(call)                     \
-    do {                               \
-        const int _r = (call);         \
-        if (_r != FS2_OK) return _r;   \
-    } while (0)
-
-int vdev_alloc(fs2_vocoder* v, void** out, size_t bytes) {
-    VHIP(v, hipMalloc(out, bytes ? bytes : 16));
-    v->allocs.push_back(*out);
-    return FS2_OK;
+// fp32 host values -> the generator's storage dtype (weights) or fp32 (biases) on the device
+int vupload(fs2_vocoder* v, const std::vector<float>& h, int dt, void** out) {
+    return upload_as(*v, v->allocs, h.data(), h.size(), dt, out, FS2_ERR_HIP);
 }
 
 int next_pow2(int x) {
@@ -133,22 +102,6 @@ void frag_order(int dt, const std::vector<float>& W, int n, int cin, int cin_pad
         }
 }
 
-int upload_frags(fs2_vocoder* v, const std::vector<float>& stage, void** out) {
-    if (v->dt == FS2_F32) {
-        VCHK(vdev_alloc(v, out, stage.size() * 4));
-        VHIP(v, hipMemcpy(*out, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-    } else {
-        std::vector<unsigned short> h(stage.size());
-        if (v->dt == FS2_F16)
-            for (size_t i = 0; i < stage.size(); ++i) h[i] = f32_to_f16_sat(stage[i]).v;  // the storage rule of a device store
-        else
-            for (size_t i = 0; i < stage.size(); ++i) h[i] = f32_to_bf16(stage[i]).v;
-        VCHK(vdev_alloc(v, out, h.size() * 2));
-        VHIP(v, hipMemcpy(*out, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    }
-    return FS2_OK;
-}
-
 int pack_layer(fs2_vocoder* v, const std::vector<float>& W, const std::vector<float>& bias, int n, int cin, int taps,
                int dil, int pad, bool post, VocLayer* L) {
     L->cin = cin;
@@ -157,30 +110,28 @@ int pack_layer(fs2_vocoder* v, const std::vector<float>& W, const std::vector<fl
     L->taps = taps;
     L->dil = dil;
     L->pad = pad;
-    if (!post && n % 32) return vfail(v, FS2_ERR_SHAPE, "channel count %d is not a multiple of 32", n);
+    if (!post && n % 32) return v->fail(FS2_ERR_SHAPE, "channel count %d is not a multiple of 32", n);
     L->wn = wave_cols(n, post);
     std::vector<float> stage;
     frag_order(v->dt, W, n, cin, L->cin_pad, taps, L->wn, post, &stage);
-    VCHK(upload_frags(v, stage, &L->w));
+    FS2_TRY(vupload(v, stage, v->dt, &L->w));
     std::vector<float> bp(post ? 32 : n, 0.f);
     for (size_t i = 0; i < bias.size() && i < bp.size(); ++i) bp[i] = bias[i];
-    VCHK(vdev_alloc(v, (void**)&L->b, bp.size() * 4));
-    VHIP(v, hipMemcpy(L->b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-    return FS2_OK;
+    return vupload(v, bp, FS2_F32, (void**)&L->b);
 }
 
 int conv_layer(fs2_vocoder* v, const std::string& name, int n, int cin, int k, int dil, bool post, VocLayer* L) {
-    const HostT& w = v->host.at(name + ".weight");
-    const HostT& b = v->host.at(name + ".bias");
+    const auto& w = v->w.at(name + ".weight");
+    const auto& b = v->w.at(name + ".bias");
     return pack_layer(v, w.data, b.data, n, cin, k, dil, (k - 1) / 2 * dil, post, L);
 }
 
 // ConvTranspose1d weight (cin, cout, k), stride s, padding p  ->  conv form (s*cout, cin, K)
 int up_layer(fs2_vocoder* v, const std::string& name, int cin, int cout, int k, int s, VocLayer* L) {
-    const HostT& w = v->host.at(name + ".weight");
-    const HostT& b = v->host.at(name + ".bias");
+    const auto& w = v->w.at(name + ".weight");
+    const auto& b = v->w.at(name + ".bias");
     const int p = (k - s) / 2;
-    if (k - 2 * p != s) return vfail(v, FS2_ERR_SHAPE, "%s: kernel %d / stride %d: kernel - 2*padding must equal the stride", name.c_str(), k, s);
+    if (k - 2 * p != s) return v->fail(FS2_ERR_SHAPE, "%s: kernel %d / stride %d: kernel - 2*padding must equal the stride", name.c_str(), k, s);
     int m_lo = 1 << 30, m_hi = -(1 << 30);
     for (int f = 0; f < s; ++f)
         for (int m = -k; m <= k; ++m) {
@@ -218,7 +169,7 @@ int up_layer(fs2_vocoder* v, const std::string& name, int cin, int cout, int k, 
                     W[(((size_t)f * cout + co) * cin + ci) * K2 + j2] = w.data[((size_t)ci * cout + co) * k + kk];
             }
         }
-    VCHK(pack_layer(v, W, bias, s * cout, cin, K2, 1, pad, false, L));
+    FS2_TRY(pack_layer(v, W, bias, s * cout, cin, K2, 1, pad, false, L));
     L->shift_from = two && fshift < s ? fshift * cout : 0;
     return FS2_OK;
 }
@@ -237,7 +188,7 @@ int run_conv(fs2_vocoder* v, hipStream_t st, const VocLayer& L, const void* x, v
     int32_t code = -1;
     const int r = launch_vocoder_conv(a, v->dt, st, &code);
     if (code >= 0) v->launches.push_back(code);
-    if (r != FS2_OK) return vfail(v, r, "vocoder conv launch failed (cin=%d n=%d k=%d dil=%d S=%d)", L.cin, L.n, L.taps, L.dil, S);
+    if (r != FS2_OK) return v->fail(r, "vocoder conv launch failed (cin=%d n=%d k=%d dil=%d S=%d)", L.cin, L.n, L.taps, L.dil, S);
     return FS2_OK;
 }
 
@@ -253,44 +204,43 @@ int fs2_voc_create(const fs2_voc_config* cfg, fs2_vocoder** out) {
         return FS2_ERR_SHAPE;
     if (cfg->n_mels < 4 || cfg->n_mels % 4 || (cfg->initial_channel >> cfg->n_stages) % 32) return FS2_ERR_SHAPE;
     if (!is_storage_dtype(cfg->dtype)) return FS2_ERR_ARG;  // FS2_F32, FS2_BF16 or FS2_F16: the engine modes are not storage types
-    fs2_vocoder* v = new fs2_vocoder();
+    std::unique_ptr<fs2_vocoder> v(new fs2_vocoder());
     v->cfg = *cfg;
     v->dt = cfg->dtype;
     v->esz = elem_bytes(cfg->dtype);
     const int C0 = cfg->initial_channel;
-    v->spec["conv_pre.weight"] = {C0, cfg->n_mels, 7};
-    v->spec["conv_pre.bias"] = {C0};
+    v->w.expect("conv_pre.weight", {C0, cfg->n_mels, 7});
+    v->w.expect("conv_pre.bias", {C0});
     v->chan.push_back(C0);
     v->upf.push_back(1);
     for (int i = 0; i < cfg->n_stages; ++i) {
         const int cin = C0 >> i, cout = C0 >> (i + 1);
-        if (cfg->up_rates[i] < 1 || cfg->up_kernels[i] < cfg->up_rates[i]) { delete v; return FS2_ERR_SHAPE; }
+        if (cfg->up_rates[i] < 1 || cfg->up_kernels[i] < cfg->up_rates[i]) return FS2_ERR_SHAPE;
         const std::string u = "ups." + std::to_string(i);
-        v->spec[u + ".weight"] = {cin, cout, cfg->up_kernels[i]};
-        v->spec[u + ".bias"] = {cout};
+        v->w.expect(u + ".weight", {cin, cout, cfg->up_kernels[i]});
+        v->w.expect(u + ".bias", {cout});
         v->chan.push_back(cout);
         v->upf.push_back(v->upf.back() * cfg->up_rates[i]);
         for (int j = 0; j < cfg->n_kernels; ++j) {
             const int k = cfg->rb_kernels[j];
-            if (k < 1 || !(k & 1)) { delete v; return FS2_ERR_SHAPE; }
+            if (k < 1 || !(k & 1)) return FS2_ERR_SHAPE;
             const std::string r = "resblocks." + std::to_string(i * cfg->n_kernels + j);
             for (int m = 0; m < 3; ++m) {
-                v->spec[r + ".convs1." + std::to_string(m) + ".weight"] = {cout, cout, k};
-                v->spec[r + ".convs1." + std::to_string(m) + ".bias"] = {cout};
-                v->spec[r + ".convs2." + std::to_string(m) + ".weight"] = {cout, cout, k};
-                v->spec[r + ".convs2." + std::to_string(m) + ".bias"] = {cout};
+                v->w.expect(r + ".convs1." + std::to_string(m) + ".weight", {cout, cout, k});
+                v->w.expect(r + ".convs1." + std::to_string(m) + ".bias", {cout});
+                v->w.expect(r + ".convs2." + std::to_string(m) + ".weight", {cout, cout, k});
+                v->w.expect(r + ".convs2." + std::to_string(m) + ".bias", {cout});
             }
         }
     }
-    v->spec["conv_post.weight"] = {1, v->chan.back(), 7};
-    v->spec["conv_post.bias"] = {1};
-    *out = v;
+    v->w.expect("conv_post.weight", {1, v->chan.back(), 7});
+    v->w.expect("conv_post.bias", {1});
+    *out = v.release();
     return FS2_OK;
 }
 
 void fs2_voc_destroy(fs2_vocoder* v) {
     if (!v) return;
-    for (void* p : v->allocs) (void)hipFree(p);
     if (v->ws) (void)hipFree(v->ws);
     delete v;
 }
@@ -298,45 +248,33 @@ void fs2_voc_destroy(fs2_vocoder* v) {
 const char* fs2_voc_last_error(const fs2_vocoder* v) { return v ? v->err : "null vocoder"; }
 
 int fs2_voc_load_weight(fs2_vocoder* v, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
-    if (!v || !name || !data || !shape) return v ? vfail(v, FS2_ERR_ARG, "bad load_weight argument") : FS2_ERR_ARG;
-    if (v->finalized) return vfail(v, FS2_ERR_STATE, "weights are frozen after fs2_voc_finalize");
-    auto it = v->spec.find(name);
-    if (it == v->spec.end()) return vfail(v, FS2_ERR_WEIGHT, "unknown weight '%s'", name);
-    const auto& want = it->second;
-    bool ok = (size_t)ndim == want.size();
-    size_t n = 1;
-    for (int i = 0; ok && i < ndim; ++i) { ok = shape[i] == want[i]; n *= (size_t)shape[i]; }
-    if (!ok) return vfail(v, FS2_ERR_WEIGHT, "shape mismatch for '%s'", name);
-    HostT t;
-    t.shape.assign(shape, shape + ndim);
-    t.data.assign(data, data + n);
-    v->host[name] = std::move(t);
-    return FS2_OK;
+    if (!v || !name || !data || !shape) return v ? v->fail(FS2_ERR_ARG, "bad load_weight argument") : FS2_ERR_ARG;
+    if (v->finalized) return v->fail(FS2_ERR_STATE, "weights are frozen after fs2_voc_finalize");
+    return v->w.load(*v, name, data, shape, ndim);
 }
 
 int fs2_voc_finalize(fs2_vocoder* v) {
     if (!v) return FS2_ERR_ARG;
     if (v->finalized) return FS2_OK;
-    for (auto& kv : v->spec)
-        if (!v->host.count(kv.first)) return vfail(v, FS2_ERR_WEIGHT, "missing weight '%s'", kv.first.c_str());
+    if (const char* missing = v->w.first_missing()) return v->fail(FS2_ERR_WEIGHT, "missing weight '%s'", missing);
     const fs2_voc_config& c = v->cfg;
-    VCHK(conv_layer(v, "conv_pre", c.initial_channel, c.n_mels, 7, 1, false, &v->pre));
+    FS2_TRY(conv_layer(v, "conv_pre", c.initial_channel, c.n_mels, 7, 1, false, &v->pre));
     v->ups.resize(c.n_stages);
     v->c1.resize((size_t)c.n_stages * c.n_kernels * 3);
     v->c2.resize(v->c1.size());
     for (int i = 0; i < c.n_stages; ++i) {
         const int cin = v->chan[i], cout = v->chan[i + 1];
-        VCHK(up_layer(v, "ups." + std::to_string(i), cin, cout, c.up_kernels[i], c.up_rates[i], &v->ups[i]));
+        FS2_TRY(up_layer(v, "ups." + std::to_string(i), cin, cout, c.up_kernels[i], c.up_rates[i], &v->ups[i]));
         for (int j = 0; j < c.n_kernels; ++j) {
             const std::string r = "resblocks." + std::to_string(i * c.n_kernels + j);
             for (int m = 0; m < 3; ++m) {
                 const size_t idx = ((size_t)i * c.n_kernels + j) * 3 + m;
-                VCHK(conv_layer(v, r + ".convs1." + std::to_string(m), cout, cout, c.rb_kernels[j], c.rb_dilations[j][m], false, &v->c1[idx]));
-                VCHK(conv_layer(v, r + ".convs2." + std::to_string(m), cout, cout, c.rb_kernels[j], 1, false, &v->c2[idx]));
+                FS2_TRY(conv_layer(v, r + ".convs1." + std::to_string(m), cout, cout, c.rb_kernels[j], c.rb_dilations[j][m], false, &v->c1[idx]));
+                FS2_TRY(conv_layer(v, r + ".convs2." + std::to_string(m), cout, cout, c.rb_kernels[j], 1, false, &v->c2[idx]));
             }
         }
     }
-    VCHK(conv_layer(v, "conv_post", 1, v->chan.back(), 7, 1, true, &v->post));
+    FS2_TRY(conv_layer(v, "conv_post", 1, v->chan.back(), 7, 1, true, &v->post));
     // narrow stages: the six convs of a resblock back to back for the LDS-resident kernel
     v->rb.resize((size_t)c.n_stages * c.n_kernels);
     for (int i = 0; i < c.n_stages; ++i) {
@@ -347,8 +285,8 @@ int fs2_voc_finalize(fs2_vocoder* v) {
             std::vector<float> all, bias;
             for (int m = 0; m < 3; ++m)
                 for (const char* grp : {".convs1.", ".convs2."}) {
-                    const HostT& w = v->host.at(r + grp + std::to_string(m) + ".weight");
-                    const HostT& b = v->host.at(r + grp + std::to_string(m) + ".bias");
+                    const auto& w = v->w.at(r + grp + std::to_string(m) + ".weight");
+                    const auto& b = v->w.at(r + grp + std::to_string(m) + ".bias");
                     std::vector<float> st;
                     frag_order(v->dt, w.data, C, C, C, c.rb_kernels[j], C / 32, false, &st);
                     all.insert(all.end(), st.begin(), st.end());
@@ -356,12 +294,11 @@ int fs2_voc_finalize(fs2_vocoder* v) {
                 }
             fs2_vocoder::FusedRb& f = v->rb[(size_t)i * c.n_kernels + j];
             f.conv_bytes = all.size() / 6 * v->esz;
-            VCHK(upload_frags(v, all, &f.w));
-            VCHK(vdev_alloc(v, (void**)&f.b, bias.size() * 4));
-            VHIP(v, hipMemcpy(f.b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+            FS2_TRY(vupload(v, all, v->dt, &f.w));
+            FS2_TRY(vupload(v, bias, FS2_F32, (void**)&f.b));
         }
     }
-    v->host.clear();
+    v->w.drop();
     v->finalized = true;
     return FS2_OK;
 }
@@ -370,13 +307,12 @@ int32_t fs2_voc_hop(const fs2_vocoder* v) { return v ? v->upf.back() : 0; }
 
 int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths, int32_t B, int32_t T, float* wav,
                        void* stream) {
-    if (!v || !mel || !wav || B <= 0 || T <= 0) return v ? vfail(v, FS2_ERR_ARG, "bad synthesize argument") : FS2_ERR_ARG;
-    if (!v->finalized) return vfail(v, FS2_ERR_STATE, "fs2_voc_finalize not called");
+    if (!v || !mel || !wav || B <= 0 || T <= 0) return v ? v->fail(FS2_ERR_ARG, "bad synthesize argument") : FS2_ERR_ARG;
+    if (!v->finalized) return v->fail(FS2_ERR_STATE, "fs2_voc_finalize not called");
     hipStream_t st = (hipStream_t)stream;
     const fs2_voc_config& c = v->cfg;
     const int ns = c.n_stages;
     // workspace: one output per stage (kept for the parity taps) + 4 scratch tensors of the largest stage
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     size_t need = 0, big = 0;
     std::vector<size_t> sb(ns + 1);
     for (int i = 0; i <= ns; ++i) {
@@ -385,13 +321,13 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
         if (i > 0 && sb[i] > big) big = sb[i];
     }
     need += 4 * big;
-    if ((size_t)T * v->upf.back() > (size_t)0x7fffffff / 4) return vfail(v, FS2_ERR_SHAPE, "T too large");
+    if ((size_t)T * v->upf.back() > (size_t)0x7fffffff / 4) return v->fail(FS2_ERR_SHAPE, "T too large");
     if (need > v->ws_bytes) {
-        VHIP(v, hipStreamSynchronize(st));
+        FS2_HIP(v, hipStreamSynchronize(st));
         if (v->ws) (void)hipFree(v->ws);
         v->ws = nullptr;
         v->ws_bytes = 0;
-        if (hipMalloc(&v->ws, need) != hipSuccess) return vfail(v, FS2_ERR_NOMEM, "workspace of %zu bytes", need);
+        if (hipMalloc(&v->ws, need) != hipSuccess) return v->fail(FS2_ERR_NOMEM, "workspace of %zu bytes", need);
         v->ws_bytes = need;
     }
     char* base = (char*)v->ws;
@@ -405,7 +341,7 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
     v->lastT = T;
     v->launches.clear();
 
-    VCHK(run_conv(v, st, v->pre, mel, v->stage_out[0], nullptr, lengths, 1, B, T, 1.f, 1.f, false, /*in_fp32=*/true));
+    FS2_TRY(run_conv(v, st, v->pre, mel, v->stage_out[0], nullptr, lengths, 1, B, T, 1.f, 1.f, false, /*in_fp32=*/true));
     const float inv = 1.0f / (float)c.n_kernels;
     for (int i = 0; i < ns; ++i) {
         // transposed conv, at the INPUT resolution, to up_rate * Cout phase-major channels
@@ -431,7 +367,7 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
                 if (!voc_resblock_mi16(pa, v->dt)) stage_act = false;
             }
         }
-        VCHK(run_conv(v, st, v->ups[i], v->stage_out[i], u, nullptr, lengths, v->upf[i], B, T * v->upf[i], 0.1f, 1.f, false, false,
+        FS2_TRY(run_conv(v, st, v->ups[i], v->stage_out[i], u, nullptr, lengths, v->upf[i], B, T * v->upf[i], 0.1f, 1.f, false, false,
                       false, stage_act ? 0.1f : 1.f));
         for (int j = 0; j < c.n_kernels; ++j) {
             const fs2_vocoder::FusedRb& f = v->rb[(size_t)i * c.n_kernels + j];
@@ -447,7 +383,7 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
                     int32_t code = -1;
                     const int rr = launch_vocoder_resblock(ra, v->dt, st, &code);
                     if (code >= 0) v->launches.push_back(code);
-                    if (rr != FS2_OK) return vfail(v, rr, "fused resblock launch failed (C=%d k=%d)", ra.C, ra.taps);
+                    if (rr != FS2_OK) return v->fail(rr, "fused resblock launch failed (C=%d k=%d)", ra.C, ra.taps);
                     continue;
                 }
                 // else pair by pair: a (c1, c2) pair on an LDS-resident tile where it fits and pays,
@@ -478,12 +414,12 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
                         int32_t code = -1;
                         const int rr = launch_vocoder_resblock(pa, v->dt, st, &code);
                         if (code >= 0) v->launches.push_back(code);
-                        if (rr != FS2_OK) return vfail(v, rr, "fused conv pair launch failed (C=%d k=%d)", ra.C, ra.taps);
+                        if (rr != FS2_OK) return v->fail(rr, "fused conv pair launch failed (C=%d k=%d)", ra.C, ra.taps);
                     } else {
                         const size_t idx = ((size_t)i * c.n_kernels + j) * 3 + m;
                         // c1 stores lrelu(out): c2 then stages it untouched (LDS-DMA fill in vocoder_conv.hip)
-                        VCHK(run_conv(v, st, v->c1[idx], rin, a, nullptr, lengths, sc, B, S, 0.1f, 1.f, false, false, false, 0.1f));
-                        VCHK(run_conv(v, st, v->c2[idx], a, o, rin, lengths, sc, B, S, 1.f, m < 2 ? 1.f : inv, m == 2 && j > 0));
+                        FS2_TRY(run_conv(v, st, v->c1[idx], rin, a, nullptr, lengths, sc, B, S, 0.1f, 1.f, false, false, false, 0.1f));
+                        FS2_TRY(run_conv(v, st, v->c2[idx], a, o, rin, lengths, sc, B, S, 1.f, m < 2 ? 1.f : inv, m == 2 && j > 0));
                     }
                     rin = o;
                 }
@@ -493,29 +429,29 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
             for (int m = 0; m < 3; ++m) {
                 const size_t idx = ((size_t)i * c.n_kernels + j) * 3 + m;
                 // c1 stores lrelu(out): c2 then stages it untouched (LDS-DMA fill in vocoder_conv.hip)
-                VCHK(run_conv(v, st, v->c1[idx], r, a, nullptr, lengths, sc, B, S, 0.1f, 1.f, false, false, false, 0.1f));
+                FS2_TRY(run_conv(v, st, v->c1[idx], r, a, nullptr, lengths, sc, B, S, 0.1f, 1.f, false, false, false, 0.1f));
                 if (m < 2) {
                     void* o = m == 0 ? r1 : r2;
-                    VCHK(run_conv(v, st, v->c2[idx], a, o, r, lengths, sc, B, S, 1.f, 1.f, false));
+                    FS2_TRY(run_conv(v, st, v->c2[idx], a, o, r, lengths, sc, B, S, 1.f, 1.f, false));
                     r = o;
                 } else {  // last pair of the block: (xt + x) / n_kernels summed into the stage output
-                    VCHK(run_conv(v, st, v->c2[idx], a, v->stage_out[i + 1], r, lengths, sc, B, S, 1.f, inv, j > 0));
+                    FS2_TRY(run_conv(v, st, v->c2[idx], a, v->stage_out[i + 1], r, lengths, sc, B, S, 1.f, inv, j > 0));
                 }
             }
         }
     }
-    VCHK(run_conv(v, st, v->post, v->stage_out[ns], wav, nullptr, lengths, v->upf[ns], B, T * v->upf[ns], 0.01f, 1.f, false,
+    FS2_TRY(run_conv(v, st, v->post, v->stage_out[ns], wav, nullptr, lengths, v->upf[ns], B, T * v->upf[ns], 0.01f, 1.f, false,
                   false, /*post=*/true));
     return FS2_OK;
 }
 
 int fs2_voc_debug_copy(fs2_vocoder* v, int32_t stage, float* dst, void* stream) {
     if (!v || !dst) return FS2_ERR_ARG;
-    if (stage < 0 || stage > v->cfg.n_stages || v->stage_out.empty()) return vfail(v, FS2_ERR_STATE, "no such stage output");
+    if (stage < 0 || stage > v->cfg.n_stages || v->stage_out.empty()) return v->fail(FS2_ERR_STATE, "no such stage output");
     const size_t n = (size_t)v->lastB * v->lastT * v->upf[stage] * v->chan[stage];
     ConvertArgs a{v->stage_out[stage], dst, n};
     const int r = launch_convert(a, v->dt, FS2_F32, (hipStream_t)stream);
-    if (r != FS2_OK) return vfail(v, r, "convert failed");
+    if (r != FS2_OK) return v->fail(r, "convert failed");
     return FS2_OK;
 }
 

@@ -218,10 +218,13 @@ _PRECISIONS = {"bf16": _lib.FS2_BF16, "fp32": _lib.FS2_F32}
 _TORCH_DTYPES = {"bf16": torch.bfloat16, "fp32": torch.float32}
 
 
-class FastDiff:
+class FastDiff(_lib.Handle):
     """Device-resident FastDiff.  ``state_dict``: the reference's names, checkpoint form (weight_g / weight_v) or plain.
     ``precision``: "fp32" (parity mode) or "bf16" (weights, predicted kernels and the streams between launches in bf16; the
     diffusion state, noise, eps, sampler and gate arithmetic stay fp32)."""
+    _prefix = "fs2_fd"
+    _label = "fastdiff "
+    _load_what = "load_weight {}"
 
     def __init__(self, cfg: FastDiffConfig, state_dict, precision: str = "bf16", device="cuda:0"):
         self.cfg, self.device = cfg, torch.device(device)
@@ -231,10 +234,8 @@ class FastDiff:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
         if not cfg._schedule_is_default():
             raise ValueError("only the reference's training schedule (beta 1e-6 .. 0.01, T = 1000, one audio channel) is supported")
-        self.lib = _lib.load()
+        _lib.Handle.__init__(self)
         self.precision, self.dtype = precision, _PRECISIONS[precision]
-        self.handle = C.c_void_p()
-        self._ws = None
         ratios = (C.c_int32 * len(cfg.upsample_ratios))(*cfg.upsample_ratios)
         with torch.cuda.device(self.device):
             st = self.lib.fs2_fd_create(_lib.FS2_ABI_VERSION, self.dtype, *cfg._c_args(ratios), C.byref(self.handle))
@@ -245,30 +246,11 @@ class FastDiff:
                 missing = [k for k in spec if k not in sd]
                 if missing:
                     raise KeyError(f"FastDiff weights missing: {missing[:4]}{'...' if len(missing) > 4 else ''}")
-                for name in spec:
-                    a = np.ascontiguousarray(sd[name], dtype=np.float32)
-                    shp = (C.c_int64 * a.ndim)(*a.shape)
-                    self._check(self.lib.fs2_fd_load_weight(self.handle, name.encode(), a.ctypes.data_as(C.c_void_p), shp, a.ndim),
-                                f"load_weight {name}")
-                self._check(self.lib.fs2_fd_finalize(self.handle), "finalize")
+                self.load_weights(spec, sd)
             except Exception:
                 self.close()
                 raise
         self.hop = int(self.lib.fs2_fd_hop(self.handle))
-
-    def _check(self, status, what):
-        _lib.check(status, self.handle, f"fastdiff {what}", "fs2_fd_last_error")
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.fs2_fd_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def tile_rows(self) -> int:
@@ -286,13 +268,6 @@ class FastDiff:
         n = C.c_size_t()
         self._check(self.lib.fs2_fd_workspace_bytes(self.handle, B, T, C.byref(n)), "workspace_bytes")
         return n.value
-
-    def _workspace(self, B, T):
-        need = self.workspace_bytes(B, T)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def _inputs(self, mel, lengths):
         mel = mel.to(self.device, torch.float32).contiguous()
@@ -313,7 +288,7 @@ class FastDiff:
             raise ValueError(f"x must be ({B}, {T * self.hop})")
         eps = out if out is not None else torch.zeros(B, T * self.hop, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            ws = self._workspace(B, T)
+            ws = self._workspace(self.workspace_bytes(B, T))
             self._check(self.lib.fs2_fd_denoise(self.handle, x, mel, ld, float(step), eps, ws, ws.numel(), B, T,
                                                 torch.cuda.current_stream(self.device)), "denoise")
         return eps
@@ -329,7 +304,7 @@ class FastDiff:
         if tuple(noise.shape) != (N, B, T * self.hop):
             raise ValueError(f"noise must be ({N}, {B}, {T * self.hop})")
         with torch.cuda.device(self.device):
-            ws = self._workspace(B, T)
+            ws = self._workspace(self.workspace_bytes(B, T))
             self._check(self.lib.fs2_fd_sample(self.handle, mel, ld, noise, N, wav, ws, ws.numel(), B, T,
                                                torch.cuda.current_stream(self.device)), "sample")
         return wav
@@ -375,7 +350,7 @@ class FastDiff:
         K = torch.zeros(B, T, 24576, dtype=td, device=self.device)
         kb = torch.zeros(B, T, 256, dtype=td, device=self.device)
         with torch.cuda.device(self.device):
-            ws = self._workspace(B, T)
+            ws = self._workspace(self.workspace_bytes(B, T))
             self._check(self.lib.fs2_fd_predict_kernels(self.handle, block, mel, ld, float(step), K, kb, ws, ws.numel(), B, T,
                                                         torch.cuda.current_stream(self.device)), "predict_kernels")
         return K, kb

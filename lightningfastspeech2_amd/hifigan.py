@@ -179,27 +179,32 @@ def wav_pack(wav: torch.Tensor, lengths: Optional[torch.Tensor], hop: int, dtype
     return out, offsets
 
 
-class HifiGan:
+class HifiGan(_lib.Handle):
     """Device-resident generator.  ``state_dict`` may be the checkpoint form (weight_g / weight_v) or
     plain weights; names are the reference generator's own.
 
     ``precision``: "fp32" (parity mode, fp32 MFMA), "bf16" (throughput mode, the default) or "fp16": bf16's kernels, tiles and
     byte counts with every stored tensor (weights, the mel slab, the streams between launches, the stage means) in IEEE binary16
     - three more mantissa bits; stores saturate at +-65504.  Accumulation, biases, tanh and the wav are fp32 in all three."""
+    _prefix = "fs2_voc"
+    _load_what = "load_weight {}"
 
     def __init__(self, cfg: HifiGanConfig, state_dict, precision: str = "bf16", device="cuda:0"):
         self.cfg, self.device = cfg, torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the HiFi-GAN generator runs on an MI355X only (no CPU fallback)")
-        self.lib = _lib.load()
+        _lib.Handle.__init__(self)
         if precision not in _PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
         self.precision = precision
         self.dtype = _PRECISIONS[precision]
-        self.handle = C.c_void_p()
         cc = _config_to_c(cfg, self.dtype)
         with torch.cuda.device(self.device):  # no global set_device: the reference Synthesiser has no such side effect
-            self._init(cfg, cc, state_dict)
+            try:
+                self._init(cfg, cc, state_dict)
+            except Exception:
+                self.close()
+                raise
         self._last = None
 
     def _init(self, cfg, cc, state_dict):
@@ -210,24 +215,8 @@ class HifiGan:
         missing = [k for k in spec if k not in sd]
         if missing:
             raise KeyError(f"generator weights missing: {missing[:4]}{'...' if len(missing) > 4 else ''}")
-        for name in spec:
-            a = np.ascontiguousarray(sd[name], dtype=np.float32)
-            shp = (C.c_int64 * a.ndim)(*a.shape)
-            self._check(self.lib.fs2_voc_load_weight(self.handle, name.encode(), a.ctypes.data_as(C.c_void_p), shp, a.ndim),
-                        f"load_weight {name}")
-        self._check(self.lib.fs2_voc_finalize(self.handle), "finalize")
+        self.load_weights(spec, sd)
         self.hop = int(self.lib.fs2_voc_hop(self.handle))
-
-    def _check(self, status, what):
-        _lib.check(status, self.handle, what, "fs2_voc_last_error")
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.fs2_voc_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
     def _generate(self, mel: torch.Tensor, lengths: Optional[torch.Tensor], zero_pads: bool):
         mel = mel.to(self.device, torch.float32).contiguous()

@@ -34,12 +34,13 @@ _PRECISIONS = {"fp32": _lib.FS2_F32, "f32": _lib.FS2_F32, "bf16": _lib.FS2_BF16,
 # (FS2_F32_X3): ~1e-5 on the mel against "fp32" at about half its time
 
 
-class Engine:
+class Engine(_lib.Handle):
     """Thin owner of one ``fs2_engine`` handle (one per device)."""
+    _prefix = "fs2"
 
     def __init__(self, cfg: Fs2Config, state_dict, precision: str = "fp32", device="cuda:0",
                  torch_workspace: bool = True, graphs: Optional[bool] = None):
-        self.lib = _lib.load()
+        _lib.Handle.__init__(self)
         # torch_workspace: the forward's device workspace comes from torch's caching allocator through
         # fs2_workspace_bytes / fs2_set_workspace (SURVEY 8b: caller-owned memory); False = the
         # engine's own grow-only hipMalloc arenas
@@ -51,7 +52,6 @@ class Engine:
         self.precision = precision
         self.dtype = _PRECISIONS[precision]
         self.device = torch.device(device)
-        self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
             cc = _lib.config_to_c(cfg, self.dtype)
             st = self.lib.fs2_create(C.byref(cc), C.byref(self.handle))
@@ -79,7 +79,7 @@ class Engine:
         """Another engine over the same device weights (fs2_clone): own workspace and host-side state."""
         other = Engine.__new__(Engine)
         other.lib, other.torch_workspace = self.lib, self.torch_workspace
-        other._ws_persist = other._ws_scratch = None
+        other._ws = other._ws_persist = other._ws_scratch = None
         other.cfg, other.precision, other.dtype, other.device = self.cfg, self.precision, self.dtype, self.device
         other.handle = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -94,25 +94,7 @@ class Engine:
         for name in spec:
             if name not in state_dict:
                 raise KeyError(f"state_dict is missing '{name}'")
-            v = state_dict[name]
-            if isinstance(v, torch.Tensor):
-                v = v.detach().cpu().float().numpy()
-            a = np.ascontiguousarray(v, dtype=np.float32)
-            shape = (C.c_int64 * a.ndim)(*a.shape)
-            st = self.lib.fs2_load_weight(self.handle, name.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim)
-            _lib.check(st, self.handle, f"load_weight({name})")
-        _lib.check(self.lib.fs2_finalize(self.handle), self.handle, "finalize")
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.fs2_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.load_weights(spec, state_dict)
 
     def _stream(self):
         return torch.cuda.current_stream(self.device)

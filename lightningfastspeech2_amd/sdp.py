@@ -9,7 +9,6 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-import numpy as np
 import torch
 
 from . import _lib
@@ -27,50 +26,28 @@ def supported(in_channels: int, filter_size: int, kernel_size: int, n_flows: int
     return bool(_lib.load().fs2_sdp_supported(in_channels, filter_size, kernel_size, n_flows))
 
 
-class StochasticDurationPredictor:
+class StochasticDurationPredictor(_lib.Handle):
     """One ``fs2_sdp`` handle.  ``state_dict``: the reference's names, either full (``variance_adaptor.duration_predictor.sdp.*``)
     or relative to the duration predictor (``sdp.*``); the training-only tensors may be present (they are checked and dropped) or
     absent."""
+    _prefix = "fs2_sdp"
+    _label = "sdp "
 
     def __init__(self, in_channels: int, filter_size: int, kernel_size: int, n_flows: int, state_dict, device="cuda:0"):
-        self.lib = _lib.load()
-        self.handle = C.c_void_p()
+        _lib.Handle.__init__(self)
         self.device = torch.device(device)
         self.in_channels, self.n_flows = in_channels, n_flows
         st = self.lib.fs2_sdp_create(_lib.FS2_ABI_VERSION, in_channels, filter_size, kernel_size, n_flows, C.byref(self.handle))
         try:
             self._check(st, "create")
-            for name, v in state_dict.items():
-                if name.startswith(SDP_PREFIX):
-                    name = name[len(SDP_PREFIX):]
-                if not name.startswith("sdp."):
-                    continue
-                if isinstance(v, torch.Tensor):
-                    v = v.detach().cpu().float().numpy()
-                a = np.ascontiguousarray(v, dtype=np.float32)
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                self._check(self.lib.fs2_sdp_load_weight(self.handle, name.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim),
-                            f"load_weight({name})")
+            # (a tensor present under both its full and its relative name is loaded once, with the value that comes later in
+            #  state_dict: what two loads in order left in the handle)
+            sd = {(k[len(SDP_PREFIX):] if k.startswith(SDP_PREFIX) else k): v for k, v in state_dict.items()}
             with torch.cuda.device(self.device):
-                self._check(self.lib.fs2_sdp_finalize(self.handle), "finalize")
+                self.load_weights([k for k in sd if k.startswith("sdp.")], sd)
         except Exception:
             self.close()
             raise
-        self._ws = None
-
-    def _check(self, st, what):
-        _lib.check(st, self.handle, f"sdp {what}", last_error="fs2_sdp_last_error")
-
-    def close(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.fs2_sdp_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def tile_rows(self) -> int:
@@ -97,11 +74,9 @@ class StochasticDurationPredictor:
         pad = pad_mask.to(self.device, dtype=torch.uint8).contiguous()
         noise = noise.to(self.device, dtype=torch.float32).contiguous()
         logw = out if out is not None else torch.empty(B, L, dtype=torch.float32, device=self.device)
-        need = self.workspace_bytes(B, L)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self.workspace_bytes(B, L))
         with torch.cuda.device(self.device):
-            st = self.lib.fs2_sdp_forward(self.handle, _DTYPES[x.dtype], x, pad, noise, logw, self._ws, self._ws.numel(), B, L,
+            st = self.lib.fs2_sdp_forward(self.handle, _DTYPES[x.dtype], x, pad, noise, logw, ws, ws.numel(), B, L,
                                           torch.cuda.current_stream(self.device))
         self._check(st, "forward")
         return logw

@@ -72,7 +72,7 @@ def main():
         # the kernel predictors alone: three blocks per step
         td = torch.bfloat16 if prec == "bf16" else torch.float32
         Kf, kbf = torch.empty(B, T, 24576, device=dev, dtype=td), torch.empty(B, T, 256, device=dev, dtype=td)
-        ws, stream = fd._workspace(B, T), torch.cuda.current_stream()
+        ws, stream = fd._workspace(fd.workspace_bytes(B, T)), torch.cuda.current_stream()
 
         def predict():
             for blk in range(3):
