@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "../../include/fs2.h"
+#include "fs2_common.h"  // bf16, f16
 
 namespace fs2 {
 
@@ -313,8 +314,16 @@ int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t str
 int voc_steps_padded(int taps, int cin_pad, int dtype);
 int voc_pick_mi16(const VocConvArgs& a, int esz, size_t* smem);  // rows per wave (x16) this layer's slab leaves room for; 0 = none
 int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream, int32_t* launched = nullptr);
-struct bf16;
-struct f16;  // fs2_common.h
+// A storage type as a value: a launcher turns a runtime dtype into template arguments by handing Ty<T>{} to a generic lambda,
+// which names T as `typename decltype(t)::type`.
+template <typename T> struct Ty { using type = T; };
+template <typename F>
+int with_storage_type(int dtype, F&& f) {  // f(Ty<T>) for a storage dtype (is_storage_dtype), anything else FS2_ERR_ARG
+    if (dtype == FS2_BF16) return f(Ty<bf16>{});
+    if (dtype == FS2_F16) return f(Ty<f16>{});
+    if (dtype == FS2_F32) return f(Ty<float>{});
+    return FS2_ERR_ARG;
+}
 template <typename T> constexpr int voc_dtype_of() {  // the storage dtype a vocoder kernel's T stands for
     return std::is_same<T, float>::value ? FS2_F32 : std::is_same<T, f16>::value ? FS2_F16 : FS2_BF16;
 }

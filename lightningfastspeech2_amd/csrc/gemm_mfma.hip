@@ -1115,7 +1115,6 @@ static unsigned dtype_pair(int in, int out) {
     if (in == FS2_F16) return out == FS2_F16 ? DT_F16 : out == FS2_F32 ? DT_F16_F32 : 0;
     return 0;
 }
-template <typename T> struct Ty { using type = T; };
 template <unsigned SET, typename F>
 static int with_dtypes(int in, int out, F&& f) {  // f(Ty<T>, Ty<OutT>)
     const unsigned p = dtype_pair(in, out);

@@ -398,22 +398,15 @@ int launch_vocoder_conv(const VocConvArgs& a, int dtype, hipStream_t stream, int
     size_t smem = 0;
     const int mi = voc_pick_mi16(a, (int)elem_bytes(dtype), &smem);
     if (!mi) return FS2_ERR_SHAPE;
-    if (dtype == FS2_BF16) {
-        if (mi == 14) return voc_launch_t<bf16, 14>(a, smem, stream, launched);
-        if (mi == 8) return voc_launch_t<bf16, 8>(a, smem, stream, launched);
-        if (mi == 4) return voc_launch_t<bf16, 4>(a, smem, stream, launched);
-        return voc_launch_t<bf16, 2>(a, smem, stream, launched);
-    }
-    if (dtype == FS2_F16) {  // bf16's tiles, LDS sizes and grids: the two differ in Vec16 / Mma16 only
-        if (mi == 14) return voc_launch_t<f16, 14>(a, smem, stream, launched);
-        if (mi == 8) return voc_launch_t<f16, 8>(a, smem, stream, launched);
-        if (mi == 4) return voc_launch_t<f16, 4>(a, smem, stream, launched);
-        return voc_launch_t<f16, 2>(a, smem, stream, launched);
-    }
-    if (mi == 14) return voc_launch_t<float, 14>(a, smem, stream, launched);
-    if (mi == 8) return voc_launch_t<float, 8>(a, smem, stream, launched);
-    if (mi == 4) return voc_launch_t<float, 4>(a, smem, stream, launched);
-    return voc_launch_t<float, 2>(a, smem, stream, launched);
+    return with_storage_type(dtype, [&](auto t) {  // f16 takes bf16's tiles, LDS sizes and grids: the two differ in Vec16 / Mma16 only
+        using T = typename decltype(t)::type;
+        switch (mi) {
+            case 14: return voc_launch_t<T, 14>(a, smem, stream, launched);
+            case 8: return voc_launch_t<T, 8>(a, smem, stream, launched);
+            case 4: return voc_launch_t<T, 4>(a, smem, stream, launched);
+            default: return voc_launch_t<T, 2>(a, smem, stream, launched);
+        }
+    });
 }
 
 }  // namespace fs2

@@ -48,9 +48,7 @@ struct fs2_vocoder : ErrorBase {
     struct FusedRb { void* w = nullptr; float* b = nullptr; size_t conv_bytes = 0; };
     std::vector<FusedRb> rb;       // [stage * n_kernels + j]: six convs back to back (narrow stages)
     std::vector<int> chan, upf;    // channels / cumulative upsampling after stage i (index 0 = conv_pre)
-    // workspace
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
+    Arena ws;                      // one output per stage + 4 scratch tensors of the largest stage, laid out per synthesize
     std::vector<void*> stage_out;  // x after conv_pre and after each stage
     int lastB = 0, lastT = 0;
     std::vector<int32_t> launches;  // fs2_voc_last_launches: one code per kernel launch of the last synthesize
@@ -192,6 +190,53 @@ int run_conv(fs2_vocoder* v, hipStream_t st, const VocLayer& L, const void* x, v
     return FS2_OK;
 }
 
+// The resident launch of resblock j of stage i: the whole block (m < 0) or its pair m.  The last pair, and so the whole block, adds
+// (xt + x) / n_kernels into the stage output; an earlier pair hands x on as it is.  With the defaults: the shape alone, which is
+// all voc_resblock_mi16 reads.
+VocResblockArgs rb_args(const fs2_vocoder* v, int i, int j, int m, const int32_t* lengths = nullptr, int B = 0, int T = 0,
+                        const void* x = nullptr, void* out = nullptr, bool x_act = false, bool out_act = false) {
+    const fs2_voc_config& c = v->cfg;
+    const fs2_vocoder::FusedRb& f = v->rb[(size_t)i * c.n_kernels + j];
+    const int first = m < 0 ? 0 : m;
+    const bool last = m < 0 || m == 2;
+    VocResblockArgs a{};
+    a.tune = &op_tuning();  // the calling thread's A/B switches
+    a.x = x; a.out = out; a.lengths = lengths; a.len_scale = v->upf[i + 1];
+    a.B = B; a.S = T * v->upf[i + 1]; a.C = v->chan[i + 1]; a.taps = c.rb_kernels[j]; a.wn = a.C / 32; a.npairs = m < 0 ? 3 : 1;
+    a.w = (const char*)f.w + f.conv_bytes * 2 * first;
+    a.bias = f.b + (size_t)2 * first * a.C;
+    for (int q = 0; q < 3; ++q) a.dil[q] = c.rb_dilations[j][q];
+    a.dil[0] = c.rb_dilations[j][first];
+    a.slope = 0.1f; a.scale = last ? 1.0f / (float)c.n_kernels : 1.f; a.accumulate = last && j > 0 ? 1 : 0;
+    a.x_act = x_act ? 1 : 0; a.out_act = out_act ? 1 : 0;
+    return a;
+}
+
+int run_resblock(fs2_vocoder* v, hipStream_t st, const VocResblockArgs& a) {
+    int32_t code = -1;
+    const int r = launch_vocoder_resblock(a, v->dt, st, &code);
+    if (code >= 0) v->launches.push_back(code);
+    if (r != FS2_OK) return v->fail(r, "fused %s launch failed (C=%d k=%d)", a.npairs == 3 ? "resblock" : "conv pair", a.C, a.taps);
+    return FS2_OK;
+}
+
+// How a resblock runs: in one resident launch (`whole`), else pair by pair, pair m on an LDS-resident tile where it fits and pays
+// (`pair[m]`) and as two plain convs otherwise.  Each entry is a form of voc_resblock_mi16 (408 / 808 / 804) or 0.
+struct BlockForm {
+    int whole = 0, pair[3] = {0, 0, 0};
+    bool resident() const { return whole || (pair[0] && pair[1] && pair[2]); }
+};
+
+// ... of resblock j of stage i, for the calling thread's knobs.  A block that fs2_voc_finalize did not pack (a wide stage) has no
+// resident form; the pairs are asked only when the whole block is refused.
+BlockForm block_form(const fs2_vocoder* v, int i, int j) {
+    BlockForm f;
+    if (!v->rb[(size_t)i * v->cfg.n_kernels + j].w) return f;
+    f.whole = voc_resblock_mi16(rb_args(v, i, j, -1), v->dt);
+    for (int m = 0; m < 3 && !f.whole; ++m) f.pair[m] = voc_resblock_mi16(rb_args(v, i, j, m), v->dt);
+    return f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -241,7 +286,7 @@ int fs2_voc_create(const fs2_voc_config* cfg, fs2_vocoder** out) {
 
 void fs2_voc_destroy(fs2_vocoder* v) {
     if (!v) return;
-    if (v->ws) (void)hipFree(v->ws);
+    v->ws.release();
     delete v;
 }
 
@@ -322,121 +367,61 @@ int fs2_voc_synthesize(fs2_vocoder* v, const float* mel, const int32_t* lengths,
     }
     need += 4 * big;
     if ((size_t)T * v->upf.back() > (size_t)0x7fffffff / 4) return v->fail(FS2_ERR_SHAPE, "T too large");
-    if (need > v->ws_bytes) {
-        FS2_HIP(v, hipStreamSynchronize(st));
-        if (v->ws) (void)hipFree(v->ws);
-        v->ws = nullptr;
-        v->ws_bytes = 0;
-        if (hipMalloc(&v->ws, need) != hipSuccess) return v->fail(FS2_ERR_NOMEM, "workspace of %zu bytes", need);
-        v->ws_bytes = need;
-    }
-    char* base = (char*)v->ws;
+    if (need > v->ws.cap) FS2_HIP(v, hipStreamSynchronize(st));  // it grows: the last pass may still use the block about to be freed
+    if (v->ws.reserve(need) != FS2_OK) return v->fail(FS2_ERR_NOMEM, "workspace of %zu bytes", need);
     v->stage_out.assign(ns + 1, nullptr);
-    for (int i = 0; i <= ns; ++i) { v->stage_out[i] = base; base += sb[i]; }
-    void* u = base;
-    void* a = base + big;
-    void* r1 = base + 2 * big;
-    void* r2 = base + 3 * big;
+    for (int i = 0; i <= ns; ++i) v->stage_out[i] = v->ws.take(sb[i]);
+    void* u = v->ws.take(big);
+    void* a = v->ws.take(big);
+    void* r1 = v->ws.take(big);
+    void* r2 = v->ws.take(big);
     v->lastB = B;
     v->lastT = T;
     v->launches.clear();
 
     FS2_TRY(run_conv(v, st, v->pre, mel, v->stage_out[0], nullptr, lengths, 1, B, T, 1.f, 1.f, false, /*in_fp32=*/true));
     const float inv = 1.0f / (float)c.n_kernels;
+    // a stream between two resident launches travels as lrelu(x) (x_act / out_act below); knob 9 keeps every stream raw
+    const bool act = op_tuning().voc_fused_resblock != 9;
     for (int i = 0; i < ns; ++i) {
-        // transposed conv, at the INPUT resolution, to up_rate * Cout phase-major channels
         const int S = T * v->upf[i + 1], sc = v->upf[i + 1];
         // when every resblock of this stage runs on LDS-resident tiles, the upsampled stream travels as lrelu(x):
         // all its consumers then fill their slabs by plain LDS-DMA (x_act, vocoder_resblock.hip)
-        const int g_voc_fused_resblock = op_tuning().voc_fused_resblock;
-        bool stage_act = g_voc_fused_resblock != 9;
-        for (int j = 0; j < c.n_kernels && stage_act; ++j) {
-            const fs2_vocoder::FusedRb& f = v->rb[(size_t)i * c.n_kernels + j];
-            if (!f.w) { stage_act = false; break; }
-            VocResblockArgs ra;
-                ra.tune = &op_tuning();
-            ra.x = u; ra.out = v->stage_out[i + 1]; ra.w = f.w; ra.bias = f.b; ra.lengths = lengths; ra.len_scale = sc;
-            ra.B = B; ra.S = S; ra.C = v->chan[i + 1]; ra.taps = c.rb_kernels[j]; ra.wn = ra.C / 32; ra.npairs = 3;
-            for (int m = 0; m < 3; ++m) ra.dil[m] = c.rb_dilations[j][m];
-            ra.slope = 0.1f; ra.scale = 1.f; ra.accumulate = 0;
-            if (voc_resblock_mi16(ra, v->dt)) continue;
-            for (int m = 0; m < 3 && stage_act; ++m) {
-                VocResblockArgs pa = ra;
-                pa.npairs = 1;
-                pa.dil[0] = c.rb_dilations[j][m];
-                if (!voc_resblock_mi16(pa, v->dt)) stage_act = false;
-            }
+        BlockForm form[FS2_VOC_MAX_KERNELS];
+        bool stage_act = act;
+        for (int j = 0; j < c.n_kernels; ++j) {
+            form[j] = block_form(v, i, j);
+            stage_act = stage_act && form[j].resident();
         }
+        // transposed conv, at the INPUT resolution, to up_rate * Cout phase-major channels
         FS2_TRY(run_conv(v, st, v->ups[i], v->stage_out[i], u, nullptr, lengths, v->upf[i], B, T * v->upf[i], 0.1f, 1.f, false, false,
                       false, stage_act ? 0.1f : 1.f));
         for (int j = 0; j < c.n_kernels; ++j) {
-            const fs2_vocoder::FusedRb& f = v->rb[(size_t)i * c.n_kernels + j];
-            if (f.w) {
-                VocResblockArgs ra;
-                ra.tune = &op_tuning();
-                ra.x = u; ra.out = v->stage_out[i + 1]; ra.w = f.w; ra.bias = f.b; ra.lengths = lengths; ra.len_scale = sc;
-                ra.B = B; ra.S = S; ra.C = v->chan[i + 1]; ra.taps = c.rb_kernels[j]; ra.wn = ra.C / 32; ra.npairs = 3;
-                for (int m = 0; m < 3; ++m) ra.dil[m] = c.rb_dilations[j][m];
-                ra.slope = 0.1f; ra.scale = inv; ra.accumulate = j > 0 ? 1 : 0;
-                ra.x_act = stage_act ? 1 : 0;
-                if (voc_resblock_mi16(ra, v->dt)) {  // the whole block in one launch
-                    int32_t code = -1;
-                    const int rr = launch_vocoder_resblock(ra, v->dt, st, &code);
-                    if (code >= 0) v->launches.push_back(code);
-                    if (rr != FS2_OK) return v->fail(rr, "fused resblock launch failed (C=%d k=%d)", ra.C, ra.taps);
-                    continue;
-                }
-                // else pair by pair: a (c1, c2) pair on an LDS-resident tile where it fits and pays,
-                // two plain convs otherwise
-                const void* rin = u;
-                bool resident[3];
-                for (int m = 0; m < 3; ++m) {
-                    VocResblockArgs pa = ra;
-                    pa.npairs = 1;
-                    pa.dil[0] = c.rb_dilations[j][m];
-                    resident[m] = voc_resblock_mi16(pa, v->dt) != 0;
-                }
-                for (int m = 0; m < 3; ++m) {
-                    void* o = m == 0 ? r1 : (m == 1 ? r2 : v->stage_out[i + 1]);
-                    VocResblockArgs pa = ra;
-                    pa.npairs = 1;
-                    pa.dil[0] = c.rb_dilations[j][m];
-                    pa.x = rin;
-                    pa.out = o;
-                    pa.w = (const char*)f.w + f.conv_bytes * 2 * m;
-                    pa.bias = f.b + (size_t)2 * m * ra.C;
-                    if (m < 2) { pa.scale = 1.f; pa.accumulate = 0; }
-                    // between two resident pairs the residual stream travels as lrelu(x): the consumer's slab fill is
-                    // then a plain LDS-DMA copy and it recovers x by the inverse map it applies anyway
-                    pa.x_act = (m == 0 ? stage_act : (resident[m - 1] && resident[m] && g_voc_fused_resblock != 9)) ? 1 : 0;
-                    pa.out_act = m < 2 && resident[m] && resident[m + 1] && g_voc_fused_resblock != 9;
-                    if (resident[m]) {
-                        int32_t code = -1;
-                        const int rr = launch_vocoder_resblock(pa, v->dt, st, &code);
-                        if (code >= 0) v->launches.push_back(code);
-                        if (rr != FS2_OK) return v->fail(rr, "fused conv pair launch failed (C=%d k=%d)", ra.C, ra.taps);
-                    } else {
-                        const size_t idx = ((size_t)i * c.n_kernels + j) * 3 + m;
-                        // c1 stores lrelu(out): c2 then stages it untouched (LDS-DMA fill in vocoder_conv.hip)
-                        FS2_TRY(run_conv(v, st, v->c1[idx], rin, a, nullptr, lengths, sc, B, S, 0.1f, 1.f, false, false, false, 0.1f));
-                        FS2_TRY(run_conv(v, st, v->c2[idx], a, o, rin, lengths, sc, B, S, 1.f, m < 2 ? 1.f : inv, m == 2 && j > 0));
-                    }
-                    rin = o;
-                }
+            const BlockForm& f = form[j];
+            if (f.whole) {  // the whole block in one launch
+                FS2_TRY(run_resblock(v, st, rb_args(v, i, j, -1, lengths, B, T, u, v->stage_out[i + 1], stage_act)));
                 continue;
             }
-            const void* r = u;
+            // else pair by pair: a (c1, c2) pair on an LDS-resident tile where it fits and pays, two plain convs otherwise
+            // (always, in a stage too wide to be packed)
+            const void* rin = u;
+            bool x_act = stage_act;
             for (int m = 0; m < 3; ++m) {
-                const size_t idx = ((size_t)i * c.n_kernels + j) * 3 + m;
-                // c1 stores lrelu(out): c2 then stages it untouched (LDS-DMA fill in vocoder_conv.hip)
-                FS2_TRY(run_conv(v, st, v->c1[idx], r, a, nullptr, lengths, sc, B, S, 0.1f, 1.f, false, false, false, 0.1f));
-                if (m < 2) {
-                    void* o = m == 0 ? r1 : r2;
-                    FS2_TRY(run_conv(v, st, v->c2[idx], a, o, r, lengths, sc, B, S, 1.f, 1.f, false));
-                    r = o;
-                } else {  // last pair of the block: (xt + x) / n_kernels summed into the stage output
-                    FS2_TRY(run_conv(v, st, v->c2[idx], a, v->stage_out[i + 1], r, lengths, sc, B, S, 1.f, inv, j > 0));
+                void* o = m == 0 ? r1 : (m == 1 ? r2 : v->stage_out[i + 1]);
+                // between two resident pairs the residual stream travels as lrelu(x): the consumer's slab fill is
+                // then a plain LDS-DMA copy and it recovers x by the inverse map it applies anyway
+                const bool out_act = act && m < 2 && f.pair[m] && f.pair[m + 1];
+                if (f.pair[m]) {
+                    FS2_TRY(run_resblock(v, st, rb_args(v, i, j, m, lengths, B, T, rin, o, x_act, out_act)));
+                } else {
+                    const size_t idx = ((size_t)i * c.n_kernels + j) * 3 + m;
+                    // c1 stores lrelu(out): c2 then stages it untouched (LDS-DMA fill in vocoder_conv.hip)
+                    FS2_TRY(run_conv(v, st, v->c1[idx], rin, a, nullptr, lengths, sc, B, S, 0.1f, 1.f, false, false, false, 0.1f));
+                    // last pair of the block: (xt + x) / n_kernels summed into the stage output
+                    FS2_TRY(run_conv(v, st, v->c2[idx], a, o, rin, lengths, sc, B, S, 1.f, m < 2 ? 1.f : inv, m == 2 && j > 0));
                 }
+                rin = o;
+                x_act = out_act;
             }
         }
     }

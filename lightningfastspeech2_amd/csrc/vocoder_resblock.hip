@@ -511,16 +511,11 @@ int launch_vocoder_resblock(const VocResblockArgs& a, int dtype, hipStream_t str
     if (!cfg) return FS2_ERR_SHAPE;
     const int nw = cfg / 100, mi = cfg % 100;
     const size_t smem = rb_lds_bytes(a, nw, mi, (int)elem_bytes(dtype));
-    if (dtype == FS2_BF16) {
-        if (nw == 4) return rb_launch_t<bf16, 8, 4>(a, smem, stream, launched);
-        return mi == 8 ? rb_launch_t<bf16, 8, 8>(a, smem, stream, launched) : rb_launch_t<bf16, 4, 8>(a, smem, stream, launched);
-    }
-    if (dtype == FS2_F16) {  // bf16's tiles, LDS sizes and grids
-        if (nw == 4) return rb_launch_t<f16, 8, 4>(a, smem, stream, launched);
-        return mi == 8 ? rb_launch_t<f16, 8, 8>(a, smem, stream, launched) : rb_launch_t<f16, 4, 8>(a, smem, stream, launched);
-    }
-    if (nw == 4) return rb_launch_t<float, 8, 4>(a, smem, stream, launched);
-    return mi == 8 ? rb_launch_t<float, 8, 8>(a, smem, stream, launched) : rb_launch_t<float, 4, 8>(a, smem, stream, launched);
+    return with_storage_type(dtype, [&](auto t) {  // f16 takes bf16's tiles, LDS sizes and grids
+        using T = typename decltype(t)::type;
+        if (nw == 4) return rb_launch_t<T, 8, 4>(a, smem, stream, launched);
+        return mi == 8 ? rb_launch_t<T, 8, 8>(a, smem, stream, launched) : rb_launch_t<T, 4, 8>(a, smem, stream, launched);
+    });
 }
 
 }  // namespace fs2
