@@ -265,6 +265,10 @@ int fs2_profile_read(fs2_engine* e, int32_t kernel_class, double* total_ms, int6
  *   220/221 bf16 pointwise launches of more tiles than CUs: one tile per workgroup / the persistent kernel (default); bit-identical
  *   230/231 wide depth-wise predictors: the last LayerNorm + Linear(filter, 1) head as a normalise pass over stored activations / from
  *           row sums the last GEMM's epilogue leaves (fs2_op_gemm_head, default); equal to fp32 rounding of another summation order
+ *   240..242 slab kernel K loop, 16-bit operands stored as they came in: two weight stages, a tile requested one step before it is read /
+ *           the lead-2 loop (three weight stages, the tile of step s + 2 requested at step s behind a counted wait) for the launch
+ *           classes that measured faster with it (default) / wherever it exists: pointwise launches at tiles of up to 128 rows (192 with the plain epilogue), conv
+ *           launches with k = 3 or 9 taps at up to 128 rows; bit-identical outputs (211, the r04 ring of whole operand stages, stays retired)
  *   500/501 fp32 slab-kernel launches: fp32 MFMA (default) / bf16 x 3 split products (what FS2_MIXED_X3 uses in its front; operator level)
  *   700/701 bf16 fs2_op_bgemm tile order: plain / XCD-contiguous (default)
  *   800/801 bf16 fs2_op_bgemm: generic instantiation only / the bounds-free one for full, aligned tiles (default)
@@ -372,6 +376,10 @@ int fs2_op_gemm_splitk_choice(int32_t dtype, int32_t M, int32_t N, int32_t Cin, 
  * weights packed on the fly; two_launch = a LayerNorm request served as GEMM into ln_tmp + the LayerNorm kernel. */
 int32_t fs2_op_gemm_route(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
                           uint32_t present, int32_t bias_aligned);
+/* The same request's K loop on the slab kernel: 0 = two weight stages (also: another family), 1 / 2 = the lead-2 loop's pointwise / conv
+ * form (switches 240..242); -status where the request is refused. */
+int32_t fs2_op_gemm_route_lead(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
+                               uint32_t present, int32_t bias_aligned);
 int fs2_op_gemm_splitk(int32_t dtype, int32_t out_dtype, const void* x, const void* w, void* c, float* part, int32_t M, int32_t N,
                        int32_t Cin, int32_t taps, int32_t S, int32_t ksplit, int32_t accumulate, void* hip_stream);
 /* ... with the ReLU (and dropout) backward of a data-gradient product folded into the store: c = gate > 0 ? scale * (x w^T + bias)

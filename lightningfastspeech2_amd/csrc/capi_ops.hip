@@ -55,6 +55,7 @@ int apply_knob(Tuning& t, int variant) {
     else if (variant == 500 || variant == 501) t.split_f32 = variant - 500;            // operator level: fp32 slab launches as fp32 MFMA (default) / bf16 x 3 split
     else if (variant == 230 || variant == 231) t.head_sums = variant - 230;           // predictor head from a normalise pass / from the last GEMM's epilogue sums (default)
     else if (variant == 220 || variant == 221) t.gemm_persist = variant - 220;         // multi-round bf16 pointwise launches one tile per workgroup / on the persistent kernel (default)
+    else if (variant >= 240 && variant <= 242) t.slab_lead = variant - 240;            // slab kernel K loop: two weight stages / the lead-2 loop for the launch classes that measured faster (default) / wherever it applies
     else if (variant >= 200 && variant <= 202) t.slab_xcd_remap = variant - 200;       // slab kernel tile order plain / XCD-contiguous (default) / + column pairs per XCD for wide weight panels
     else if (variant >= 0 && variant <= 7 && variant != 2) t.gemm_variant = variant;    // kernel family / forced tile height of the forward GEMM launcher (gemm_mfma.hip: route_gemm; 2 was the 128x256 DMA ring: tools/probes/gemm_forms)
     else ok = 0;
@@ -230,8 +231,8 @@ int fs2_op_gemm_splitk_choice(int32_t dtype, int32_t M, int32_t N, int32_t Cin, 
 }
 
 // Which kernel the forward GEMM launcher would take for a request, under the calling thread's tuning: host arithmetic, no GPU.
-int32_t fs2_op_gemm_route(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
-                          uint32_t present, int32_t bias_aligned) {
+static GemmRoute route_of_request(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
+                                  uint32_t present, int32_t bias_aligned) {
     static float dummy[8];  // only the members' presence and the bias pointer's alignment are looked at
     void* p = (void*)(((uintptr_t)dummy + 15) & ~(uintptr_t)15);
     GemmArgs a = gemm_args(p, p, nullptr, p, M, N, Cin, taps, S, (present & GF_RELU) != 0);
@@ -252,10 +253,23 @@ int32_t fs2_op_gemm_route(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N
     if (present & GF_CLO) a.C_lo = p;
     if (present & GF_SPLIT) a.split = 1;
     if (present & GF_WPRE) a.w_presplit = 1;
-    const GemmRoute r = route_gemm(a, dtype, out_dtype);
+    return route_gemm(a, dtype, out_dtype);
+}
+int32_t fs2_op_gemm_route(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
+                          uint32_t present, int32_t bias_aligned) {
+    const GemmRoute r = route_of_request(dtype, out_dtype, M, N, Cin, taps, S, ksplit, present, bias_aligned);
     if (r.status != FS2_OK) return -r.status;
     return r.family | r.mi << 4 | (r.ln ? 1 : 0) << 8 | (r.split ? 1 : 0) << 9 | (r.defer ? 1 : 0) << 10 | (r.xpre ? 1 : 0) << 11 |
            (r.zr ? 1 : 0) << 12 | (r.presplit ? 1 : 0) << 13 | (r.two_launch ? 1 : 0) << 16;
+}
+
+// ... and which K loop the slab kernel would run for it: 0 two weight stages, 1 / 2 the lead-2 loop's pointwise / conv form (an answer
+// of its own, so that fs2_op_gemm_route's stays what the recorded launcher gave)
+int32_t fs2_op_gemm_route_lead(int32_t dtype, int32_t out_dtype, int32_t M, int32_t N, int32_t Cin, int32_t taps, int32_t S, int32_t ksplit,
+                               uint32_t present, int32_t bias_aligned) {
+    const GemmRoute r = route_of_request(dtype, out_dtype, M, N, Cin, taps, S, ksplit, present, bias_aligned);
+    if (r.status != FS2_OK) return -r.status;
+    return r.family == GEMM_SLAB ? r.lead : 0;
 }
 
 int fs2_op_gemm_splitk(int32_t dtype, int32_t out_dtype, const void* x, const void* w, void* c, float* part, int32_t M, int32_t N,

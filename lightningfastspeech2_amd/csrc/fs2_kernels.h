@@ -29,6 +29,7 @@ struct Tuning {
     int head_sums = 1;         // wide predictors: last LayerNorm + Linear head from the last GEMM's epilogue sums (GemmArgs::head_out) / a normalise pass
     int gemm_persist = 1;      // bf16 pointwise launches of more tiles than CUs on the persistent kernel (gemm_persist.hip)
     int slab_xcd_remap = 1;    // slab kernel tile order: 0 plain, 1 XCD-contiguous (default), 2 = 1 + column pairs per XCD where the weight panel exceeds an L2 (fewer bytes fetched, 1 % slower: r05)
+    int slab_lead = 1;         // slab kernel's lead-2 K loop (three weight stages): 0 never, 1 for the launch classes that measured faster, 2 wherever it applies
     int split_f32 = 0;         // operator level only (tests): every fp32 slab launch in the bf16 x 3 split arithmetic
     int attn_pipe = 3;         // 0 attention_kernel only; 1 / 2 / 4 the pipelined kernel with 32 / 64 / 96 queries per wave; 3 by size
     int attn_x3 = 1;           // fp32-storage split modes: attention on bf16 x 3 split products (1) or fp32 MFMA (0)
@@ -120,6 +121,7 @@ struct GemmRoute {
     int status = FS2_OK;       // != FS2_OK: nothing is launched
     int family = GEMM_NONE;    // GEMM_NONE with FS2_OK: nothing to do (M <= 0)
     int mi = 0;                // slab / persistent kernel: tile height / 32
+    int lead = 0;              // slab kernel: 0 = two weight stages, 1 / 2 = the lead-2 K loop's pointwise / conv form
     int in_dtype = 0, out_dtype = 0;
     bool ln = false, split = false, defer = false, xpre = false;  // the slab kernel's template flags
     bool zr = false;           // the 128x128 kernel's zero_rows instantiation

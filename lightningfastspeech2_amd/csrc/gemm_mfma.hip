@@ -177,6 +177,8 @@ __global__ __launch_bounds__(256) void gemm_conv_kernel(GemmArgs p) {
 // [0, S) of the utterance read the zero page.  Two slab buffers + two weight buffers, each its own
 // LDS object; every step: explicit vmcnt(0) + __syncthreads, issue the
 // next step's DMAs, multiply the current one.
+// (LEAD = 1 / 2, 16-bit operands: a third weight buffer, the weight tile requested TWO steps ahead behind a counted vmcnt - the
+// lead-2 K loop below; same MFMA sequence, same bits; taken for the launch classes slab_lead_form lists.)
 // =================================================================================================
 // Slab-kernel weight tile: MFMA row i (= lane group fg*4 + r in the accumulator) of fragment ni is
 // mapped to output channel  (ni>>1)*32 + (i>>2)*8 + (ni&1)*4 + (i&3)  of the wave's 64, so that a lane
@@ -217,20 +219,24 @@ __device__ unsigned long long g_slab_stamps[4][8];
 #define SLAB_STAMP(i) do { } while (0)
 #endif
 
-template <typename T, typename OutT, int MI, bool LN, bool SPLIT = false, bool DEFER = false, bool XPRE = false>
+template <typename T, typename OutT, int MI, bool LN, bool SPLIT = false, bool DEFER = false, bool XPRE = false, int LEAD = 0>
 __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
     static_assert(!XPRE || SPLIT, "XPRE: the split arithmetic's conv form (activation slab split in place when it lands)");
+    static_assert(LEAD == 0 || (!SPLIT && sizeof(T) == 2), "the lead-2 K loop is the 16-bit kernels'");
+    static_assert(LEAD >= 0 && LEAD <= 2 && (LEAD != 2 || MI <= 4), "lead-2: pointwise (1) up to 192 rows, conv (2) up to 128 - what three weight stages leave of the LDS");
     static_assert(!SPLIT || sizeof(T) == 4, "the split arithmetic takes fp32 operands");
     static_assert(!(DEFER && LN), "deferred LayerNorm is what a launch WITHOUT the fused epilogue leaves behind");
 #if defined(__HIP_DEVICE_COMPILE__)  // the buffer-resource builtins only exist in the device pass
     using Cfg = SlabCfg<MI>;
     constexpr int BMs = Cfg::BM;
     constexpr int SI = Cfg::SI;
-    constexpr int SLAB_B = Cfg::SLAB_BYTES;
+    // (the pointwise lead-2 form sizes a slab stage for what taps = 1 reads, BM rows: the k <= 31 halo is what does not fit beside a third weight stage at 192 rows)
+    constexpr int SLAB_B = LEAD == 1 ? BMs * ROWB : Cfg::SLAB_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned char slab0[SLAB_B];
     __shared__ __attribute__((aligned(16))) unsigned char slab1[SLAB_B];
     __shared__ __attribute__((aligned(16))) unsigned char wt0[S_BN * ROWB];  // 32 KiB weight tile per stage
     __shared__ __attribute__((aligned(16))) unsigned char wt1[S_BN * ROWB];
+    __shared__ __attribute__((aligned(16))) unsigned char wt2[LEAD ? S_BN * ROWB : 16];  // lead-2 forms: the third stage (never named otherwise: not allocated)
     // The column tile's per-channel epilogue constants - bias, and for the fused LayerNorm epilogue gamma, beta, the predictor head's
     // weights - fetched at the TOP of the kernel (one value per thread, their round trip under the first operand DMAs') and parked
     // in LDS.  (Until r05 the epilogues fetched them behind the K loop: sixteen bias loads per lane, then gamma / beta - the
@@ -295,7 +301,7 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
     // waves 4-7 and idle at the barrier, while an LDS-DMA instruction costs its wave 100-150 issue cycles next to
     // MFMAs (tools/probes/slab_stamps.py, step_shape_mfma.hip): the ~500 cycles of DMA issue per step belong on
     // the waves that have the slack, off the critical ones.
-    constexpr int DW = 4, DSI = SI * 8 / DW, DWI = 32 / DW;
+    constexpr int DW = 4, DSI = LEAD == 1 ? MI : SI * 8 / DW, DWI = 32 / DW;
     const bool dma_wave = wave < DW;
     unsigned svoff[DSI];
 #pragma unroll
@@ -329,6 +335,22 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
         for (int i = 0; i < DWI; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)(dst + (i * DW + wave) * 1024),
                                                      16, wvoff[i], koff, 0, 0);
+    };
+    // The lead-2 K loop's requests: never under a branch (the caller is the DMA waves' copy of the loop) and never skipped - a
+    // request past the last step goes out with every lane out of range (no memory traffic, zeros into a stage nobody reads
+    // again), so that every step issues the SAME number of DMA instructions and its counted wait is a compile-time number.
+    auto issue_slab_l = [&](unsigned char* dst, int cc, bool live) {
+#pragma unroll
+        for (int i = 0; i < DSI; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(dst + (i * DW + wave) * 1024),
+                                                     16, live ? svoff[i] : OOB, live ? cc * ROWB : 0, 0, 0);
+    };
+    auto issue_w_l = [&](unsigned char* dst, int cc, int tap, bool live) {
+        const int koff = live ? (tap * p.Cin + (cc0 + cc) * KE) * (int)sizeof(T) : 0;
+#pragma unroll
+        for (int i = 0; i < DWI; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)(dst + (i * DW + wave) * 1024),
+                                                     16, live ? wvoff[i] : OOB, koff, 0, 0);
     };
 
     f32x4_t acc[4][MI];  // [ni][mi]
@@ -451,8 +473,14 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
     // 35 k-tick out-projection + LayerNorm launch sat in front of the first DMA, tools/probes/slab_phase_stamps.py) and the two
     // round trips now overlap
     SLAB_STAMP(1);
-    issue_slab(slab0, 0);
-    issue_w(wt0, 0, 0);
+    if constexpr (LEAD == 0) {
+        issue_slab(slab0, 0);
+        issue_w(wt0, 0, 0);
+    } else if (dma_wave) {  // with the second step's weight tile: two tiles are in flight from here on.  ONE branch around all three
+        issue_slab_l(slab0, 0, true);  // requests: behind a join whose other side has requests pending hipcc takes them for the newest
+        issue_w_l(wt0, 0, 0, true);
+        issue_w_l(wt1, ntap == 1 ? 1 : 0, ntap == 1 ? 0 : 1, ncc * ntap > 1);
+    }
     float prm[LN ? 4 : 1];
     if (tid < S_BN) {
         const int n = n0 + tid;
@@ -588,6 +616,7 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
         }
     }
     SLAB_STAMP(6);
+    if constexpr (LEAD == 0) {
     for (int cc = 0; cc < ncc; cc += 2) {
         for (int tap = 0; tap < ntap; tap += 2) {
             FS2_SLAB_STEP(slab0, slab1, wt0, wt1, cc, tap)
@@ -599,6 +628,108 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
                 if (tap + 1 < ntap) FS2_SLAB_STEP(slab1, slab0, wt0, wt1, cc + 1, tap + 1)
             }
         }
+    }
+    } else {
+        // ---- lead-2 K loop: the weight tile of step s + 2 is requested at the top of step s, into the third stage ----
+        // In the loop above a tile is asked for exactly one step before it is read, so a step is never shorter than one round trip
+        // to L2, whatever its MFMA work; at 128- and 192-row tiles (1024 / 1536 MFMA cycles per step and SIMD) the trip is the
+        // longer of the two.  Here step s = (cc, tap) reads weight stage s % 3 and slab stage cc & 1, and at its top
+        //   1. waits with a COUNTED vmcnt: vector-memory operations retire in issue order, so leaving exactly the instructions
+        //      issued behind tile s in flight (tile s + 1, and the next channel block's slab where that went out behind it)
+        //      means tile s and everything older has landed;
+        //   2. barrier: everyone's share has, and every wave has left step s - 1 - stage (s + 2) % 3 and the other slab are free;
+        //   3. requests tile s + 2 (pointwise: the next step's slab first, it is read one step earlier).
+        // (Nothing pins the requests to the top of the step: in the compiled loop hipcc spreads them through the step's MFMAs, some as
+        //  late as its end, so tile s + 2 leaves between one and two steps before it is read, not a full two.  Left so on purpose: a
+        //  DMA issue costs its wave 100-150 cycles next to MFMAs, and fourteen of them in a block in front of the first fragment read
+        //  is what the interleaving avoids; a variant pinned by a sched_barrier was not measured.)
+        // Conv launches (LEAD = 2, taps a multiple of 3: the stage of a step is tap % 3, a static name): the next channel block's
+        // slab goes out at tap 0 BEHIND that step's weight tile, so the waits of taps 1 and 2 leave it in flight (DWI + DSI).
+        // Every step issues the same instructions (dead requests go out of range), so each count is a compile-time number; the
+        // loop exists twice, for the DMA waves and for the others, instead of holding its requests under a branch (at a join
+        // hipcc's LDS-DMA scoreboard turns "maybe issued" into a vmcnt(0) in front of the fragment reads).
+        // Same MFMA sequence per output element as the loop above: bit-identical results.
+        const int nsteps = ncc * ntap;
+        auto kloop = [&](auto dmaw_c) {
+            constexpr bool DMAW = decltype(dmaw_c)::value;
+            // The counts are right only while the DMA instructions of a step reach the queue in SOURCE order (slab group before weight
+            // group in the pointwise form, weight group before slab group in the conv form).  hipcc keeps that order in this build (every
+            // DMA rewrites M0, which serialises them; checked in the ISA of each step instance), but nothing in the language promises it
+            // for stores into LDS objects it can prove distinct: after a compiler update, read the ISA again - the bit-equality tests
+            // of tests/test_gpu_slab_lead.py are the only net that would catch a reordering.
+#define FS2_LEAD_WAIT(cnt)                                                                                              \
+            /* vmcnt(cnt) (the other waves: none) + lgkmcnt(0), then the BARE barrier: __syncthreads()'s fence counts a */  \
+            /* pending LDS-DMA as a pending LDS write and drains it with a vmcnt(0) of its own                          */  \
+            __builtin_amdgcn_s_waitcnt(DMAW ? (0x0070 | (cnt)) : 0xC07F);                                               \
+            __builtin_amdgcn_s_barrier();
+            if constexpr (LEAD == 1) {
+#define FS2_LEAD_STEP(slab_cur, slab_nxt, w_cur, w_nn, sv)                                                              \
+                {                                                                                                       \
+                    FS2_LEAD_WAIT(DWI)                                                                                  \
+                    if constexpr (DMAW) {                                                                               \
+                        issue_slab_l(slab_nxt, (sv) + 1, (sv) + 1 < nsteps);                                            \
+                        issue_w_l(w_nn, (sv) + 2, 0, (sv) + 2 < nsteps);                                                \
+                    }                                                                                                   \
+                    compute(slab_cur, w_cur, 0);                                                                        \
+                }
+                // (the first step stands in front of the loop: with it at the loop header hipcc's scoreboard, merging the prologue's
+                //  requests with the loop's own, put a vmcnt(0) behind the header's barrier - every sixth step fell back to one step
+                //  of lead; so placed, the routed 32-row forms have none.  The taller forms still keep one, ISA-checked: they are
+                //  reachable with knob 242 only.)
+                FS2_LEAD_STEP(slab0, slab1, wt0, wt2, 0)
+                for (int s = 1; s < nsteps; s += 6) {
+                    FS2_LEAD_STEP(slab1, slab0, wt1, wt0, s)
+                    if (s + 1 >= nsteps) break;
+                    FS2_LEAD_STEP(slab0, slab1, wt2, wt1, s + 1)
+                    if (s + 2 >= nsteps) break;
+                    FS2_LEAD_STEP(slab1, slab0, wt0, wt2, s + 2)
+                    if (s + 3 >= nsteps) break;
+                    FS2_LEAD_STEP(slab0, slab1, wt1, wt0, s + 3)
+                    if (s + 4 >= nsteps) break;
+                    FS2_LEAD_STEP(slab1, slab0, wt2, wt1, s + 4)
+                    if (s + 5 >= nsteps) break;
+                    FS2_LEAD_STEP(slab0, slab1, wt0, wt2, s + 5)
+                }
+#undef FS2_LEAD_STEP
+            } else {
+                // tile s + 2 of step (ccv, tapv): two taps on, wrapping into the next channel block
+#define FS2_LEAD_STEP(slab_cur, slab_nxt, w_cur, w_nn, ccv, tapv, cnt, slab_req)                                        \
+                {                                                                                                       \
+                    FS2_LEAD_WAIT(cnt)                                                                                  \
+                    if constexpr (DMAW) {                                                                               \
+                        int t2 = (tapv) + 2, c2 = (ccv);                                                                \
+                        if (t2 >= ntap) { t2 -= ntap; ++c2; }                                                           \
+                        issue_w_l(w_nn, c2, t2, c2 < ncc);                                                              \
+                        if constexpr (slab_req) issue_slab_l(slab_nxt, (ccv) + 1, (ccv) + 1 < ncc);                     \
+                    }                                                                                                   \
+                    compute(slab_cur, w_cur, (tapv));                                                                   \
+                }
+#define FS2_LEAD_BLOCK(slab_cur, slab_nxt, ccv)                                                                         \
+                {                                                                                                       \
+                    FS2_LEAD_STEP(slab_cur, slab_nxt, wt0, wt2, ccv, 0, DWI, true)                                      \
+                    FS2_LEAD_STEP(slab_cur, slab_nxt, wt1, wt0, ccv, 1, DWI + DSI, false)                               \
+                    FS2_LEAD_STEP(slab_cur, slab_nxt, wt2, wt1, ccv, 2, DWI + DSI, false)                               \
+                    for (int tap = 3; tap < ntap; tap += 3) {                                                           \
+                        FS2_LEAD_STEP(slab_cur, slab_nxt, wt0, wt2, ccv, tap, DWI, false)                               \
+                        FS2_LEAD_STEP(slab_cur, slab_nxt, wt1, wt0, ccv, tap + 1, DWI, false)                           \
+                        FS2_LEAD_STEP(slab_cur, slab_nxt, wt2, wt1, ccv, tap + 2, DWI, false)                           \
+                    }                                                                                                   \
+                }
+                static_assert(DWI + DSI <= 15, "vmcnt's low four bits");
+                for (int cc = 0;; cc += 2) {
+                    FS2_LEAD_BLOCK(slab0, slab1, cc)
+                    if (cc + 1 >= ncc) break;
+                    FS2_LEAD_BLOCK(slab1, slab0, cc + 1)
+                    if (cc + 2 >= ncc) break;
+                }
+#undef FS2_LEAD_BLOCK
+#undef FS2_LEAD_STEP
+            }
+#undef FS2_LEAD_WAIT
+        };
+        if (dma_wave) kloop(BoolC<true>{});
+        else kloop(BoolC<false>{});
+        dma_drain();  // the dead requests of the last two steps: landed before the epilogues reuse the operand buffers behind their barrier
     }
     SLAB_STAMP(2);
 #undef FS2_SLAB_STEP
@@ -1053,7 +1184,7 @@ __global__ __launch_bounds__(512) void gemm_conv_slab_kernel(GemmArgs p) {
 #endif
 }
 
-template <typename T, typename OutT, int MI, bool LN, bool SPLIT = false, bool DEFER = false, bool XPRE = false>
+template <typename T, typename OutT, int MI, bool LN, bool SPLIT = false, bool DEFER = false, bool XPRE = false, int LEAD = 0>
 static int launch_slab_t(const GemmArgs& a0, hipStream_t stream) {
     GemmArgs a = a0;
     a.xcd_remap = tuning_of(a0.tune).slab_xcd_remap;
@@ -1066,7 +1197,7 @@ static int launch_slab_t(const GemmArgs& a0, hipStream_t stream) {
     }
     if (a.taps == 1) a.S = a.M;  // plain GEMM: one "utterance" of M rows
     const int tiles = (a.M / a.S) * ((a.S + BMs - 1) / BMs) * ((a.N + S_BN - 1) / S_BN) * (a.ksplit > 1 ? a.ksplit : 1);
-    hipLaunchKernelGGL((gemm_conv_slab_kernel<T, OutT, MI, LN, SPLIT, DEFER, XPRE>), dim3(tiles), dim3(512), 0, stream, a);
+    hipLaunchKernelGGL((gemm_conv_slab_kernel<T, OutT, MI, LN, SPLIT, DEFER, XPRE, LEAD>), dim3(tiles), dim3(512), 0, stream, a);
     return hipGetLastError() == hipSuccess ? FS2_OK : FS2_ERR_HIP;
 }
 
@@ -1192,6 +1323,28 @@ static bool rules_hold(const Request& q, unsigned subject, int family) {
     return true;
 }
 
+// The slab kernel's lead-2 K loop (three weight stages, tile s + 2 requested at step s; bit-identical to the two-stage loop): 0 = not
+// taken, 1 = its pointwise form, 2 = its conv form.  It EXISTS for 16-bit operands stored as they came in, no split-K: pointwise
+// launches at tiles of up to 128 rows with any epilogue and at 192 rows with the plain epilogue (with the LayerNorm or the deferred
+// epilogue the 192-row form needs 256 registers and spills: not built, never routed), conv launches with taps a multiple of 3
+// (k = 3, 9) at up to 128 rows.  It is TAKEN (Tuning::slab_lead = 1) for the launch classes that measured faster with it - a choice by
+// (taps, K, tile height, epilogue), never by the batch.
+static int slab_lead_form(int knob, const GemmArgs& a, int in_dtype, int out_dtype, int mi, bool ln, bool defer) {
+    if (!knob || !is_16bit(in_dtype) || out_dtype != in_dtype || a.ksplit > 1) return 0;
+    const bool plain = !ln && !defer;
+    const int form = a.taps == 1 ? (mi <= 4 || (mi == 6 && plain) ? 1 : 0) : (a.taps % 3 == 0 && mi <= 4 ? 2 : 0);
+    if (knob >= 2 || !form) return form;
+    // Measured per launch class (tools/bench_slab_lead.py, profiles/slab_lead_ab.md) with operands cold, which is the state the
+    // ENCODER's launches are in inside a forward (profiles/HISTORY.md section 4, "Round 4"): faster by more than the spread of the
+    // two-stage rounds are  k = 9 plain at 128 rows (encoder conv1, 45.4 -> 38.6 us),  K = 1024 + LayerNorm at 32 rows (encoder conv2,
+    // 25.0 -> 21.6)  and  k = 3 + LayerNorm at 32 rows (19.6 -> 15.6).  Exactly these three (taps, K or tile, epilogue) classes are
+    // routed, whatever their N and Cin, which were not varied.  Everything else keeps the two-stage loop: the four-step K = 256
+    // launches (0.3-0.5 us lower, at their spread), other tap counts, K and tile heights (not measured), and the decoder's launches,
+    // whose input the previous launch has just written - with warm operands the loop is neutral there.
+    if (form == 2) return (mi == 4 && plain && a.taps == 9) || (mi == 1 && ln && a.taps == 3) ? 2 : 0;
+    return mi == 1 && ln && a.K == 1024 ? 1 : 0;
+}
+
 // One launch for the request as it stands.  With ln_g set the question is whether the slab kernel takes it with the LayerNorm in
 // its epilogue (whole rows per workgroup); GEMM_NONE with FS2_OK and M > 0 then means it does not.
 static GemmRoute route_one(const GemmArgs& a, int in_dtype, int out_dtype) {
@@ -1258,6 +1411,7 @@ static GemmRoute route_one(const GemmArgs& a, int in_dtype, int out_dtype) {
         r.split = in_dtype == FS2_F32 && out_dtype == FS2_F32 && (q.have & ND_SPLIT_ON);
         r.xpre = r.split && a.taps > 1;  // conv launches of the split arithmetic: the slab is split in place when it lands
         r.presplit = r.split && !a.w_presplit;
+        r.lead = slab_lead_form(tn.slab_lead, a, in_dtype, out_dtype, mi, ln, defer);
     }
     return r;
 }
@@ -1316,6 +1470,13 @@ static int launch_slab_e(const GemmRoute& r, const GemmArgs& a, hipStream_t stre
         if constexpr (sizeof(T) == 4) {
             if (r.xpre) return launch_slab_t<T, OutT, MI, LN, true, DEFER, true>(a, stream);
             if (r.split) return launch_slab_t<T, OutT, MI, LN, true, DEFER>(a, stream);
+        } else if constexpr (sizeof(OutT) == 2 && MI <= 6) {  // the lead-2 K loop: 16-bit in and out (slab_lead_form says which forms exist)
+            if constexpr (MI <= 4 || (!LN && !DEFER)) {
+                if (r.lead == 1) return launch_slab_t<T, OutT, MI, LN, false, DEFER, false, 1>(a, stream);
+            }
+            if constexpr (MI <= 4) {
+                if (r.lead == 2) return launch_slab_t<T, OutT, MI, LN, false, DEFER, false, 2>(a, stream);
+            }
         }
         return launch_slab_t<T, OutT, MI, LN, false, DEFER>(a, stream);
     });
