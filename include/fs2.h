@@ -688,6 +688,54 @@ int fs2_op_wav_pack(const float* wav, const int32_t* lengths, int32_t B, int32_t
                     int64_t out_capacity, int64_t* offsets, void* hip_stream);
 
 /* ================================================================================================
+ * Waveform augmentation on the packed buffer (csrc/augment.hip, DESIGN.md "Augmentation"): what the reference's SpeechGenerator does
+ * on the host per utterance behind the vocoder (generate.py:82-104 RoomSimulator + AddGaussianSNR, generator.py:181,197-201 resample),
+ * restated from the definitions below - no library is pinned.  Stateless entry points on the layout fs2_op_wav_pack writes: `in`
+ * (packed) float32 holds utterance b's n_b = offsets[b + 1] - offsets[b] samples contiguously, offsets (B + 1) int64 ON THE DEVICE.
+ * The host knows capacities only: max_len is a host upper bound on every n_b and sizes the grids (an n_b beyond it is clamped to
+ * it; a negative one counts as 0).  Where lengths change the entry point writes out_offsets (B + 1) itself.  Samples outside an
+ * utterance's [0, n_b) count as zero: they are never read from a neighbour and nothing at or past offsets[B] is read; out beyond
+ * out_offsets[B] is left alone.  out_capacity (elements) below the worst case for (max_len, B, mode) is FS2_ERR_ARG.  Every argument
+ * (FS2_ERR_ARG) or shape (FS2_ERR_SHAPE; also B > 65535, max_len > 2^30) error is answered before any device call.  The heavy sums
+ * are exact-fp32 MFMA GEMMs whose order depends on (position in the tile, R, table shape) only: results are bitwise batch-invariant.
+ * Nothing is allocated, nothing synchronises.  out must not overlap in (except fs2_op_wav_add_noise, where out == in is allowed).
+ *
+ * fs2_op_wav_resample, orig_freq -> new_freq (torchaudio's published sinc_interp_hann definition; not pinned against its output):
+ *   orig = orig_freq / gcd, new = new_freq / gcd, lpw = 6, rolloff = 0.99, base = min(orig, new) * rolloff,
+ *   width = ceil(lpw * orig / base), K = 2 * width + orig; for p < new, q < K:
+ *   t = clip((-p / new + (q - width) / orig) * base, -lpw, lpw), tab[p][q] = sinc(pi t) * cos^2(pi t / (2 lpw)) * base / orig.
+ *   m_b = ceil(new * n_b / orig) (int64), y[i * new + p] = sum_q tab[p][q] * x[i * orig + q - width] for i * new + p < m_b.
+ *   tab: (new, K) float32 row-major ON THE DEVICE, built by the caller in float64 and rounded once (augment.resample_table).
+ *   Worst case m = ceil(new * max_len / orig) per utterance.  Supported: new <= 640, K <= 1024; else FS2_ERR_SHAPE.
+ * fs2_op_wav_convolve: y_b[t] = sum_{k < R} h[k] x_b[t - k], h = row rir_index[b] of the bank rir (n_rir, R_max) float32,
+ *   R = rir_len[that row] (clamped to [1, R_max]); rir_len (n_rir) int32, rir_index (B) int32, all on the device.  rir_index[b] < 0
+ *   (or >= n_rir) copies the utterance bit for bit, in either mode.  FS2_CONV_SAME keeps t < n_b (audiomentations'
+ *   leave_length_unchanged), FS2_CONV_FULL t < n_b + R - 1 (an empty utterance stays empty).  No rescaling: the response is applied as
+ *   given.  1 <= R_max <= 16384; larger is FS2_ERR_SHAPE.  Worst case per utterance: max_len (SAME), max_len + R_max - 1 (FULL).
+ * fs2_op_wav_add_noise (AddGaussianSNR's rule, noise_rms = signal_rms / 10^(snr / 20)): rms_b = sqrt(sum x^2 / n_b), the sum in fp64
+ *   in a fixed order; scale_b = (float)(rms_b / 10^(snr_b / 20)) evaluated in fp64 and rounded once (0 for an empty utterance);
+ *   y = x + scale_b * z as one fp32 multiply and one fp32 add, uncontracted.  snr (B) float32 device, +inf = leave the utterance
+ *   alone bit for bit (scale 0); z = packed float32 noise addressed by the same offsets; scales_out (B) float32 is written for the
+ *   caller.  ws: fs2_op_wav_add_noise_ws_bytes(B, max_len) device bytes, 8-byte aligned (FS2_ERR_NOMEM if short).
+ * fs2_op_wav_convolve_tile is DIAGNOSTIC (as fs2_mel_tile_frames): the consecutive outputs one workgroup of the convolution owns,
+ *   counted from the utterance's first sample - where its tile seams lie.
+ *   fs2_op_wav_resample_tile likewise: the consecutive INPUT samples (a multiple of 32 * orig) one workgroup of the resampler owns for
+ *   this table shape, 0 for a shape fs2_op_wav_resample refuses.
+ * ================================================================================================ */
+#define FS2_CONV_SAME 0
+#define FS2_CONV_FULL 1
+int fs2_op_wav_resample(const float* in, const int64_t* in_offsets, int32_t B, int64_t max_len, const float* tab, int32_t orig,
+                        int32_t new_rate, int32_t width, float* out, int64_t out_capacity, int64_t* out_offsets, void* hip_stream);
+int fs2_op_wav_convolve(const float* in, const int64_t* in_offsets, int32_t B, int64_t max_len, const float* rir,
+                        const int32_t* rir_len, const int32_t* rir_index, int32_t n_rir, int32_t R_max, int32_t mode, float* out,
+                        int64_t out_capacity, int64_t* out_offsets, void* hip_stream);
+size_t fs2_op_wav_add_noise_ws_bytes(int32_t B, int64_t max_len);
+int fs2_op_wav_add_noise(const float* in, const int64_t* offsets, int32_t B, int64_t max_len, const float* z, const float* snr,
+                         void* ws, size_t ws_bytes, float* out, float* scales_out, void* hip_stream);
+int32_t fs2_op_wav_convolve_tile(void);
+int32_t fs2_op_wav_resample_tile(int32_t orig, int32_t new_rate, int32_t width);
+
+/* ================================================================================================
  * Analysis front end: waveform -> log-mel spectrogram and frame energy (csrc/analysis.hip, DESIGN.md "Analysis front end").
  * What the reference computes per item on the CPU with torchaudio and librosa (TTSDataset.__getitem__ / _create_variances,
  * litfass/dataset/datasets.py:183-199,369-380,600-618,630-648), for a padded batch, on the device.  For one utterance x of

@@ -3,7 +3,8 @@ from .config import Fs2Config, preset  # noqa: F401
 from .weights import state_dict_spec, synth_state_dict, synth_inputs  # noqa: F401
 
 __all__ = ["Fs2Config", "preset", "state_dict_spec", "synth_state_dict", "synth_inputs", "FastSpeech2", "Trainer", "MelAnalyzer",
-           "slaney_mel_basis", "finish_contour", "masked_row_mean", "FastDiff", "FastDiffConfig"]
+           "slaney_mel_basis", "finish_contour", "masked_row_mean", "FastDiff", "FastDiffConfig", "DeviceAugment", "Resample", "RoomImpulse",
+           "GaussianSNR"]
 
 
 def __getattr__(name):
@@ -21,4 +22,8 @@ def __getattr__(name):
     if name in ("MelAnalyzer", "slaney_mel_basis", "finish_contour", "masked_row_mean"):
         from . import analysis
         return getattr(analysis, name)
+    # augmentation of the packed waveform on the device: resample, impulse response, noise at an SNR
+    if name in ("DeviceAugment", "Resample", "RoomImpulse", "GaussianSNR"):
+        from . import augment
+        return getattr(augment, name)
     raise AttributeError(name)

@@ -695,5 +695,23 @@ int fs2_op_wav_pack(const float* wav, const int32_t* lengths, int32_t B, int32_t
     WavPackArgs a{wav, lengths, out, offsets, (long long)out_capacity, B, T, hop, kind};
     return launch_wav_pack(a, (hipStream_t)stream);
 }
+int fs2_op_wav_resample(const float* in, const int64_t* in_offsets, int32_t B, int64_t max_len, const float* tab, int32_t orig,
+                        int32_t new_rate, int32_t width, float* out, int64_t out_capacity, int64_t* out_offsets, void* stream) {
+    return launch_wav_resample(in, in_offsets, B, (long long)max_len, tab, orig, new_rate, width, out, (long long)out_capacity,
+                               out_offsets, (hipStream_t)stream);
+}
+int fs2_op_wav_convolve(const float* in, const int64_t* in_offsets, int32_t B, int64_t max_len, const float* rir,
+                        const int32_t* rir_len, const int32_t* rir_index, int32_t n_rir, int32_t R_max, int32_t mode, float* out,
+                        int64_t out_capacity, int64_t* out_offsets, void* stream) {
+    return launch_wav_convolve(in, in_offsets, B, (long long)max_len, rir, rir_len, rir_index, n_rir, R_max, mode, out,
+                               (long long)out_capacity, out_offsets, (hipStream_t)stream);
+}
+size_t fs2_op_wav_add_noise_ws_bytes(int32_t B, int64_t max_len) { return wav_add_noise_ws_bytes(B, (long long)max_len); }
+int fs2_op_wav_add_noise(const float* in, const int64_t* offsets, int32_t B, int64_t max_len, const float* z, const float* snr,
+                         void* ws, size_t ws_bytes, float* out, float* scales_out, void* stream) {
+    return launch_wav_add_noise(in, offsets, B, (long long)max_len, z, snr, ws, ws_bytes, out, scales_out, (hipStream_t)stream);
+}
+int32_t fs2_op_wav_convolve_tile(void) { return wav_convolve_tile(); }
+int32_t fs2_op_wav_resample_tile(int32_t orig, int32_t new_rate, int32_t width) { return wav_resample_tile(orig, new_rate, width); }
 
 }  // extern "C"

@@ -412,6 +412,18 @@ struct WavPackArgs {
 };
 int launch_wav_pack(const WavPackArgs& a, hipStream_t stream);
 
+// augmentation of the packed waveform (augment.hip; include/fs2.h "Waveform augmentation"): errors are answered before any device call
+int launch_wav_resample(const float* in, const int64_t* in_off, int B, long long max_len, const float* tab, int orig, int nw, int width,
+                        float* out, long long capacity, int64_t* out_off, hipStream_t stream);
+int launch_wav_convolve(const float* in, const int64_t* in_off, int B, long long max_len, const float* rir, const int32_t* rir_len,
+                        const int32_t* rir_index, int n_rir, int R_max, int mode, float* out, long long capacity, int64_t* out_off,
+                        hipStream_t stream);
+int wav_convolve_tile();
+int wav_resample_tile(int orig, int nw, int width);
+size_t wav_add_noise_ws_bytes(int B, long long max_len);
+int launch_wav_add_noise(const float* in, const int64_t* off, int B, long long max_len, const float* z, const float* snr, void* ws,
+                         size_t ws_bytes, float* out, float* scales_out, hipStream_t stream);
+
 struct EmbedArgs {
     const int64_t* phones;  // (B, L)
     const float* table;     // (n_phones, H), row 0 == 0

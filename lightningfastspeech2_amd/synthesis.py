@@ -1,6 +1,8 @@
 """Mel forward -> vocoder, the core of the reference's ``SpeechGenerator.generate_samples``
-(litfass/synthesis/generator.py:151-223) without its optional post-processing (voicefixer, audio
-augmentations — off-path).
+(litfass/synthesis/generator.py:151-223).  Of its optional post-processing, the audio augmentations that are well-defined
+array operations - the resample, a room impulse response, Gaussian noise at an SNR (generate.py:82-104, generator.py:181,197-201) -
+run on the device on the packed waveform (``augmentations=``, augment.py); VoiceFixer, ``PitchShift`` and the room simulation
+itself (geometry -> impulse response) stay off-path.
 
 The reference loops over utterances on the host: ``mel = result["mel"][i][~result["tgt_mask"][i]]``
 goes to the CPU and back, one ``Synthesiser`` call each (generator.py:163-170).  Here the padded mel
@@ -44,9 +46,31 @@ class SpeechGenerator:
     reference draws them; ``audio_dtype="int16"`` is refused.  The reference adds ``fastdiff_var`` to the mel first
     (generator.py:167); the engine does not expose it, so this is the mel alone."""
 
-    def __init__(self, model: FastSpeech2, vocoder: "HifiGan | FastDiff", g2p_model=None):
-        self.model, self.synth, self.g2p = model, vocoder, g2p_model
+    def __init__(self, model: FastSpeech2, vocoder: "HifiGan | FastDiff", g2p_model=None, augmentations=None):
+        """``augmentations``: a ``DeviceAugment`` (augment.py) applied to the float32 packed waveform on the device, between the
+        vocoder and the copy to the host - to the int16-quantised samples rescaled, as the reference augments them, or to FastDiff's
+        unquantised samples.  ``"fs"`` of a result is then the chain's final rate; ``audio_dtype="int16"`` is refused.  None (the
+        default) leaves every path as it is without."""
+        self.model, self.synth, self.g2p, self.augmentations = model, vocoder, g2p_model, augmentations
         self.model.eval()
+
+    @property
+    def fs(self) -> int:
+        """the rate of the audio handed back"""
+        fs = self.model.hparams.sampling_rate
+        return fs if self.augmentations is None else self.augmentations.out_fs(fs)
+
+    def _check_dtype(self, audio_dtype: str):
+        if self.augmentations is not None and audio_dtype == "int16":
+            raise ValueError("audio_dtype='int16' cannot be combined with augmentations: they run on the float32 samples")
+
+    def _synthesize(self, result, audio_dtype: str):
+        """vocoder + packing (+ augmentation) on the current stream -> (packed, offsets), device tensors"""
+        packed, offsets = self.synth.synthesize_packed(result["mel"], self._lengths(result), audio_dtype)
+        if self.augmentations is not None:
+            max_len = result["mel"].shape[1] * self.synth.hop  # the host knows the padded frame count only
+            packed, offsets, _ = self.augmentations(packed, offsets, self.model.hparams.sampling_rate, max_len)
+        return packed, offsets
 
     def generate_from_text(self, text: str, speaker) -> np.ndarray:
         """generator.py:96-150 for the default (no priors) d-vector model: text -> phones the model
@@ -73,10 +97,11 @@ class SpeechGenerator:
         int16_samples_to_float32); the default is the reference's float32."""
         if audio_dtype not in ("float32", "int16"):
             raise ValueError(f"audio_dtype must be 'float32' or 'int16', got {audio_dtype!r}")
+        self._check_dtype(audio_dtype)
         result = self.model(batch, inference=True)                       # generator.py:158
         # float -> int16 (numpy's cast as Synthesiser.__call__ does it, __init__.py:39-43: truncation, tanh's +1.0 wraps to -32768),
         # the rescale by 1/32767 and the removal of the pads run on the device (fs2_op_wav_pack): one packed buffer comes across
-        packed, offsets = self.synth.synthesize_packed(result["mel"], self._lengths(result), audio_dtype)
+        packed, offsets = self._synthesize(result, audio_dtype)
         off = offsets.cpu().numpy()                                      # waits for the generator; 8 (B + 1) bytes
         n = int(off[-1])
         host = self._pinned(n * packed.element_size())[:n * packed.element_size()].view(packed.dtype)
@@ -84,7 +109,7 @@ class SpeechGenerator:
         torch.cuda.current_stream(packed.device).synchronize()
         flat = host.numpy()
         audios: List[np.ndarray] = [flat[off[b]:off[b + 1]].copy() for b in range(len(off) - 1)]  # owned: the staging buffer is reused
-        out = {"fs": self.model.hparams.sampling_rate, "audios": audios}
+        out = {"fs": self.fs, "audios": audios}
         if return_duration:
             out["durations"] = [d.cpu() for d in result["duration_rounded"]]
         return out
@@ -107,9 +132,9 @@ class SpeechPipeline:
 
     Each result is the dict ``generate_samples(batch, return_duration, audio_dtype)`` returns, bit for bit.  Stages:
       - the mel forward on a ``ForwardPipeline`` (``in_flight`` engine replicas, a stream and a thread each);
-      - generator + fs2_op_wav_pack on ONE vocoder stream driven by ONE thread: the fs2_vocoder handle has no clone and must not be
+      - generator + fs2_op_wav_pack (+ the generator's ``augmentations``) on ONE vocoder stream driven by ONE thread: the fs2_vocoder handle has no clone and must not be
         entered concurrently.  The frame counts go from the forward's mask to the generator on the device;
-      - the packed buffer (capacity ``B*T*hop``: the total is known on the device only) and its offsets to pinned memory on one copy
+      - the packed buffer (capacity ``B*T*hop``, or the augmentation chain's worst case: the total is known on the device only) and its offsets to pinned memory on one copy
         stream behind an event, queued by a copier thread (a small copy blocks its caller until the stream reaches it);
       - slicing by the offsets on the calling thread, once the copy has landed.
     The GPU never waits for the host's finishing; the host reads the forward's frame count T (as ever) and the landed offsets.
@@ -125,6 +150,7 @@ class SpeechPipeline:
             raise ValueError("in_flight >= 1")
         if audio_dtype not in _WAV_KINDS:
             raise ValueError(f"audio_dtype must be one of {sorted(_WAV_KINDS)}, got {audio_dtype!r}")
+        gen._check_dtype(audio_dtype)
         self.gen, self.audio_dtype, self.return_duration = gen, audio_dtype, return_duration
         self.device = gen.synth.device
         self.fwd = ForwardPipeline(gen.model, in_flight)
@@ -143,7 +169,7 @@ class SpeechPipeline:
         with torch.cuda.device(self.device), torch.cuda.stream(vs):
             vs.wait_event(fwd_done)
             ForwardPipeline._record(out, vs)  # allocated on the forward's stream, read here
-            packed, offsets = self.gen.synth.synthesize_packed(out["mel"], self.gen._lengths(out), self.audio_dtype)
+            packed, offsets = self.gen._synthesize(out, self.audio_dtype)  # one thread: an augmentation draws in submission order
             done = torch.cuda.Event()
             done.record(vs)
         return self.copy_pool.submit(self._to_host, out, fwd_done, packed, offsets, done, slot)
@@ -178,7 +204,7 @@ class SpeechPipeline:
         out, fwd_done, host, host_off, done = fut.result().result()
         done.synchronize()  # the copy has landed
         off, flat = host_off.numpy(), host.numpy()
-        res = {"fs": self.gen.model.hparams.sampling_rate, "audios": [flat[off[b]:off[b + 1]] for b in range(len(off) - 1)]}
+        res = {"fs": self.gen.fs, "audios": [flat[off[b]:off[b + 1]] for b in range(len(off) - 1)]}
         if self.return_duration:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(fwd_done)
