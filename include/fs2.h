@@ -789,8 +789,8 @@ int fs2_op_segment_mean(const float* values, const int32_t* frames, const int32_
 /* ================================================================================================
  * Training targets from audio: frame SNR, contour finishing, priors (csrc/analysis.hip, DESIGN.md "Analysis front end").  What
  * TTSDataset._create_variances (litfass/dataset/datasets.py:562-650) and __getitem__ (:398-463) do to the "snr" and "pitch"
- * variances and for the priors, on the device.  F0 tracking is NOT here (the reference uses pyworld): a caller supplies the raw F0
- * contour in frames, 0 where unvoiced.  CWT decomposition, the "log" transform and "srmr" are not here either.
+ * variances and for the priors, on the device.  The raw F0 contour in frames, 0 where unvoiced, is the caller's (pyworld's, as in the
+ * reference) or the project's own tracker's (fs2_mel_pitch below).  CWT decomposition, the "log" transform and "srmr" are not here.
  *
  * 1. Windowed WADA (SNR.windowed_wada(window = win_length, stride = hop / win_length, use_samples = True), litfass/dataset/snr.py:
  *    194-271, 328-371).  Per utterance x of n >= 1 samples, s and x~ = s x (an fp32 product) as in fs2_mel_run; Te = ceil(n / hop)
@@ -846,6 +846,51 @@ int fs2_op_contour_finish(const float* values, const int32_t* frames, const int3
                           int32_t* frames_out, float* prior, void* hip_stream);
 int fs2_op_masked_row_mean(const float* values, const int32_t* counts, const int32_t* skip, int32_t B, int32_t N, float* out,
                            void* hip_stream);
+
+/* ================================================================================================
+ * F0 tracking: YIN contours from the waveform (csrc/analysis.hip, DESIGN.md "F0 tracking on the device").  The tracker is YIN
+ * (de Cheveigne & Kawahara, "YIN, a fundamental frequency estimator for speech and music", JASA 111(4), 2002), written from the
+ * published definition.  It is NOT PINNED AGAINST PYWORLD'S OUTPUT: the reference takes its contour from pw.dio + pw.stonemask
+ * (litfass/dataset/datasets.py:567-575), pyworld is no dependency of this project and was not available to compare with, and the
+ * contours of the two trackers differ.  Statistics that normalise a contour (mean / std, bins) must come from the tracker that made
+ * it.  Only the CONTRACT of the output is pyworld's, so it goes into fs2_op_contour_finish(zero_is_missing = 1) unchanged: one value
+ * per frame in Hz, 0 where unvoiced, Tf = 1 + n / hop frames, frame t centred on sample t hop.
+ *
+ * Per utterance x of n >= 1 samples, x[j] = 0 outside [0, n); W = win_length and hop of the handle;
+ *     tau_max = ceil(sr / f0_floor),  tau_min = max(2, floor(sr / f0_ceil))
+ * (pyworld's range 71 .. 800 Hz at 22050 Hz: 27 .. 311; the usual threshold is 0.1).
+ *   1. frames t = 0 .. Tf - 1, Tf = 1 + n / hop, s = t hop - W / 2
+ *   2. difference function, tau = 0 .. tau_max + 1:  d(tau) = sum_{j = 0}^{W - 1} (x[s + j] - x[s + j + tau])^2
+ *   3. cumulative mean normalised difference:  d'(0) = 1,  d'(tau) = d(tau) tau / sum_{k = 1}^{tau} d(k),  1 where that sum is 0
+ *   4. pick: the smallest tau in [tau_min, tau_max] with d'(tau) < threshold; then, while tau + 1 <= tau_max and
+ *      d'(tau + 1) < d'(tau), step forward.  No lag below the threshold: the frame is unvoiced, f0 = 0 and dmin = min d' over
+ *      [tau_min, tau_max]
+ *   5. refinement on d':  a, b, c = d'(tau - 1), d'(tau), d'(tau + 1),  curv = a - 2 b + c,
+ *      delta = (a - c) / (2 curv) clamped to [-0.5, 0.5] if curv > 0, else 0;  f0 = sr / (tau + delta),  dmin = b
+ *   6. frames at or past Tf are zeros in every output
+ * The definition is scale-invariant (d' is a ratio of sums of squares), so there is no peak normalisation and no workspace.
+ * Arithmetic: the direct form (x[j] - x[j + tau])^2 in fp32 - no cancellation, unlike e(0) + e(tau) - 2 r(tau); where W % hop == 0
+ * per-hop partial sums, a frame's W / hop added left to right; the running sum of step 3, the quotient and step 5 in fp64, rounded
+ * once.  No sum's order depends on B, S, the padding or the row: results are bitwise batch-invariant.  Samples at or past
+ * lengths[b] are never read.
+ *
+ * fs2_mel_pitch: wav (B, S) fp32, lengths (B) int32 (clamped to [0, S]; 0 = no frames): device.  f0 (B, Tf_max) fp32 with
+ * Tf_max >= 1 + S / hop; f0_frames (B) int32 or NULL; dmin (B, Tf_max) or NULL; cmnd (B, Tf_max, n_lags) or NULL - DIAGNOSTIC, d' for
+ * tau = 0 .. n_lags - 1, what the tests hold the continuous stage to; n_lags must equal tau_max + 2 when cmnd is given and is ignored
+ * otherwise.  Device, each written in full.  One launch on the caller's stream; allocates nothing, never synchronises.
+ * FS2_ERR_SHAPE when tau_max + 2 > 1024, tau_min >= tau_max, threshold lies outside (0, 1], sample_rate, f0_floor or f0_ceil is not
+ * positive, hop is no multiple of 4 (the span is read in 16-byte words), or one frame's span and partials do not fit LDS;
+ * FS2_ERR_ARG for NULL wav / lengths / f0, B or S < 1, Tf_max too small, a wrong n_lags; B > 65535 is FS2_ERR_SHAPE.  Every error is
+ * answered before the launch, with a message in fs2_mel_last_error, and writes nothing.
+ * fs2_mel_pitch_lags validates (sample_rate, f0_floor, f0_ceil) on the host alone and reports the lag range.
+ * fs2_mel_pitch_tile_frames is DIAGNOSTIC (as fs2_mel_tile_frames): the consecutive frames one workgroup owns - where the kernel's
+ * seams lie -, 0 for a range fs2_mel_pitch_lags would refuse.
+ * ================================================================================================ */
+int fs2_mel_pitch(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B, int32_t S, int32_t sample_rate, float f0_floor,
+                  float f0_ceil, float threshold, float* f0, int32_t Tf_max, int32_t* f0_frames, float* dmin, float* cmnd, int32_t n_lags,
+                  void* hip_stream);
+int fs2_mel_pitch_lags(fs2_mel* m, int32_t sample_rate, float f0_floor, float f0_ceil, int32_t* tau_min, int32_t* tau_max);
+int32_t fs2_mel_pitch_tile_frames(fs2_mel* m, int32_t sample_rate, float f0_floor);
 
 /* ================================================================================================
  * Stochastic duration predictor at inference (duration_stochastic=True: the VITS spline-flow predictor of

@@ -16,8 +16,10 @@ contours (silent phones and unvoiced frames become missing, gaps are filled by `
 
 * the WADA table is an argument - the project ships none.  It is Kim & Stern's table for gamma shape 0.4; a litfass installation has
   it as ``litfass/data/wada_values.npy``: ``MelAnalyzer(wada_table=np.load(...))``.
-* F0 tracking is not here (the reference uses pyworld's dio + stonemask): ``items(pitch=...)`` takes the raw F0 contour per
-  utterance, one value per frame, 0 where unvoiced, as pyworld returns it.
+* the raw F0 contour is the caller's or the project's own: ``items(pitch=...)`` takes it per utterance, one value per frame, 0
+  where unvoiced, as pyworld's dio + stonemask return it (what the reference uses), or tracks it on the device with
+  ``pitch="track"`` (``MelAnalyzer.pitch``: YIN, written from the published definition and NOT pinned against pyworld's output -
+  its contours differ from DIO + StoneMask's, so ``stats`` must come from the tracker that made the contours they normalise).
 * two deliberate differences: the reference's closing energy split ``10 log10(dSigEng / dNoiseEng)`` (the estimate again, to
   float64 rounding) is not reproduced, and phone-level means average the original frames (the reference writes them in place
   while reading, which differs only after leading zero-duration phones).
@@ -300,15 +302,50 @@ class MelAnalyzer(_lib.Handle):
         self._check(st, "fs2_mel_snr")
         return {"snr": out, "snr_lengths": out_len}
 
-    def items(self, wavs: Sequence, durations: Sequence, silent: Optional[Sequence] = None, pitch: Optional[Sequence] = None,
+    def pitch(self, wav, lengths=None, f0_floor: float = 71.0, f0_ceil: float = 800.0, threshold: float = 0.1,
+              return_cmnd: bool = False) -> Dict[str, torch.Tensor]:
+        """The raw F0 contour by YIN (de Cheveigne & Kawahara 2002; the definition is stated in include/fs2.h "F0 tracking"): wav
+        and lengths as in ``__call__`` -> device tensors f0 (B, 1 + S // hop) fp32 in Hz - 0 where unvoiced, frame t centred on
+        sample t * hop, rows past an utterance's own count zero: pyworld's contract, what ``finish_contour(zero_is_missing=True)``
+        takes -, f0_lengths (B) int32, dmin (B, 1 + S // hop) the normalised difference at the picked lag (its minimum over the lag
+        range on an unvoiced frame) and, with return_cmnd, cmnd (B, 1 + S // hop, tau_max + 2) the whole normalised difference
+        function (diagnostic).  Lags run from max(2, floor(sr / f0_ceil)) to ceil(sr / f0_floor); the defaults are pyworld's range.
+
+        NOT pinned against pyworld's output: pyworld is not a dependency of this project and was not available to compare with.
+        The contours differ from DIO + StoneMask's; statistics (mean / std, bins) must come from the same tracker as the contours
+        they normalise.  The definition is scale-invariant, so there is no peak normalisation."""
+        wav, lengths = self._batch(wav, lengths)
+        B, S = wav.shape
+        dev = self.device
+        tau_min, tau_max = C.c_int32(), C.c_int32()
+        self._check(self.lib.fs2_mel_pitch_lags(self.handle, self.sampling_rate, f0_floor, f0_ceil, C.byref(tau_min), C.byref(tau_max)),
+                    "fs2_mel_pitch_lags")
+        Tf_max, n_lags = 1 + S // self.hop_length, tau_max.value + 2
+        f0 = torch.empty(B, Tf_max, dtype=torch.float32, device=dev)
+        dmin = torch.empty(B, Tf_max, dtype=torch.float32, device=dev)
+        f0_len = torch.empty(B, dtype=torch.int32, device=dev)
+        cmnd = torch.empty(B, Tf_max, n_lags, dtype=torch.float32, device=dev) if return_cmnd else None
+        with torch.cuda.device(dev):
+            st = self.lib.fs2_mel_pitch(self.handle, wav, lengths, B, S, self.sampling_rate, f0_floor, f0_ceil, threshold, f0, Tf_max, f0_len,
+                                        dmin, cmnd, n_lags, torch.cuda.current_stream(dev))
+        self._check(st, "fs2_mel_pitch")
+        out = {"f0": f0, "f0_lengths": f0_len, "dmin": dmin}
+        if return_cmnd:
+            out["cmnd"] = cmnd
+        return out
+
+    def items(self, wavs: Sequence, durations: Sequence, silent: Optional[Sequence] = None, pitch=None,
               stats: Optional[dict] = None, variances: Sequence[str] = ("pitch", "energy", "snr"),
-              levels: Sequence[str] = ("frame",) * 3, priors: Sequence[str] = (), peak_normalize: bool = True) -> List[dict]:
+              levels: Sequence[str] = ("frame",) * 3, priors: Sequence[str] = (), peak_normalize: bool = True,
+              pitch_options: Optional[dict] = None) -> List[dict]:
         """Per-utterance HOST items in the shape ``TTSDataset.__getitem__`` gives them (datasets.py:398-463): ``mel``, ``duration``,
         ``variances`` {name: (sum(d),) at level "frame", (L,) at level "phone"}, ``priors`` {name: float}, ``silence_mask``
         (sum(d),) and ``unexpanded_silence_mask`` (L,) bool.  A caller adds "phones" and "speaker" and hands the list to
         ``frontend.collate``.  ``silent``: per utterance, True where a phone is silence (None: none is).  ``pitch``: per utterance
-        the raw F0 contour, one value per frame and 0 where unvoiced (pyworld's output; F0 tracking is not part of this project) -
-        required when "pitch" is asked for.  "snr" needs the WADA table.  ``energy`` gets no silence handling, as in the reference.
+        the raw F0 contour, one value per frame and 0 where unvoiced (pyworld's output), or the string "track": the contours are
+        then tracked on the device by ``self.pitch(wavs, **pitch_options)`` and go to the finishing without leaving it (see
+        ``pitch`` on what that tracker is and is not; ``stats["pitch"]`` must belong to it) - one of the two is required when "pitch"
+        is asked for.  "snr" needs the WADA table.  ``energy`` gets no silence handling, as in the reference.
         ``stats`` {name: {"mean", "std"}} normalises; priors are taken before normalisation (over non-silent frames, or phones at
         level "phone"; "duration": over non-silent phones)."""
         variances, levels, priors = list(variances), list(levels), list(priors)
@@ -322,7 +359,12 @@ class MelAnalyzer(_lib.Handle):
                 raise ValueError(f"prior {p!r} is neither 'duration' nor one of the variances {variances}")
         if "pitch" in variances and pitch is None:
             raise ValueError("variances includes 'pitch': pass pitch= (the raw F0 contour per utterance, 0 where unvoiced)")
-        if len(wavs) != len(durations) or (silent is not None and len(silent) != len(wavs)) or (pitch is not None and len(pitch) != len(wavs)):
+        track = isinstance(pitch, str)
+        if track and pitch != "track":
+            raise ValueError(f"pitch must be the F0 contours or 'track', got {pitch!r}")
+        if pitch_options is not None and not track:
+            raise ValueError("pitch_options belongs to pitch='track'")
+        if len(wavs) != len(durations) or (silent is not None and len(silent) != len(wavs)) or (pitch is not None and not track and len(pitch) != len(wavs)):
             raise ValueError("one duration array (and silent / pitch array) per waveform")
         B = len(wavs)
         durs = [np.asarray(d.cpu() if isinstance(d, torch.Tensor) else d, np.int64).reshape(-1) for d in durations]
@@ -342,7 +384,7 @@ class MelAnalyzer(_lib.Handle):
         for i, total in enumerate(totals):
             if total > mel_len[i] or total > en_len[i]:
                 raise ValueError(f"utterance {i}: durations sum to {total} frames, the audio has {mel_len[i]} mel / {en_len[i]} energy frames")
-            if pitch is not None and "pitch" in variances and len(pitch[i]) < total:
+            if pitch is not None and not track and "pitch" in variances and len(pitch[i]) < total:
                 raise ValueError(f"utterance {i}: durations sum to {total} frames, the F0 contour has {len(pitch[i])}")
         tot_dev = torch.tensor(totals, dtype=torch.int32, device=dev)
         fs_pad = np.zeros((B, max(1, out["energy"].shape[1])), np.int32)  # frame-level silence, for the energy prior
@@ -363,6 +405,9 @@ class MelAnalyzer(_lib.Handle):
                 if name == "snr":
                     s = self.snr(list(wavs), peak_normalize=peak_normalize)
                     raw, raw_len, kw = s["snr"], s["snr_lengths"], dict(zero_is_missing=False, all_missing_value=0.0)
+                elif track:  # (its frame count is the mel's, checked against the durations above)
+                    p = self.pitch(list(wavs), **(pitch_options or {}))
+                    raw, raw_len, kw = p["f0"], p["f0_lengths"], dict(zero_is_missing=True, all_missing_value=1e-7)
                 else:
                     f0 = [np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p, np.float32).reshape(-1) for p in pitch]
                     host = np.zeros((B, max(1, max(len(p) for p in f0))), np.float32)

@@ -538,6 +538,203 @@ __global__ __launch_bounds__(256) void masked_row_mean_kernel(const float* __res
     }
 }
 
+// ---- F0 tracking: YIN (include/fs2.h "F0 tracking"; DESIGN.md "F0 tracking on the device")
+static constexpr int PITCH_MAX_LAGS = 1024;           // tau_max + 2 at the most
+static constexpr size_t PITCH_LDS_TARGET = 64u * 1024u;  // at least two workgroups per CU where a tile fits this; no LDS reservation needed
+
+struct PitchGeom {
+    int blk, r;    // a frame is r blocks of blk samples, block h of a tile starting h * hop samples into its span
+    int nl, lc;    // lags 0 .. nl - 1 = tau_max + 1; lag capacity: nl rounded up to 64 (a 16-lane group owns 64 lags)
+    int tile, P;   // frames one workgroup owns; blocks it reduces = tile + r - 1
+    int span;      // floats of the staged span, the slack behind the last lag's last sample included (a multiple of 4)
+    size_t lds;
+};
+
+// W % hop == 0: per-hop partial sums, shared by the W / hop frames that overlap a hop.  Otherwise a frame is its own single block.
+static PitchGeom pitch_geom(int win, int hop, int tau_max, int tile) {
+    PitchGeom g;
+    g.r = win % hop == 0 ? win / hop : 1;
+    g.blk = win % hop == 0 ? hop : win;
+    g.nl = tau_max + 2;
+    g.lc = (g.nl + 63) & ~63;
+    g.tile = tile;
+    g.P = tile + g.r - 1;
+    g.span = (g.P - 1) * hop + ((g.blk + 3) & ~3) + g.lc + 8;  // (+ 8: the window word and the word read one step ahead)
+    g.lds = ((size_t)g.span + (size_t)g.P * g.lc + (size_t)MEL_WAVES * g.lc) * sizeof(float);
+    return g;
+}
+
+struct PitchKernelArgs {
+    const float* wav;        // (B, S)
+    const int32_t* lengths;  // (B)
+    float* f0;               // (B, Tf_max)
+    int32_t* f0_frames;      // (B) or null
+    float* dmin;             // (B, Tf_max) or null
+    float* cmnd;             // (B, Tf_max, nl) or null
+    int S, Tf_max, hop, win, blk, r, nl, lc, tile, P, span, tau_min, tau_max;
+    float threshold;
+    double sr;
+};
+
+// One workgroup = one utterance x `tile` consecutive frames.
+//   1. The sample span of the tile - (tile - 1) hop + W + tau_max + 1 samples from t0 hop - W / 2, zero outside [0, n) - goes into
+//      LDS once (plus slack that only lags past tau_max + 1 and the read one step ahead touch).
+//   2. Block partials p(h, tau) = sum_{j < blk} (x[h hop + j] - x[h hop + j + tau])^2 in the direct form on the VALU.  A 16-lane
+//      group owns one block and 64 lags, a lane four consecutive lags 4 q .. 4 q + 3.  Per four samples j0 .. j0 + 3 a lane reads
+//      one 16-byte word the whole group shares (x[j0 ..], a broadcast) and one of its own (x[j0 + 4 q + 4 ..], consecutive lanes in
+//      consecutive 16-byte slots: conflict-free within a block and across blocks where hop is a multiple of 64; DESIGN.md has the other cases), both one step ahead of their use; with the word kept from the step before that
+//      is the seven-sample window the sixteen pairs need - LDS is read once per sample per group, not once per pair.  Sixteen independent fp32 accumulators
+//      (j mod 4, lag); a lag's four are added as (0 + 1) + (2 + 3).
+//   3. A wave per frame: d(tau) = the frame's r partials added left to right in fp32; the running sum over the lags is an fp64
+//      wave scan with a carry from one 64-lag chunk to the next; d' = d tau / sum formed in fp64 and rounded once, into the wave's
+//      own LDS row (and the diagnostic output).
+//   4. The same wave picks (first lag under the threshold by a wave minimum, the walk and the refinement uniformly) and stores.
+// Nothing depends on B, S or the row: the order of every sum is a function of (t mod tile, tau) alone.
+__global__ __launch_bounds__(MEL_THREADS) void mel_pitch_kernel(const PitchKernelArgs a) {
+    extern __shared__ float4 pitch_smem[];
+    float* span = reinterpret_cast<float*>(pitch_smem);  // (stage 2 reads the same words through pitch_smem: no __restrict__)
+    float* __restrict__ part = span + a.span;        // [P][lc]
+    float* __restrict__ rows = part + a.P * a.lc;    // [wave][lc]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, t0 = blockIdx.x * a.tile;
+    const int n = mel_len(a.lengths, b, a.S);
+    const int Tf = n > 0 ? 1 + n / a.hop : 0;
+    if (blockIdx.x == 0 && tid == 0 && a.f0_frames) a.f0_frames[b] = Tf;
+    const int nrows = a.Tf_max - t0 < a.tile ? a.Tf_max - t0 : a.tile;  // frames of this tile that exist in the outputs
+    const size_t out0 = (size_t)b * a.Tf_max + t0;
+    if (t0 >= Tf) {  // uniform: a tile past the utterance's last frame is zeros
+        for (int i = tid; i < nrows; i += MEL_THREADS) {
+            a.f0[out0 + i] = 0.0f;
+            if (a.dmin) a.dmin[out0 + i] = 0.0f;
+        }
+        if (a.cmnd)
+            for (size_t i = tid; i < (size_t)nrows * a.nl; i += MEL_THREADS) a.cmnd[out0 * a.nl + i] = 0.0f;
+        return;
+    }
+    // ---- 1. the sample span -> LDS
+    {
+        const float* __restrict__ x = a.wav + (size_t)b * a.S;
+        const long long g0 = (long long)t0 * a.hop - a.win / 2;
+        for (int i = tid; i < a.span; i += MEL_THREADS) {
+            const long long g = g0 + i;
+            span[i] = (g >= 0 && g < n) ? x[g] : 0.0f;
+        }
+    }
+    __syncthreads();
+    // ---- 2. block partials
+    {
+        const int nqg = a.lc >> 6, units = a.P * nqg;
+        const int full = a.blk >> 2, rest = a.blk & 3;  // steps of four samples; the samples of a last, short step
+        for (int u = wave * 4 + (lane >> 4); u < units; u += MEL_THREADS / 16) {
+            const int h = u / nqg, q = (u - h * nqg) * 16 + (lane & 15);
+            // 16-byte words: hop is a multiple of 4, so a block starts on one
+            const float4* __restrict__ xb = pitch_smem + ((h * a.hop) >> 2);
+            const float4* __restrict__ xw = xb + q;
+            float acc[4][4];
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) acc[jj][tt] = 0.0f;
+            auto pairs = [&acc](const float4& c, const float4& lo, const float4& hi, int live) {
+                const float xs[4] = {c.x, c.y, c.z, c.w};
+                const float w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+                    if (jj < live) {
+#pragma unroll
+                        for (int tt = 0; tt < 4; ++tt) {
+                            const float d = xs[jj] - w[jj + tt];
+                            acc[jj][tt] = fmaf(d, d, acc[jj][tt]);
+                        }
+                    }
+            };
+            float4 c = xb[0], lo = xw[0], hi = xw[1];
+            for (int k = 0; k < full; ++k) {
+                const float4 cn = xb[k + 1], hn = xw[k + 2];  // the next step's words are in flight under this step's pairs
+                pairs(c, lo, hi, 4);
+                c = cn, lo = hi, hi = hn;
+            }
+            if (rest) pairs(c, lo, hi, rest);  // (a block whose length is no multiple of 4)
+            float4 p;
+            p.x = (acc[0][0] + acc[1][0]) + (acc[2][0] + acc[3][0]);
+            p.y = (acc[0][1] + acc[1][1]) + (acc[2][1] + acc[3][1]);
+            p.z = (acc[0][2] + acc[1][2]) + (acc[2][2] + acc[3][2]);
+            p.w = (acc[0][3] + acc[1][3]) + (acc[2][3] + acc[3][3]);
+            *reinterpret_cast<float4*>(part + h * a.lc + 4 * q) = p;
+        }
+    }
+    __syncthreads();
+    // ---- 3 + 4. a wave per frame
+    float* __restrict__ row = rows + wave * a.lc;
+    for (int f = wave; f < nrows; f += MEL_WAVES) {
+        const int t = t0 + f;
+        float* __restrict__ cm = a.cmnd ? a.cmnd + (out0 + f) * a.nl : nullptr;
+        if (t >= Tf) {  // uniform per wave
+            if (lane == 0) {
+                a.f0[out0 + f] = 0.0f;
+                if (a.dmin) a.dmin[out0 + f] = 0.0f;
+            }
+            if (cm)
+                for (int tau = lane; tau < a.nl; tau += 64) cm[tau] = 0.0f;
+            continue;
+        }
+        double carry = 0.0;
+        for (int c0 = 0; c0 < a.nl; c0 += 64) {
+            const int tau = c0 + lane;
+            float d = 0.0f;
+            if (tau < a.nl) {
+                d = part[f * a.lc + tau];
+                for (int i = 1; i < a.r; ++i) d += part[(f + i) * a.lc + tau];
+            }
+            double s = (tau >= 1 && tau < a.nl) ? (double)d : 0.0;
+            for (int o = 1; o < 64; o <<= 1) {
+                const double up = __shfl_up(s, o);
+                if (lane >= o) s += up;
+            }
+            const double cum = carry + s;
+            carry = __shfl(cum, 63);
+            if (tau < a.nl) {
+                const float v = (tau == 0 || cum == 0.0) ? 1.0f : (float)((double)d * (double)tau / cum);
+                row[tau] = v;
+                if (cm) cm[tau] = v;
+            }
+        }
+        mel_wave_sync();  // the row is the wave's own: its stores before its loads, no workgroup barrier
+        int tau = 0x7fffffff;
+        for (int k = a.tau_min + lane; k <= a.tau_max; k += 64)
+            if (row[k] < a.threshold) {
+                tau = k;
+                break;
+            }
+        for (int o = 32; o; o >>= 1) {
+            const int other = __shfl_xor(tau, o);
+            tau = other < tau ? other : tau;
+        }
+        float f0 = 0.0f, dm;
+        if (tau <= a.tau_max) {  // uniform from here: every lane walks the same lags
+            while (tau + 1 <= a.tau_max && row[tau + 1] < row[tau]) ++tau;
+            const double p = row[tau - 1], q = row[tau], r = row[tau + 1];
+            const double curv = p - 2.0 * q + r;
+            double delta = 0.0;
+            if (curv > 0.0) {
+                delta = (p - r) / (2.0 * curv);
+                delta = delta < -0.5 ? -0.5 : (delta > 0.5 ? 0.5 : delta);
+            }
+            f0 = (float)(a.sr / ((double)tau + delta));
+            dm = (float)q;
+        } else {
+            dm = __builtin_inff();
+            for (int k = a.tau_min + lane; k <= a.tau_max; k += 64) dm = fminf(dm, row[k]);
+            for (int o = 32; o; o >>= 1) dm = fminf(dm, __shfl_xor(dm, o));
+        }
+        if (lane == 0) {
+            a.f0[out0 + f] = f0;
+            if (a.dmin) a.dmin[out0 + f] = dm;
+        }
+        mel_wave_sync();  // the row is rewritten for the wave's next frame
+    }
+}
+
 typedef void (*MelKernelFn)(const MelKernelArgs);
 
 static MelKernelFn mel_kernel_for(int mt, int nt) {
@@ -585,6 +782,31 @@ struct fs2_mel : ErrorBase {
 namespace {
 
 size_t mel_ws_need(int B) { return (((size_t)B * sizeof(uint32_t)) + 255) & ~(size_t)255; }
+
+// The lag range and the tile of a (sample_rate, f0_floor, f0_ceil) on this handle's geometry, or the FS2_ERR_SHAPE that refuses it
+int pitch_plan(fs2_mel* m, int sample_rate, float f0_floor, float f0_ceil, int* tau_min, int* tau_max, PitchGeom* geom) {
+    if (m->hop < 1) return m->fail(FS2_ERR_STATE, "fs2_mel_create did not succeed");  // no geometry to judge
+    if (sample_rate <= 0 || !(f0_floor > 0.0f) || !(f0_ceil > 0.0f) || !isfinite(f0_floor) || !isfinite(f0_ceil))
+        return m->fail(FS2_ERR_SHAPE, "sample_rate %d, f0_floor %g, f0_ceil %g: all three must be positive", sample_rate, (double)f0_floor,
+                       (double)f0_ceil);
+    const double hi = ceil((double)sample_rate / (double)f0_floor), lo = floor((double)sample_rate / (double)f0_ceil);
+    if (hi + 2.0 > (double)PITCH_MAX_LAGS)
+        return m->fail(FS2_ERR_SHAPE, "tau_max = ceil(%d / %g) = %.0f: tau_max + 2 exceeds %d lags", sample_rate, (double)f0_floor, hi, PITCH_MAX_LAGS);
+    const int tmax = (int)hi, tmin = lo < 2.0 ? 2 : (lo > (double)PITCH_MAX_LAGS ? PITCH_MAX_LAGS : (int)lo);
+    if (tmin >= tmax) return m->fail(FS2_ERR_SHAPE, "tau_min = %d is not below tau_max = %d: f0_ceil must lie above f0_floor", tmin, tmax);
+    if (m->hop % 4) return m->fail(FS2_ERR_SHAPE, "hop %d is no multiple of 4: the tracker reads its span in 16-byte words", m->hop);
+    PitchGeom g{};
+    int tile = 64;  // the tallest tile of 64, 32, ... frames within the LDS target; a single frame may take the whole CU's LDS
+    for (; tile >= 1; tile >>= 1) {
+        g = pitch_geom(m->win, m->hop, tmax, tile);
+        if (g.lds <= (tile > 1 ? PITCH_LDS_TARGET : MEL_LDS_LIMIT)) break;
+    }
+    if (tile < 1) return m->fail(FS2_ERR_SHAPE, "win_length %d with hop %d and %d lags does not fit one frame into LDS", m->win, m->hop, tmax + 2);
+    if (tau_min) *tau_min = tmin;
+    if (tau_max) *tau_max = tmax;
+    if (geom) *geom = g;
+    return FS2_OK;
+}
 
 }  // namespace
 
@@ -778,6 +1000,43 @@ int fs2_mel_snr(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B,
     hipLaunchKernelGGL(mel_snr_kernel, dim3((Te_max + SNR_TILE - 1) / SNR_TILE, B), dim3(256), lds, st, wav, lengths, peak, m->snr_table,
                        m->snr_k, snr, snr_frames, S, Te_max, m->hop, m->win);
     if (hipGetLastError() != hipSuccess) return m->fail(FS2_ERR_HIP, "a launch of fs2_mel_snr failed");
+    return FS2_OK;
+}
+
+int fs2_mel_pitch_lags(fs2_mel* m, int32_t sample_rate, float f0_floor, float f0_ceil, int32_t* tau_min, int32_t* tau_max) {
+    if (!m) return FS2_ERR_ARG;
+    if (!tau_min || !tau_max) return m->fail(FS2_ERR_ARG, "tau_min and tau_max must not be null");
+    return pitch_plan(m, sample_rate, f0_floor, f0_ceil, tau_min, tau_max, nullptr);
+}
+
+int32_t fs2_mel_pitch_tile_frames(fs2_mel* m, int32_t sample_rate, float f0_floor) {
+    if (!m) return 0;
+    PitchGeom g{};
+    return pitch_plan(m, sample_rate, f0_floor, (float)sample_rate, nullptr, nullptr, &g) == FS2_OK ? g.tile : 0;
+}
+
+int fs2_mel_pitch(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t B, int32_t S, int32_t sample_rate, float f0_floor,
+                  float f0_ceil, float threshold, float* f0, int32_t Tf_max, int32_t* f0_frames, float* dmin, float* cmnd, int32_t n_lags,
+                  void* hip_stream) {
+    if (!m) return FS2_ERR_ARG;
+    int tau_min = 0, tau_max = 0;
+    PitchGeom g{};
+    FS2_TRY(pitch_plan(m, sample_rate, f0_floor, f0_ceil, &tau_min, &tau_max, &g));
+    if (!(threshold > 0.0f && threshold <= 1.0f)) return m->fail(FS2_ERR_SHAPE, "threshold %g lies outside (0, 1]", (double)threshold);
+    if (!m->ready) return m->fail(FS2_ERR_STATE, "fs2_mel_create did not succeed");
+    if (!wav || !lengths || !f0) return m->fail(FS2_ERR_ARG, "wav, lengths and f0 must not be null");
+    if (B < 1 || S < 1) return m->fail(FS2_ERR_ARG, "B = %d, S = %d: both must be at least 1", B, S);
+    if (B > 65535) return m->fail(FS2_ERR_SHAPE, "B = %d exceeds the grid's 65535 utterances", B);
+    if (Tf_max < 1 + S / m->hop) return m->fail(FS2_ERR_ARG, "Tf_max = %d < 1 + S / hop = %d", Tf_max, 1 + S / m->hop);
+    if (cmnd && n_lags != tau_max + 2) return m->fail(FS2_ERR_ARG, "n_lags = %d, cmnd holds tau_max + 2 = %d lags", n_lags, tau_max + 2);
+    // the reservation belongs to the kernel, not to a handle: a single-frame tile above the default limit asks for its own each time
+    if (g.lds > PITCH_LDS_TARGET &&
+        hipFuncSetAttribute((const void*)mel_pitch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds) != hipSuccess)
+        return m->fail(FS2_ERR_HIP, "cannot reserve %zu bytes of LDS: %s", g.lds, hipGetErrorString(hipGetLastError()));
+    PitchKernelArgs a{wav, lengths, f0, f0_frames, dmin, cmnd, S, Tf_max, m->hop, m->win, g.blk, g.r, g.nl, g.lc, g.tile, g.P, g.span,
+                      tau_min, tau_max, threshold, (double)sample_rate};
+    hipLaunchKernelGGL(mel_pitch_kernel, dim3((Tf_max + g.tile - 1) / g.tile, B), dim3(MEL_THREADS), g.lds, (hipStream_t)hip_stream, a);
+    if (hipGetLastError() != hipSuccess) return m->fail(FS2_ERR_HIP, "the launch of fs2_mel_pitch failed");
     return FS2_OK;
 }
 

@@ -2,7 +2,7 @@
 """Benchmark of the analysis front end (waveform -> log-mel + energy, fs2_mel_run) at the mel forward's own output size:
 B utterances x S samples of noise resident in HBM -> (B, 1 + S / hop, n_mels) log-mel and (B, S / hop) energy.
 
-    python tools/bench_analysis.py [--batch 32 --samples 393216 --steps 20 --loops 5 --warmup 3 --no-cpu]
+    python tools/bench_analysis.py [--batch 32 --samples 393216 --steps 20 --loops 5 --warmup 3 --no-cpu --snr --pitch]
 
 One process, the fastest of --loops timed loops (device events around --steps calls) each:
   * the whole operator (peak + STFT / mel + energy launches) and the STFT / mel launch alone;
@@ -15,6 +15,10 @@ same batch, its HBM floor - the waveform read twice, once for the peak and once 
 loop of the same definition on --snr-cpu-rows utterances of the batch (one window at a time, as the reference's loop goes), scaled to
 the batch.  The WADA table is an argument of the operator (the project ships none): --wada-table names an .npy, or an .npz with a
 "wada_table" array (default: the test fixture).
+With --pitch, in the same process: the F0 tracker (fs2_mel_pitch, one launch) on a harmonic glide with noise of the same batch size,
+the rate of its hot loop - sample-lag pairs (x[j] - x[j + tau])^2 per second, per-hop partials counted once, 3 FLOP a pair against
+the 157.3 TFLOP/s the fp32 vector units have on paper - and this project's own numpy float32 restatement of the same definition
+(per-hop partials, one lag at a time) on --cpu-threads threads, the fastest of --loops loops each.
 Prints ONE JSON line.  No GPU, no figure: the tool fails without a device.
 """
 import argparse
@@ -33,6 +37,7 @@ import torch
 from lightningfastspeech2_amd import _lib
 from lightningfastspeech2_amd.analysis import MelAnalyzer
 
+VALU_F32 = 157.3e12  # the fp32 vector rate on paper (packed FMA on every lane of 256 CUs at 2.4 GHz)
 MFMA_F32, HBM, L2 = 155e12, 6.29e12, 17e12  # measured rates (fp32 MFMA, float4 copy, rows shared by every workgroup from L2)
 
 
@@ -61,6 +66,40 @@ def wada_numpy(x, win, hop, g):
     return out
 
 
+def yin_numpy(x, win, hop, sr, tau_min, tau_max, threshold):
+    """the definition of include/fs2.h "F0 tracking" on one float32 utterance (win % hop == 0): per-hop partial sums one lag at a
+    time, a frame's win / hop added left to right, everything in float32 -> (f0 (Tf,), voiced (Tf,))"""
+    n, r, nl = len(x), win // hop, tau_max + 2
+    tf = 1 + n // hop
+    blocks = tf + r - 1
+    xp = np.zeros(blocks * hop + nl, np.float32)
+    xp[win // 2:win // 2 + n] = x
+    a = xp[:blocks * hop]
+    part = np.empty((blocks, nl), np.float32)
+    for tau in range(nl):
+        diff = a - xp[tau:tau + blocks * hop]
+        part[:, tau] = (diff * diff).reshape(blocks, hop).sum(axis=1)
+    d = part[:tf].copy()
+    for i in range(1, r):
+        d += part[i:i + tf]
+    cum = np.cumsum(d[:, 1:], axis=1, dtype=np.float32)
+    cm = np.ones_like(d)
+    np.divide(d[:, 1:] * np.arange(1, nl, dtype=np.float32), cum, out=cm[:, 1:], where=cum != 0)
+    below = cm[:, tau_min:tau_max + 1] < threshold
+    voiced = below.any(axis=1)
+    tau = tau_min + below.argmax(axis=1)
+    rows = np.arange(tf)
+    while True:  # the forward walk, on all frames that still step
+        step = voiced & (tau + 1 <= tau_max) & (cm[rows, np.minimum(tau + 1, nl - 1)] < cm[rows, tau])
+        if not step.any():
+            break
+        tau = tau + step
+    p, q, s = cm[rows, tau - 1], cm[rows, tau], cm[rows, tau + 1]
+    curv = p - 2 * q + s
+    delta = np.where(curv > 0, np.clip((p - s) / np.where(curv > 0, 2 * curv, 1), -0.5, 0.5), 0)
+    return np.where(voiced, sr / (tau + delta), 0).astype(np.float32), voiced
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -72,6 +111,8 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--snr", action="store_true")
     ap.add_argument("--snr-cpu-rows", type=int, default=2)
+    ap.add_argument("--pitch", action="store_true")
+    ap.add_argument("--pitch-cpu-rows", type=int, default=0, help="rows the numpy restatement runs (0: the whole batch); scaled to the batch")
     ap.add_argument("--wada-table", default=os.path.join(ROOT, "tests", "golden", "frontend_targets.npz"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -174,6 +215,50 @@ def main():
                         "snr_numpy_loop_ms_scaled_to_batch": round(loop_ms * B / rows, 1),
                         "snr_speedup_vs_numpy_loop": round(loop_ms * B / rows / snr_ms, 0),
                         "snr_max_abs_db_vs_numpy_loop": float(np.abs(ref[both] - got[both]).max()) if both.any() else None})
+    if a.pitch:
+        sr, floor, ceil, thr = an.sampling_rate, 71.0, 800.0, 0.1
+        lo, hi = C.c_int32(), C.c_int32()
+        assert lib.fs2_mel_pitch_lags(an.handle, sr, floor, ceil, C.byref(lo), C.byref(hi)) == 0
+        nl, tile = hi.value + 2, lib.fs2_mel_pitch_tile_frames(an.handle, sr, floor)
+        # a harmonic glide 100 -> 400 Hz per row (six harmonics at 1 / k) with the batch's noise 20 dB below it
+        phase = 2 * np.pi * torch.cumsum(torch.linspace(100.0, 400.0, S, dtype=torch.float64), 0) / sr
+        voice = sum(torch.sin(k * phase) / k for k in range(1, 7)).to(torch.float32).to(dev)
+        pwav = (0.5 * voice[None, :] / voice.abs().max() + 0.1 * wav).contiguous()
+        f0 = torch.empty(B, T, device=dev)
+        dmin = torch.empty(B, T, device=dev)
+        ff = torch.empty(B, dtype=torch.int32, device=dev)
+
+        def run_pitch(_full=True):
+            st = lib.fs2_mel_pitch(an.handle, pwav, lengths, B, S, sr, floor, ceil, thr, f0, T, ff, dmin, None, 0, stream)
+            assert st == 0, lib.fs2_mel_last_error(an.handle)
+
+        pitch_ms, pitch_loops = fastest(True, run_pitch)
+        assert ff.tolist() == [T] * B and bool(torch.isfinite(f0).all())
+        pairs = float(B) * (T + an.win_length // hop - 1) * hop * nl  # every hop of an utterance once, every lag
+        out.update({"pitch_ms": round(pitch_ms, 4), "pitch_loops_ms": [round(x, 4) for x in pitch_loops], "pitch_frames": B * T,
+                    "pitch_lags": nl, "pitch_tile_frames": tile, "pitch_form": "direct (x[j] - x[j + tau])^2, fp32 VALU",
+                    "pitch_gpairs": round(pairs / 1e9, 2), "pitch_gpairs_per_s": round(pairs / pitch_ms / 1e6, 1),
+                    "pitch_share_of_fp32_vector_157tf": round(3.0 * pairs / (pitch_ms / 1e3) / VALU_F32, 4),
+                    "pitch_voiced_share": round(float((f0 > 0).float().mean()), 4),
+                    "pitch_audio_seconds_per_second": round(B * S / sr / (pitch_ms / 1e3), 1)})
+        if not a.no_cpu:
+            from concurrent.futures import ThreadPoolExecutor
+            rows = B if a.pitch_cpu_rows <= 0 else min(a.pitch_cpu_rows, B)
+            x = pwav[:rows].cpu().numpy()
+            one = lambda r: yin_numpy(r, an.win_length, hop, sr, lo.value, hi.value, thr)
+            cpu = []
+            with ThreadPoolExecutor(a.cpu_threads) as pool:  # numpy releases the GIL inside its loops: a row per thread
+                for _ in range(a.loops):
+                    t0 = time.perf_counter()
+                    ref = list(pool.map(one, x))
+                    cpu.append((time.perf_counter() - t0) * 1e3 * B / rows)
+            got = f0[:rows].cpu().numpy()
+            rf0, rv = np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref])
+            both = rv & (got > 0)
+            out.update({"pitch_numpy_rows": rows, "pitch_numpy_threads": a.cpu_threads, "pitch_numpy_ms": round(min(cpu), 1),
+                        "pitch_numpy_loops_ms": [round(v, 1) for v in cpu], "pitch_speedup_vs_numpy": round(min(cpu) / pitch_ms, 0),
+                        "pitch_voiced_flags_equal_share": round(float((rv == (got > 0)).mean()), 6),
+                        "pitch_max_rel_f0_vs_numpy": float(np.abs(got[both] / rf0[both] - 1).max()) if both.any() else None})
     print(json.dumps(out), flush=True)
 
 
