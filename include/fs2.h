@@ -790,7 +790,7 @@ int fs2_op_segment_mean(const float* values, const int32_t* frames, const int32_
  * Training targets from audio: frame SNR, contour finishing, priors (csrc/analysis.hip, DESIGN.md "Analysis front end").  What
  * TTSDataset._create_variances (litfass/dataset/datasets.py:562-650) and __getitem__ (:398-463) do to the "snr" and "pitch"
  * variances and for the priors, on the device.  The raw F0 contour in frames, 0 where unvoiced, is the caller's (pyworld's, as in the
- * reference) or the project's own tracker's (fs2_mel_pitch below).  CWT decomposition, the "log" transform and "srmr" are not here.
+ * reference) or the project's own tracker's (fs2_mel_pitch below).  The "cwt" transform is fs2_op_cwt_decompose further below; "srmr" is not here.
  *
  * 1. Windowed WADA (SNR.windowed_wada(window = win_length, stride = hop / win_length, use_samples = True), litfass/dataset/snr.py:
  *    194-271, 328-371).  Per utterance x of n >= 1 samples, s and x~ = s x (an fp32 product) as in fs2_mel_run; Te = ceil(n / hop)
@@ -891,6 +891,42 @@ int fs2_mel_pitch(fs2_mel* m, const float* wav, const int32_t* lengths, int32_t 
                   void* hip_stream);
 int fs2_mel_pitch_lags(fs2_mel* m, int32_t sample_rate, float f0_floor, float f0_ceil, int32_t* tau_min, int32_t* tau_max);
 int32_t fs2_mel_pitch_tile_frames(fs2_mel* m, int32_t sample_rate, float f0_floor);
+
+/* ================================================================================================
+ * CWT and log variance targets: CWT.decompose on the device (csrc/cwt.hip, DESIGN.md "CWT decomposition on the device").  What the
+ * reference's transform step does to a variance whose transform is "cwt" (litfass/dataset/datasets.py:641-642, dataset/cwt.py:30-46)
+ * over scipy.signal.cwt and scipy.signal.ricker AS SCIPY 1.14 PUBLISHED THEM, written from that definition.  It is NOT PINNED AGAINST
+ * scipy.signal.cwt'S OUTPUT: SciPy removed both functions in 1.15 and they were not available to compare with; tests/_cwt_ref.py
+ * restates them and is held to the reference's own text where that tree is present.
+ *
+ * values (B, S) fp32, a finished contour per row (frame level: fs2_op_contour_finish; phone level: fs2_op_segment_mean); counts (B)
+ * int32 clamped to [0, S], or NULL (= S); n_scales in 1 .. 16 (the reference: 10); tau (the reference: 0.2833425).  Per row, n = count:
+ *   1. original[j] = values[j], an exact 0 (of either sign) replaced by float32(1e-7)
+ *   2. signal[j] = log(original[j]) in fp64, rounded to fp32; a negative entry gives NaN, as numpy does
+ *   3. mean = the mean of signal[0 .. n), std = the population standard deviation sqrt(mean((signal - mean)^2)): fp64; entry j is
+ *      added to partial j mod 256 in ascending order and the 256 partials by a binary tree - an order that depends on n alone.
+ *      mean_std[b] = {float32(mean), float32(std)}
+ *   4. x[j] = (signal[j] - mean) / (std + float32(1e-7)) with the fp32 operands and fp32 arithmetic the reference has
+ *   5. per scale i = 1 .. n_scales:  w = 2^(i + 1) tau;  N = min(10 w, n), a real number, an integer only when n truncates it;
+ *      M = ceil(N) points;  r[m] = A (1 - v^2 / w^2) exp(-v^2 / (2 w^2)) with v = m - (N - 1) / 2 and A = 2 / (sqrt(3 w) pi^(1/4)) -
+ *      for a non-integer N the wavelet is NOT symmetric about its middle sample, and that is reproduced;
+ *          c_i[k] = sum_j x[j] r[M - 1 - (k + (M - 1) / 2 - j)]     (integer division; over the j whose index lies in [0, M))
+ *      - scipy.signal.convolve(x, r[::-1], mode = "same") as SciPy centres it -;  spectrogram[k][i - 1] = float32(c_i[k] (i + 2.5)^(-5/2)).
+ *      Wavelet values, products and sums are fp64: one accumulator per output from +0, taps in ascending order of j (fused
+ *      multiply-adds), so the result is the fp32 rounding of what the reference computes in float64.
+ *   6. every entry of original, signal and spectrogram at or past n is written as zero.  n = 0: mean_std[b] is NaN (numpy's mean of
+ *      nothing) and nothing else of the row is written.  n = 1 or a constant row: std = 0 exactly and a spectrogram of exact zeros.
+ * No sum's order depends on B, S or the row's place in the batch: results are bitwise batch-invariant.  values at or past a row's
+ * count are never read.
+ *
+ * fs2_op_cwt_decompose: original (B, S), signal (B, S), spectrogram (B, S, n_scales), mean_std (B, 2): fp32, device, each may be
+ * NULL (a NULL spectrogram skips steps 4 and 5).  One launch on the caller's stream; allocates nothing, never synchronises, needs no
+ * workspace.  LIMITS: S <= 4096 (fs2_op_contour_finish's cap) and B <= 65535, FS2_ERR_SHAPE beyond; FS2_ERR_ARG for NULL values,
+ * B or S < 1, n_scales outside 1 .. 16, tau outside [1e-100, 1e100] or NaN.  A refusal writes nothing.
+ * The "log" transform (datasets.py:643-644) needs no operator: it is the log of the unnormalised variance.
+ * ================================================================================================ */
+int fs2_op_cwt_decompose(const float* values, const int32_t* counts, int32_t B, int32_t S, int32_t n_scales, double tau, float* original,
+                         float* signal, float* spectrogram, float* mean_std, void* hip_stream);
 
 /* ================================================================================================
  * Stochastic duration predictor at inference (duration_stochastic=True: the VITS spline-flow predictor of

@@ -3,7 +3,7 @@ from .config import Fs2Config, preset  # noqa: F401
 from .weights import state_dict_spec, synth_state_dict, synth_inputs  # noqa: F401
 
 __all__ = ["Fs2Config", "preset", "state_dict_spec", "synth_state_dict", "synth_inputs", "FastSpeech2", "Trainer", "MelAnalyzer",
-           "slaney_mel_basis", "finish_contour", "masked_row_mean", "FastDiff", "FastDiffConfig", "DeviceAugment", "Resample", "RoomImpulse",
+           "slaney_mel_basis", "finish_contour", "masked_row_mean", "cwt_decompose", "FastDiff", "FastDiffConfig", "DeviceAugment", "Resample", "RoomImpulse",
            "GaussianSNR"]
 
 
@@ -19,7 +19,7 @@ def __getattr__(name):
         from . import fastdiff
         return getattr(fastdiff, name)
     # the analysis front end: waveform -> log-mel + energy + training targets on the device
-    if name in ("MelAnalyzer", "slaney_mel_basis", "finish_contour", "masked_row_mean"):
+    if name in ("MelAnalyzer", "slaney_mel_basis", "finish_contour", "masked_row_mean", "cwt_decompose"):
         from . import analysis
         return getattr(analysis, name)
     # augmentation of the packed waveform on the device: resample, impulse response, noise at an SNR

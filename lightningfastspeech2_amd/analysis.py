@@ -23,6 +23,12 @@ contours (silent phones and unvoiced frames become missing, gaps are filled by `
 * two deliberate differences: the reference's closing energy split ``10 log10(dSigEng / dNoiseEng)`` (the estimate again, to
   float64 rounding) is not reproduced, and phone-level means average the original frames (the reference writes them in place
   while reading, which differs only after leading zero-duration phones).
+
+Variance transforms (include/fs2.h "CWT and log variance targets"): :func:`cwt_decompose` is the reference's ``CWT.decompose``
+(litfass/dataset/cwt.py) and ``items(transforms=...)`` its transform step (datasets.py:641-648), so the class-default
+configuration - phone-level variances, the pitch as a CWT item - comes from audio, durations and silence flags too.  The transform is
+written from the definition of ``scipy.signal.cwt`` / ``ricker`` as SciPy 1.14 published them and is NOT pinned against their output:
+SciPy removed both in 1.15.
 """
 from __future__ import annotations
 
@@ -157,6 +163,48 @@ def masked_row_mean(values: torch.Tensor, counts=None, skip=None) -> torch.Tenso
         st = _lib.load().fs2_op_masked_row_mean(values, cn, sk, B, N, out, torch.cuda.current_stream(values.device))
     _lib.check(st, None, "op_masked_row_mean")
     return out
+
+
+def cwt_decompose(values: torch.Tensor, counts=None, n_scales: int = 10, tau: float = 0.2833425) -> Dict[str, torch.Tensor]:
+    """``CWT.decompose`` (litfass/dataset/cwt.py:30-46) on the device: values (B, S) fp32 a finished contour per row (frame level
+    from :func:`finish_contour`, phone level from :func:`segment_mean`), counts (B) entries per row or None -> {"original_signal"
+    (B, S): values with an exact 0 replaced by 1e-7; "signal" (B, S): its log; "spectrogram" (B, S, n_scales): the Ricker CWT of the
+    normalised signal at the widths 2^(i + 1) tau, each scale times (i + 2.5)^(-5/2); "mean", "std" (B,): of the signal over the
+    row's own entries}, zeros at and past a row's count.  S <= 4096.  The definition is stated in include/fs2.h.
+
+    NOT pinned against ``scipy.signal.cwt``'s output: SciPy removed ``cwt`` and ``ricker`` in 1.15 and they were not available to
+    compare with.  It follows their definition as SciPy 1.14 published it, in float64, rounded once."""
+    if values.device.type != "cuda":
+        raise RuntimeError("cwt_decompose runs on an MI355X only (no CPU fallback)")
+    values = values.to(torch.float32).contiguous()
+    if values.dim() != 2:
+        raise ValueError(f"values must be (B, S), got {tuple(values.shape)}")
+    B, S = values.shape
+    cn = None if counts is None else torch.as_tensor(counts).to(values.device, torch.int32).contiguous()
+    if cn is not None and tuple(cn.shape) != (B,):
+        raise ValueError(f"counts must be ({B},), got {tuple(cn.shape)}")
+    # zeros, not empty: a row whose count is 0 is not written
+    orig, sig = torch.zeros(B, S, dtype=torch.float32, device=values.device), torch.zeros(B, S, dtype=torch.float32, device=values.device)
+    spec = torch.zeros(B, S, max(0, int(n_scales)), dtype=torch.float32, device=values.device)
+    ms = torch.empty(B, 2, dtype=torch.float32, device=values.device)
+    with torch.cuda.device(values.device):
+        st = _lib.load().fs2_op_cwt_decompose(values, cn, B, S, int(n_scales), float(tau), orig, sig, spec, ms,
+                                              torch.cuda.current_stream(values.device))
+    if st == _lib.FS2_ERR_SHAPE:
+        raise ValueError(f"cwt_decompose holds one utterance in LDS: S = {S} <= 4096 entries (and B = {B} <= 65535 rows)")
+    _lib.check(st, None, "op_cwt_decompose")
+    return {"original_signal": orig, "signal": sig, "spectrogram": spec, "mean": ms[:, 0].contiguous(), "std": ms[:, 1].contiguous()}
+
+
+_TRANSFORMS = ("none", "log", "cwt")
+
+
+def _check_transforms(transforms, variances) -> List[str]:
+    """items' ``transforms`` argument -> one of "none", "log", "cwt" per variance (None: "none" for each)"""
+    transforms = ["none"] * len(variances) if transforms is None else list(transforms)
+    if len(transforms) != len(variances) or any(t not in _TRANSFORMS for t in transforms):
+        raise ValueError(f"transforms must name one of {_TRANSFORMS} for each of {list(variances)}, got {transforms}")
+    return transforms
 
 
 class MelAnalyzer(_lib.Handle):
@@ -337,7 +385,7 @@ class MelAnalyzer(_lib.Handle):
     def items(self, wavs: Sequence, durations: Sequence, silent: Optional[Sequence] = None, pitch=None,
               stats: Optional[dict] = None, variances: Sequence[str] = ("pitch", "energy", "snr"),
               levels: Sequence[str] = ("frame",) * 3, priors: Sequence[str] = (), peak_normalize: bool = True,
-              pitch_options: Optional[dict] = None) -> List[dict]:
+              pitch_options: Optional[dict] = None, transforms: Optional[Sequence[str]] = None) -> List[dict]:
         """Per-utterance HOST items in the shape ``TTSDataset.__getitem__`` gives them (datasets.py:398-463): ``mel``, ``duration``,
         ``variances`` {name: (sum(d),) at level "frame", (L,) at level "phone"}, ``priors`` {name: float}, ``silence_mask``
         (sum(d),) and ``unexpanded_silence_mask`` (L,) bool.  A caller adds "phones" and "speaker" and hands the list to
@@ -347,10 +395,18 @@ class MelAnalyzer(_lib.Handle):
         ``pitch`` on what that tracker is and is not; ``stats["pitch"]`` must belong to it) - one of the two is required when "pitch"
         is asked for.  "snr" needs the WADA table.  ``energy`` gets no silence handling, as in the reference.
         ``stats`` {name: {"mean", "std"}} normalises; priors are taken before normalisation (over non-silent frames, or phones at
-        level "phone"; "duration": over non-silent phones)."""
+        level "phone"; "duration": over non-silent phones).
+        ``transforms``: per variance "none" (the default for each), "log" or "cwt" - the reference's ``variance_transforms``
+        (datasets.py:641-648; its class default is ("cwt", "none", "none") at levels ("phone",) * 3).  A transformed variance is
+        taken UNNORMALISED, ``stats`` are not applied to it (the reference's ``elif``), and priors are taken before any transform.
+        "log": the natural log of the variance.  "cwt": ``variances[name]`` is the dict :func:`cwt_decompose` describes, per
+        utterance - "signal", "original_signal" (n,), "spectrogram" (n, 10), "mean", "std" (np.float32) over the n = L phone means
+        (1e-7 for an empty phone) at level "phone", the n = sum(d) frames otherwise - which ``frontend.collate`` flattens to the
+        ``variances_<name>_signal`` / ``_spectrogram`` / ``_mean`` / ``_std`` that ``Trainer.training_step`` reads."""
         variances, levels, priors = list(variances), list(levels), list(priors)
         if len(levels) != len(variances) or any(lv not in ("frame", "phone") for lv in levels):
             raise ValueError(f"levels must name 'frame' or 'phone' for each of {variances}, got {levels}")
+        transforms = _check_transforms(transforms, variances)
         for v in variances:
             if v not in ("pitch", "energy", "snr"):
                 raise ValueError(f"variance {v!r} is none of 'pitch', 'energy', 'snr'")
@@ -391,8 +447,9 @@ class MelAnalyzer(_lib.Handle):
         for i, f in enumerate(frame_sil):
             fs_pad[i, :len(f)] = f
         var_host, prior_host = {}, {}
-        for name, level in zip(variances, levels):
-            mean, std = (float(stats[name]["mean"]), float(stats[name]["std"])) if stats is not None else (0.0, 1.0)
+        for name, level, transform in zip(variances, levels, transforms):
+            normalise = stats is not None and transform == "none"  # a transformed variance is taken unnormalised
+            mean, std = (float(stats[name]["mean"]), float(stats[name]["std"])) if normalise else (0.0, 1.0)
             phone = level == "phone"
             if name == "energy":
                 frame_vals, frames = out["energy"], tot_dev
@@ -427,15 +484,26 @@ class MelAnalyzer(_lib.Handle):
                 else:
                     pr = fprior
                 prior_host[name] = pr.cpu().numpy()
+            if transform == "cwt":
+                dec = cwt_decompose(vals, n_phones if phone else frames)
+                var_host[name] = {k: v.cpu().numpy() for k, v in dec.items()}
+                continue
+            if transform == "log":  # in fp64, rounded once: what "signal" is in a CWT item
+                vals = torch.log(vals.to(torch.float64)).to(torch.float32)
             var_host[name] = vals.cpu().numpy()
         if "duration" in priors:
             prior_host["duration"] = masked_row_mean(torch.from_numpy(dpad).to(dev, torch.float32), n_phones, torch.from_numpy(spad)).cpu().numpy()
         mel = out["mel"].cpu().numpy()
+        def variance(host, i, n):
+            if not isinstance(host, dict):
+                return np.ascontiguousarray(host[i, :n], np.float32)
+            return {k: np.float32(host[k][i]) if k in ("mean", "std") else np.ascontiguousarray(host[k][i, :n], np.float32)
+                    for k in ("signal", "original_signal", "spectrogram", "mean", "std")}  # CWT.decompose's keys, in its order
         items = []
         for i, d in enumerate(durs):
             n = {"frame": totals[i], "phone": len(d)}
             items.append({"mel": mel[i, :totals[i]].copy(), "duration": d,
-                          "variances": {v: np.ascontiguousarray(var_host[v][i, :n[lv]], np.float32) for v, lv in zip(variances, levels)},
+                          "variances": {v: variance(var_host[v], i, n[lv]) for v, lv in zip(variances, levels)},
                           "priors": {p: float(prior_host[p][i]) for p in priors},
                           "silence_mask": frame_sil[i], "unexpanded_silence_mask": sils[i]})
         return items

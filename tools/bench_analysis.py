@@ -2,7 +2,7 @@
 """Benchmark of the analysis front end (waveform -> log-mel + energy, fs2_mel_run) at the mel forward's own output size:
 B utterances x S samples of noise resident in HBM -> (B, 1 + S / hop, n_mels) log-mel and (B, S / hop) energy.
 
-    python tools/bench_analysis.py [--batch 32 --samples 393216 --steps 20 --loops 5 --warmup 3 --no-cpu --snr --pitch]
+    python tools/bench_analysis.py [--batch 32 --samples 393216 --steps 20 --loops 5 --warmup 3 --no-cpu --snr --pitch --cwt]
 
 One process, the fastest of --loops timed loops (device events around --steps calls) each:
   * the whole operator (peak + STFT / mel + energy launches) and the STFT / mel launch alone;
@@ -19,6 +19,11 @@ With --pitch, in the same process: the F0 tracker (fs2_mel_pitch, one launch) on
 the rate of its hot loop - sample-lag pairs (x[j] - x[j + tau])^2 per second, per-hop partials counted once, 3 FLOP a pair against
 the 157.3 TFLOP/s the fp32 vector units have on paper - and this project's own numpy float32 restatement of the same definition
 (per-hop partials, one lag at a time) on --cpu-threads threads, the fastest of --loops loops each.
+With --cwt, in the same process: the CWT decomposition (fs2_op_cwt_decompose, one launch) on --batch contours of 1536 entries (frame
+level) and of 256 (phone level), against two floors - the HBM floor of two reads of the contour plus the writes of original, signal
+and the 10-scale spectrogram, and the launch floor, measured as the same launch with every count 0 (each workgroup returns at once) -
+the rate of its fp64 multiply-adds (taps that fall inside the utterance), and this project's own numpy restatement of the same
+definition (np.convolve per scale, a row per thread) on --cpu-threads threads.
 Prints ONE JSON line.  No GPU, no figure: the tool fails without a device.
 """
 import argparse
@@ -100,6 +105,33 @@ def yin_numpy(x, win, hop, sr, tau_min, tau_max, threshold):
     return np.where(voiced, sr / (tau + delta), 0).astype(np.float32), voiced
 
 
+def cwt_numpy(v, n_scales=10, tau=0.2833425):
+    """the definition of include/fs2.h "CWT and log variance targets" on one float32 contour -> the (n, n_scales) spectrogram"""
+    s = np.where(v == 0, np.float32(1e-7), v)
+    s = np.log(s.astype(np.float64)).astype(np.float32)
+    x = (s - s.mean()) / (s.std() + np.float32(1e-7))
+    out = np.empty((len(v), n_scales), np.float32)
+    for i in range(1, n_scales + 1):
+        w = 2 ** (i + 1) * tau
+        N = min(10 * w, len(v))
+        vec = np.arange(0, N) - (N - 1.0) / 2
+        r = 2 / (np.sqrt(3 * w) * np.pi ** 0.25) * (1 - vec ** 2 / w ** 2) * np.exp(-vec ** 2 / (2 * w ** 2))
+        full = np.convolve(x, r[::-1])
+        start = (len(full) - len(v)) // 2
+        out[:, i - 1] = full[start:start + len(v)] * (i + 2.5) ** (-5 / 2)
+    return out
+
+
+def cwt_taps(n, n_scales=10, tau=0.2833425):
+    """multiply-adds of one utterance: per scale and output, the taps that fall inside [0, n)"""
+    total = 0
+    for i in range(1, n_scales + 1):
+        M = int(np.ceil(min(10 * 2 ** (i + 1) * tau, n)))
+        j = np.arange(n)[:, None] - M // 2 + np.arange(M)[None, :]
+        total += int(((j >= 0) & (j < n)).sum())
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -113,6 +145,7 @@ def main():
     ap.add_argument("--snr-cpu-rows", type=int, default=2)
     ap.add_argument("--pitch", action="store_true")
     ap.add_argument("--pitch-cpu-rows", type=int, default=0, help="rows the numpy restatement runs (0: the whole batch); scaled to the batch")
+    ap.add_argument("--cwt", action="store_true")
     ap.add_argument("--wada-table", default=os.path.join(ROOT, "tests", "golden", "frontend_targets.npz"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -259,6 +292,40 @@ def main():
                         "pitch_numpy_loops_ms": [round(v, 1) for v in cpu], "pitch_speedup_vs_numpy": round(min(cpu) / pitch_ms, 0),
                         "pitch_voiced_flags_equal_share": round(float((rv == (got > 0)).mean()), 6),
                         "pitch_max_rel_f0_vs_numpy": float(np.abs(got[both] / rf0[both] - 1).max()) if both.any() else None})
+    if a.cwt:
+        from concurrent.futures import ThreadPoolExecutor
+        ns, tau = 10, 0.2833425
+        for level, Sc in (("frame", 1536), ("phone", 256)):
+            rs = np.random.RandomState(Sc)  # contours shaped like F0: log-normal about 180 Hz, a slow wander plus jitter
+            host = (180.0 * np.exp(0.3 * np.sin(np.arange(Sc)[None, :] / 11.0 + rs.uniform(0, 6, (B, 1))) + 0.05 * rs.standard_normal((B, Sc)))).astype(np.float32)
+            vals = torch.from_numpy(host).to(dev)
+            full, none = torch.full((B,), Sc, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
+            orig, sig = torch.empty(B, Sc, device=dev), torch.empty(B, Sc, device=dev)
+            spec, ms2 = torch.empty(B, Sc, ns, device=dev), torch.empty(B, 2, device=dev)
+
+            def run_cwt(counts):
+                assert lib.fs2_op_cwt_decompose(vals, counts, B, Sc, ns, tau, orig, sig, spec, ms2, stream) == 0
+
+            cwt_ms, cwt_loops = fastest(full, run_cwt)
+            assert bool(torch.isfinite(spec).all())
+            launch_ms, _ = fastest(none, run_cwt)
+            floor_ms = 4.0 * B * Sc * (2 + 2 + ns) / HBM * 1e3
+            fmas = float(B) * cwt_taps(Sc, ns, tau)
+            res = {"entries": Sc, "ms": round(cwt_ms, 4), "loops_ms": [round(x, 4) for x in cwt_loops], "hbm_floor_ms": round(floor_ms, 5),
+                   "launch_floor_ms": round(launch_ms, 4), "ratio_to_hbm_floor": round(cwt_ms / floor_ms, 1),
+                   "ratio_to_launch_floor": round(cwt_ms / launch_ms, 1), "fp64_fmas": fmas, "fp64_gfma_per_s": round(fmas / cwt_ms / 1e6, 1)}
+            if not a.no_cpu:
+                cpu = []
+                with ThreadPoolExecutor(a.cpu_threads) as pool:  # numpy releases the GIL inside np.convolve: a row per thread
+                    for _ in range(a.loops):
+                        t0 = time.perf_counter()
+                        ref = np.stack(list(pool.map(cwt_numpy, host)))
+                        cpu.append((time.perf_counter() - t0) * 1e3)
+                run_cwt(full)
+                res.update({"numpy_ms": round(min(cpu), 2), "numpy_threads": a.cpu_threads, "numpy_loops_ms": [round(v, 2) for v in cpu],
+                            "speedup_vs_numpy": round(min(cpu) / cwt_ms, 0),
+                            "max_abs_vs_numpy_over_peak": float(np.abs(spec.cpu().numpy() - ref).max() / np.abs(ref).max())})
+            out[f"cwt_{level}"] = res
     print(json.dumps(out), flush=True)
 
 
